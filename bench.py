@@ -10,15 +10,19 @@ all-reduce of 256 doubles when N > 1]).  Default workload = the configuration BA
 is quoted on (C3 of SURVEY.md section 8): 1e6 synthetic stars per GPU x 256 walkers, rotation +
 dispersion + fixed single-Gaussian background mixture, float64.  Star records and the walker table are
 resident in HBM before the timed region.  For N > 1 every rank holds its own 1e6-star shard (weak
-scaling) and the per-walker partial sums are all-reduced over xGMI.  Every run (any N, default
-workload) also times the north-star strong-scaling case, C4: ONE 1e7-star catalogue sharded over the N
-ranks (``c4_strong`` in the JSON line), so that a sweep over N yields the strong-scaling curve.
+scaling) and the per-walker partial sums are all-reduced over xGMI.
+
+A plain run sets up, warms up, times the K steps and prints the headline fields; ``--dump-outputs DIR``
+also writes the log-likelihoods of the last timed step.  ``--full`` adds every other figure: sampled
+kernel times and the roofline, the blocking call, the sampler-driven rate, the CPU baselines and, for
+the default workload at any N, the north-star strong-scaling case, C4: ONE 1e7-star catalogue sharded
+over the N ranks (``c4_strong`` in the JSON line), so that a sweep over N yields the strong-scaling curve.
 
 No PyTorch anywhere: the launcher's environment (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_*) is read
 directly, rank 0's RCCL unique id, barriers and max-over-ranks travel over ``mcmc_dynamics_amd.hostgroup``
 (plain TCP), so the process runs on the ROCm libraries ``libmcd_hip.so`` was built against.
 
-Rank 0 prints ONE JSON line (contract in the task statement) carrying `roofline` and `cpu_baseline`.
+Rank 0 prints ONE JSON line; `roofline` and `cpu_baseline` are null unless ``--full`` measured them.
 If the collective cannot be set up or its first all-reduce hangs, rank 0 prints a line with
 ``"degraded": true`` and ``"value": null`` and EVERY rank exits with status 3: no number is reported
 from a process that sits beside a blocked GPU context.
@@ -88,7 +92,18 @@ def parse_args():
     ap.add_argument("--no-mcmc", action="store_true", help="skip the sampler-driven end-to-end figure (profiling runs)")
     ap.add_argument("--no-c4-strong", action="store_true", help="skip the 1e7-star strong-scaling sub-record")
     ap.add_argument("--c4-stars", type=int, default=10000000, help="total stars of the strong-scaling sub-record")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: sampled kernel times and the roofline, the "
+                         "blocking call, the sampler-driven rate, the C4 strong-scaling record, the CPU baselines (the "
+                         "--no-* flags above select among these); without it a run sets up, warms up, times the K steps "
+                         "and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the log-likelihoods of the last timed step, as the caller of mcd_loglike_fetch receives "
+                         "them, to DIR/loglike.npy (float64; above 64 MB an evenly strided sample of them)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def build_catalog(native, ctx, synthetic, cat, model, precision="f64", bin_offsets=None):
@@ -195,6 +210,20 @@ def cpu_baseline_all_cores(cat, pos, model, per_walker_s, budget_s):
 
 
 # ---------------------------------------------------------------------------------------------- helpers
+DUMP_MAX_BYTES = 63 << 20           # a dump stays under 64 MB, .npy header included
+
+
+def dump_outputs(directory, loglike):
+    """--dump-outputs: the log-likelihoods of the last timed step ([bins x] walkers, float64) as DIR/loglike.npy.  Above
+    DUMP_MAX_BYTES the flattened array is thinned to every k-th value, k fixed by the shape, so that two builds run with
+    the same arguments can still be compared value for value."""
+    os.makedirs(directory, exist_ok=True)
+    out = np.ascontiguousarray(loglike, dtype=np.float64)
+    if out.nbytes > DUMP_MAX_BYTES:
+        out = out.reshape(-1)[::out.nbytes // DUMP_MAX_BYTES + 1]
+    np.save(os.path.join(directory, "loglike.npy"), out)
+
+
 def mapped_libraries():
     """Which HIP runtime / RCCL / kernel library this process actually mapped (from /proc/self/maps)."""
     found = {}
@@ -295,25 +324,27 @@ def first_collective(gpu_cat, group, rank, world, args):
         fail_collective(rank, world, args, "first all-reduce", why)
 
 
-def timed_steps(gpu_cat, group, steps, warmup, ramp_seconds, stride):
+def timed_steps(gpu_cat, group, steps, warmup, ramp_seconds, stride, sample_kernels=True):
     """W untimed warm-up steps (after an untimed clock ramp), then exactly K pipelined steps between two barriers +
-    device syncs; returns the max-over-ranks wall time and this rank's sampled kernel time."""
+    device syncs; returns the max-over-ranks wall time and this rank's sampled kernel time.  sample_kernels=False: no HIP
+    events at all (no cold launches, no sampled kernel times, no one-lane pass), the wall time of the K steps only."""
     def barrier():
         gpu_cat.sync()
         if group is not None:
             group.barrier()
 
-    gpu_cat.set_option("timing", 2)
-    gpu_cat.set_option("timing_reserve", min(65536, max(steps, warmup) + 32))   # no hipEventCreate inside the timed region
-    # first launches after idle (no ramp): what a short job sees before the clocks have settled
-    gpu_cat.set_option("timing_stride", 1)
-    gpu_cat.enqueue()
-    gpu_cat.sync()
-    gpu_cat.timing_collect()
-    for _ in range(20):
+    if sample_kernels:
+        gpu_cat.set_option("timing", 2)
+        gpu_cat.set_option("timing_reserve", min(65536, max(steps, warmup) + 32))   # no hipEventCreate inside the timed region
+        # first launches after idle (no ramp): what a short job sees before the clocks have settled
+        gpu_cat.set_option("timing_stride", 1)
         gpu_cat.enqueue()
-    cold_ms, cold_n = gpu_cat.timing_collect()
-    gpu_cat.set_option("timing_stride", stride)
+        gpu_cat.sync()
+        gpu_cat.timing_collect()
+        for _ in range(20):
+            gpu_cat.enqueue()
+        cold_ms, cold_n = gpu_cat.timing_collect()
+        gpu_cat.set_option("timing_stride", stride)
     # Clock ramp (untimed, before the W warm-up steps): the GPU needs some 100 ms of load to reach its sustained clocks.
     # Every rank runs the same number of launches (the all-reduce is collective).  No HIP events in the ramp and the
     # warm-up: hundreds of recorded-but-unread event pairs make the FIRST launch after the next synchronisation cost
@@ -339,7 +370,8 @@ def timed_steps(gpu_cat, group, steps, warmup, ramp_seconds, stride):
     gpu_cat.sync()
     if warmup > 0:
         gpu_cat.enqueue()
-    gpu_cat.set_option("timing", 2)                  # (synchronises; the event pairs were created by timing_reserve)
+    if sample_kernels:
+        gpu_cat.set_option("timing", 2)              # (synchronises; the event pairs were created by timing_reserve)
     barrier()
     t0 = time.perf_counter()
     if os.environ.get("MCD_BENCH_DEBUG"):
@@ -359,6 +391,8 @@ def timed_steps(gpu_cat, group, steps, warmup, ramp_seconds, stride):
     if group is not None:
         group.barrier()
         elapsed = float(group.allreduce(np.array([elapsed]), op="max")[0])
+    if not sample_kernels:
+        return {"elapsed": elapsed, "ramp_steps": ramp_steps}
     kernel_ms_total, n_launch = gpu_cat.timing_collect()
     # The same kernel alone on the chip: with two lanes consecutive launches of the timed region overlap, so a
     # launch's own duration above includes time it shares with its neighbours.  A short pass on ONE lane (untimed for
@@ -454,7 +488,7 @@ def main():
 
     # Extra CPU figure (all host cores) -- forked workers, so it runs before anything initialises the HIP runtime.
     all_cores = None
-    if (world == 1 and not args.no_cpu_baseline and not args.no_cpu_all_cores
+    if (args.full and world == 1 and not args.no_cpu_baseline and not args.no_cpu_all_cores
             and args.workload in ("c2", "c3", "c3gb", "c3const")):
         try:
             cat0 = synthetic.make_catalog(n_stars, config=config, seed=synthetic.CATALOG_SEED_BASE + config,
@@ -555,31 +589,37 @@ def main():
     if group is not None:
         first_collective(gpu_cat, group, rank, world, args)
 
-    # HIP events around every 4th (K < 64) or 8th main-kernel launch of the timed region: an event pair costs two signal
+    # --full: HIP events around every 4th (K < 64) or 8th main-kernel launch of the timed region; an event pair costs two signal
     # packets (~6 us per step between back-to-back kernels, tools/event_cost_probe.py), so the kernel time is sampled
     stride = 8 if args.steps >= 64 else 4
     try:
-        t = timed_steps(gpu_cat, group, args.steps, args.warmup, args.clock_ramp_seconds, stride)
+        t = timed_steps(gpu_cat, group, args.steps, args.warmup, args.clock_ramp_seconds, stride, sample_kernels=args.full)
     except Exception as exc:
         if group is None:
             raise
         fail_collective(rank, world, args, "timed region", repr(exc))
-    elapsed, kernel_s = t["elapsed"], t["kernel_s"]
-    result = gpu_cat.fetch()
-    info = gpu_cat.launch_info()
-    info["kernel_family"] = {0: "plain", 1: "fast", 2: "fast, narrow-range variant", -1: "none"}[gpu_cat.fast_level]
-    info["prefetch"] = gpu_cat.last_prefetch             # 1: the instantiation that prefetches the next iteration's records
+    elapsed = t["elapsed"]
+    # (every rank fetches: a re-evaluation with the plain kernels inside the fetch is collective)
+    result = gpu_cat.fetch() if args.full or args.dump_outputs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, result)
 
-    # blocking C-ABI call (host params in, host results out): the PCIe/sync-inclusive rate, never `value`
-    n_sync = max(20, min(50, args.steps))
-    sync_med, sync_mean = blocking_calls(gpu_cat, pos, n_sync)
-    if group is not None:
-        sync_med = float(group.allreduce(np.array([sync_med]), op="max")[0])
+    if args.full:
+        kernel_s = t["kernel_s"]
+        info = gpu_cat.launch_info()
+        info["kernel_family"] = {0: "plain", 1: "fast", 2: "fast, narrow-range variant", -1: "none"}[gpu_cat.fast_level]
+        info["prefetch"] = gpu_cat.last_prefetch         # 1: the instantiation that prefetches the next iteration's records
+
+        # blocking C-ABI call (host params in, host results out): the PCIe/sync-inclusive rate, never `value`
+        n_sync = max(20, min(50, args.steps))
+        sync_med, sync_mean = blocking_calls(gpu_cat, pos, n_sync)
+        if group is not None:
+            sync_med = float(group.allreduce(np.array([sync_med]), op="max")[0])
 
     # sampler-driven end-to-end rate (1 GPU only): the built-in stretch move makes two blocking calls of W/2
     # proposals per step, exactly the batching emcee's default move produces (hard parts)
     mcmc = None
-    if world == 1 and n_bins == 1 and not args.no_mcmc and model != "profile":
+    if args.full and world == 1 and n_bins == 1 and not args.no_mcmc and model != "profile":
         import logging
         from mcmc_dynamics_amd import DataReader, Gaussian
         from mcmc_dynamics_amd.analysis import ConstantFit, ConstantFitGB
@@ -628,7 +668,7 @@ def main():
             mcmc["host_numbers_steps_per_s"] = n_mcmc / (time.perf_counter() - t2)
         fit.close()
 
-    if world == 1 and n_bins > 1 and not args.no_mcmc and model == "const" and args.precision == "f64":
+    if args.full and world == 1 and n_bins > 1 and not args.no_mcmc and model == "const" and args.precision == "f64":
         # C5: one ensemble per radial bin in lockstep (the reference runs one MCMC per bin, bin/run_tests.py:75-124);
         # blocks of steps inside the library (mcd_stretch_move with n_bins = B) and, beside it, the NumPy loop
         import logging
@@ -665,13 +705,15 @@ def main():
         fit.close()
 
     # per-rank figures of the headline workload, gathered before the catalogue goes away
-    kernel_us_ranks = [kernel_s * 1e6]
-    if group is not None:
-        kernel_us_ranks = [float(x[0]) for x in group.allgather_array(np.array([kernel_s * 1e6]))]
+    if args.full:
+        kernel_us_ranks = [kernel_s * 1e6]
+        if group is not None:
+            kernel_us_ranks = [float(x[0]) for x in group.allgather_array(np.array([kernel_s * 1e6]))]
     gpu_cat.close()
 
     strong_rec = None
-    if args.workload == "c3" and not args.no_c4_strong and args.stars is None and args.walkers is None and args.precision == "f64":
+    if (args.full and args.workload == "c3" and not args.no_c4_strong and args.stars is None and args.walkers is None
+            and args.precision == "f64"):
         try:
             strong_rec = c4_strong(native, synthetic, ctx, group, rank, world, args)
         except Exception as exc:
@@ -688,10 +730,10 @@ def main():
     terms_per_step = float(total_stars) * n_walkers
     value = terms_per_step * args.steps / elapsed
     local_terms = float(len(cat["v"])) * n_walkers
-    streaming_gbps = local_terms * bytes_per_term / kernel_s / 1e9
+    streaming_gbps = local_terms * bytes_per_term / kernel_s / 1e9 if args.full else None
 
     traffic, traffic_src = None, None                # PMC bytes per launch: imported from the committed rocprofv3 passes
-    if args.stars is None and args.walkers is None and args.precision == "f64" and not strong:
+    if args.full and args.stars is None and args.walkers is None and args.precision == "f64" and not strong:
         try:
             with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as f:
                 pmc = json.load(f)
@@ -702,7 +744,7 @@ def main():
             pass
 
     roofline = None
-    if args.precision == "f64":
+    if args.full and args.precision == "f64":
         isa_key = model if model in ("bgfixed", "bggauss", "profile") and info["kernel_family"].endswith("narrow-range variant") else \
             (model + "_general" if model in ("bgfixed", "bggauss", "profile") else model)
         row, src = isa_counts(isa_key)
@@ -738,7 +780,7 @@ def main():
         else:
             roofline = {"bound": "valu_f64", "achieved": None, "peak": VALU_F64_PEAK, "unit": "VALU wave-instructions/s",
                         "frac": None, "traffic": traffic, "kernel_us": kernel_s * 1e6, "error": src}
-    else:
+    elif args.full:
         # float32 modes (the C5 sweep): the roof is f32 vector-instruction issue, 2 cycles per wave64 instruction
         row, src = isa_counts(model + "_" + args.precision) if model in ("const", "bgfixed") else (None, "no instruction count for this model in float32")
         roofline = {"bound": "valu_f32", "achieved": None, "peak": VALU_F32_PEAK, "unit": "VALU wave-instructions/s", "frac": None,
@@ -797,14 +839,6 @@ def main():
                        "note": "independent evaluations in flight on two HIP streams with their own partial-sum and result "
                                "buffers; a sampler's chain (mcmc_end_to_end) and the blocking call (value_blocking) cannot overlap "
                                "evaluations and run on one"},
-        "kernel_us_per_rank": kernel_us_ranks,
-        # SURVEY 8(d)'s own protocol beside `value`: the BLOCKING C-ABI call (parameters in, walker prep, kernels, reduction
-        # [, all-reduce], results out, synchronisation), median of 50 calls after 3 warm-ups
-        "value_blocking": local_terms * world / sync_med,
-        "blocking_call_us_median": sync_med * 1e6, "blocking_call_us_mean": sync_mean * 1e6,
-        "blocking_call_terms_per_s": local_terms * world / sync_med,
-        "launch": info,
-        "mcmc_end_to_end": mcmc,
         "collective": None if world == 1 else {
             "kind": "ncclAllReduce(sum, f64, count = {0}) per step; pipelined steps run it on the communication stream, beside the two compute lanes".format(n_walkers * n_bins),
             "comm_size": comm["size"], "comm_rank_of_rank0": comm["rank"], "rccl_version": comm["rccl_version"],
@@ -813,13 +847,24 @@ def main():
             "library_override": os.environ.get("MCD_RCCL_LIBRARY")},
         "libraries": mapped_libraries(),
         "option_overrides": os.environ.get("MCD_BENCH_OPTIONS") or None,
-        "c4_strong": strong_rec,
     }
+    if args.full:
+        out.update({
+            "kernel_us_per_rank": kernel_us_ranks,
+            # SURVEY 8(d)'s own protocol beside `value`: the BLOCKING C-ABI call (parameters in, walker prep, kernels,
+            # reduction [, all-reduce], results out, synchronisation), median of 50 calls after 3 warm-ups
+            "value_blocking": local_terms * world / sync_med,
+            "blocking_call_us_median": sync_med * 1e6, "blocking_call_us_mean": sync_mean * 1e6,
+            "blocking_call_terms_per_s": local_terms * world / sync_med,
+            "launch": info,
+            "mcmc_end_to_end": mcmc,
+            "c4_strong": strong_rec,
+        })
     out["dtype"] = {"f64": "f64", "f32": "f32", "f32acc64": "f32 terms, f64 accumulation"}[args.precision]
     if n_bins > 1:
         out["config"]["radial_bins"] = n_bins
         out["config"]["outputs_per_step"] = n_bins * n_walkers
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         base, vals = cpu_baseline(cat, pos[0] if n_bins > 1 else pos, model, args.cpu_seconds)
         out["cpu_baseline"] = base
         got = result.sum(axis=0) if n_bins > 1 else result          # same walkers in every bin: sum over bins == un-binned

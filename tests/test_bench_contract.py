@@ -53,7 +53,8 @@ def test_default_bench_line_is_the_headline_configuration():
     assert d["dtype"] == "f64" and d["config"]["likelihood"] == "bgfixed"
     assert d["gpu_vs_cpu_port_max_rel_err"] < 1e-12
     if not os.path.basename(paths[-1]).startswith("r01_"):
-        # every default run also carries the north-star strong-scaling record (one 1e7-star catalogue over the ranks)
+        # every --full run of the default workload also carries the north-star strong-scaling record (one 1e7-star
+        # catalogue over the ranks)
         c4 = d["c4_strong"]
         assert c4["stars_total"] == 10000000 and c4["scaling"] == "strong" and c4["walkers"] == 256
         assert abs(c4["terms_per_s"] * c4["ms_per_step"] * 1e-3 - 2.56e9) < 1e-6 * 2.56e9
@@ -62,8 +63,20 @@ def test_default_bench_line_is_the_headline_configuration():
 def test_bench_cli():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup", "--workload"):
+    for flag in ("--gpus", "--steps", "--warmup", "--workload", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_dumped_outputs_stay_under_64_mb(tmp_path):
+    import numpy as np
+    import bench
+    small = np.arange(512.0).reshape(2, 256)
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert np.array_equal(np.load(str(tmp_path / "small" / "loglike.npy")), small)
+    big = np.arange(9e6)                                         # 72 MB of float64: every second value is kept
+    bench.dump_outputs(str(tmp_path / "big"), big)
+    assert os.path.getsize(str(tmp_path / "big" / "loglike.npy")) <= 64 << 20
+    assert np.array_equal(np.load(str(tmp_path / "big" / "loglike.npy")), big[::2])
 
 
 def test_bench_imports_no_torch():

@@ -3,7 +3,6 @@ instruction counts DESIGN.md section 3 quotes are a budget -- a compiler or sour
 inner loop (a canonicalising v_max, a spilled register, a lost scalar load) should fail here, not in a profile later."""
 import os
 import re
-import subprocess
 import sys
 
 import pytest
@@ -28,15 +27,18 @@ BUDGET = {                                   # VALU instructions per star-walker
 
 
 @pytest.fixture(scope="module")
-def isa_table():
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_mix.py")], capture_output=True, text=True, timeout=900)
-    assert res.returncode == 0, res.stderr[-2000:]
-    rows = {}
-    for line in res.stdout.splitlines():
-        m = re.match(r"^(.*?)\s{2,}([\d.]+)\s+([\d.]+)\s+([\d.]+)\s+([\d.]+)\s+([\d.]+)\s*$", line)
-        if m:
-            rows[m.group(1).strip()] = float(m.group(2))
-    return rows
+def isa_build(tmp_path_factory):
+    """tools/isa_mix.py's compile of the hot kernels into a directory of this run's own: (table rows, path of the ISA)."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_mix
+    out = str(tmp_path_factory.mktemp("isa_mix"))
+    rows = isa_mix.analyse(out)
+    return rows, os.path.join(out, "mcd_kernels-hip-amdgcn-amd-amdhsa-gfx950.s")
+
+
+@pytest.fixture(scope="module")
+def isa_table(isa_build):
+    return {r["name"]: r["valu_per_term"] for r in isa_build[0]}
 
 
 def test_inner_loops_stay_within_their_instruction_budget(isa_table):
@@ -45,11 +47,8 @@ def test_inner_loops_stay_within_their_instruction_budget(isa_table):
         assert isa_table[name] <= limit, (name, isa_table[name], limit)
 
 
-def test_hot_kernels_use_scalar_record_loads_and_no_scratch():
-    asm_path = "/tmp/isa_mix/mcd_kernels-hip-amdgcn-amd-amdhsa-gfx950.s"
-    if not os.path.exists(asm_path):
-        subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_mix.py")], capture_output=True, timeout=900, check=True)
-    asm = open(asm_path).read()
+def test_hot_kernels_use_scalar_record_loads_and_no_scratch(isa_build):
+    asm = open(isa_build[1]).read()
     for tag, vgpr_limit, scratch_limit in (
             ("ILi0ELb0EddLi1ELb0ELi4E", 64, 0), ("ILi1ELb0EddLi2ELb0ELi4E", 64, 0), ("ILi1ELb0EddLi2ELb1ELi4E", 64, 0),
             ("ILi2ELb0EddLi2ELb1ELi4E", 128, 0),

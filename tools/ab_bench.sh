@@ -11,7 +11,7 @@ for w in $WORKLOADS; do
     for v in "$@"; do
         lib=mcmc_dynamics_amd/libmcd_hip_$v.so
         [ "$v" = default ] && lib=mcmc_dynamics_amd/libmcd_hip.so
-        MCD_LIB_PATH=$PWD/$lib timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 30 --no-cpu-baseline --no-mcmc \
+        MCD_LIB_PATH=$PWD/$lib timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 30 --no-cpu-baseline --no-mcmc \
             > $O/ab_${w}_$v.json 2> $O/ab_${w}_$v.err || { tail -5 $O/ab_${w}_$v.err; exit 1; }
         python - "$w" "$v" $O/ab_${w}_$v.json <<'PY'
 import json, sys

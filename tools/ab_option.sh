@@ -10,7 +10,7 @@ O=gpurun_out
 mkdir -p $O
 for w in $WORKLOADS; do
     for v in "$@"; do
-        MCD_BENCH_OPTIONS="$KEY=$v" timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 30 --no-cpu-baseline --no-mcmc --no-c4-strong \
+        MCD_BENCH_OPTIONS="$KEY=$v" timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 30 --no-cpu-baseline --no-mcmc --no-c4-strong \
             > $O/abo_${w}_${KEY}_$v.json 2> $O/abo_${w}_${KEY}_$v.err || { tail -5 $O/abo_${w}_${KEY}_$v.err; exit 1; }
         python - "$w" "$KEY=$v" $O/abo_${w}_${KEY}_$v.json <<'PY'
 import json, sys

@@ -11,6 +11,6 @@ i=0
 for set in "$A" "$B" "$C"; do
     i=$((i+1))
     rm -rf $O/sq_pass$i
-    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/sq_pass$i -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-mcmc > $O/sq_pass$i.log 2>&1 || { tail -5 $O/sq_pass$i.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/sq_pass$i -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-mcmc > $O/sq_pass$i.log 2>&1 || { tail -5 $O/sq_pass$i.log; exit 1; }
     echo "pass $i done"
 done

@@ -11,7 +11,7 @@ i=0
 for set in "$A" "$B" "$C"; do
     i=$((i+1))
     rm -rf $O/sq_w${W}_pass$i
-    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/sq_w${W}_pass$i -- python3 bench.py --walkers $W --steps 20 --warmup 5 --no-cpu-baseline --no-mcmc --no-c4-strong > $O/sq_w${W}_pass$i.log 2>&1 || { tail -5 $O/sq_w${W}_pass$i.log; exit 1; }
+    timeout -k 10 300 rocprofv3 --pmc $set --output-format csv -d $O/sq_w${W}_pass$i -- python3 bench.py --full --walkers $W --steps 20 --warmup 5 --no-cpu-baseline --no-mcmc --no-c4-strong > $O/sq_w${W}_pass$i.log 2>&1 || { tail -5 $O/sq_w${W}_pass$i.log; exit 1; }
 done
 python tools/summarize_rocprof.py sq $O/sq_w${W}.json loglike_kernel $((1000000*W)) $O/sq_w${W}_pass1 $O/sq_w${W}_pass2 $O/sq_w${W}_pass3
 done
