@@ -393,25 +393,32 @@ class Catalog(object):
         _check(self.lib, self.lib.mcd_loglike_per_star(self.handle, p.size, _ptr(p), _ptr(out)), "mcd_loglike_per_star")
         return out
 
-    def _stretch_desc(self, plan, w, p, n_bins):
+    def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):
+        """What both kinds of block check and pass: ``pos`` ([B,] W, P) and ``lnp`` ([B,] W), the descriptor built from
+        ``plan``, the optional outputs.  Returns the C call's leading and trailing arguments and the arrays they point to."""
+        self._alive()
+        for a in (pos, lnp):
+            if a.dtype != np.float64 or not a.flags.c_contiguous:
+                raise ValueError(name + " needs C-contiguous arrays of the documented dtypes")
+        if pos.ndim not in (2, 3) or lnp.shape != pos.shape[:-1]:
+            raise ValueError(name + ": inconsistent array shapes")
+        lead, (w, p) = pos.shape[:-2], pos.shape[-2:]
         cols = [np.ascontiguousarray(plan["col_source"], dtype=np.int32), _f64(plan["col_const"]), _f64(plan["col_factor"]),
                 _f64(plan["lo"]), _f64(plan["hi"])]
         if cols[0].size != self.k or cols[1].size != self.k or cols[2].size != self.k or cols[3].size != p or cols[4].size != p:
             raise ValueError("stretch_move: plan does not match the catalogue / the number of free parameters")
         d = StretchDesc()
-        d.n_walkers, d.n_dim, d.k, d.n_bins = w, p, self.k, n_bins
+        d.n_walkers, d.n_dim, d.k, d.n_bins = w, p, self.k, lead[0] if lead else 1
         d.col_source = cols[0].ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
         d.col_const, d.col_factor, d.lo, d.hi = (_ptr(c) for c in cols[1:])
         d.fixed_ok = 1 if plan.get("fixed_ok", True) else 0
-        return d, cols                                          # (cols: keeps the arrays the descriptor points to alive)
-
-    @staticmethod
-    def _stretch_outputs(n_steps, lead, w, p, chain, lnprob_chain, accepted):
         for a, shape in ((chain, (n_steps,) + lead + (w, p)), (lnprob_chain, (n_steps,) + lead + (w,))):
             if a is not None and (a.dtype != np.float64 or not a.flags.c_contiguous or a.shape != shape):
                 raise ValueError("stretch_move: chain buffers must be C-contiguous float64 of shape (steps, [B,] W, P) / (steps, [B,] W)")
         if accepted is not None and (accepted.dtype != np.int64 or accepted.shape != lead + (w,) or not accepted.flags.c_contiguous):
             raise ValueError("stretch_move: accepted must be a C-contiguous int64 array of shape ([B,] W)")
+        return ((self.handle, ctypes.byref(d), n_steps, _ptr(pos), _ptr(lnp)),
+                (_ptr(chain), _ptr(lnprob_chain), accepted.ctypes.data_as(_c_int64_p) if accepted is not None else None), cols)
 
     def stretch_move(self, plan, pos, lnp, order, zz, thr, pick, chain=None, lnprob_chain=None, accepted=None):
         """``mcd_stretch_move``: advance the ensemble by ``len(order)`` stretch-move steps with the half-step loop inside
@@ -422,49 +429,29 @@ class Catalog(object):
         Binned catalogues: ``pos`` (B, W, P), ``lnp`` (B, W), ``order`` (steps, B, W), ``zz`` / ``thr`` / ``pick``
         (steps, 2, B, W/2), ``chain`` (steps, B, W, P), ``lnprob_chain`` (steps, B, W), ``accepted`` (B, W): B independent
         ensembles in lockstep, one per radial bin, as ``analysis.binned.BinnedSampler`` draws them."""
-        self._alive()
-        binned = pos.ndim == 3
-        lead = pos.shape[:1] if binned else ()
-        n_bins = pos.shape[0] if binned else 1
-        n_steps, w = order.shape[0], order.shape[-1]
-        p = pos.shape[-1]
-        for a, dt in ((pos, np.float64), (lnp, np.float64), (zz, np.float64), (thr, np.float64), (order, np.int32), (pick, np.int32)):
+        head, tail, _keep = self._stretch_args("stretch_move", plan, pos, lnp, order.shape[0], chain, lnprob_chain, accepted)
+        for a, dt in ((zz, np.float64), (thr, np.float64), (order, np.int32), (pick, np.int32)):
             if a.dtype != dt or not a.flags.c_contiguous:
                 raise ValueError("stretch_move needs C-contiguous arrays of the documented dtypes")
-        half_shape = (n_steps, 2) + lead + (w // 2,)
-        if pos.shape != lead + (w, p) or lnp.shape != lead + (w,) or order.shape != (n_steps,) + lead + (w,) or \
-                zz.shape != half_shape or thr.shape != half_shape or pick.shape != half_shape:
+        half_shape = (order.shape[0], 2) + pos.shape[:-2] + (pos.shape[-2] // 2,)
+        if order.shape != order.shape[:1] + lnp.shape or zz.shape != half_shape or thr.shape != half_shape or \
+                pick.shape != half_shape:
             raise ValueError("stretch_move: inconsistent array shapes")
-        d, _keep = self._stretch_desc(plan, w, p, n_bins)
-        self._stretch_outputs(n_steps, lead, w, p, chain, lnprob_chain, accepted)
-        rc = self.lib.mcd_stretch_move(self.handle, ctypes.byref(d), n_steps, _ptr(pos), _ptr(lnp),
-                                       order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(zz), _ptr(thr),
-                                       pick.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(chain), _ptr(lnprob_chain),
-                                       accepted.ctypes.data_as(_c_int64_p) if accepted is not None else None)
+        rc = self.lib.mcd_stretch_move(*head, order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(zz), _ptr(thr),
+                                       pick.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), *tail)
         _check(self.lib, rc, "mcd_stretch_move")
-        self._walkers = w // 2
+        self._walkers = pos.shape[-2] // 2
 
     def stretch_move_seeded(self, plan, pos, lnp, seed, step0, n_steps, chain=None, lnprob_chain=None, accepted=None):
         """``mcd_stretch_move_seeded``: the same block with its random numbers generated inside the library from the
         counter-based generator of csrc/mcd_rng.h -- steps ``step0 .. step0 + n_steps - 1`` of the chain that ``seed`` names.
         ``chain_numbers(seed, step0, n_steps, ...)`` returns the numbers those steps use."""
-        self._alive()
-        binned = pos.ndim == 3
-        lead = pos.shape[:1] if binned else ()
-        n_bins = pos.shape[0] if binned else 1
-        w, p = pos.shape[-2], pos.shape[-1]
-        for a in (pos, lnp):
-            if a.dtype != np.float64 or not a.flags.c_contiguous:
-                raise ValueError("stretch_move_seeded needs C-contiguous float64 arrays")
-        if lnp.shape != lead + (w,) or n_steps < 0 or step0 < 0:
+        if n_steps < 0 or step0 < 0:
             raise ValueError("stretch_move_seeded: inconsistent array shapes")
-        d, _keep = self._stretch_desc(plan, w, p, n_bins)
-        self._stretch_outputs(n_steps, lead, w, p, chain, lnprob_chain, accepted)
-        rc = self.lib.mcd_stretch_move_seeded(self.handle, ctypes.byref(d), n_steps, _ptr(pos), _ptr(lnp),
-                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), _ptr(chain), _ptr(lnprob_chain),
-                                              accepted.ctypes.data_as(_c_int64_p) if accepted is not None else None)
+        head, tail, _keep = self._stretch_args("stretch_move_seeded", plan, pos, lnp, n_steps, chain, lnprob_chain, accepted)
+        rc = self.lib.mcd_stretch_move_seeded(*head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail)
         _check(self.lib, rc, "mcd_stretch_move_seeded")
-        self._walkers = w // 2
+        self._walkers = pos.shape[-2] // 2
 
     @property
     def last_prefetch(self):

@@ -13,20 +13,20 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .. import _native
+from ..sampler import _reserve, _run_blocks, _setup
 from .constant import ConstantFit
 
 logger = logging.getLogger(__name__)
 
 
 class BinnedSampler(object):
-    """B lock-stepped affine-invariant ensembles (same move as ``sampler.EnsembleSampler``), one per radial bin: the
-    reference runs one MCMC per bin (bin/run_tests.py:75-124); here the bins share every evaluation.
+    """B lock-stepped affine-invariant ensembles (same move as ``sampler.EnsembleSampler``, same driver: ``sampler._run_blocks``),
+    one per radial bin: the reference runs one MCMC per bin (bin/run_tests.py:75-124); here the bins share every evaluation.
 
     ``block_fn`` (what ``BinnedConstantFit`` passes for box priors): a callable that advances all ensembles by a whole block
     of steps from the random numbers drawn here -- ``mcd_stretch_move`` with ``n_bins = B`` runs the same half-step loop in
-    C++ (csrc/mcd_stretch.h), bit-identical to the Python loop below.  The Python loop costs ~7 ms of NumPy per step at
-    55 bins x 512 walkers against 0.17 ms of device time per step; the library's loop ~0.2 ms."""
+    C++ (csrc/mcd_stretch.h), bit-identical to the NumPy loop.  The NumPy loop costs ~7 ms per step at 55 bins x 512
+    walkers against 0.17 ms of device time per step; the library's loop ~0.2 ms."""
 
     N_STREAMS = 8          # part of the definition of the random stream (2: 334, 4: 313, 8: 297 us per step at 55 x 512)
 
@@ -36,47 +36,25 @@ class BinnedSampler(object):
         ``"host"``: NumPy's Mersenne twister on the host, as emcee draws (B x W numbers per step cross PCIe: the draws, not
         the device, bound the rate -- 3400 steps/s at 55 bins x 512 walkers against 6000 of device time).
 
-        ``"device"``: the counter-based generator of csrc/mcd_rng.h (Philox4x64-10): every number is a function of (seed,
-        step, half step, bin, walker) alone.  ``seeded_block_fn`` (``Runner._stretch_block_seeded``) runs whole blocks with
-        the numbers generated on the device (csrc/mcd_stretch.hip: chain_numbers_kernel); without it (expression priors) the NumPy loop below takes the SAME
-        numbers from ``_native.chain_numbers`` -- one chain whichever way it is run, and however it is cut into blocks."""
-        if nwalkers % 2 or nwalkers < 2 * ndim:
-            raise ValueError("need an even number of walkers, at least twice the dimension")
-        if rng not in ("host", "device"):
-            raise ValueError("rng must be 'host' or 'device'")
-        if rng == "device" and float(a) != 2.0:
-            raise ValueError("rng='device' implements the stretch move with a = 2 (emcee's default)")
-        self.rng = rng
-        self.seeded_block_fn = seeded_block_fn
-        self.n_bins, self.nwalkers, self.ndim = int(n_bins), int(nwalkers), int(ndim)
+        ``"device"``: the counter-based generator of csrc/mcd_rng.h: every number is a function of (seed, step, half step,
+        bin, walker) alone (``sampler._setup``).  ``seeded_block_fn`` (``Runner._stretch_block_seeded``) runs whole blocks
+        with the numbers generated on the device; without it (expression priors) the NumPy loop takes the SAME numbers
+        from ``_native.chain_numbers`` -- one chain whichever way it is run, and however it is cut into blocks."""
+        self.n_bins = int(n_bins)
+        _setup(self, (self.n_bins,), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn)
         self.log_prob_fn = log_prob_fn
-        self.block_fn = block_fn
         self.block_steps = 64                     # steps whose random numbers are drawn together (defines the stream)
-        self.a = float(a)
-        self._random = np.random.RandomState(seed)
-        # rng="device": the 64-bit name of the chain (no seed: from NumPy's global generator, which the reference seeds at
-        # analysis/runner.py:59 -- `np.random.seed` before the run makes it reproducible, as with emcee)
-        self.seed64 = None
-        if rng == "device":                       # (only then: drawing a seed moves NumPy's global generator)
-            self.seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else \
-                (int(np.random.randint(0, 2 ** 32)) << 32) | int(np.random.randint(0, 2 ** 32))
         self.device_block_steps = 256             # rng="device": steps per library call (NOT part of the stream's definition)
-        # the steps of a block are drawn by N_STREAMS generators seeded from the master (see run_mcmc: draw)
+        self._random = np.random.RandomState(seed)
+        # the steps of a block are drawn by N_STREAMS generators seeded from the master (see _draw)
         self._streams = [np.random.RandomState(int(s)) for s in self._random.randint(0, 2 ** 31 - 1, size=self.N_STREAMS)]
-        from concurrent.futures import ThreadPoolExecutor
-        self._pool = ThreadPoolExecutor(max_workers=self.N_STREAMS)
-        self._lookahead = ThreadPoolExecutor(max_workers=1)
-        self.iteration = 0
-        self._chain = np.empty((0, self.n_bins, self.nwalkers, self.ndim))
-        self._lnprob = np.empty((0, self.n_bins, self.nwalkers))
-        self._accepted = np.zeros((self.n_bins, self.nwalkers))
+        self._pool = None
 
     def close(self):
-        """Release the drawing threads (also done when the sampler is garbage-collected)."""
-        for pool in (getattr(self, "_pool", None), getattr(self, "_lookahead", None)):
-            if pool is not None:
-                pool.shutdown(wait=False)
-        self._pool = self._lookahead = None
+        """Release the drawing threads (also done when the sampler is garbage-collected; the next run starts them again)."""
+        pool, self._pool = getattr(self, "_pool", None), None
+        if pool is not None:
+            pool.shutdown(wait=False)
 
     def __del__(self):
         try:
@@ -100,124 +78,64 @@ class BinnedSampler(object):
     def reserve(self, total_steps):
         """Chain storage for ``total_steps`` steps in all (a run continued by further ``run_mcmc`` calls otherwise grows its
         storage geometrically and copies the rows it holds: 1.1 MB per step at 55 bins x 512 walkers)."""
-        B, W, P = self.n_bins, self.nwalkers, self.ndim
-        if int(total_steps) > self._chain.shape[0]:
-            chain, lnprob = np.empty((int(total_steps), B, W, P)), np.empty((int(total_steps), B, W))
-            chain[:self.iteration], lnprob[:self.iteration] = self._chain[:self.iteration], self._lnprob[:self.iteration]
-            self._chain, self._lnprob = chain, lnprob
+        _reserve(self, total_steps)
 
-    def run_mcmc(self, pos, nsteps, log_prob0=None):
-        pos = np.ascontiguousarray(pos, dtype=np.float64).copy()
-        B, W, P = self.n_bins, self.nwalkers, self.ndim
-        if pos.shape != (B, W, P):
-            raise ValueError("incompatible input dimensions {0}".format(pos.shape))
-        lnp = np.array(self.log_prob_fn(pos), dtype=np.float64) if log_prob0 is None else np.array(log_prob0, dtype=np.float64)
-        if np.any(np.isnan(lnp)):
-            raise ValueError("Probability function returned NaN")
-        nsteps = int(nsteps)
-        need = self.iteration + nsteps
-        if need > self._chain.shape[0]:
-            self.reserve(max(need, 2 * self._chain.shape[0]))
-        half = W // 2
-        rows = np.arange(B)[:, None]
-        am1, inv_a, dm1 = self.a - 1.0, 1.0 / self.a, P - 1.0
+    def _draw(self, n):
+        # B x W numbers per step make the draws the bottleneck (1.3 ms per step at 55 x 512 on one core, against 0.2 ms of
+        # device time): the block is cut into len(streams) slices of steps, every slice drawn from its own generator on its
+        # own thread (NumPy releases the interpreter lock).  Which numbers a step gets depends only on (seed, block_steps,
+        # the step's place in the block), never on thread timing.
+        B, W, half = self.n_bins, self.nwalkers, self.nwalkers // 2
+        am1, inv_a, dm1 = self.a - 1.0, 1.0 / self.a, self.ndim - 1.0
+        order, zz, thr, pick = out = (np.empty((n, B, W), dtype=np.int32), np.empty((n, 2, B, half)),
+                                      np.empty((n, 2, B, half)), np.empty((n, 2, B, half), dtype=np.int32))
 
-        def draw_slice(rnd, out, lo, hi):
-            # steps lo..hi of a block in a handful of vectorised draws (sampler.EnsembleSampler draws the same way): split
-            # of every ensemble = argsort of uniform keys, stretch factors z ~ g(z), log acceptance thresholds (accept iff
-            # thr < new_lnp - old_lnp), partner indices; written straight into the block's arrays
-            n = hi - lo
-            order, zz, thr, pick = out
-            order[lo:hi] = np.argsort(rnd.rand(n, B, W), axis=2)
-            u = rnd.rand(n, 4, B, half)
+        def draw_slice(rnd, lo, hi):
+            # steps lo..hi in a handful of vectorised draws (as sampler.EnsembleSampler draws): split of every ensemble =
+            # argsort of uniform keys, stretch factors z ~ g(z), log acceptance thresholds (accept iff thr < new_lnp -
+            # old_lnp), partner indices; written straight into the block's arrays
+            order[lo:hi] = np.argsort(rnd.rand(hi - lo, B, W), axis=2)
+            u = rnd.rand(hi - lo, 4, B, half)
             z = zz[lo:hi]
             np.multiply(u[:, :2], am1, out=z)
             z += 1.0
             z *= z
             z *= inv_a
             np.subtract(np.log(u[:, 2:]), dm1 * np.log(z), out=thr[lo:hi])
-            pick[lo:hi] = rnd.randint(half, size=(n, 2, B, half))
+            pick[lo:hi] = rnd.randint(half, size=(hi - lo, 2, B, half))
 
-        if self._pool is None:                               # (closed: the pools come back on the next run)
+        k = len(self._streams)
+        cuts = [n * i // k for i in range(k + 1)]
+        jobs = [(self._streams[i], cuts[i], cuts[i + 1]) for i in range(k) if cuts[i + 1] > cuts[i]]
+        if len(jobs) > 1:
+            list(self._pool.map(lambda job: draw_slice(*job), jobs))
+        else:
+            draw_slice(*jobs[0])
+        return out
+
+    def _log_prob(self, values):
+        lnp = np.asarray(self.log_prob_fn(values), dtype=np.float64)
+        self.n_calls += 1
+        if np.any(np.isnan(lnp)):
+            raise ValueError("Probability function returned NaN")
+        return lnp
+
+    def run_mcmc(self, pos, nsteps, log_prob0=None):
+        pos = np.ascontiguousarray(pos, dtype=np.float64).copy()
+        B, W, P = self.n_bins, self.nwalkers, self.ndim
+        if pos.shape != (B, W, P):
+            raise ValueError("incompatible input dimensions {0}".format(pos.shape))
+        # (C order: the NumPy loop updates pos and lnp through flat views of them)
+        lnp = np.array(self._log_prob(pos) if log_prob0 is None else log_prob0, dtype=np.float64, order="C")
+        if np.any(np.isnan(lnp)):
+            raise ValueError("Probability function returned NaN")
+        if self._pool is None:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=self.N_STREAMS)
-            self._lookahead = ThreadPoolExecutor(max_workers=1)
-
-        def draw(n):
-            # B x W numbers per step make the draws the bottleneck (1.3 ms per step at 55 x 512 on one core, against
-            # 0.2 ms of device time): the block is cut into len(streams) slices of steps, every slice drawn from its own
-            # generator on its own thread (NumPy releases the interpreter lock).  Which numbers a step gets depends only
-            # on (seed, block_steps, the step's place in the block), never on thread timing.
-            out = (np.empty((n, B, W), dtype=np.int32), np.empty((n, 2, B, half)), np.empty((n, 2, B, half)),
-                   np.empty((n, 2, B, half), dtype=np.int32))
-            k = len(self._streams)
-            cuts = [n * i // k for i in range(k + 1)]
-            jobs = [(self._streams[i], out, cuts[i], cuts[i + 1]) for i in range(k) if cuts[i + 1] > cuts[i]]
-            if len(jobs) > 1:
-                list(self._pool.map(lambda job: draw_slice(*job), jobs))
-            else:
-                draw_slice(*jobs[0])
-            return out
-
-        done = 0
         # (blocks of very many ensembles are kept below ~8 M walker-steps: 200 MB of numbers in, 340 MB of rows out)
-        chunk = max(1, min(int(self.block_steps), (1 << 23) // (B * W)))
-        device_rng = self.rng == "device"
-        if device_rng:
-            chunk = max(1, min(int(self.device_block_steps), (1 << 23) // (B * W)))
-            if self.seeded_block_fn is None:
-                from .. import _native as native
-
-                def draw(n):                                 # noqa: F811 -- the same numbers the device generates
-                    return native.chain_numbers(self.seed64, self.iteration, n, B, W, P)
-        pending = None
-        while done < nsteps:
-            n = min(chunk, nsteps - done)
-            if device_rng and self.seeded_block_fn is not None:
-                it = self.iteration
-                accepted = np.zeros((B, W), dtype=np.int64)
-                self.seeded_block_fn(pos, lnp, self.seed64, it, n, self._chain[it:it + n], self._lnprob[it:it + n], accepted)
-                self._accepted += accepted
-                self.iteration += n
-                done += n
-                continue
-            order_b, zz_b, thr_b, pick_b = pending.result() if pending is not None else draw(n)
-            pending = None
-            if self.block_fn is not None and done + n < nsteps and not device_rng:
-                # the next block's numbers are drawn while the library call of this block waits for the device
-                pending = self._lookahead.submit(draw, min(chunk, nsteps - done - n))
-            it = self.iteration
-            if self.block_fn is not None and not device_rng:
-                accepted = np.zeros((B, W), dtype=np.int64)
-                try:
-                    self.block_fn(pos, lnp, order_b, zz_b, thr_b, pick_b, self._chain[it:it + n], self._lnprob[it:it + n], accepted)
-                except BaseException:
-                    if pending is not None:
-                        pending.result()                   # (the generators have moved past the block that was never run)
-                    raise
-                self._accepted += accepted
-                self.iteration += n
-                done += n
-                continue
-            for i in range(n):
-                order = order_b[i]
-                for h, (first, second) in enumerate(((order[:, :half], order[:, half:]), (order[:, half:], order[:, :half]))):
-                    s = pos[rows, first]
-                    partners = pos[rows, np.take_along_axis(second, pick_b[i, h], axis=1)]
-                    proposal = partners - (partners - s) * zz_b[i, h][:, :, None]
-                    new_lnp = np.asarray(self.log_prob_fn(proposal), dtype=np.float64)
-                    if np.any(np.isnan(new_lnp)):
-                        raise ValueError("Probability function returned NaN")
-                    accept = thr_b[i, h] < new_lnp - lnp[rows, first]
-                    bb, jj = np.nonzero(accept)
-                    ww = first[bb, jj]
-                    pos[bb, ww] = proposal[bb, jj]
-                    lnp[bb, ww] = new_lnp[bb, jj]
-                    self._accepted[bb, ww] += 1
-                self._chain[self.iteration] = pos
-                self._lnprob[self.iteration] = lnp
-                self.iteration += 1
-            done += n
+        steps = self.device_block_steps if self.rng == "device" else self.block_steps
+        chunk = max(1, min(int(steps), (1 << 23) // (B * W)))
+        _run_blocks(self, pos, lnp, nsteps, chunk, chunk, self._draw, self._log_prob)
         return pos, lnp, self._random.get_state()
 
 

@@ -452,8 +452,8 @@ class Runner(object):
         self._stretch_cache = (plan, out)
         return out
 
-    def _stretch_block_seeded(self, pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted):
-        """One block of steps with the random numbers generated inside the library (``_native.Catalog.stretch_move_seeded``)."""
+    def _stretch_catalog(self, pos):
+        """The catalogue a library block runs on, after the checks both kinds of block share."""
         plan = self._plan()
         if not plan.simple:
             raise RuntimeError("the parameter configuration changed to one with expression priors / constraints during a run")
@@ -462,19 +462,17 @@ class Runner(object):
         cat = self._catalog
         if cat is None or plan.catalog_key != self._catalog_key:
             cat = self._ensure_catalog()
-        cat.stretch_move_seeded(self._stretch_plan(), pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted)
+        return cat
+
+    def _stretch_block_seeded(self, pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted):
+        """One block of steps with the random numbers generated inside the library (``_native.Catalog.stretch_move_seeded``)."""
+        self._stretch_catalog(pos).stretch_move_seeded(self._stretch_plan(), pos, lnp, seed, step0, n_steps, chain,
+                                                       lnprob_chain, accepted)
 
     def _stretch_block(self, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted):
         """One block of stretch-move steps inside the library (``_native.Catalog.stretch_move``)."""
-        plan = self._plan()
-        if not plan.simple:
-            raise RuntimeError("the parameter configuration changed to one with expression priors / constraints during a run")
-        if self._context is not None and getattr(self._context, "n_ranks", 1) > 1:
-            self._check_ranks_agree(pos)
-        cat = self._catalog
-        if cat is None or plan.catalog_key != self._catalog_key:
-            cat = self._ensure_catalog()
-        cat.stretch_move(self._stretch_plan(), pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted)
+        self._stretch_catalog(pos).stretch_move(self._stretch_plan(), pos, lnp, order, zz, thr, pick, chain, lnprob_chain,
+                                                accepted)
 
     def __call__(self, n_walkers=100, n_steps=500, n_burn=100, n_threads=1, n_out=None, pos=None, lnprob0=None,
                  plot=False, prefix="sampler", true_values=None, **kwargs):

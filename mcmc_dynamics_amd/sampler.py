@@ -15,6 +15,11 @@ expects ``(n,)`` back; otherwise the function is mapped over the rows (optionall
 of steps from the random numbers drawn here -- ``libmcd_hip.so``'s ``mcd_stretch_move`` runs the same half-step loop in
 C++ (csrc/mcd_stretch.h), bit-identical to the Python loop below, with a few microseconds of host time between two
 kernel launches instead of ~50.
+
+The stretch-move driver itself -- argument checks, chain storage, the block loop with its three ways of running a block
+and the NumPy half-step -- is written once below (``_setup`` / ``_reserve`` / ``_run_blocks``) for B lock-stepped
+ensembles; ``EnsembleSampler`` runs one ensemble without an ensemble axis, ``analysis.binned.BinnedSampler`` B of them.
+Each sampler keeps what defines its random stream: how a block's numbers are drawn and how a run is cut into blocks.
 """
 import numpy as np
 
@@ -34,51 +39,165 @@ def _draw_pool():
     return _DRAW_POOL or None
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The driver shared by EnsembleSampler and analysis.binned.BinnedSampler.  It works on the sampler's attributes: ``lead``
+# is the shape of the ensemble axis, () for one ensemble without one, (B,) for B ensembles; pos is lead + (W, P), lnp and
+# the acceptance counts lead + (W,), a block's numbers (steps,) + lead + (W,) (order) and (steps, 2) + lead + (W/2,).
+
+def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn):
+    """Checks and state common to both samplers.  ``rng="device"``: the move's random numbers come from the counter-based
+    generator of csrc/mcd_rng.h (Philox4x64-10) instead of NumPy's Mersenne twister -- a function of (seed, step, half
+    step, ensemble, walker) alone, generated on the device (csrc/mcd_stretch.hip: chain_numbers_kernel) by
+    ``seeded_block_fn`` (``Runner._stretch_block_seeded``), or taken from ``_native.chain_numbers`` by the NumPy loop when
+    there is none: the same chain either way, and however it is cut into blocks."""
+    if rng not in ("host", "device"):
+        raise ValueError("rng must be 'host' or 'device'")
+    if rng == "device" and float(a) != 2.0:
+        raise ValueError("rng='device' implements the stretch move with a = 2 (emcee's default)")
+    # rng="device": the 64-bit name of the chain (no seed: from NumPy's global generator, which the reference seeds at
+    # analysis/runner.py:59 -- `np.random.seed` before the run makes it reproducible, as with emcee).  Only then: drawing
+    # a seed moves NumPy's global generator.
+    s.seed64 = None
+    if rng == "device":
+        s.seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else \
+            (int(np.random.randint(0, 2 ** 32)) << 32) | int(np.random.randint(0, 2 ** 32))
+    if nwalkers < 2 * ndim:
+        raise ValueError("The number of walkers must be at least twice the dimension.")   # as emcee
+    if nwalkers % 2:
+        raise ValueError("The number of walkers must be even.")
+    s._lead, s.nwalkers, s.ndim, s.a = tuple(lead), int(nwalkers), int(ndim), float(a)
+    s.rng, s.block_fn, s.seeded_block_fn = rng, block_fn, seeded_block_fn
+    _clear(s)
+
+
+def _clear(s):
+    """No steps, no storage, no accepted moves, no posterior calls."""
+    s.iteration = 0
+    s._chain = np.empty((0,) + s._lead + (s.nwalkers, s.ndim))
+    s._lnprob = np.empty((0,) + s._lead + (s.nwalkers,))
+    s._accepted = np.zeros(s._lead + (s.nwalkers,))
+    s.n_calls = 0
+
+
+def _reserve(s, total_steps):
+    """Chain storage for ``total_steps`` steps in all; the rows already held are kept."""
+    total = int(total_steps)
+    if total > s._chain.shape[0]:
+        chain, lnprob = np.empty((total,) + s._chain.shape[1:]), np.empty((total,) + s._lnprob.shape[1:])
+        chain[:s.iteration], lnprob[:s.iteration] = s._chain[:s.iteration], s._lnprob[:s.iteration]
+        s._chain, s._lnprob = chain, lnprob
+
+
+def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
+    """Advance ``pos`` / ``lnp`` (C-contiguous, updated in place) by ``nsteps`` steps in blocks of ``first``, then ``chunk``
+    steps.  A block runs in one of three ways:
+
+    * ``rng="device"`` with ``seeded_block_fn``: inside the library, its numbers generated there;
+    * ``rng="host"`` with ``block_fn``: inside the library (csrc/mcd_stretch.h), from the numbers ``draw(n)`` returns.  The
+      numbers of the NEXT block are drawn by a helper thread while the library call of this one waits for the device
+      (both release the interpreter lock).  One drawing thread at a time, blocks drawn in order: the stream of random
+      numbers is the serial one.  (If the library call raises, the generators have already moved past the block that
+      was never run.)
+    * otherwise the NumPy half-step loop below, around ``evaluate`` (proposals lead + (W/2, P) -> lead + (W/2,); it
+      counts its calls in ``n_calls``), with the numbers of ``draw`` -- or, with ``rng="device"``, of ``_native.chain_numbers``: the ones the device generates.
+    """
+    nsteps = int(nsteps)
+    if store and s.iteration + nsteps > s._chain.shape[0]:    # geometric growth: amortised O(1) per stored step
+        _reserve(s, max(s.iteration + nsteps, 2 * s._chain.shape[0]))
+    device = s.rng == "device"
+    if device:
+        from . import _native
+
+        def draw(n):                                          # noqa: F811 -- the same numbers the device generates
+            return _native.chain_numbers(s.seed64, s.iteration, n, lnp.size // s.nwalkers, s.nwalkers, s.ndim,
+                                         squeeze=not s._lead)
+    library = s.seeded_block_fn if device else s.block_fn
+    lookahead = None
+    if library is not None and not device and nsteps > first:
+        from concurrent.futures import ThreadPoolExecutor
+        lookahead = ThreadPoolExecutor(max_workers=1)
+    pending, done = None, 0
+    try:
+        while done < nsteps:
+            n = min(first if done == 0 else chunk, nsteps - done)
+            it = s.iteration
+            rows = (s._chain[it:it + n], s._lnprob[it:it + n]) if store else (None, None)
+            if device and library is not None:
+                numbers = (s.seed64, it, n)
+            else:
+                numbers = pending.result() if pending is not None else draw(n)
+                pending = None
+                if lookahead is not None and done + n < nsteps:
+                    pending = lookahead.submit(draw, min(chunk, nsteps - done - n))
+            if library is None:
+                _half_steps(s, pos, lnp, numbers, evaluate, store)
+            else:
+                accepted = np.zeros(s._lead + (s.nwalkers,), dtype=np.int64)
+                library(pos, lnp, *numbers, *rows, accepted)
+                s._accepted += accepted
+                s.iteration += n
+                s.n_calls += 2 * n
+            done += n
+    finally:
+        if lookahead is not None:
+            lookahead.shutdown()                              # (waits for a pending draw: only when the library call raised)
+
+
+def _half_steps(s, pos, lnp, numbers, evaluate, store):
+    """The stretch move in NumPy, one block of steps: every half step proposes for one half of every ensemble against the
+    other half, in one ``evaluate`` call.  Walkers are addressed as rows of the flat (B * W, P) ensemble."""
+    order_b, zz_b, thr_b, pick_b = numbers
+    n, W, P = order_b.shape[0], s.nwalkers, s.ndim
+    B, half = lnp.size // W, W // 2
+    flat_pos, flat_lnp, flat_acc = pos.reshape(B * W, P), lnp.reshape(B * W), s._accepted.reshape(B * W)
+    if not (np.may_share_memory(flat_pos, pos) and np.may_share_memory(flat_lnp, lnp)):
+        raise ValueError("the NumPy loop updates pos and lnp in place: they must be C-contiguous")
+    order_b = order_b.reshape(n, B, W) + (W * np.arange(B))[:, None]                 # ensemble b's walkers: rows b * W + j
+    pick_b = pick_b.reshape(n, 2, B, half) + (half * np.arange(B))[:, None]          # partner of half-row b * half + j
+    zz_b, thr_b = zz_b.reshape(n, 2, B * half), thr_b.reshape(n, 2, B * half)
+    for i in range(n):
+        order = order_b[i]
+        halves = (order[:, :half].ravel(), order[:, half:].ravel())
+        for h in (0, 1):
+            first, second = halves[h], halves[1 - h]
+            s_pos = flat_pos[first]
+            partners = flat_pos[second[pick_b[i, h].ravel()]]
+            proposal = partners - (partners - s_pos) * zz_b[i, h][:, None]
+            new_lnp = np.reshape(evaluate(proposal.reshape(s._lead + (half, P))), B * half)
+            accept = thr_b[i, h] < new_lnp - flat_lnp[first]
+            idx = first[accept]
+            flat_pos[idx] = proposal[accept]
+            flat_lnp[idx] = new_lnp[accept]
+            flat_acc[idx] += 1
+        if store:
+            s._chain[s.iteration] = pos
+            s._lnprob[s.iteration] = lnp
+        s.iteration += 1
+
+
 class EnsembleSampler(object):
 
     def __init__(self, nwalkers, ndim, log_prob_fn, pool=None, a=2.0, vectorize=False, seed=None, block_fn=None, rng="host",
                  seeded_block_fn=None):
-        """``rng="device"``: the move's random numbers come from the counter-based generator of csrc/mcd_rng.h instead of
-        NumPy's Mersenne twister -- a function of (seed, step, half step, walker) alone, generated on the device (csrc/mcd_stretch.hip: chain_numbers_kernel) by
-        ``seeded_block_fn`` (``Runner._stretch_block_seeded``), or taken from ``_native.chain_numbers`` by the Python loop
-        below when there is none: the same chain either way, and however it is cut into blocks."""
-        if rng not in ("host", "device"):
-            raise ValueError("rng must be 'host' or 'device'")
-        if rng == "device" and float(a) != 2.0:
-            raise ValueError("rng='device' implements the stretch move with a = 2 (emcee's default)")
-        self.rng = rng
-        self.seeded_block_fn = seeded_block_fn
-        self.seed64 = None
-        if rng == "device":                       # (only then: drawing a seed moves NumPy's global generator)
-            self.seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else \
-                (int(np.random.randint(0, 2 ** 32)) << 32) | int(np.random.randint(0, 2 ** 32))
-        if nwalkers < 2 * ndim:
-            raise ValueError("The number of walkers must be at least twice the dimension.")   # as emcee
-        if nwalkers % 2:
-            raise ValueError("The number of walkers must be even.")
-        self.nwalkers, self.ndim = int(nwalkers), int(ndim)
+        """``rng``: ``"host"`` (NumPy's Mersenne twister, as emcee) or ``"device"`` (the counter-based generator of
+        csrc/mcd_rng.h, see ``_setup``)."""
+        _setup(self, (), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn)
         self.log_prob_fn = log_prob_fn
         self.pool = pool
-        self.a = float(a)
         self.vectorize = bool(vectorize)
-        self.block_fn = block_fn
         # steps whose random numbers are drawn together (and, with block_fn, run as one library call: the device then
         # idles only once per block while the results travel back and the next block goes up, ~0.1 ms).  Part of the
-        # definition of the random stream: samplers that should produce the same chain need the same value.
+        # definition of the random stream: samplers that should produce the same chain need the same value.  Also the
+        # block length of rng="device" runs (there NOT part of the stream's definition).
         self.block_steps = 256
         # ... except the FIRST block of a run with several blocks: its draws cannot overlap anything (nothing runs yet), so it
         # is kept short -- the device starts after 0.8 ms of draws instead of 3 ms (1e5 stars x 256 walkers: 3 of 39 us per
         # step over a 1024-step run).  Also part of the definition of the random stream.
         self.first_block_steps = 64
         self._random = np.random.RandomState(seed)
-        self.reset()
 
     def reset(self):
-        self.iteration = 0
-        self._chain = np.empty((0, self.nwalkers, self.ndim))
-        self._lnprob = np.empty((0, self.nwalkers))
-        self._accepted = np.zeros(self.nwalkers)
-        self.n_calls = 0
+        _clear(self)
 
     # ------------------------------------------------------------------ emcee-compatible views
     @property
@@ -112,9 +231,15 @@ class EnsembleSampler(object):
 
     # ------------------------------------------------------------------ posterior calls
     def compute_log_prob(self, coords):
-        coords = np.asarray(coords, dtype=np.float64)
-        if not np.isfinite(coords).all():
-            raise ValueError("At least one parameter value was infinite or NaN")
+        return self._log_prob(coords, checked=True)
+
+    def _log_prob(self, coords, checked):
+        """(n, P) -> (n,) with emcee's checks, one call in ``n_calls``.  ``checked``: convert and check the coordinates
+        first (the half steps of a vectorised run skip that: its proposals are finite float64 arrays already)."""
+        if checked:
+            coords = np.asarray(coords, dtype=np.float64)
+            if not np.isfinite(coords).all():
+                raise ValueError("At least one parameter value was infinite or NaN")
         if self.vectorize:
             lp = np.asarray(self.log_prob_fn(coords), dtype=np.float64)
         elif self.pool is not None:
@@ -129,6 +254,40 @@ class EnsembleSampler(object):
         return lp
 
     # ------------------------------------------------------------------ sampling
+    def _draw(self, block):
+        # Random numbers for a block of steps in a handful of vectorised draws (the per-step host cost is what limits the
+        # sampler once the posterior call takes ~0.1 ms): split of the ensemble = argsort of uniform keys, stretch factors
+        # z ~ g(z) and log acceptance thresholds, partner indices.  The generator is consumed in this order by ONE thread
+        # (the stream is the serial one); what follows the raw draws -- the row-wise argsort and the logarithms, 80 % of the
+        # time -- is a pure function of them and is spread over a few threads by rows (NumPy releases the interpreter lock
+        # there): at 1e5 stars a 256-step block of 256 walkers takes the device 9 ms and one host thread 8 ms to draw.
+        half = self.nwalkers // 2
+        inv_a, am1, dm1 = 1.0 / self.a, self.a - 1.0, self.ndim - 1.0
+        keys = self._random.rand(block, self.nwalkers)
+        u = self._random.rand(block, 4, half)
+        pick_b = self._random.randint(half, size=(block, 2, half)).astype(np.int32)
+        order_b = np.empty((block, self.nwalkers), dtype=np.int32)
+        zz_b = np.empty((block, 2, half))
+        thr_b = np.empty((block, 2, half))
+
+        def rows(lo, hi):
+            order_b[lo:hi] = np.argsort(keys[lo:hi], axis=1)
+            z = am1 * u[lo:hi, :2] + 1.0
+            z *= z
+            z *= inv_a
+            zz_b[lo:hi] = z
+            thr_b[lo:hi] = np.log(u[lo:hi, 2:]) - dm1 * np.log(z)      # accept iff thr < new_lnp - old_lnp
+
+        workers = _draw_pool()
+        if workers is None or block < 32:
+            rows(0, block)
+        else:
+            n_parts = 4
+            edges = [block * k // n_parts for k in range(n_parts + 1)]
+            for f in [workers.submit(rows, edges[k], edges[k + 1]) for k in range(n_parts)]:
+                f.result()
+        return order_b, zz_b, thr_b, pick_b
+
     def run_mcmc(self, initial_state, nsteps, log_prob0=None, rstate0=None, progress=False, store=True, **kwargs):
         """Advance the ensemble by ``nsteps``.  Returns ``(pos, log_prob, random_state)``."""
         pos = np.array(initial_state, dtype=np.float64)
@@ -136,143 +295,13 @@ class EnsembleSampler(object):
             raise ValueError("incompatible input dimensions {0}".format(pos.shape))
         if rstate0 is not None:
             self._random.set_state(rstate0)
-        lnp = self.compute_log_prob(pos) if log_prob0 is None else np.array(log_prob0, dtype=np.float64)
+        lnp = np.array(self.compute_log_prob(pos) if log_prob0 is None else log_prob0, dtype=np.float64)
         if np.shape(lnp) != (self.nwalkers,):
             raise ValueError("incompatible input dimensions for log_prob0")
-        if store:
-            need = self.iteration + int(nsteps)
-            if need > self._chain.shape[0]:               # geometric growth: amortised O(1) per stored step
-                cap = max(need, 2 * self._chain.shape[0])
-                chain = np.empty((cap, self.nwalkers, self.ndim))
-                lnprob = np.empty((cap, self.nwalkers))
-                chain[:self.iteration] = self._chain[:self.iteration]
-                lnprob[:self.iteration] = self._lnprob[:self.iteration]
-                self._chain, self._lnprob = chain, lnprob
-        half = self.nwalkers // 2
-        rnd = self._random
-        nsteps = int(nsteps)
-        fast_eval = self.vectorize                     # skip the generic wrapper's per-call conversions in the hot loop
-        inv_a, am1, dm1 = 1.0 / self.a, self.a - 1.0, self.ndim - 1.0
-        done = 0
-
-        def draw(block):
-            # Random numbers for a block of steps in a handful of vectorised draws (the per-step host cost is what limits
-            # the sampler once the posterior call takes ~0.1 ms): split of the ensemble = argsort of uniform keys,
-            # stretch factors z ~ g(z) and log acceptance thresholds, partner indices.  The generator is consumed in this
-            # order by ONE thread (the stream is the serial one); what follows the raw draws -- the row-wise argsort and the
-            # logarithms, 80 % of the time -- is a pure function of them and is spread over a few threads by rows (NumPy
-            # releases the interpreter lock there): at 1e5 stars a 256-step block of 256 walkers takes the device 9 ms and
-            # one host thread 8 ms to draw.
-            keys = rnd.rand(block, self.nwalkers)
-            u = rnd.rand(block, 4, half)
-            pick_b = rnd.randint(half, size=(block, 2, half))
-            order_b = np.empty((block, self.nwalkers), dtype=np.int64)
-            zz_b = np.empty((block, 2, half))
-            thr_b = np.empty((block, 2, half))
-
-            def rows(lo, hi):
-                order_b[lo:hi] = np.argsort(keys[lo:hi], axis=1)
-                z = am1 * u[lo:hi, :2] + 1.0
-                z *= z
-                z *= inv_a
-                zz_b[lo:hi] = z
-                thr_b[lo:hi] = np.log(u[lo:hi, 2:]) - dm1 * np.log(z)      # accept iff thr < new_lnp - old_lnp
-
-            workers = _draw_pool()
-            if workers is None or block < 32:
-                rows(0, block)
-            else:
-                n_parts = 4
-                edges = [block * k // n_parts for k in range(n_parts + 1)]
-                for f in [workers.submit(rows, edges[k], edges[k + 1]) for k in range(n_parts)]:
-                    f.result()
-            if self.block_fn is not None:
-                return (np.ascontiguousarray(order_b, dtype=np.int32), np.ascontiguousarray(zz_b), np.ascontiguousarray(thr_b),
-                        np.ascontiguousarray(pick_b, dtype=np.int32))
-            return order_b, zz_b, thr_b, pick_b
-
-        # With the loop inside the library the draws of the NEXT block (~2 ms per 64 steps of 256 walkers: a seventh of the
-        # block's device time) are made by a helper thread while the library call of the current block waits for the
-        # device -- both release the interpreter lock.  One generator, one drawing thread at a time, blocks drawn in order:
-        # the stream of random numbers is the serial one.  (If the library call raises, the generator has already moved
-        # past the block that was never run.)
-        pool = None
+        # (the same partition into blocks with and without block_fn: the two then consume the generator alike; rng="device"
+        # has no draws to hide: equal blocks)
         chunk = max(1, int(self.block_steps))
-        device_rng = self.rng == "device"
-        if device_rng and self.seeded_block_fn is None:
-            from . import _native as native
-
-            def draw(block):                                 # noqa: F811 -- the same numbers the device generates
-                order_b, zz_b, thr_b, pick_b = native.chain_numbers(self.seed64, self.iteration, block, 1, self.nwalkers,
-                                                                    self.ndim, squeeze=True)
-                return order_b.astype(np.int64), zz_b, thr_b, pick_b
-        if self.block_fn is not None and nsteps > chunk and not device_rng:
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=1)
-        pending = None
-        try:
-            # (the same partition into blocks with and without block_fn: the two then consume the generator alike)
-            first = max(1, min(chunk, int(self.first_block_steps))) if nsteps > chunk else chunk
-            if device_rng:
-                first = chunk                                 # (no draws to hide: equal blocks)
-            while done < nsteps:
-                block = min(first if done == 0 else chunk, nsteps - done)
-                if device_rng and self.seeded_block_fn is not None:
-                    it = self.iteration
-                    accepted = np.zeros(self.nwalkers, dtype=np.int64)
-                    self.seeded_block_fn(pos, lnp, self.seed64, it, block, self._chain[it:it + block] if store else None,
-                                         self._lnprob[it:it + block] if store else None, accepted)
-                    self._accepted += accepted
-                    self.iteration += block
-                    self.n_calls += 2 * block
-                    done += block
-                    continue
-                order_b, zz_b, thr_b, pick_b = pending.result() if pending is not None else draw(block)
-                pending = None
-                if pool is not None and done + block < nsteps:
-                    pending = pool.submit(draw, min(chunk, nsteps - done - block))
-                if self.block_fn is not None and not device_rng:
-                    # the same half-step loop, in the library (csrc/mcd_stretch.h): identical numbers, no Python between launches
-                    it = self.iteration
-                    accepted = np.zeros(self.nwalkers, dtype=np.int64)
-                    self.block_fn(pos, lnp, order_b, zz_b, thr_b, pick_b,
-                                  self._chain[it:it + block] if store else None, self._lnprob[it:it + block] if store else None,
-                                  accepted)
-                    self._accepted += accepted
-                    self.iteration += block
-                    self.n_calls += 2 * block
-                    done += block
-                    continue
-                for i in range(block):
-                    order = order_b[i]
-                    halves = (order[:half], order[half:])
-                    for h in (0, 1):
-                        first, second = halves[h], halves[1 - h]
-                        s = pos[first]
-                        partners = pos[second[pick_b[i, h]]]
-                        proposal = partners - (partners - s) * zz_b[i, h][:, None]
-                        if fast_eval:
-                            new_lnp = np.asarray(self.log_prob_fn(proposal), dtype=np.float64)
-                            self.n_calls += 1
-                            if new_lnp.shape != (half,):
-                                raise ValueError("log_prob_fn returned shape {0} for {1} positions".format(new_lnp.shape, half))
-                            if np.isnan(new_lnp).any():
-                                raise ValueError("Probability function returned NaN")
-                        else:
-                            new_lnp = self.compute_log_prob(proposal)
-                        accept = thr_b[i, h] < new_lnp - lnp[first]
-                        idx = first[accept]
-                        pos[idx] = proposal[accept]
-                        lnp[idx] = new_lnp[accept]
-                        self._accepted[idx] += 1
-                    if store:
-                        self._chain[self.iteration] = pos
-                        self._lnprob[self.iteration] = lnp
-                    self.iteration += 1
-                done += block
-        finally:
-            if pool is not None:
-                if pending is not None:
-                    pending.result()                       # (only when the library call raised)
-                pool.shutdown()
+        first = chunk if self.rng == "device" or int(nsteps) <= chunk else max(1, min(chunk, int(self.first_block_steps)))
+        _run_blocks(self, pos, lnp, nsteps, first, chunk, self._draw,
+                    lambda proposal: self._log_prob(proposal, checked=not self.vectorize), store=store)
         return pos, lnp, self._random.get_state()
