@@ -178,6 +178,18 @@ int mcd_membership(mcd_catalog* cat, int32_t k, const double* params, double* ou
 /* Per-star mixture log-likelihood for ONE parameter row, `lnlike(values, no_sum=True)` of
  * ModelFitConstantBackground (analysis/model.py:565-623); defined for every background model. */
 int mcd_loglike_per_star(mcd_catalog* cat, int32_t k, const double* params, double* out);
+/* Per-star summaries over S posterior samples (params: row-major [S][K], the kernel columns of mcd_loglike_batch).
+ * lppd[i]    = log( (1/S) sum_s exp(lnL_is) )      lnl_var[i] = sample variance (S-1) of lnL_is (0 when S == 1)
+ * pmem_mean[i], pmem_std[i]: mean and standard deviation (S-1; 0 when S == 1) of the membership probability
+ * lnL_is is the star's term of lnlike (the mixture for background models), so sum_i lppd_i == lnlike(row) when S == 1.
+ * Any output pointer may be NULL (not computed); pmem_* must be NULL for models without a background.
+ * Un-binned catalogues only; out arrays hold this process' n_stars; synchronous.  The pointwise terms of WAIC (Watanabe;
+ * Gelman, Hwang & Vehtari 2014) and the posterior mean of the membership probability of mcd_membership.  The samples
+ * reach the device in passes of at most 65536 rows (catalogue option "posterior_pass"); deterministic: no atomics, and
+ * the partial states of sample slices are merged in a fixed order.  With option "timing" on, mcd_last_kernel_ms gives
+ * the HIP-event time of the kernels (walker prep, slice and merge kernels of every pass, summed over the shards). */
+int mcd_pointwise_posterior(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params,
+                            double* lppd, double* lnl_var, double* pmem_mean, double* pmem_std);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

@@ -49,6 +49,8 @@ SYMBOLS = {
     "mcd_sync": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_membership": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "mcd_loglike_per_star": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "mcd_pointwise_posterior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p,
+                                               _c_double_p, _c_double_p, _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -391,6 +393,26 @@ class Catalog(object):
         p = _f64(params_row).reshape(-1)
         out = np.empty(self.n_stars, dtype=np.float64)
         _check(self.lib, self.lib.mcd_loglike_per_star(self.handle, p.size, _ptr(p), _ptr(out)), "mcd_loglike_per_star")
+        return out
+
+    def pointwise_posterior(self, table, membership=False):
+        """Per-star summaries over S posterior samples: ``table`` (S, K) in the kernel's column order -> dict of (n_stars,)
+        arrays ``lppd`` (log of the sample mean of exp(lnL_is)) and ``lnl_var`` (sample variance of lnL_is), and with
+        ``membership`` (background models only) ``pmem_mean`` / ``pmem_std`` of the membership probability."""
+        self._alive()
+        if self.n_sets > 1:
+            raise ValueError("pointwise_posterior is defined for un-binned catalogues only")
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (S, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        names = ("lppd", "lnl_var") + (("pmem_mean", "pmem_std") if membership else ())
+        out = {k: np.empty(self.n_stars, dtype=np.float64) for k in names}
+        ptrs = [_ptr(out[k]) if k in out else None for k in ("lppd", "lnl_var", "pmem_mean", "pmem_std")]
+        rc = self.lib.mcd_pointwise_posterior(self.handle, p.shape[0], self.k, _ptr(p), *ptrs)
+        _check(self.lib, rc, "mcd_pointwise_posterior")
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

@@ -241,6 +241,10 @@ class BinnedConstantFit(ConstantFit):
         sampler.run_mcmc(pos, n_steps)
         return sampler
 
+    def _pointwise_posterior(self, chain, n_burn, thin, membership):
+        raise NotImplementedError("BinnedConstantFit: per-star posterior summaries (pointwise_posterior, waic) are defined "
+                                  "for un-binned fits only; fit the bins' stars with ConstantFit to compare models")
+
     def compute_bestfit_values(self, chain, n_burn):
         """List of per-bin result tables (median / uperr / loerr), as the per-bin loop of
         bin/run_tests.py:105-113 collects them."""

@@ -108,6 +108,30 @@ class _BatchPlan(object):
         return t if self.kernel_fac is None else t * self.kernel_fac
 
 
+# Vehtari, Gelman & Gabry (2017): WAIC's estimate is unreliable when the posterior variance of a star's lnL exceeds 0.4
+WAIC_VAR_WARNING = 0.4
+
+
+def waic_summary(lppd, lnl_var, n_samples, group=None):
+    """WAIC from the per-star arrays of ``Runner.pointwise_posterior`` (Watanabe; Gelman, Hwang & Vehtari 2014):
+    elpd_i = lppd_i - Var_s(lnL_is), elpd_waic = sum_i elpd_i, p_waic = sum_i Var_s(lnL_is), waic = -2 elpd_waic,
+    se = sqrt(N Var_i(elpd_i)) (sample variance over the N stars).  ``group``: the host group of a multi-rank job, whose
+    ranks hold disjoint stars -- the totals (sums of lppd, p_waic, elpd, elpd^2, N and the warning count) are summed over
+    it, so every rank returns the same scalars; ``pointwise`` stays this rank's stars."""
+    lppd = np.asarray(lppd, dtype=np.float64)
+    var = np.asarray(lnl_var, dtype=np.float64)
+    elpd = lppd - var
+    totals = np.array([lppd.sum(), var.sum(), elpd.sum(), np.dot(elpd, elpd), float(elpd.size),
+                       float(np.count_nonzero(var > WAIC_VAR_WARNING))])
+    if group is not None:
+        totals = np.asarray(group.allreduce(totals), dtype=np.float64)
+    s_lppd, s_p, s_elpd, s_elpd2, n, n_warn = (float(t) for t in totals)
+    var_i = (s_elpd2 - s_elpd * s_elpd / n) / (n - 1.0) if n > 1 else 0.0
+    return {"elpd_waic": s_elpd, "p_waic": s_p, "waic": -2.0 * s_elpd, "se": float(np.sqrt(n * max(var_i, 0.0))),
+            "lppd": s_lppd, "n_samples": int(n_samples), "n_stars": int(n), "n_high_variance": int(n_warn),
+            "pointwise": elpd}
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -627,6 +651,60 @@ class Runner(object):
         flat = np.reshape(np.asarray(chain)[:, n_burn:], (-1, np.shape(chain)[-1]))
         indices = np.random.randint(0, flat.shape[0], (n_samples,))
         return [self.fetch_parameter_values(row) for row in flat[indices]]
+
+    # ------------------------------------------------------------------ per-star posterior summaries (new)
+    def _has_background(self):
+        model = self._catalog_spec()[0][0]
+        return model not in (_native.MODEL_CONST, _native.MODEL_PROFILE)
+
+    def _pointwise_posterior(self, chain, n_burn, thin, membership):
+        """mcd_pointwise_posterior over the post-burn-in samples of ``chain`` (W, steps, P), every ``thin``-th step, in the
+        order of ``convert_to_parameters``; fixed parameters, constraints and unit factors as in ``lnprob_batch``."""
+        chain = np.asarray(chain, dtype=np.float64)
+        if chain.ndim != 3 or chain.shape[2] != self.n_fitted_parameters:
+            raise ValueError("chain must have shape (n_walkers, n_steps, {0})".format(self.n_fitted_parameters))
+        if int(thin) < 1:
+            raise ValueError("thin must be >= 1")
+        flat = chain[:, n_burn::int(thin), :].reshape(-1, chain.shape[2])
+        if flat.shape[0] == 0:
+            raise ValueError("no samples left after n_burn = {0}".format(n_burn))
+        group = self._rank_group()
+        if group is not None and not group.same_everywhere(flat):
+            raise RuntimeError("the ranks of this job passed different chains: their stars' summaries would not belong to "
+                               "one posterior (every rank must pass the same chain)")
+        resolved = self.parameters.resolve_batch(flat)
+        cat = self._ensure_catalog()
+        out = cat.pointwise_posterior(self._kernel_table(resolved), membership=membership)
+        out["n_samples"] = flat.shape[0]
+        return out
+
+    def pointwise_posterior(self, chain, n_burn, thin=1):
+        """Per-star summaries over the S post-burn-in samples of ``chain`` (W, steps, P), computed on the device in one
+        call: ``lppd`` = log of the posterior mean of exp(lnL_i), ``lnl_var`` = posterior variance of lnL_i (lnL_i: the
+        star's term of ``lnlike``), and for the models with a background ``pmem_mean`` / ``pmem_std``, the posterior mean
+        and standard deviation of the membership probability; plus ``n_samples``.  Several ranks: this rank's stars."""
+        return self._pointwise_posterior(chain, n_burn, thin, self._has_background())
+
+    def waic(self, chain, n_burn, thin=1):
+        """Widely applicable information criterion of the model for the post-burn-in samples of ``chain``
+        (``waic_summary``): ``elpd_waic``, ``p_waic``, ``waic`` = -2 elpd_waic, ``se``, ``lppd``, ``n_samples``,
+        ``n_stars``, ``n_high_variance`` (stars whose posterior variance of lnL exceeds 0.4, logged) and ``pointwise``
+        (elpd_i of this rank's stars).  A lower ``waic`` is the better model for the same stars."""
+        pp = self._pointwise_posterior(chain, n_burn, thin, False)
+        out = waic_summary(pp["lppd"], pp["lnl_var"], pp["n_samples"], self._rank_group())
+        if out["n_high_variance"]:
+            logger.warning("WAIC: %d of %d stars have a posterior variance of lnL above %.1f; the estimate may be "
+                           "unreliable (Vehtari, Gelman & Gabry 2017)", out["n_high_variance"], out["n_stars"],
+                           WAIC_VAR_WARNING)
+        return out
+
+    def posterior_membership_probabilities(self, chain, n_burn, thin=1):
+        """(mean, std) per star of the membership probability over the post-burn-in samples of ``chain`` -- the posterior
+        average that ``calculate_membership_probabilities`` (the reference's value at the median parameters) leaves out."""
+        if not self._has_background():
+            raise ValueError("{0} has no background component: every star is a member".format(type(self).__name__))
+        pp = self._pointwise_posterior(chain, n_burn, thin, True)
+        return pp["pmem_mean"], pp["pmem_std"]
 
     # ------------------------------------------------------------------ device catalogue
     # Sub-classes set `_model_id` and the ordered (name, canonical unit) columns of the kernel's parameter

@@ -27,6 +27,7 @@
 #include "mcd_internal.h"
 #include "mcd_guard.h"
 #include "mcd_math.h"
+#include "mcd_posterior.h"
 #include "mcd_rng.h"
 #include "mcd_stretch.h"
 
@@ -237,6 +238,7 @@ struct mcd_catalog {
     int f32_domain = 1;                // option "f32_domain": 1 calls outside the float32 accuracy domain (mcd_guard.h) are refused
                                        // with MCD_ERR_INVALID, 0 they are evaluated anyway (mcd_last_f32_domain tells)
     mcd::F32Domain last_f32;           // verdict on the last staged parameter table (float32 catalogues)
+    int64_t posterior_pass = 65536;    // option "posterior_pass": samples per device pass of mcd_pointwise_posterior
     int combine = 1;                   // option "combine": balanced plans may use 8- / 16-wave workgroups that combine their
                                        // chunks' sums: 0 never, 1 the largest the plan allows, 8 / 16 at most that many waves
     // state of the last evaluation
@@ -1619,6 +1621,89 @@ int mcd_loglike_per_star(mcd_catalog* cat, int32_t k, const double* params, doub
 }
 
 namespace {
+// device scratch of mcd_pointwise_posterior (one shard), released on every exit path
+struct PosteriorScratch {
+    double *params = nullptr, *inv = nullptr, *part = nullptr, *state = nullptr, *out = nullptr;
+    void* wpar = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~PosteriorScratch() {
+        for (double* p : {params, inv, part, state, out})
+            if (p) (void)hipFree(p);
+        if (wpar) (void)hipFree(wpar);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double* const outs[4]) {
+    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: null catalogue or params");
+    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: n_samples must be >= 1");
+    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: parameter rows have the wrong number of columns");
+    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: defined for un-binned catalogues only");
+    const bool mem = outs[2] || outs[3];
+    if (mem && mcd::bg_kind(cat->model) == mcd::BG_NONE)
+        return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: membership outputs need a background model (pmem_* must be NULL)");
+    if (cat->n_stars == 0 || !(outs[0] || outs[1] || mem)) return MCD_OK;
+    const size_t term_bytes = cat->precision == MCD_F64 ? 8 : 4;
+    const int nf = mcd::post_fields(mem);
+    const int64_t pass_len = std::min<int64_t>(S, cat->posterior_pass);
+    const int64_t n_passes = (S + pass_len - 1) / pass_len;
+    double kernel_ms = 0.0;
+    for (Shard& sh : cat->shards) {
+        if (sh.n == 0) continue;
+        const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+        MCD_HIP(hipSetDevice(slot.device));
+        // scratch for the longest pass and for the plan with the most slices (the first pass or the shorter last one)
+        int64_t len_full = 0, len_last = 0;
+        const int64_t sl_full = mcd::posterior_slices(sh.n, pass_len, &len_full);
+        const int64_t sl_last = mcd::posterior_slices(sh.n, S - (n_passes - 1) * pass_len, &len_last);
+        const int64_t max_slices = std::max(sl_full, sl_last), max_len = std::max(len_full, len_last);
+        PosteriorScratch d;
+        MCD_HIP(hipMalloc(&d.params, (size_t)pass_len * k * sizeof(double)));
+        MCD_HIP(hipMalloc(&d.wpar, (size_t)pass_len * mcd::KD * term_bytes));
+        MCD_HIP(hipMalloc(&d.inv, (size_t)max_len * sizeof(double)));
+        MCD_HIP(hipMalloc(&d.part, (size_t)max_slices * nf * sh.n * sizeof(double)));
+        if (n_passes > 1) MCD_HIP(hipMalloc(&d.state, (size_t)nf * sh.n * sizeof(double)));
+        MCD_HIP(hipMalloc(&d.out, (size_t)4 * sh.n * sizeof(double)));
+        std::vector<double> inv((size_t)max_len);
+        for (int64_t j = 0; j < max_len; ++j) inv[j] = 1.0 / (double)(j + 1);
+        MCD_HIP(hipMemcpy(d.inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (cat->timing) {
+            MCD_HIP(hipEventCreate(&d.e0));
+            MCD_HIP(hipEventCreate(&d.e1));
+        }
+        const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+        for (int64_t p = 0; p < n_passes; ++p) {
+            const int64_t s0 = p * pass_len, ns = std::min(pass_len, S - s0);
+            int64_t slice_len = 0;
+            const int64_t n_slices = mcd::posterior_slices(sh.n, ns, &slice_len);
+            MCD_HIP(hipMemcpyAsync(d.params, params + s0 * k, (size_t)ns * k * sizeof(double), hipMemcpyHostToDevice,
+                                   slot.stream));
+            if (d.e0 && p == 0) MCD_HIP(hipEventRecord(d.e0, slot.stream));
+            MCD_HIP(mcd::launch_prepare_walkers(slot.stream, d.params, ns, k, cat->model, cat->free_centre, cat->precision,
+                                                d.wpar));
+            MCD_HIP(mcd::launch_posterior(slot.stream, shape, mem, sh.records, sh.n, d.wpar, ns, d.inv, slice_len, n_slices,
+                                          d.part, d.state, s0, S, d.out));
+            if (d.e1 && p == n_passes - 1) MCD_HIP(hipEventRecord(d.e1, slot.stream));
+        }
+        for (int f = 0; f < 4; ++f)
+            if (outs[f])
+                MCD_HIP(hipMemcpyAsync(outs[f] + sh.star_begin, d.out + f * sh.n, (size_t)sh.n * sizeof(double),
+                                       hipMemcpyDeviceToHost, slot.stream));
+        MCD_HIP(hipStreamSynchronize(slot.stream));
+        if (d.e0) {
+            float ms = 0.f;
+            MCD_HIP(hipEventElapsedTime(&ms, d.e0, d.e1));
+            kernel_ms += ms;
+        }
+    }
+    if (cat->timing) {
+        cat->last_kernel_ms = kernel_ms;
+        cat->timing_pending = false;
+    }
+    return MCD_OK;
+}
+
 // device scratch of mcd_kde_background, released on every exit path
 struct KdeScratch {
     double *comp = nullptr, *v = nullptr, *verr = nullptr, *dmin = nullptr, *sum = nullptr, *out = nullptr;
@@ -1631,6 +1716,14 @@ struct KdeScratch {
     }
 };
 }  // namespace
+
+int mcd_pointwise_posterior(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double* lppd,
+                            double* lnl_var, double* pmem_mean, double* pmem_std) {
+    try {
+    double* const outs[4] = {lppd, lnl_var, pmem_mean, pmem_std};
+    return pointwise_posterior(cat, n_samples, k, params, outs);
+    } catch (...) { return on_exception("mcd_pointwise_posterior"); }
+}
 
 int mcd_kde_background(mcd_ctx* ctx, int64_t n_comp, const double* comp, int64_t n, const double* v,
                        const double* verr, double sigma_int, double* out, double* kernel_ms) {
@@ -1832,6 +1925,11 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
     if (!std::strcmp(key, "fused_reduce")) { cat->fused_reduce = value != 0; return MCD_OK; }
     if (!std::strcmp(key, "defer_guard")) { cat->defer_guard = value != 0; return MCD_OK; }
     if (!std::strcmp(key, "f32_domain")) { cat->f32_domain = value != 0; return MCD_OK; }
+    if (!std::strcmp(key, "posterior_pass")) {
+        if (value < 1) return fail(MCD_ERR_INVALID, "posterior_pass must be >= 1");
+        cat->posterior_pass = value;
+        return MCD_OK;
+    }
     if (!std::strcmp(key, "two_lanes")) {
         int rc = sync_all(cat);
         if (rc != MCD_OK) return rc;
