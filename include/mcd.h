@@ -190,6 +190,22 @@ int mcd_loglike_per_star(mcd_catalog* cat, int32_t k, const double* params, doub
  * the HIP-event time of the kernels (walker prep, slice and merge kernels of every pass, summed over the shards). */
 int mcd_pointwise_posterior(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params,
                             double* lppd, double* lnl_var, double* pmem_mean, double* pmem_std);
+/* Pareto-smoothed importance-sampling leave-one-out cross-validation per star over S posterior samples (params:
+ * row-major [S][K], the kernel columns of mcd_loglike_batch), as psis() / loo() of the R package loo state it (Vehtari,
+ * Gelman & Gabry 2017): log ratios r_s = -lnL_is (lnL_is as in mcd_pointwise_posterior), a generalized Pareto fit to the
+ * M = min(ceil(0.2 S), ceil(3 sqrt(S / r_eff))) largest, smoothed and truncated weights.
+ * elpd_loo[i] = log sum_s w_s exp(lnL_is) / sum_s w_s     pareto_k[i] = the fitted shape k^ (+inf when M < 5 or the fit
+ * fails; -inf when the tail is constant -- loo says +inf there)     lppd[i] as mcd_pointwise_posterior computes it (to
+ * rounding)     n_eff[i] = r_eff / sum_s w~_s^2 (normalised weights).
+ * Any output pointer may be NULL.  r_eff > 0 (MCD_ERR_INVALID otherwise); M <= 2560 (S / r_eff up to ~7.3e5).
+ * Un-binned catalogues only; out arrays hold this process' n_stars; synchronous.  Device scratch (the sample table and a
+ * tile of [star][S] float64 terms) stays within catalogue option "loo_scratch_mb" (default 2048) and is released on
+ * every exit path; the samples reach the device in passes of "posterior_pass" rows.  Deterministic: no floating-point
+ * atomics, fixed reduction orders, and a star's result depends on its own terms only (not on tiles, shards or ranks).
+ * With option "timing" on, mcd_last_kernel_ms gives the HIP-event time of the kernels (sample prep, term and tail
+ * kernels of every tile, summed over the shards). */
+int mcd_psis_loo(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double r_eff,
+                 double* elpd_loo, double* pareto_k, double* lppd, double* n_eff);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

@@ -51,6 +51,8 @@ SYMBOLS = {
     "mcd_loglike_per_star": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_double_p, _c_double_p]),
     "mcd_pointwise_posterior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p,
                                                _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_psis_loo": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_double,
+                                    _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -413,6 +415,24 @@ class Catalog(object):
         ptrs = [_ptr(out[k]) if k in out else None for k in ("lppd", "lnl_var", "pmem_mean", "pmem_std")]
         rc = self.lib.mcd_pointwise_posterior(self.handle, p.shape[0], self.k, _ptr(p), *ptrs)
         _check(self.lib, rc, "mcd_pointwise_posterior")
+        return out
+
+    def psis_loo(self, table, r_eff=1.0):
+        """PSIS-LOO per star over S posterior samples: ``table`` (S, K) in the kernel's column order -> dict of (n_stars,)
+        arrays ``elpd_loo``, ``pareto_k`` (the fitted shape k^), ``lppd`` and ``n_eff`` (include/mcd.h: mcd_psis_loo)."""
+        self._alive()
+        if self.n_sets > 1:
+            raise ValueError("psis_loo is defined for un-binned catalogues only")
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (S, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        names = ("elpd_loo", "pareto_k", "lppd", "n_eff")
+        out = {k: np.empty(self.n_stars, dtype=np.float64) for k in names}
+        rc = self.lib.mcd_psis_loo(self.handle, p.shape[0], self.k, _ptr(p), float(r_eff), *[_ptr(out[k]) for k in names])
+        _check(self.lib, rc, "mcd_psis_loo")
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

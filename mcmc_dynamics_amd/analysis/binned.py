@@ -245,6 +245,10 @@ class BinnedConstantFit(ConstantFit):
         raise NotImplementedError("BinnedConstantFit: per-star posterior summaries (pointwise_posterior, waic) are defined "
                                   "for un-binned fits only; fit the bins' stars with ConstantFit to compare models")
 
+    def loo(self, chain, n_burn, thin=1, r_eff=1.0):
+        raise NotImplementedError("BinnedConstantFit: PSIS-LOO is defined for un-binned fits only; fit the bins' stars "
+                                  "with ConstantFit to compare models")
+
     def compute_bestfit_values(self, chain, n_burn):
         """List of per-bin result tables (median / uperr / loerr), as the per-bin loop of
         bin/run_tests.py:105-113 collects them."""

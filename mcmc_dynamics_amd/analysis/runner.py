@@ -132,6 +132,48 @@ def waic_summary(lppd, lnl_var, n_samples, group=None):
             "pointwise": elpd}
 
 
+def loo_k_threshold(n_samples):
+    """The Pareto k^ above which a star's PSIS-LOO estimate is unreliable: min(1 - 1/log10(S), 0.7) (Vehtari et al. 2024)."""
+    return min(1.0 - 1.0 / np.log10(float(n_samples)), 0.7) if n_samples > 1 else -np.inf
+
+
+def loo_summary(elpd_loo, lppd, pareto_k, n_samples, group=None):
+    """PSIS-LOO totals from the per-star arrays of ``Catalog.psis_loo``: elpd_loo = sum_i elpd_loo_i, p_loo = sum_i (lppd_i -
+    elpd_loo_i), looic = -2 elpd_loo, se = sqrt(N Var_i(elpd_loo_i)), and the count of stars whose k^ exceeds
+    ``loo_k_threshold(S)`` (k^ = +inf, a tail too short to fit, counts).  ``group``: the host group of a multi-rank job
+    (ranks hold disjoint stars) -- the totals are summed over it, so every rank returns the same scalars; ``pointwise``
+    and ``pareto_k`` stay this rank's stars."""
+    elpd = np.asarray(elpd_loo, dtype=np.float64)
+    lppd = np.asarray(lppd, dtype=np.float64)
+    k = np.asarray(pareto_k, dtype=np.float64)
+    thr = loo_k_threshold(n_samples)
+    totals = np.array([lppd.sum(), elpd.sum(), np.dot(elpd, elpd), float(elpd.size), float(np.count_nonzero(k > thr))])
+    if group is not None:
+        totals = np.asarray(group.allreduce(totals), dtype=np.float64)
+    s_lppd, s_elpd, s_elpd2, n, n_bad = (float(t) for t in totals)
+    var_i = (s_elpd2 - s_elpd * s_elpd / n) / (n - 1.0) if n > 1 else 0.0
+    return {"elpd_loo": s_elpd, "p_loo": s_lppd - s_elpd, "looic": -2.0 * s_elpd,
+            "se": float(np.sqrt(n * max(var_i, 0.0))), "lppd": s_lppd, "n_samples": int(n_samples), "n_stars": int(n),
+            "k_threshold": float(thr), "n_bad_k": int(n_bad), "pareto_k": k, "pointwise": elpd}
+
+
+def elpd_compare(a, b, group=None):
+    """Difference of two models' expected log predictive densities on the same stars: ``a``, ``b`` are ``waic()`` or
+    ``loo()`` results.  elpd_diff = sum_i (a_i - b_i) (positive: ``a`` predicts better), se_diff = sqrt(N Var_i(a_i - b_i)),
+    the paired standard error (not the difference or the quadrature sum of the two ``se``).  ``group``: as in
+    ``loo_summary`` (each rank passes its own stars' results)."""
+    pa, pb = np.asarray(a["pointwise"], dtype=np.float64), np.asarray(b["pointwise"], dtype=np.float64)
+    if pa.shape != pb.shape:
+        raise ValueError("the two results hold different stars ({0} and {1} pointwise values)".format(pa.size, pb.size))
+    d = pa - pb
+    totals = np.array([d.sum(), np.dot(d, d), float(d.size)])
+    if group is not None:
+        totals = np.asarray(group.allreduce(totals), dtype=np.float64)
+    s_d, s_d2, n = (float(t) for t in totals)
+    var_i = (s_d2 - s_d * s_d / n) / (n - 1.0) if n > 1 else 0.0
+    return {"elpd_diff": s_d, "se_diff": float(np.sqrt(n * max(var_i, 0.0))), "n_stars": int(n), "pointwise": d}
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -660,6 +702,13 @@ class Runner(object):
     def _pointwise_posterior(self, chain, n_burn, thin, membership):
         """mcd_pointwise_posterior over the post-burn-in samples of ``chain`` (W, steps, P), every ``thin``-th step, in the
         order of ``convert_to_parameters``; fixed parameters, constraints and unit factors as in ``lnprob_batch``."""
+        table, n_samples = self._posterior_table(chain, n_burn, thin)
+        out = self._ensure_catalog().pointwise_posterior(table, membership=membership)
+        out["n_samples"] = n_samples
+        return out
+
+    def _posterior_table(self, chain, n_burn, thin):
+        """The kernel table (S, K) of the post-burn-in samples of ``chain`` and S; refuses ranks with different chains."""
         chain = np.asarray(chain, dtype=np.float64)
         if chain.ndim != 3 or chain.shape[2] != self.n_fitted_parameters:
             raise ValueError("chain must have shape (n_walkers, n_steps, {0})".format(self.n_fitted_parameters))
@@ -673,10 +722,8 @@ class Runner(object):
             raise RuntimeError("the ranks of this job passed different chains: their stars' summaries would not belong to "
                                "one posterior (every rank must pass the same chain)")
         resolved = self.parameters.resolve_batch(flat)
-        cat = self._ensure_catalog()
-        out = cat.pointwise_posterior(self._kernel_table(resolved), membership=membership)
-        out["n_samples"] = flat.shape[0]
-        return out
+        self._ensure_catalog()
+        return self._kernel_table(resolved), flat.shape[0]
 
     def pointwise_posterior(self, chain, n_burn, thin=1):
         """Per-star summaries over the S post-burn-in samples of ``chain`` (W, steps, P), computed on the device in one
@@ -696,6 +743,22 @@ class Runner(object):
             logger.warning("WAIC: %d of %d stars have a posterior variance of lnL above %.1f; the estimate may be "
                            "unreliable (Vehtari, Gelman & Gabry 2017)", out["n_high_variance"], out["n_stars"],
                            WAIC_VAR_WARNING)
+        return out
+
+    def loo(self, chain, n_burn, thin=1, r_eff=1.0):
+        """Pareto-smoothed importance-sampling leave-one-out cross-validation (PSIS-LOO; Vehtari, Gelman & Gabry 2017) of
+        the model for the post-burn-in samples of ``chain``, computed on the device (``loo_summary``): ``elpd_loo``,
+        ``p_loo``, ``looic`` = -2 elpd_loo, ``se``, ``lppd``, ``n_samples``, ``n_stars``, ``k_threshold``, ``n_bad_k``
+        (stars whose Pareto k^ exceeds the threshold, logged), and this rank's per-star ``pareto_k``, ``pointwise``
+        (elpd_loo_i) and ``n_eff``.  ``r_eff``: the relative efficiency of the samples (a scalar; 1 for independent
+        draws).  A higher ``elpd_loo`` is the better model for the same stars; compare two with ``elpd_compare``."""
+        table, n_samples = self._posterior_table(chain, n_burn, thin)
+        res = self._ensure_catalog().psis_loo(table, r_eff=r_eff)
+        out = loo_summary(res["elpd_loo"], res["lppd"], res["pareto_k"], n_samples, self._rank_group())
+        out["n_eff"] = res["n_eff"]
+        if out["n_bad_k"]:
+            logger.warning("PSIS-LOO: %d of %d stars have a Pareto k above %.2f; their leave-one-out estimates are "
+                           "unreliable (see pareto_k)", out["n_bad_k"], out["n_stars"], out["k_threshold"])
         return out
 
     def posterior_membership_probabilities(self, chain, n_burn, thin=1):

@@ -28,6 +28,7 @@
 #include "mcd_guard.h"
 #include "mcd_math.h"
 #include "mcd_posterior.h"
+#include "mcd_psis.h"
 #include "mcd_rng.h"
 #include "mcd_stretch.h"
 
@@ -239,6 +240,7 @@ struct mcd_catalog {
                                        // with MCD_ERR_INVALID, 0 they are evaluated anyway (mcd_last_f32_domain tells)
     mcd::F32Domain last_f32;           // verdict on the last staged parameter table (float32 catalogues)
     int64_t posterior_pass = 65536;    // option "posterior_pass": samples per device pass of mcd_pointwise_posterior
+    int64_t loo_scratch_mb = 2048;    // option "loo_scratch_mb": device scratch of mcd_psis_loo (sample table + term tile)
     int combine = 1;                   // option "combine": balanced plans may use 8- / 16-wave workgroups that combine their
                                        // chunks' sums: 0 never, 1 the largest the plan allows, 8 / 16 at most that many waves
     // state of the last evaluation
@@ -1704,6 +1706,90 @@ int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* pa
     return MCD_OK;
 }
 
+// device scratch of mcd_psis_loo (one shard), released on every exit path
+struct PsisScratch {
+    double *params = nullptr, *terms = nullptr, *out = nullptr;
+    void* wpar = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~PsisScratch() {
+        for (double* p : {params, terms, out})
+            if (p) (void)hipFree(p);
+        if (wpar) (void)hipFree(wpar);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// Per shard: the S derived sample rows once (uploaded in passes of posterior_pass rows), then tiles of stars whose
+// [star][S] terms fit the scratch budget with them: the term kernel fills the tile, the tail kernel reduces it.
+int psis_loo(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double r_eff, double* const outs[4]) {
+    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_psis_loo: null catalogue or params");
+    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_psis_loo: n_samples must be >= 1");
+    if (S > INT32_MAX) return fail(MCD_ERR_INVALID, "mcd_psis_loo: n_samples must be < 2^31");
+    if (!(r_eff > 0.0) || !std::isfinite(r_eff)) return fail(MCD_ERR_INVALID, "mcd_psis_loo: r_eff must be > 0 and finite");
+    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_psis_loo: parameter rows have the wrong number of columns");
+    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_psis_loo: defined for un-binned catalogues only");
+    const int64_t M = mcd::psis_tail_len(S, r_eff);
+    if (M > mcd::kPsisMaxTail)
+        return fail(MCD_ERR_INVALID, "mcd_psis_loo: the Pareto tail of " + std::to_string(M) + " samples exceeds " +
+                                         std::to_string(mcd::kPsisMaxTail) + " (S / r_eff too large)");
+    if (cat->n_stars == 0 || !(outs[0] || outs[1] || outs[2] || outs[3])) return MCD_OK;
+    const size_t term_bytes = cat->precision == MCD_F64 ? 8 : 4;
+    const size_t rec_bytes = term_bytes * (size_t)mcd::record_doubles(cat->model, cat->free_centre);
+    const int64_t pass_len = std::min<int64_t>(S, cat->posterior_pass);
+    const int64_t fixed = (int64_t)((size_t)pass_len * k * sizeof(double) + (size_t)S * mcd::KD * term_bytes);
+    const int64_t budget = cat->loo_scratch_mb * (int64_t)1048576;
+    double kernel_ms = 0.0;
+    for (Shard& sh : cat->shards) {
+        if (sh.n == 0) continue;
+        const int64_t tile = mcd::psis_tile_stars(sh.n, S, fixed, budget);
+        if (tile < 1)
+            return fail(MCD_ERR_INVALID, "mcd_psis_loo: option loo_scratch_mb = " + std::to_string(cat->loo_scratch_mb) +
+                                             " cannot hold the sample table and one star's " + std::to_string(S) + " terms");
+        const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+        MCD_HIP(hipSetDevice(slot.device));
+        PsisScratch d;
+        MCD_HIP(hipMalloc(&d.params, (size_t)pass_len * k * sizeof(double)));
+        MCD_HIP(hipMalloc(&d.wpar, (size_t)S * mcd::KD * term_bytes));
+        MCD_HIP(hipMalloc(&d.terms, (size_t)tile * S * sizeof(double)));
+        MCD_HIP(hipMalloc(&d.out, (size_t)4 * sh.n * sizeof(double)));
+        if (cat->timing) {
+            MCD_HIP(hipEventCreate(&d.e0));
+            MCD_HIP(hipEventCreate(&d.e1));
+        }
+        for (int64_t s0 = 0; s0 < S; s0 += pass_len) {
+            const int64_t ns = std::min(pass_len, S - s0);
+            MCD_HIP(hipMemcpyAsync(d.params, params + s0 * k, (size_t)ns * k * sizeof(double), hipMemcpyHostToDevice,
+                                   slot.stream));
+            if (d.e0 && s0 == 0) MCD_HIP(hipEventRecord(d.e0, slot.stream));
+            MCD_HIP(mcd::launch_prepare_walkers(slot.stream, d.params, ns, k, cat->model, cat->free_centre, cat->precision,
+                                                (char*)d.wpar + (size_t)s0 * mcd::KD * term_bytes));
+        }
+        const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+        for (int64_t t0 = 0; t0 < sh.n; t0 += tile) {
+            const int64_t nt = std::min(tile, sh.n - t0);
+            MCD_HIP(mcd::launch_psis(slot.stream, shape, (const char*)sh.records + (size_t)t0 * rec_bytes, nt, d.wpar, S, M,
+                                     r_eff, d.terms, d.out + t0, sh.n));
+        }
+        if (d.e1) MCD_HIP(hipEventRecord(d.e1, slot.stream));
+        for (int f = 0; f < 4; ++f)
+            if (outs[f])
+                MCD_HIP(hipMemcpyAsync(outs[f] + sh.star_begin, d.out + f * sh.n, (size_t)sh.n * sizeof(double),
+                                       hipMemcpyDeviceToHost, slot.stream));
+        MCD_HIP(hipStreamSynchronize(slot.stream));
+        if (d.e0) {
+            float ms = 0.f;
+            MCD_HIP(hipEventElapsedTime(&ms, d.e0, d.e1));
+            kernel_ms += ms;
+        }
+    }
+    if (cat->timing) {
+        cat->last_kernel_ms = kernel_ms;
+        cat->timing_pending = false;
+    }
+    return MCD_OK;
+}
+
 // device scratch of mcd_kde_background, released on every exit path
 struct KdeScratch {
     double *comp = nullptr, *v = nullptr, *verr = nullptr, *dmin = nullptr, *sum = nullptr, *out = nullptr;
@@ -1723,6 +1809,14 @@ int mcd_pointwise_posterior(mcd_catalog* cat, int64_t n_samples, int32_t k, cons
     double* const outs[4] = {lppd, lnl_var, pmem_mean, pmem_std};
     return pointwise_posterior(cat, n_samples, k, params, outs);
     } catch (...) { return on_exception("mcd_pointwise_posterior"); }
+}
+
+int mcd_psis_loo(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double r_eff, double* elpd_loo,
+                 double* pareto_k, double* lppd, double* n_eff) {
+    try {
+    double* const outs[4] = {elpd_loo, pareto_k, lppd, n_eff};
+    return psis_loo(cat, n_samples, k, params, r_eff, outs);
+    } catch (...) { return on_exception("mcd_psis_loo"); }
 }
 
 int mcd_kde_background(mcd_ctx* ctx, int64_t n_comp, const double* comp, int64_t n, const double* v,
@@ -1925,6 +2019,11 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
     if (!std::strcmp(key, "fused_reduce")) { cat->fused_reduce = value != 0; return MCD_OK; }
     if (!std::strcmp(key, "defer_guard")) { cat->defer_guard = value != 0; return MCD_OK; }
     if (!std::strcmp(key, "f32_domain")) { cat->f32_domain = value != 0; return MCD_OK; }
+    if (!std::strcmp(key, "loo_scratch_mb")) {
+        if (value < 1) return fail(MCD_ERR_INVALID, "loo_scratch_mb must be >= 1");
+        cat->loo_scratch_mb = value;
+        return MCD_OK;
+    }
     if (!std::strcmp(key, "posterior_pass")) {
         if (value < 1) return fail(MCD_ERR_INVALID, "posterior_pass must be >= 1");
         cat->posterior_pass = value;
