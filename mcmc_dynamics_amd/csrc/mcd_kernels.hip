@@ -130,12 +130,17 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
     // fast mixtures: the 2^(j/1024) table of exp_tab lives in LDS (8 KiB per workgroup), four entries copied per thread
     constexpr bool kUsesExpTab = FAST && bg_kind(MODEL) != BG_NONE && sizeof(T) == 8;
     __shared__ double exptab_lds[kUsesExpTab ? kExpTabSize : 1];
+    // the kernels with the narrow-range BGFIXED variant keep the exponent-biased table (mcd_math.h: exp_tab_scaled)
+    constexpr bool kTabBiased = kUsesExpTab && FAST == 2 && MODEL == MODEL_BGFIXED;
     __shared__ double combine_lds[kCombine ? WAVES : 1][kCombine ? kWave : 1];
     if constexpr (kUsesExpTab) {
         static_assert(kExpTabSize % kThreads == 0, "whole table entries per thread");
         const double* __restrict__ src = exp_table_is_sqrt2_scaled(MODEL) ? kExpTabSqrt2Device : kExpTabDevice;
 #pragma unroll
-        for (int i = 0; i < kExpTabSize / kThreads; ++i) exptab_lds[i * kThreads + threadIdx.x] = src[i * kThreads + threadIdx.x];
+        for (int i = 0; i < kExpTabSize / kThreads; ++i) {
+            const int j = i * kThreads + threadIdx.x;
+            exptab_lds[j] = kTabBiased ? exp_tab_bias(src[j], j) : src[j];
+        }
         __syncthreads();
     }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -196,8 +201,8 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             // general fast form; the flag is wave-uniform (one scalar byte load), so this is a scalar branch
             // (the narrow-range profile variant without background has no per-star conditions: no flags, one form)
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
-            if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
-            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
+            if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
+            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }

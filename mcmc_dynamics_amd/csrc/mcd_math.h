@@ -515,8 +515,55 @@ MCD_HD double rsqrt2_newton(double m) {
 // copies it there; the per-lane lookup is a ds_read_b64, off the VALU), a static array on the host.
 // k comes out of the low word of u * (N / ln 2) + 1.5 * 2^52 (round-to-nearest-even), so no v_rndne / v_cvt.
 // Requires |u| < 1.4e6 (k inside int32; callers clamp or are bounded by the host guard, mcd_guard.h).
-template <bool TWO_STEP = true>
+// x with the integer v added to the high word of its bit pattern (v << 20 scales a normal x by 2^v; one v_add_u32)
+MCD_HD double add_hi_word(double x, int32_t v) {
+    uint32_t w[2];                                    // little-endian: w[1] is the high word (sign, exponent, top of mantissa)
+    std::memcpy(w, &x, sizeof w);
+    w[1] += (uint32_t)v;                              // a 32-bit add: a 64-bit one would be a v_lshl_add_u64
+    std::memcpy(&x, w, sizeof x);
+    return x;
+}
+
+// Exponent-biased table (the narrow-range BGFIXED kernels, mcd_kernels.hip): entry j holds T[j] with j << (20 - B)
+// subtracted from the high word of its bit pattern (B = kExpTabBits; j << (20 - B) < 2^20, so the entry stays a
+// positive normal number).  Since k = 2^B e + j, adding k << (20 - B) to the entry's high word gives back T[j] with e
+// added to its exponent field: the table address (k & (N - 1)) * 8 and that ONE v_lshl_add_u32 replace k >> B and
+// v_ldexp_f64 (exp_tab_scaled).  The general form reads the same table and restores T[j] exactly (exp_tab<.., true>).
+constexpr int kExpTabHiShift = 20 - kExpTabBits;
+MCD_HD double exp_tab_bias(double t, int j) { return add_hi_word(t, -(j << kExpTabHiShift)); }
+
+// k of exp_tab and its reduced argument: k comes out of the low word of u * (N / ln 2) + 1.5 * 2^52 (round-to-nearest-even)
+template <bool TWO_STEP>
+MCD_HD double exp_tab_reduce(double u, int& k) {
+    constexpr double kMagic = 6755399441055744.0;            // 1.5 * 2^52
+    const double shifted = fma_(u, kExpTabInvStep, kMagic);
+    const double kf = shifted - kMagic;
+    uint64_t bits;
+    std::memcpy(&bits, &shifted, sizeof bits);
+    k = (int)(uint32_t)bits;
+    if constexpr (TWO_STEP) {
+        const double r = fma_(-kf, kExpTabStepHi, u);
+        return fma_(-kf, kExpTabStepLo, r);
+    } else {
+        return fma_(-kf, kExpTabStepHi + kExpTabStepLo, u);
+    }
+}
+
+template <bool TWO_STEP = true, bool BIASED = false>
 MCD_HD double exp_tab(double u, int& e_out, const double* __restrict__ tab) {
+    if constexpr (BIASED) {
+        // general form on the exponent-biased table: T[j] restored exactly (one integer instruction), then as below
+        int k;
+        const double r = exp_tab_reduce<TWO_STEP>(u, k);
+        double p;
+        if constexpr (kExpPolyDegree == 4) p = fma_(fma_(r, kExpPolyC4, kExpPolyC3), r, kExpPolyC2);
+        else p = fma_(r, kExpPolyC3, kExpPolyC2);
+        p = fma_(p, r, 1.0);
+        p = fma_(p, r, 1.0);
+        e_out = k >> kExpTabBits;
+        const int j = k & (kExpTabSize - 1);
+        return add_hi_word(tab[j], j << kExpTabHiShift) * p;
+    }
     constexpr double kMagic = 6755399441055744.0;            // 1.5 * 2^52
     const double shifted = fma_(u, kExpTabInvStep, kMagic);
     const double kf = shifted - kMagic;
@@ -539,6 +586,27 @@ MCD_HD double exp_tab(double u, int& e_out, const double* __restrict__ tab) {
     p = fma_(p, r, 1.0);
     e_out = k >> kExpTabBits;
     return tab[k & (kExpTabSize - 1)] * p;
+}
+
+// e^u = (T[j] 2^e) e^r from the exponent-biased table, with no v_ldexp_f64 and no k >> B: the integer part e is added
+// straight into the high word of the table entry (see exp_tab_bias).  k is first raised to kExpTabKMin = -1021 N, so that
+// T[j] 2^e e^r stays a normal number (T[j] e^r >= 1 - 2^-11); wherever k >= kExpTabKMin the result is then bit-identical
+// to ldexp(exp_tab(u), e) (scaling by a power of two commutes with the rounding of the product while nothing is
+// subnormal).  Where the clamp acts the result is some value < 2^-1019 instead of e^u < 2^-1019:
+// callers add it, scaled by at most 2^31, to a number >= 2^-53 (BgFixedAcc::add<.., NARROW>), which absorbs both exactly.
+// Requires -1.4e6 < u < 700 (k inside int32 and k << (20 - B) without overflow).
+constexpr int kExpTabKMin = -1021 * kExpTabSize;
+template <bool TWO_STEP = false>
+MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
+    int k;
+    const double r = exp_tab_reduce<TWO_STEP>(u, k);
+    double p;
+    if constexpr (kExpPolyDegree == 4) p = fma_(fma_(r, kExpPolyC4, kExpPolyC3), r, kExpPolyC2);
+    else p = fma_(r, kExpPolyC3, kExpPolyC2);
+    p = fma_(p, r, 1.0);
+    p = fma_(p, r, 1.0);
+    k = k > kExpTabKMin ? k : kExpTabKMin;                    // v_max_i32
+    return add_hi_word(tab[k & (kExpTabSize - 1)], (int32_t)((uint32_t)k << kExpTabHiShift)) * p;
 }
 
 // x == +-0 tested on the bit pattern: for a wave-uniform x (SGPR pair) this stays on the scalar unit.
@@ -606,7 +674,9 @@ struct BgFixedAcc {
     // hence eight raw factors can be multiplied between two rescales without the per-star mantissa/exponent split,
     // without the k > 1000 exponent carry and without the denormal-regime tracking; g comes from the one-step Newton
     // form (rsqrt2_newton).
-    template <bool UNIFORM_OMP = true, bool HALVED = false, bool NARROW = false>
+    // TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias); NARROW then inserts the exponent with one integer
+    // instruction instead of v_ldexp_f64 (exp_tab_scaled: same y bit for bit), the general form restores the entries.
+    template <bool UNIFORM_OMP = true, bool HALVED = false, bool NARROW = false, bool TAB_BIASED = false>
     // The prior weight p of the cluster component is folded into the exponent by the record preparation:
     // nbp = -(b + 1/2 log 2pi) + log p (floored at -2000, where e^u is an exact 0: p == 0 gives y = 1 - p = 1), so
     // y = (1 - p) + g e^{u} with u = -1/2 d^2 g^2 + nbp needs no multiplication by p.
@@ -619,8 +689,15 @@ struct BgFixedAcc {
         // (NARROW: the guard bounds |v - v_los|^2 / norm by 2e6 and the record floors nbp at -2000, so u > -1.1e6 needs no clamp)
         const double u0 = HALVED ? fnma_sgpr_addend(dg, dg, nbp) : fma_sgpr_addend(-0.5 * dg, dg, nbp);
         const double u = NARROW ? u0 : fmax_raw(u0, -1100.0);
+        if constexpr (NARROW && TAB_BIASED) {
+            // u < 60 (nbp <= -lnL_bg <= 60) and y >= 1 - p >= 2^-53 > 2^31 2^-1019: exp_tab_scaled's conditions hold
+            const double es = exp_tab_scaled<false>(u, exptab);
+            const double y = UNIFORM_OMP ? fma_sgpr_addend(g, es, omp) : fma_(g, es, omp);
+            l.mul(y);
+            return;
+        }
         int k;
-        const double er = exp_tab<!NARROW>(u, k, exptab);
+        const double er = exp_tab<!NARROW, TAB_BIASED>(u, k, exptab);
         if constexpr (NARROW) {
             const double y = UNIFORM_OMP ? fma_sgpr_addend(g, ldexp_(er, k), omp) : fma_(g, ldexp_(er, k), omp);
             l.mul(y);
@@ -921,7 +998,8 @@ MCD_HD constexpr bool exp_table_is_sqrt2_scaled(int model) { return model == MOD
 // FAST: 0 = plain (the reference's expressions term by term), 1 = fast formulation, 2 = fast formulation with the
 // narrow-range products of BgFixedAcc::add (MODEL_BGFIXED, MODEL_PROFILE_BGDENS) / BgGaussAcc::add (MODEL_BGGAUSS,
 // MODEL_PROFILE_BGGAUSS); for the models without background the same as 1.
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false>
+// TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
                             const double* __restrict__ exptab) {
     constexpr int ND = record_doubles(MODEL, FREE);
@@ -1115,17 +1193,33 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
                 double d, n;
                 star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
                 if constexpr (HALVED) n = fma_(kScale, rr[1], s2x);
-                acc.add<true, HALVED, NARROW>(d, n, rr[XB + 2], rr[XB + 3], exptab);
+                acc.add<true, HALVED, NARROW, TAB_BIASED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
             }
         };
         const int n4 = count >> 2;
-        if constexpr (NARROW) {
+        if constexpr (NARROW && PF) {
+            // eight raw factors per rescale in one 8-star iteration (two scalar record-load batches): the prefetch's
+            // address and exec-mask instructions and the loop branch are paid once per eight terms, and the rescale needs
+            // no branch and no register copy -- 23.6 VALU instructions per term instead of 24.0.  Same
+            // products and rescale points as the 4-star loop below.  (Without the prefetch hipcc hoists the second
+            // group's record loads and takes 76 VGPRs, i.e. 6 waves per SIMD: that instantiation keeps 4-star groups.)
+            for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
+                RecordPrefetch<8 * ND * 8, PF> pf;
+                pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
+                four(r);
+                four(r + 4 * ND);
+                pf.retire(acc.l.p);
+                acc.rescale_narrow();
+            }
+            if (n4 & 1) {
+                four(r);
+                r += 4 * ND;
+                acc.rescale_narrow();
+            }
+        } else if constexpr (NARROW) {
             // eight raw factors per rescale: every second 4-star group (one scalar record-load batch each)
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
-                RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
                 four(r);
-                pf.retire(acc.l.p);
                 if (g & 1) { MCD_KEEP_BRANCH(); acc.rescale_narrow(); }    // wave-uniform: a scalar branch, not a select
             }
             if (n4 & 1) acc.rescale_narrow();
@@ -1142,7 +1236,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             double d, n;
             star_d_n<MODEL, double, FREE, true>(r, w, d, n);
             if constexpr (HALVED) n = fma_(kScale, r[1], s2x);
-            acc.add<true, HALVED, NARROW>(d, n, r[XB + 2], r[XB + 3], exptab);
+            acc.add<true, HALVED, NARROW, TAB_BIASED>(d, n, r[XB + 2], r[XB + 3], exptab);
             acc.rescale();
         }
         result = acc.finish();

@@ -7,7 +7,8 @@
 
 For every fast-path instantiation the hot loop nest is located (label .. backward branch) and its vector instructions are
 counted per star-walker term.  The narrow-range mixture variants rescale their running product on every second 4-star
-iteration (a block behind a scalar branch): their count is (2 x loop body + rescale block) / 8.
+iteration (a block behind a scalar branch): their count is (2 x loop body + rescale block) / 8.  The prefetching BGFIXED
+narrow-range instantiation runs 8-star iterations with the rescale inside the loop body.
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -26,7 +27,8 @@ CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 SOURCES = ("mcd_kernels.hip", "mcd_math.h", "mcd_exp_table.h", "mcd_internal.h", "mcd_chunks.h", "mcd_reduce.h")
 SLOT_NS = 2.33
 
-# (template tag, name, bench model key, stars per inner iteration, inner trips per outer iteration, selector)
+# (template tag, name, bench model key, stars per inner iteration, inner trips per outer iteration, selector
+#  [, (stars, trips, selector) of the instantiation with the prefetch when its loop differs])
 #   selector(Counter of the loop body) -> bool picks the loop among the kernel's innermost loops
 def _sel(rsq=None, frexp=None, rcp=None):
     def f(c):
@@ -39,7 +41,7 @@ KERNELS = [
     ("ILi0ELb0EddLi1E", "CONST fixed centre", "const", 16, 1, _sel(rsq=0, rcp=1)),
     ("ILi0ELb1EddLi1E", "CONST free centre", "const_free", 8, 1, None),
     ("ILi1ELb0EddLi1E", "BGFIXED fixed centre", "bgfixed_general", 4, 1, _sel(rsq=4, frexp=4)),
-    ("ILi1ELb0EddLi2E", "BGFIXED fixed, narrow", "bgfixed", 4, 2, _sel(rsq=4, frexp=0)),
+    ("ILi1ELb0EddLi2E", "BGFIXED fixed, narrow", "bgfixed", 4, 2, _sel(rsq=4, frexp=0), (8, 1, _sel(rsq=8, frexp=1))),
     ("ILi2ELb0EddLi1E", "BGGAUSS fixed centre", "bggauss_general", 4, 1, _sel(rsq=8, frexp=4)),
     ("ILi2ELb0EddLi2E", "BGGAUSS fixed, narrow", "bggauss", 4, 2, _sel(rsq=8, frexp=0)),
     ("ILi3ELb0EddLi1E", "PROFILE fixed centre", "profile_general", 8, 1, None),
@@ -78,8 +80,9 @@ def analyse(out="/tmp/isa_mix"):
     # parameter PF, the last one of the mangled name): the main row is the instantiation without, `*_prefetch` fields and
     # a second table line give the one with
     # (the 4-wave instantiations: the combining 8- / 16-wave ones of the balanced plans run the same loops)
-    variants = [(tag + "Lb0ELi4EE", name, key, per, trips, selector, False) for tag, name, key, per, trips, selector in KERNELS]
-    variants += [(tag + "Lb1ELi4EE", name + ", prefetch", key, per, trips, selector, True) for tag, name, key, per, trips, selector in KERNELS]
+    variants = [(row[0] + "Lb0ELi4EE", row[1], row[2], row[3], row[4], row[5], False) for row in KERNELS]
+    variants += [(row[0] + "Lb1ELi4EE", row[1] + ", prefetch", row[2]) + (row[6] if len(row) > 6 else row[3:6]) + (True,)
+                 for row in KERNELS]
     for tag, name, key, per, trips, selector, with_prefetch in variants:
         starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag)]
         if not starts:
