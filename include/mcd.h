@@ -320,6 +320,10 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      background only for un-binned catalogues from 128 MiB up (their 16-star loop hides the latency
  *                      itself; the prefetch costs binned and many-walker shapes 3 - 6 %); 0 off, 1 on.  Results do not
  *                      depend on it.
+ *   "narrow_bounded" 1 (default): where the range guard finds every mixture value of a fixed-centre MODEL_CONST_BGFIXED
+ *                      catalogue inside a bounded domain (no exponent argument below -700, 16 or 32 factors between two
+ *                      rescales), the narrow-range kernel with prefetch runs its bounded loop -- fewer instructions per
+ *                      term, the same bits; 0 never.  mcd_last_narrow_bounded tells which loop ran.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -354,6 +358,9 @@ int64_t mcd_rerun_count(const mcd_catalog* cat);
  * (option "prefetch"), 0 when not, -1 before the first launch.  The harness picks the per-term instruction count of the
  * roofline by it (csrc/isa_mix.json holds both instantiations). */
 int mcd_last_prefetch(const mcd_catalog* cat);
+/* Rescale interval R (16 or 32 factors) when the most recent main-kernel launch ran the bounded narrow-range loop (option
+ * "narrow_bounded"), 0 when it ran another loop, -1 before the first launch.  mcd_last_fast_level reports 2 for it. */
+int mcd_last_narrow_bounded(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

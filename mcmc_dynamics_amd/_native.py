@@ -71,6 +71,7 @@ SYMBOLS = {
     "mcd_timing_collect": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_int64_p]),
     "mcd_rerun_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_prefetch": (ctypes.c_int, [ctypes.c_void_p]),
+    "mcd_last_narrow_bounded": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
@@ -499,6 +500,12 @@ class Catalog(object):
     def last_prefetch(self):
         """1 / 0: the last main-kernel launch used / did not use the record-prefetching instantiation; -1 before any launch."""
         return self.lib.mcd_last_prefetch(self.handle)
+
+    @property
+    def last_narrow_bounded(self):
+        """R (16 or 32): the last main-kernel launch ran the bounded narrow-range BGFIXED loop with a rescale every R
+        factors (option ``narrow_bounded``); 0 another loop; -1 before any launch."""
+        return self.lib.mcd_last_narrow_bounded(self.handle)
 
     def stretch_info(self):
         """Where the blocks of ``stretch_move`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks', 'last_discard_status'}

@@ -168,6 +168,7 @@ struct WorkSet {
     bool mapped = false;               // last staging used the zero-copy path: results land in h_out directly
     double launch_tag = 0.0;           // tag of the last fast-path launch (written to out[n_out] by a kernel that wants a re-run)
     int fast = 0;                      // mcd::LaunchShape::fast level of the staged batch
+    int narrow_rescale = 0;            // its bounded narrow-range verdict (mcd_guard.h: bounded_rescale; R or 0)
     bool staged = false;
 };
 
@@ -233,6 +234,8 @@ struct mcd_catalog {
     int64_t target_waves = 10240;      // see mcd_chunks.h: plan_chunks
     int64_t chunk_len = 0;             // option "chunk_len": explicit nominal chunk length (0: from target_waves)
     int prefetch = -1;                 // option "prefetch": -1 by record volume (>= 8 MiB per device), 0 off, 1 on
+    int narrow_bounded = 1;            // option "narrow_bounded": 1 the bounded narrow-range BGFIXED loop where the guard
+                                       // admits it (mcd_guard.h: bounded_rescale), 0 never
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
                                        // small enough, 0 never, m > 0 forced with m workgroups per CU
     int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
@@ -263,6 +266,7 @@ struct mcd_catalog {
     int chain_last_status = 0;         // status word of the last discarded block (mcd::ChainStatus bits)
     std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
+    int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };
 
 namespace {
@@ -542,6 +546,8 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
                                                      "f32_domain = 0 to evaluate regardless): ") + cat->last_f32.reason);
     }
     const int fast = fast_level(cat, params, n_rows);
+    const int narrow_rescale = fast == 2 && cat->precision == MCD_F64
+                                   ? mcd::bounded_rescale(cat->stats, cat->model, cat->free_centre, cat->k, params, n_rows) : 0;
     for (Shard& sh : cat->shards) {
         WorkSet* w = nullptr;
         int rc = build_workset(cat, sh, n_walkers, &w);
@@ -570,6 +576,7 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
         MCD_HIP(hipEventRecord(w->ev_staged, slot.stream));
         w->lane1_knows_staging = false;
         w->fast = fast;
+        w->narrow_rescale = narrow_rescale;
         w->staged = true;
     }
     cat->cur_walkers = n_walkers;
@@ -638,6 +645,8 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         // records beyond what the caches hold between two passes: prefetch the next loop iteration's records (mcd_math.h)
         shape.prefetch = wants_prefetch(cat, sh);
         cat->last_prefetch = shape.prefetch && shape.fast != 0;
+        shape.narrow_rescale = cat->narrow_bounded ? w.narrow_rescale : 0;
+        cat->last_narrow_bounded = mcd::narrow_bounded_launch(shape) ? shape.narrow_rescale : 0;
         shape.rerun_flag = coll ? nullptr : out_buf + n_out;
         w.launch_tag = coll ? 0.0 : (double)(++cat->launch_seq);
         shape.launch_tag = w.launch_tag;
@@ -1027,6 +1036,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     shape.chunk_general = w.d_chunk_general;
     shape.prefetch = wants_prefetch(cat, sh);
     cat->last_prefetch = shape.prefetch && shape.fast != 0;
+    cat->last_narrow_bounded = 0;                      // (the resident chain keeps the narrow-range loop with its clamp)
     double* const out_buf = w.d_out;
     shape.rerun_flag = coll ? nullptr : out_buf + Bh;
     const int bgk = mcd::bg_kind(cat->model);
@@ -2035,6 +2045,11 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
         cat->two_lanes = value != 0;
         return MCD_OK;
     }
+    if (!std::strcmp(key, "narrow_bounded")) {
+        if (value < 0 || value > 1) return fail(MCD_ERR_INVALID, "narrow_bounded: 1 (where the guard admits it, default) or 0 (never)");
+        cat->narrow_bounded = (int)value;
+        return MCD_OK;
+    }
     if (!std::strcmp(key, "prefetch")) {
         if (value < -1 || value > 1) return fail(MCD_ERR_INVALID, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)");
         cat->prefetch = (int)value;
@@ -2106,6 +2121,8 @@ int mcd_stretch_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* ho
 }
 
 int mcd_last_prefetch(const mcd_catalog* cat) { return cat ? cat->last_prefetch : -1; }
+
+int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
 
 int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_theta) {
     if (!cat) return -1;

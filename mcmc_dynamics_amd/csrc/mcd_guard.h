@@ -27,6 +27,7 @@ struct StatsScalars {
     bool narrow_possible = false;                   // at most 1/8 of the stars are exceptions (else: general form throughout)
     double r_max_fixed = 0.0;                       // fixed centre: largest separation of a star from it [arcsec] (0: unknown /
                                                     // free centre) -- bounds r_peak^2 + r^2 for the narrow-range profile variant
+    double nbp_min = 0, nbp_max = 0;                // BG_FIXED: range of the records' exponent offset nbp (bounded_rescale)
 };
 
 struct CatalogStats : StatsScalars {
@@ -81,10 +82,18 @@ inline CatalogStats compute_stats(int64_t n, const double* v, const double* verr
     if ((bg == BG_FIXED || bg == BG_FIXED_DENSITY) && n > 0) {
         st.lnbg_min = std::numeric_limits<double>::infinity();
         st.lnbg_max = -st.lnbg_min;
+        if (bg == BG_FIXED) { st.nbp_min = st.lnbg_min; st.nbp_max = st.lnbg_max; }
         for (int64_t i = 0; i < n; ++i) {
             st.lnbg_min = std::min(st.lnbg_min, lnbg[i]);
             st.lnbg_max = std::max(st.lnbg_max, lnbg[i]);
-            if (bg == BG_FIXED) st.pm_max = std::max(st.pm_max, pmember[i]);
+            if (bg == BG_FIXED) {
+                st.pm_max = std::max(st.pm_max, pmember[i]);
+                // the expression of the record preparation (mcd_kernels.hip: prepare_records_kernel); NaN compares false
+                // in min / max: a NaN column fails extras_ok below
+                const double nbp = std::fmax(std::log(pmember[i]) - (lnbg[i] + kHalfLn2Pi), -2000.0);
+                st.nbp_min = std::min(st.nbp_min, nbp);
+                st.nbp_max = std::max(st.nbp_max, nbp);
+            }
         }
     }
     for (int64_t i = 0; i < n; ++i) {
@@ -296,6 +305,33 @@ MCD_HD int level_verdict(const StatsScalars& st, int model, bool f32, int64_t n_
     return 1;
 }
 
+// Bounded sub-variant of the narrow-range BGFIXED loop (chunk_loglike<.., BOUNDED>): R = 32 or 16 raw factors between two
+// rescales and no exponent clamp in exp_tab_scaled; 0 = the level-2 loop as it is.  Only for level 2, MODEL_BGFIXED and
+// a fixed centre; the chunks flagged general still take the general form.  Same bits as level 2 wherever it is admitted.
+//   Clamp: the exponent argument is u = nbp - (d g)^2 (HALVED form, g = (2 n)^-1/2), so u >= nbp_min - d_max^2 / (2 n_min).
+//   The factor 1 + 2^-20 covers the rounding of d = v - v_los (a few ulps of d_max) and of (d g)^2; the one-step Newton
+//   g is low by at most 4.1e-15, which only raises u.  u >= -700 gives k = rint(u 1024 / ln 2) >= -1034127 > kExpTabKMin
+//   = -1045504: the clamp is a no-op and e^u >= 2^-1010 stays normal.
+//   Rescale interval: every mixture value is y = (1 - p) + (2 n)^-1/2 (sqrt(2) T[j] 2^e e^r) = (1 - p) + n^-1/2 e^u (the
+//   sqrt(2)-scaled table of the HALVED form), so y_lo = 1 - pm_max <= y <= 1 + n_min^-1/2 e^{nbp_max} = y_hi.  After a
+//   rescale the product is in [1/2, 1); R factors later it lies in [2^-1 y_lo^R, y_hi^R] (y_lo <= 1 <= y_hi: every
+//   partial product too), so R log2(y_hi) <= 1000 and 1 + R (-log2 y_lo) <= 1000 keep it normal and finite with room for
+//   the rounding of y_lo and y_hi.  A pmember == 1 star (y_lo = 0), a pmember == 0 star (nbp = -2000), a far outlier
+//   or a tiny variance therefore rule the variant out.
+MCD_HD int bounded_rescale(const StatsScalars& st, int model, bool free_centre, int64_t n_rows, const ParamRanges& pr) {
+    if (model != MODEL_BGFIXED || free_centre) return 0;
+    if (level_verdict(st, model, false, n_rows, pr) != 2) return 0;
+    GuardRanges g;
+    if (!guard_verdict(st, model, false, n_rows, pr, &g)) return 0;
+    const double u_min = st.nbp_min - (1.0 + 0x1p-20) * (g.d_max * g.d_max) / (2.0 * g.n_min);
+    if (!(u_min >= -700.0)) return 0;
+    const double lo2 = -log2(1.0 - st.pm_max);                        // >= 0; +inf for pm_max == 1
+    const double hi2 = log2(1.0 + exp(st.nbp_max) / sqrt(g.n_min));    // >= 0
+    for (int R = 32; R >= 16; R /= 2)
+        if (R * hi2 <= 1000.0 && 1.0 + R * lo2 <= 1000.0) return R;
+    return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // float32 accuracy domain (MCD_F32, MCD_F32_ACC64; host only -- the resident chain is float64).  The float32 kernels round
 // every record field and every walker constant to 24 bits before the first operation, so what they can deliver is set by
@@ -378,6 +414,10 @@ inline bool fast_guard(const CatalogStats& st, int model, bool free_centre, bool
 inline int fast_level(const CatalogStats& st, int model, bool free_centre, bool f32, int k, const double* params,
                       int64_t n_rows) {
     return level_verdict(st, model, f32, n_rows, table_ranges(model, free_centre, k, params, n_rows));
+}
+
+inline int bounded_rescale(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows) {
+    return bounded_rescale(st, model, free_centre, n_rows, table_ranges(model, free_centre, k, params, n_rows));
 }
 
 }  // namespace mcd

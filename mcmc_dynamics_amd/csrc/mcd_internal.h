@@ -23,6 +23,8 @@ struct LaunchShape {
     const uint8_t* chunk_general = nullptr;   // fast == 2: chunks that must take the general fast form (hold a star that
                                               // rules out the narrow-range variant, mcd_guard.h: narrow_exception); may be null
     bool prefetch = false;          // software prefetch of the next iteration's records (catalogues beyond the caches)
+    int narrow_rescale = 0;         // fast == 2, MODEL_BGFIXED, fixed centre, f64: R = 16 or 32 runs the bounded loop of the
+                                    // prefetching kernel (mcd_guard.h: bounded_rescale), 0 the narrow-range loop as is
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };
@@ -44,6 +46,12 @@ hipError_t launch_prepare_records(hipStream_t s, const RawColumns& raw, int64_t 
 // params [n_rows][k] (float64, reference order) -> derived walker constants [n_rows][KD] in term precision
 hipError_t launch_prepare_walkers(hipStream_t s, const double* params, int64_t n_rows, int k, int model,
                                   bool free_centre, int precision, void* wpar);
+
+// The main-kernel launch of `shape` runs the bounded narrow-range loop (what mcd_last_narrow_bounded reports)
+inline bool narrow_bounded_launch(const LaunchShape& sh) {
+    return sh.fast == 2 && sh.model == MODEL_BGFIXED && !sh.free_centre && sh.precision == 0 && sh.prefetch &&
+           (sh.narrow_rescale == 16 || sh.narrow_rescale == 32);
+}
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& shape, const void* records, const Chunk* chunks,
                           int64_t n_chunks, const void* wpar, double* partials, int64_t n_walkers);

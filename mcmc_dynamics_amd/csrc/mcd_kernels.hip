@@ -111,7 +111,9 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // add up itself (mcd_stretch.hip) and for a one-wave-per-group reduction.  The second launch bound (minimum waves per
 // SIMD) keeps the register budget of the 4-wave kernel: left alone, the compiler spends up to 150 VGPRs on the 8-wave
 // BGGAUSS kernels (106 - 127 with 4 waves) and the occupancy drops from 4 to 3 waves per SIMD.
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES>
+// BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_loglike<.., BOUNDED>)
+// for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
 __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
                                                                  const Chunk* __restrict__ chunks,
                                                                  const T* __restrict__ wpar,
@@ -120,7 +122,7 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
                                                                  int uniform_len, int uniform_extra, int64_t n_records,
                                                                  double* __restrict__ rerun_flag, double launch_tag,
                                                                  const uint8_t* __restrict__ chunk_general,
-                                                                 int64_t n_slots) {
+                                                                 int64_t n_slots, int narrow_iters) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int kThreads = WAVES * kWave;
     constexpr bool kCombine = WAVES > kWavesPerBlock;
@@ -202,7 +204,8 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             // (the narrow-range profile variant without background has no per-star conditions: no flags, one form)
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
             if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
-            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
+            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(chunk_recs, ch.count, w, denormal,
+                                                                                         exptab_lds, narrow_iters);
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }
@@ -325,28 +328,36 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
                                  : main_grid(n_chunks, n_walkers);   // > 256 walkers: XCD-aware grouping, see loglike_kernel
     if (grid <= 0) return hipSuccess;
     const int64_t n_slots = combine ? grid : n_chunks;
-#define MCD_LAUNCH_MAIN(PF_, WAVES_)                                                                                         \
-    hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_>), dim3((unsigned)grid), dim3(WAVES_ * kWave), 0, \
-                       s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles, n_walkers, n_chunks,       \
-                       sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag, sh.chunk_general, n_slots)
+    // the bounded narrow-range loop (mcd_guard.h: bounded_rescale) exists in the prefetching f64 BGFIXED fixed-centre kernels
+    constexpr bool kCanBound = FAST == 2 && MODEL == MODEL_BGFIXED && !FREE && sizeof(T) == 8 && sizeof(A) == 8;
+    const bool bounded = kCanBound && sh.prefetch && narrow_bounded_launch(sh);
+    const int narrow_iters = bounded ? sh.narrow_rescale / 8 : 1;
+#define MCD_LAUNCH_MAIN(PF_, WAVES_, BOUNDED_)                                                                               \
+    hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
+                       dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
+                       n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
+                       sh.chunk_general, n_slots, narrow_iters)
     if constexpr (kCanCombine) {
         if (combine && sh.waves == 8) {
-            if (sh.prefetch) MCD_LAUNCH_MAIN(true, 8);
-            else MCD_LAUNCH_MAIN(false, 8);
+            if (bounded) MCD_LAUNCH_MAIN(true, 8, kCanBound);
+            else if (sh.prefetch) MCD_LAUNCH_MAIN(true, 8, false);
+            else MCD_LAUNCH_MAIN(false, 8, false);
             return hipGetLastError();
         }
         // 16 waves: 1024 threads, at most 128 VGPRs -- the kernels of the per-walker Gaussian background need more
         if constexpr (bg_kind(MODEL) != BG_GAUSS) {
             if (combine && sh.waves == 16) {
-                if (sh.prefetch) MCD_LAUNCH_MAIN(true, 16);
-                else MCD_LAUNCH_MAIN(false, 16);
+                if (bounded) MCD_LAUNCH_MAIN(true, 16, kCanBound);
+                else if (sh.prefetch) MCD_LAUNCH_MAIN(true, 16, false);
+                else MCD_LAUNCH_MAIN(false, 16, false);
                 return hipGetLastError();
             }
         }
         if (combine) return hipErrorInvalidValue;
     }
-    if (FAST != 0 && sh.prefetch) MCD_LAUNCH_MAIN((FAST != 0), kWavesPerBlock);
-    else MCD_LAUNCH_MAIN(false, kWavesPerBlock);
+    if (bounded) MCD_LAUNCH_MAIN(true, kWavesPerBlock, kCanBound);
+    else if (FAST != 0 && sh.prefetch) MCD_LAUNCH_MAIN((FAST != 0), kWavesPerBlock, false);
+    else MCD_LAUNCH_MAIN(false, kWavesPerBlock, false);
 #undef MCD_LAUNCH_MAIN
     return hipGetLastError();
 }

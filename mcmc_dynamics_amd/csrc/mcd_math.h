@@ -595,8 +595,18 @@ MCD_HD double exp_tab(double u, int& e_out, const double* __restrict__ tab) {
 // subnormal).  Where the clamp acts the result is some value < 2^-1019 instead of e^u < 2^-1019:
 // callers add it, scaled by at most 2^31, to a number >= 2^-53 (BgFixedAcc::add<.., NARROW>), which absorbs both exactly.
 // Requires -1.4e6 < u < 700 (k inside int32 and k << (20 - B) without overflow).
+// CLAMP = false (the bounded narrow-range loop, mcd_guard.h: bounded_rescale): the host guarantees u >= -700, so that
+// k >= -1034127 > kExpTabKMin and the v_max_i32 is a no-op -- dropped, same bits.
 constexpr int kExpTabKMin = -1021 * kExpTabSize;
-template <bool TWO_STEP = false>
+// x, opaque to the optimiser (no instruction): a constant passed through it is held in a VGPR across the loop instead
+// of being re-materialised in the loop body (a v_mov_b64 per iteration in the bounded loop)
+MCD_HD double vgpr_constant(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+template <bool TWO_STEP = false, bool CLAMP = true>
 MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
     int k;
     const double r = exp_tab_reduce<TWO_STEP>(u, k);
@@ -605,8 +615,20 @@ MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
     else p = fma_(r, kExpPolyC3, kExpPolyC2);
     p = fma_(p, r, 1.0);
     p = fma_(p, r, 1.0);
-    k = k > kExpTabKMin ? k : kExpTabKMin;                    // v_max_i32
-    return add_hi_word(tab[k & (kExpTabSize - 1)], (int32_t)((uint32_t)k << kExpTabHiShift)) * p;
+    if constexpr (CLAMP) k = k > kExpTabKMin ? k : kExpTabKMin;      // v_max_i32
+    const double t = tab[k & (kExpTabSize - 1)];
+    const int32_t kh = (int32_t)((uint32_t)k << kExpTabHiShift);
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (!CLAMP) {
+        // the same add on a two-word vector: through add_hi_word's byte copies the compiler splits it into five
+        // byte-mask operations once no v_max_i32 stands between k and the add
+        typedef uint32_t word2 __attribute__((ext_vector_type(2)));
+        word2 w = __builtin_bit_cast(word2, t);
+        w.y += (uint32_t)kh;
+        return __builtin_bit_cast(double, w) * p;
+    }
+#endif
+    return add_hi_word(t, kh) * p;
 }
 
 // x == +-0 tested on the bit pattern: for a wave-uniform x (SGPR pair) this stays on the scalar unit.
@@ -676,7 +698,8 @@ struct BgFixedAcc {
     // form (rsqrt2_newton).
     // TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias); NARROW then inserts the exponent with one integer
     // instruction instead of v_ldexp_f64 (exp_tab_scaled: same y bit for bit), the general form restores the entries.
-    template <bool UNIFORM_OMP = true, bool HALVED = false, bool NARROW = false, bool TAB_BIASED = false>
+    // CLAMP = false: the bounded sub-variant (u >= -700 by the host guard: exp_tab_scaled without its clamp).
+    template <bool UNIFORM_OMP = true, bool HALVED = false, bool NARROW = false, bool TAB_BIASED = false, bool CLAMP = true>
     // The prior weight p of the cluster component is folded into the exponent by the record preparation:
     // nbp = -(b + 1/2 log 2pi) + log p (floored at -2000, where e^u is an exact 0: p == 0 gives y = 1 - p = 1), so
     // y = (1 - p) + g e^{u} with u = -1/2 d^2 g^2 + nbp needs no multiplication by p.
@@ -691,7 +714,7 @@ struct BgFixedAcc {
         const double u = NARROW ? u0 : fmax_raw(u0, -1100.0);
         if constexpr (NARROW && TAB_BIASED) {
             // u < 60 (nbp <= -lnL_bg <= 60) and y >= 1 - p >= 2^-53 > 2^31 2^-1019: exp_tab_scaled's conditions hold
-            const double es = exp_tab_scaled<false>(u, exptab);
+            const double es = exp_tab_scaled<false, CLAMP>(u, exptab);
             const double y = UNIFORM_OMP ? fma_sgpr_addend(g, es, omp) : fma_(g, es, omp);
             l.mul(y);
             return;
@@ -999,9 +1022,11 @@ MCD_HD constexpr bool exp_table_is_sqrt2_scaled(int model) { return model == MOD
 // narrow-range products of BgFixedAcc::add (MODEL_BGFIXED, MODEL_PROFILE_BGDENS) / BgGaussAcc::add (MODEL_BGGAUSS,
 // MODEL_PROFILE_BGGAUSS); for the models without background the same as 1.
 // TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false>
+// BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
+// narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
-                            const double* __restrict__ exptab) {
+                            const double* __restrict__ exptab, int rescale_iters = 1) {
     constexpr int ND = record_doubles(MODEL, FREE);
     denormal = false;
     constexpr int XB = geometry_doubles(MODEL, FREE);      // first background slot of a record
@@ -1184,6 +1209,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         constexpr bool NARROW = FAST == 2 && MODEL == MODEL_BGFIXED;
         constexpr double kScale = NARROW ? 8.0 : 2.0;
         const double s2x = kScale * (double)w.s2;
+        const double scale = BOUNDED ? vgpr_constant(kScale) : kScale;
         BgFixedAcc acc;
         acc.init();
         auto four = [&](RecPtr<double> r4) {
@@ -1192,12 +1218,35 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
                 RecPtr<double> rr = r4 + j * ND;
                 double d, n;
                 star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-                if constexpr (HALVED) n = fma_(kScale, rr[1], s2x);
-                acc.add<true, HALVED, NARROW, TAB_BIASED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
+                if constexpr (HALVED) n = fma_(scale, rr[1], s2x);
+                acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
             }
         };
         const int n4 = count >> 2;
-        if constexpr (NARROW && PF) {
+        static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
+        if constexpr (BOUNDED) {
+            // bounded sub-variant: every mixture value lies in [y_lo, y_hi] with R log2(y_hi) <= 1000 and
+            // 1 + R (-log2 y_lo) <= 1000 (mcd_guard.h: bounded_rescale), so R = 8 rescale_iters raw factors fit between
+            // two rescales.  A scalar countdown sends every rescale_iters-th iteration to the rescale, a block outside
+            // the loop body (4 VALU instructions per R terms instead of 3 per 8; a nested loop costs a v_mov_b64 per
+            // iteration).  Rescaling multiplies by a power of two, which commutes with the rounding of every product
+            // while nothing overflows or goes subnormal: the same bits as the loop below.
+            int until = rescale_iters;
+            for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
+                RecordPrefetch<8 * ND * 8, PF> pf;
+                pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
+                four(r);
+                four(r + 4 * ND);
+                pf.retire(acc.l.p);
+                if (--until == 0) { until = rescale_iters; MCD_KEEP_BRANCH(); acc.rescale_narrow(); }
+            }
+            acc.rescale_narrow();
+            if (n4 & 1) {
+                four(r);
+                r += 4 * ND;
+                acc.rescale_narrow();
+            }
+        } else if constexpr (NARROW && PF) {
             // eight raw factors per rescale in one 8-star iteration (two scalar record-load batches): the prefetch's
             // address and exec-mask instructions and the loop branch are paid once per eight terms, and the rescale needs
             // no branch and no register copy -- 23.6 VALU instructions per term instead of 24.0.  Same
@@ -1236,7 +1285,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             double d, n;
             star_d_n<MODEL, double, FREE, true>(r, w, d, n);
             if constexpr (HALVED) n = fma_(kScale, r[1], s2x);
-            acc.add<true, HALVED, NARROW, TAB_BIASED>(d, n, r[XB + 2], r[XB + 3], exptab);
+            acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, r[XB + 2], r[XB + 3], exptab);
             acc.rescale();
         }
         result = acc.finish();

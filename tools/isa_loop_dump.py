@@ -2,6 +2,7 @@
 """Print the hot loop of one fast-path instantiation of mcd::loglike_kernel as gfx950 assembly, for annotation.
 
     python tools/isa_loop_dump.py ISA.s "BGFIXED fixed, narrow" [--prefetch]
+    python tools/isa_loop_dump.py ISA.s "BGFIXED fixed, narrow, prefetch, bounded"
 
 ISA.s is the device assembly of csrc/mcd_kernels.hip (hipcc -save-temps; tools/isa_mix.py leaves it in /tmp/isa_mix).
 The loop is located with tools/isa_mix.py's rules; for the narrow-range variants the rescale block behind the loop's
@@ -17,15 +18,19 @@ import isa_mix  # noqa: E402
 
 
 def loop_lines(asm, name, prefetch):
-    for row in isa_mix.KERNELS:
-        if row[1] == name:
-            tag, trips, selector = row[0], row[4], row[5]
-            if prefetch and len(row) > 6:
-                trips, selector = row[6][1], row[6][2]
-            break
+    bounded = name == isa_mix.BOUNDED[1]
+    if bounded:
+        tag, trips, selector = isa_mix.BOUNDED[0], isa_mix.BOUNDED[4], isa_mix.BOUNDED[5]
     else:
-        raise SystemExit("unknown kernel %r" % name)
-    tag = tag + ("Lb1ELi4EE" if prefetch else "Lb0ELi4EE")
+        for row in isa_mix.KERNELS:
+            if row[1] == name:
+                tag, trips, selector = row[0], row[4], row[5]
+                if prefetch and len(row) > 6:
+                    trips, selector = row[6][1], row[6][2]
+                break
+        else:
+            raise SystemExit("unknown kernel %r" % name)
+        tag = tag + ("Lb1ELi4ELb0EE" if prefetch else "Lb0ELi4ELb0EE")
     a = next(i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag))
     e = next(i for i in range(a, len(asm)) if asm[i].startswith(".Lfunc_end"))
     k = asm[a:e]
@@ -40,14 +45,8 @@ def loop_lines(asm, name, prefetch):
     hits = [sp for sp in ranked if selector is None or selector(Counter(isa_mix._ops(k[sp[0]:sp[1]])))]
     best = (hits or ranked)[0]
     body = k[best[0]:best[1] + 1]
-    extra = []
-    if trips > 1:
-        for j in range(best[1] + 1, min(best[1] + 16, len(k))):
-            m = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j])
-            if m:
-                if m.group(1) in labels and labels[m.group(1)] <= best[1]:
-                    extra = k[best[1] + 1:j + 1]
-                break
+    blk = isa_mix.rescale_block(k, labels, best, bounded, trips)
+    extra = k[blk[0]:blk[1] + 1] if blk else []
     return body, extra
 
 
@@ -60,7 +59,7 @@ def main():
     for l in code(body):
         print(l.strip())
     if extra:
-        print("; ---- rescale block (every second iteration)")
+        print("; ---- rescale block (every %s iteration)" % ("fourth (R = 32)" if sys.argv[2] == isa_mix.BOUNDED[1] else "second"))
         for l in code(extra):
             print(l.strip())
     tally = Counter(isa_mix._ops(code(body)))

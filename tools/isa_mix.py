@@ -8,7 +8,10 @@
 For every fast-path instantiation the hot loop nest is located (label .. backward branch) and its vector instructions are
 counted per star-walker term.  The narrow-range mixture variants rescale their running product on every second 4-star
 iteration (a block behind a scalar branch): their count is (2 x loop body + rescale block) / 8.  The prefetching BGFIXED
-narrow-range instantiation runs 8-star iterations with the rescale inside the loop body.
+narrow-range instantiation runs 8-star iterations with the rescale inside the loop body; its bounded sub-variant (template
+parameter BOUNDED, the last one of the mangled name) rescales every fourth 8-star iteration at C3's R = 32, in a block the
+loop branches out to: (4 x loop body + rescale block) / 32.  That instantiation is what C3's timed launches run, so it
+gives the "bgfixed" key's prefetch fields; the level-2 prefetching loop keeps its row under "bgfixed_level2".
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -28,7 +31,8 @@ SOURCES = ("mcd_kernels.hip", "mcd_math.h", "mcd_exp_table.h", "mcd_internal.h",
 SLOT_NS = 2.33
 
 # (template tag, name, bench model key, stars per inner iteration, inner trips per outer iteration, selector
-#  [, (stars, trips, selector) of the instantiation with the prefetch when its loop differs])
+#  [, (stars, trips, selector) of the instantiation with the prefetch when its loop differs
+#   [, model key of the instantiation with the prefetch when it differs]])
 #   selector(Counter of the loop body) -> bool picks the loop among the kernel's innermost loops
 def _sel(rsq=None, frexp=None, rcp=None):
     def f(c):
@@ -41,7 +45,8 @@ KERNELS = [
     ("ILi0ELb0EddLi1E", "CONST fixed centre", "const", 16, 1, _sel(rsq=0, rcp=1)),
     ("ILi0ELb1EddLi1E", "CONST free centre", "const_free", 8, 1, None),
     ("ILi1ELb0EddLi1E", "BGFIXED fixed centre", "bgfixed_general", 4, 1, _sel(rsq=4, frexp=4)),
-    ("ILi1ELb0EddLi2E", "BGFIXED fixed, narrow", "bgfixed", 4, 2, _sel(rsq=4, frexp=0), (8, 1, _sel(rsq=8, frexp=1))),
+    ("ILi1ELb0EddLi2E", "BGFIXED fixed, narrow", "bgfixed", 4, 2, _sel(rsq=4, frexp=0), (8, 1, _sel(rsq=8, frexp=1)),
+     "bgfixed_level2"),
     ("ILi2ELb0EddLi1E", "BGGAUSS fixed centre", "bggauss_general", 4, 1, _sel(rsq=8, frexp=4)),
     ("ILi2ELb0EddLi2E", "BGGAUSS fixed, narrow", "bggauss", 4, 2, _sel(rsq=8, frexp=0)),
     ("ILi3ELb0EddLi1E", "PROFILE fixed centre", "profile_general", 8, 1, None),
@@ -53,6 +58,9 @@ KERNELS = [
     ("ILi1ELb0EffLi1E", "BGFIXED fixed, f32", "bgfixed_f32", 4, 1, None),
     ("ILi1ELb0EfdLi1E", "BGFIXED fixed, f32 terms f64 sums", "bgfixed_f32acc64", 4, 1, None),
 ]
+
+# the bounded narrow-range loop (prefetching instantiation only): full tag, name, key, stars, trips, selector
+BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded", "bgfixed", 8, 4, _sel(rsq=8, frexp=0))
 
 
 def _ops(lines):
@@ -69,6 +77,35 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+def rescale_block(k, labels, best, bounded, trips):
+    """(first, end) lines of the rescale block of a narrow-range loop `best` (label line, closing branch line), or None.
+    The 4-star loops: behind the loop's closing conditional branch, jumping back with an unconditional s_branch.  The
+    bounded loop: the target of a forward branch out of the loop, closed by an s_branch back into it."""
+    if bounded:
+        for i in range(best[0], best[1]):
+            m = re.search(r"s_cbranch_\w+ (\.LBB\d+_\d+)", k[i])
+            if not (m and m.group(1) in labels and labels[m.group(1)] > best[1]):
+                continue
+            a0 = labels[m.group(1)]
+            for j in range(a0 + 1, min(a0 + 24, len(k))):
+                mb = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j])
+                if mb:
+                    if mb.group(1) in labels and best[0] <= labels[mb.group(1)] <= best[1]:
+                        return a0 + 1, j
+                    break
+        return None
+    if trips > 1:
+        # the rescale block of the narrow-range loops runs on every `trips`-th iteration: it sits behind the loop's
+        # closing conditional branch and jumps back with an unconditional s_branch
+        for j in range(best[1] + 1, min(best[1] + 16, len(k))):
+            m = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j])
+            if m:
+                if m.group(1) in labels and labels[m.group(1)] <= best[1]:
+                    return best[1] + 1, j
+                break
+    return None
+
+
 def analyse(out="/tmp/isa_mix"):
     os.makedirs(out, exist_ok=True)
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-c",
@@ -80,9 +117,11 @@ def analyse(out="/tmp/isa_mix"):
     # parameter PF, the last one of the mangled name): the main row is the instantiation without, `*_prefetch` fields and
     # a second table line give the one with
     # (the 4-wave instantiations: the combining 8- / 16-wave ones of the balanced plans run the same loops)
-    variants = [(row[0] + "Lb0ELi4EE", row[1], row[2], row[3], row[4], row[5], False) for row in KERNELS]
-    variants += [(row[0] + "Lb1ELi4EE", row[1] + ", prefetch", row[2]) + (row[6] if len(row) > 6 else row[3:6]) + (True,)
-                 for row in KERNELS]
+    # (every instantiation carries the BOUNDED parameter after WAVES: Lb0E unless it is the bounded loop)
+    variants = [(row[0] + "Lb0ELi4ELb0EE", row[1], row[2], row[3], row[4], row[5], False) for row in KERNELS]
+    variants += [(row[0] + "Lb1ELi4ELb0EE", row[1] + ", prefetch", row[7] if len(row) > 7 else row[2]) +
+                 (row[6] if len(row) > 6 else row[3:6]) + (True,) for row in KERNELS]
+    variants.append(BOUNDED + (True,))
     for tag, name, key, per, trips, selector, with_prefetch in variants:
         starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag)]
         if not starts:
@@ -106,15 +145,9 @@ def analyse(out="/tmp/isa_mix"):
             best = ranked[0]
         body = Counter(_ops(k[best[0]:best[1] + 1]))
         extra = Counter()
-        if trips > 1:
-            # the rescale block of the narrow-range loops runs on every `trips`-th iteration: it sits behind the loop's
-            # closing conditional branch and jumps back with an unconditional s_branch
-            for j in range(best[1] + 1, min(best[1] + 16, len(k))):
-                m = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j])
-                if m:
-                    if m.group(1) in labels and labels[m.group(1)] <= best[1]:
-                        extra = Counter(_ops(k[best[1] + 1:j]))
-                    break
+        blk = rescale_block(k, labels, best, tag == BOUNDED[0], trips)
+        if blk:
+            extra = Counter(_ops(k[blk[0]:blk[1]]))
         terms = per * trips
         total = Counter()
         for op, v in body.items():
@@ -142,7 +175,9 @@ def merge_variants(rows):
     """{model: row of the instantiation without prefetch + `<field>_prefetch` for the one with}"""
     out = {r["model"]: dict(r) for r in rows if not r["prefetch"]}
     for r in rows:
-        if r["prefetch"] and r["model"] in out:
+        if r["prefetch"] and r["model"] not in out:          # (a prefetch-only row: bgfixed_level2)
+            out[r["model"]] = dict(r)
+        if r["prefetch"]:
             for k in ("valu_per_term", "f64_per_term", "other_per_term", "slots_per_term", "salu_smem_per_term"):
                 out[r["model"]][k + "_prefetch"] = r[k]
     for r in out.values():
