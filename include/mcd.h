@@ -329,7 +329,7 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      "target_waves"); tuning aid
  *   "tail_split"    chunk schedule: 0 equal-length chunks; 1 (default): the last ~15 % of a large parameter set is
  *                      cut into half- and quarter-length chunks so that the launch ends on short waves; 2-4:
- *                      other guided schedules kept for tuning (see build_workset in mcd_api.hip)
+ *                      other guided schedules kept for tuning (see build_workset in mcd_api_catalog.hip)
  *   "balance"       balanced single-round chunk plans for small catalogues (every workgroup of the launch resident at once,
  *                      chunks of equal length: no tail, no second round): -1 (default) by work -- 2, 4 or 8 workgroups per
  *                      CU below ~1e6 work units, the multi-round table beyond; 0 never; 1 .. 8 forced

@@ -1,5 +1,5 @@
 // mcd_chunks.h -- host-only planning of the work decomposition: star shards per device / rank and the chunk table of
-// one shard.  No HIP types here, so that the C-ABI (mcd_api.hip) and the CPU test harness (tests/emul) share exactly
+// one shard.  No HIP types here, so that the C-ABI (mcd_api_catalog.hip) and the CPU test harness (tests/emul) share exactly
 // the code that decides which stars a wave evaluates (as mcd_guard.h does for the range guard).
 //
 // Reference counterpart: none.  The reference evaluates all stars of one walker in one NumPy pass
@@ -90,7 +90,7 @@ inline ChunkPlan plan_chunks(const std::vector<int64_t>& bin_offsets, int64_t st
     const int64_t n_psets = (int64_t)bin_offsets.size() - 1;
     const int64_t n_wtiles = (n_walkers + 63) / 64;
     // ---- one round of equal waves: `balance` = workgroups per CU (0: the multi-round schedules below; which catalogues
-    // take it is the caller's rule, mcd_api.hip: balance_auto_m) ----
+    // take it is the caller's rule, mcd_api_catalog.hip: balance_auto_m) ----
     if (balance > 0 && n_psets == 1 && chunk_len == 0 && n > 0 && bin_offsets[0] <= star_begin &&
         bin_offsets[1] >= star_begin + n) {
         const int64_t m = std::min<int64_t>(balance, 8);

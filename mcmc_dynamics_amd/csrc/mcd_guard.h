@@ -1,6 +1,6 @@
 // mcd_guard.h -- range guard that decides, per call, whether the fast kernel formulations may be used.
-// Shared by the C-ABI (mcd_api.hip), by the resident stretch-move chain (mcd_stretch.hip evaluates the same verdict on the
-// device for the tables it builds there) and by the CPU test harness (tests/emul), so that the randomized tests exercise
+// Shared by the C-ABI (mcd_api_eval.hip), by the resident stretch-move chain (mcd_stretch.hip evaluates the same verdict on
+// the device for the tables it builds there) and by the CPU test harness (tests/emul), so that the randomized tests exercise
 // exactly the condition the library applies.
 #pragma once
 

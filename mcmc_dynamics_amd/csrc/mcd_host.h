@@ -1,0 +1,271 @@
+// mcd_host.h -- private header of the host units behind the C-ABI of the MI355X log-likelihood library (include/mcd.h).
+//
+// Host-side responsibilities: device/stream/communicator set-up, one-off upload and packing of the
+// star catalogue into HBM, star sharding across devices, chunk tables, per-call launch sequence
+//   params H2D -> walker prep -> main kernel -> fixed-order reduce -> [RCCL all-reduce] -> D2H,
+// and HIP-event timing for the measurement harness.  No C++ exception leaves a unit, and none defines a kernel:
+//   mcd_api_ctx.hip        error state, RCCL loading, contexts, the failure / abort protocol, waits on a context's streams
+//   mcd_api_catalog.hip    catalogues, work sets and chunk plans, the main kernel's launch shape, options, mcd_last_* queries
+//   mcd_api_eval.hip       staging, enqueue, sync, fetch; the per-star outputs of one parameter row
+//   mcd_api_chain.hip      the stretch-move block, resident on the device or host-driven
+//   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
+// What crosses units is in mcd::host (hidden: not among the library's exported symbols), the rest in each unit's
+// anonymous namespace.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h>   // types and prototypes only: librccl.so is dlopen'ed on first multi-GPU use
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/mcd.h"
+#include "mcd_internal.h"
+#include "mcd_guard.h"
+#include "mcd_math.h"
+
+struct mcd_ctx;
+struct mcd_catalog;
+
+// (the visibility holds for what one namespace block declares: the units open theirs with the same macro)
+#define MCD_HOST_BEGIN namespace mcd { namespace host __attribute__((visibility("hidden"))) {
+#define MCD_HOST_END }}
+MCD_HOST_BEGIN
+
+extern thread_local std::string g_last_error;          // what mcd_last_error returns (mcd_api_ctx.hip)
+int fail(int code, const std::string& msg);
+int on_exception(const char* where) noexcept;
+
+#define MCD_HIP(call)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (call);                                                                         \
+        if (e_ != hipSuccess)                                                                           \
+            return ::mcd::host::fail(MCD_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+// RCCL entry points, resolved lazily so that single-GPU processes never load or initialise RCCL.
+struct Rccl {
+    void* handle = nullptr;
+    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
+    decltype(&ncclCommInitRank) CommInitRank = nullptr;
+    decltype(&ncclCommInitAll) CommInitAll = nullptr;
+    decltype(&ncclCommDestroy) CommDestroy = nullptr;
+    decltype(&ncclAllReduce) AllReduce = nullptr;
+    decltype(&ncclGroupStart) GroupStart = nullptr;
+    decltype(&ncclGroupEnd) GroupEnd = nullptr;
+    decltype(&ncclGetErrorString) GetErrorString = nullptr;
+    decltype(&ncclCommCount) CommCount = nullptr;
+    decltype(&ncclCommUserRank) CommUserRank = nullptr;
+    decltype(&ncclGetVersion) GetVersion = nullptr;
+};
+extern Rccl g_rccl;                                     // one per process (mcd_api_ctx.hip)
+int load_rccl();
+
+#define MCD_NCCL(call)                                                                                  \
+    do {                                                                                                \
+        ncclResult_t r_ = (call);                                                                       \
+        if (r_ != ncclSuccess)                                                                          \
+            return ::mcd::host::fail(MCD_ERR_RCCL,                                                      \
+                                   std::string(#call) + ": " + ::mcd::host::g_rccl.GetErrorString(r_)); \
+    } while (0)
+
+struct DeviceSlot {
+    int device = 0;
+    hipStream_t stream = nullptr;        // kernels, copies
+    hipStream_t stream2 = nullptr;       // second compute lane of pipelined evaluations (WorkSet: two lanes)
+    hipStream_t comm_stream = nullptr;   // the per-step all-reduce, so that it overlaps the next step's kernels
+    ncclComm_t comm = nullptr;
+};
+
+// per-(shard, walker-count) work buffers
+struct WorkSet {
+    int64_t n_walkers = 0;
+    int64_t n_chunks = 0;
+    int64_t max_chunks_per_pset = 0;
+    int uniform_len = 0;               // > 0 when the chunk table is arithmetic (single set; mcd_chunks.h: uniform_chunk)
+    int uniform_extra = 0;
+    int waves = 4;                     // 8: balanced plan whose workgroups combine their chunks' sums (f64 fast kernels only)
+    mcd::Chunk* d_chunks = nullptr;
+    int64_t* d_offsets = nullptr;      // [n_psets + 1] chunk offsets
+    uint8_t* d_chunk_general = nullptr;   // [n_chunks] chunks excluded from the narrow-range variant; null when there are none
+    double* d_params = nullptr;        // [n_psets][W][K]
+    void* d_wpar = nullptr;            // [n_psets][W][KD]
+    double* d_partials = nullptr;      // [roundup64(W) / 8][n_chunks][8]
+    double* d_out = nullptr;           // [n_psets][W] (+ flag word)
+    double* d_out2 = nullptr;          // second result buffer: collective mode alternates between the two, so that the
+                                       // all-reduce of step i (comm stream) overlaps the kernels of step i + 1
+    int buf = 0;                       // buffer the last enqueue wrote (0 for blocking calls without a collective)
+    // Pipelined evaluations on ONE device without a collective alternate between two LANES: lane 0 = the compute stream
+    // with (d_partials, d_out), lane 1 = the second stream with (d_partials2, d_out2).  Consecutive evaluations are
+    // independent (each has its parameters staged), so the reduction and the launch ramp of one overlap the main kernel
+    // of the next instead of sitting between two main kernels on one stream (enqueue(): two_lanes).
+    double* d_partials2 = nullptr;
+    hipEvent_t ev_staged = nullptr;    // parameters staged (on the compute stream): lane 1 waits for it once per staging
+    bool lane1_knows_staging = false;
+    bool lane1_used = false;           // something may be in flight on the second stream
+    hipEvent_t ev_reduced[2] = {nullptr, nullptr};   // reduce kernel done, buffer b ready for the all-reduce
+    hipEvent_t ev_comm[2] = {nullptr, nullptr};      // all-reduce of buffer b done
+    bool comm_pending[2] = {false, false};
+    double* h_params = nullptr;        // pinned + mapped
+    double* h_out = nullptr;           // pinned + mapped
+    double* m_params = nullptr;        // device view of h_params (zero-copy path of the blocking call)
+    double* m_out = nullptr;           // device view of h_out
+    bool mapped = false;               // last staging used the zero-copy path: results land in h_out directly
+    double launch_tag = 0.0;           // tag of the last fast-path launch (written to out[n_out] by a kernel that wants a re-run)
+    int fast = 0;                      // mcd::LaunchShape::fast level of the staged batch
+    int narrow_rescale = 0;            // its bounded narrow-range verdict (mcd_guard.h: bounded_rescale; R or 0)
+    bool staged = false;
+};
+
+// device arena of the resident stretch-move chain and its pinned host mirror (same layout, see stretch_block_device)
+struct ChainArena {
+    char* d = nullptr;
+    char* h = nullptr;
+    size_t bytes = 0;
+};
+
+struct Shard {
+    int slot = 0;                      // index into ctx->slots
+    int64_t star_begin = 0;            // global index of the first star held here
+    int64_t n = 0;
+    void* records = nullptr;
+    double* d_pset_const = nullptr;    // BGFIXED: sum of lnlike_bg over this shard's stars of each parameter set
+    std::map<int64_t, WorkSet> work;   // keyed by walker count
+    hipEvent_t ev_begin = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_end = nullptr;
+    // "timing" = 2: one (start, stop) event pair per main-kernel launch, summed by mcd_timing_collect
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ring;
+    size_t ring_used = 0;
+};
+
+// Device scratch of one call: hipMalloc'ed blocks and an optional pair of timing events, released on every exit path.
+struct DeviceScratch {
+    std::vector<void*> blocks;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DeviceScratch() = default;
+    DeviceScratch(const DeviceScratch&) = delete;
+    template <class T>
+    hipError_t malloc(T** p, size_t bytes) {
+        blocks.push_back(nullptr);                     // (first, so that a block is never without its entry)
+        const hipError_t e = hipMalloc(&blocks.back(), bytes);
+        *p = static_cast<T*>(blocks.back());
+        return e;
+    }
+    hipError_t create_events() {
+        const hipError_t e = hipEventCreate(&e0);
+        return e != hipSuccess ? e : hipEventCreate(&e1);
+    }
+    ~DeviceScratch() {
+        for (void* p : blocks) (void)hipFree(p);
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// ---- helpers that cross units (the comments are at the definitions) ----
+// mcd_api_ctx.hip
+int ctx_fail(mcd_ctx* ctx, const std::string& what);
+int ctx_usable(mcd_ctx* ctx);
+int wait_ctx_stream(mcd_ctx* ctx, hipStream_t s, int64_t spin_us, const char* stage);
+// mcd_api_catalog.hip
+int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out);
+LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& w, int level, bool coll, double* out_buf,
+                              int64_t n_out);
+const double* fast_pset_const(const mcd_catalog* cat, const Shard& sh, int level);
+// mcd_api_eval.hip
+int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
+int sync_all(mcd_catalog* cat);
+
+MCD_HOST_END
+
+struct mcd_ctx {
+    std::vector<mcd::host::DeviceSlot> slots;
+    int rank = 0;
+    int n_ranks = 1;
+    bool multi_process = false;
+    bool force_collective = false;     // MCD_FORCE_RCCL=1: run the all-reduce even on a 1-rank communicator (tests)
+    // collective deadline (include/mcd.h): waits on streams that carry an all-reduce poll, bounded by the deadline and
+    // by the abort flag another host thread may raise
+    int64_t collective_timeout_ms = 120000;
+    std::atomic<int> abort_flag{0};
+    std::atomic<int> failed{0};
+    std::mutex note_mutex;
+    std::string abort_reason;          // (guarded by note_mutex)
+    std::string failure;               // first failure: stage and cause
+    bool has_comm() const { return n_ranks > 1 || slots.size() > 1 || force_collective; }
+};
+
+struct mcd_catalog {
+    mcd_ctx* ctx = nullptr;
+    int model = 0;
+    bool free_centre = false;
+    int precision = 0;
+    int k = 4;
+    int64_t n_stars = 0;               // stars held by this process
+    int64_t n_psets = 1;
+    std::vector<int64_t> bin_offsets;  // [n_psets + 1], indices into this process' stars
+    std::vector<mcd::host::Shard> shards;
+    mcd::CatalogStats stats;           // range statistics for the fast-path guard (mcd_guard.h)
+    // options
+    bool timing = false;
+    bool timing_all = false;           // keep an event pair for every launch (measurement harness)
+    int allow_fast = 1;                // option "fast_path": 0 plain kernels only, 1 guard decides, 2 guard decides but never the narrow variant
+    bool zero_copy = true;             // blocking call reads params / writes results through mapped pinned memory
+    int64_t timing_stride = 1;         // "timing" = 2: event pair on every n-th launch only (option "timing_stride")
+    int64_t timing_launches = 0;
+    int64_t spin_us = 20000;           // option "spin_us": poll a stream this long before blocking in hipStreamSynchronize
+    int tail_split = 1;                // guided chunk schedule (shorter chunks at the end of a launch)
+    int64_t target_waves = 10240;      // see mcd_chunks.h: plan_chunks
+    int64_t chunk_len = 0;             // option "chunk_len": explicit nominal chunk length (0: from target_waves)
+    int prefetch = -1;                 // option "prefetch": -1 by record volume (>= 8 MiB per device), 0 off, 1 on
+    int narrow_bounded = 1;            // option "narrow_bounded": 1 the bounded narrow-range BGFIXED loop where the guard
+                                       // admits it (mcd_guard.h: bounded_rescale), 0 never
+    int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
+                                       // small enough, 0 never, m > 0 forced with m workgroups per CU
+    int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
+    int f32_domain = 1;                // option "f32_domain": 1 calls outside the float32 accuracy domain (mcd_guard.h) are refused
+                                       // with MCD_ERR_INVALID, 0 they are evaluated anyway (mcd_last_f32_domain tells)
+    mcd::F32Domain last_f32;           // verdict on the last staged parameter table (float32 catalogues)
+    int64_t posterior_pass = 65536;    // option "posterior_pass": samples per device pass of mcd_pointwise_posterior
+    int64_t loo_scratch_mb = 2048;    // option "loo_scratch_mb": device scratch of mcd_psis_loo (sample table + term tile)
+    int combine = 1;                   // option "combine": balanced plans may use 8- / 16-wave workgroups that combine their
+                                       // chunks' sums: 0 never, 1 the largest the plan allows, 8 / 16 at most that many waves
+    // state of the last evaluation
+    int64_t cur_walkers = 0;
+    double last_kernel_ms = -1.0, last_device_ms = -1.0;
+    bool timing_pending = false;
+    int64_t last_grid = 0, last_chunks = 0;
+    uint64_t launch_seq = 0;           // source of launch tags
+    int64_t n_reruns = 0;              // batches re-evaluated with the plain kernels (denormal regime of the reference)
+    // resident stretch-move chain (mcd_stretch.hip)
+    int device_chain = 1;              // option "device_chain": 0 host-driven blocks only
+    int fused_reduce = 1;              // option "fused_reduce": the step kernel adds up small launches' partial sums itself
+    int defer_guard = 1;               // option "defer_guard": one-ensemble resident blocks judge their tables at the end
+    bool chain_last_fused = false;
+    mcd::host::ChainArena chain;
+    int chain_hint = -1;               // kernel family the device's guard asked for when it last disagreed (-1: none)
+    int64_t chain_backoff = 0;         // blocks left to run host-driven after a discarded block
+    int chain_consecutive = 0;         // discarded blocks in a row (the back-off doubles with each)
+    int64_t chain_device_blocks = 0, chain_host_blocks = 0, chain_discarded = 0;
+    int chain_last_status = 0;         // status word of the last discarded block (mcd::ChainStatus bits)
+    std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
+    int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
+    int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
+};
+
+#define MCD_WAIT(ctx, stream, spin, stage)                                                              \
+    do {                                                                                                \
+        const int w_rc_ = ::mcd::host::wait_ctx_stream((ctx), (stream), (spin), (stage));               \
+        if (w_rc_ != MCD_OK) return w_rc_;                                                              \
+    } while (0)

@@ -1,4 +1,4 @@
-// mcd_internal.h -- declarations shared by the kernels (mcd_kernels.hip) and the C-ABI (mcd_api.hip).
+// mcd_internal.h -- declarations shared by the kernels (mcd_kernels.hip) and the C-ABI's host units (mcd_host.h).
 #pragma once
 
 #include <hip/hip_runtime.h>

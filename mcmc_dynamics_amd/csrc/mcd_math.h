@@ -926,7 +926,7 @@ struct RecordPrefetch {
     uint32_t t;
     // ON is a template parameter of the kernel, not a launch parameter: even switched off at run time the lane index,
     // the predicate and the asm of retire() cost the tight CONST loops 6 - 16 % (C5: 190 us against 164 us compiled
-    // out).  Which launches get the prefetching instantiation: mcd_api.hip, wants_prefetch().
+    // out).  Which launches get the prefetching instantiation: mcd_api_catalog.hip, wants_prefetch().
     template <class P>
     MCD_HD void issue(P next) {
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(MCD_NO_PREFETCH)

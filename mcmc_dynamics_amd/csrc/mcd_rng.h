@@ -1,6 +1,6 @@
 // mcd_rng.h -- counter-based random numbers of the stretch move, the same code on the device (mcd_stretch.hip:
 // chain_numbers_kernel fills a seeded block's numbers in device memory: nothing crosses PCIe) and on the host (the host-driven
-// block of mcd_api.hip, mcd_chain_numbers, the CPU test harness tests/emul), so that a chain is a function of (seed, step,
+// block of mcd_api_chain.hip, mcd_chain_numbers, the CPU test harness tests/emul), so that a chain is a function of (seed, step,
 // half step, ensemble, walker) alone and any step of it can be replayed anywhere.
 //
 //   * generator: Philox4x64-10 (Salmon et al. 2011), the algorithm of NumPy's `numpy.random.Philox` bit generator --

@@ -7,7 +7,7 @@
 // Every random number comes from the caller, in the layout mcmc_dynamics_amd/sampler.py draws them, and the arithmetic is
 // written operation for operation like the Python loop (no FMA contraction: the library is built with -ffp-contract=off),
 // so that a chain produced here is bit-identical to the one the Python loop produces from the same generator state.
-// No HIP types: shared by the C-ABI (mcd_api.hip) and the CPU test harness (tests/emul).
+// No HIP types: shared by the C-ABI (mcd_api_chain.hip) and the CPU test harness (tests/emul).
 #pragma once
 
 #include <cmath>

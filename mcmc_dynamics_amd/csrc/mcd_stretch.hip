@@ -16,7 +16,7 @@
 // What the device cannot decide alone it only detects: a NaN sum, a re-run request of the fast mixture kernels, a table
 // whose guard verdict differs from the kernel family the host enqueued, a half step with no proposal inside the prior.
 // Each sets a bit in the status word; the host then discards the block and runs it through the host-driven loop from the
-// same inputs (mcd_api.hip: mcd_stretch_move), which handles all of them.
+// same inputs (mcd_api_chain.hip: mcd_stretch_move), which handles all of them.
 #include "mcd_internal.h"   // first: <hip/hip_runtime.h> before the MCD_HD headers
 #include "mcd_guard.h"
 #include "mcd_math.h"

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- a stand-in for librccl.so that lets ONE GPU run the library's multi-rank and
-// multi-device call sequences (mcd_api.hip: ncclCommInitRank / ncclCommInitAll, ncclGroupStart/End, ncclAllReduce on the
-// catalogue's streams) with REAL shards and REAL kernels.  RCCL itself refuses two ranks on one device ("invalid usage"),
+// multi-device call sequences (mcd_api_ctx.hip: ncclCommInitRank / ncclCommInitAll; mcd_api_eval.hip, mcd_api_chain.hip:
+// ncclGroupStart/End, ncclAllReduce on the catalogue's streams) with REAL shards and REAL kernels.  RCCL itself refuses two ranks on one device ("invalid usage"),
 // so on the single-GPU development box the code that runs with star_begin > 0, per-shard background sums, re-run signals
 // crossing ranks etc. would otherwise never execute on a device.  Selected with MCD_RCCL_LIBRARY=<this .so>; never loaded
 // by the product otherwise.  It is NOT a performance model: results are staged through host memory (POSIX shared memory
