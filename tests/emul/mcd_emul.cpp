@@ -118,6 +118,17 @@ extern "C" int emul_fast_guard(int model, int free_centre, int f32, int64_t n, c
     return fast_level(st, model, free_centre != 0, f32 != 0, k, params, n_rows);
 }
 
+// The same verdict with the catalogue statistics gathered as mcd_catalog_create gathers them for a float64 catalogue: the
+// positions (and, for a fixed centre, the centre) enter for the profile models -- MODEL_PROFILE's narrow-range variant is
+// only admitted with the largest separation from the fixed centre known (CatalogStats::r_max_fixed)
+extern "C" int emul_fast_level_at(int model, int free_centre, int64_t n, const double* ra, const double* dec, const double* v,
+                                  const double* verr, const double* lnbg, const double* pmember, const double* density,
+                                  double ra_c, double dec_c, int k, const double* params, int64_t n_rows) {
+    const CatalogStats st = compute_stats(n, v, verr, lnbg, pmember, density, bg_kind(model), is_profile(model) ? ra : nullptr,
+                                          dec, free_centre == 0, ra_c, dec_c);
+    return fast_level(st, model, free_centre != 0, false, k, params, n_rows);
+}
+
 // float32 accuracy domain (csrc/mcd_guard.h: f32_domain): verdict, the two condition numbers and the reason
 extern "C" int emul_f32_domain(int model, int free_centre, int64_t n, const double* ra, const double* dec, const double* v,
                                const double* verr, const double* lnbg, const double* pmember, const double* density, int k,

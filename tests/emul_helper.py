@@ -144,6 +144,20 @@ def fast_level(cat, params, model, centre, f32=False):
                                      params.ctypes.data, params.shape[0]))
 
 
+def fast_level_at(cat, params, model, centre):
+    """fast_level for a float64 catalogue with its positions known, as mcd_catalog_create gathers the statistics (the
+    narrow-range variant of MODEL_PROFILE needs the stars' largest separation from the fixed centre)."""
+    L = lib()
+    L.emul_fast_level_at.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 7 + \
+        [ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64]
+    cols = [np.ascontiguousarray(cat[k], dtype=np.float64) if k in cat else None
+            for k in ("ra", "dec", "v", "verr", "lnlike_bg", "pmember", "density")]
+    params = np.ascontiguousarray(np.atleast_2d(params), dtype=np.float64)
+    rc, dc = (0.0, 0.0) if centre is None else (float(centre[0]), float(centre[1]))
+    return int(L.emul_fast_level_at(model, int(centre is None), len(cat["v"]), *[c.ctypes.data if c is not None else None for c in cols],
+                                    rc, dc, params.shape[1], params.ctypes.data, params.shape[0]))
+
+
 # ---- work decomposition (csrc/mcd_chunks.h) ---------------------------------------------------------------------
 def plan_chunks(bin_offsets, star_begin, n, n_walkers, target_waves=12288, tail_split=1, exceptions=(), balance=0):
     """The chunk table the library builds for the shard [star_begin, star_begin + n): dict of arrays + scalars."""

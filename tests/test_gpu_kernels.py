@@ -677,6 +677,20 @@ def _realistic_case(rng, n=None):
 CENTRE_RA, CENTRE_DEC = 56.345, -26.675
 
 
+# mcd_guard.h: fast_level for the 24 trials of the test below, from a CPU run of the host build of the guard
+# (tests/emul_helper.py: fast_level_at) on the same seeds: MODEL_CONST has no narrow variant, MODEL_PROFILE has one for a
+# fixed centre (even trials) only; the guard bounds the variance of the profile mixtures by verr^2 alone, so the trials of
+# models 4 and 5 with small errors beside the gross outliers take the general form or the plain kernels
+REALISTIC_LEVELS = {
+    0: [1] * 24,
+    1: [2] * 24,
+    2: [2] * 24,
+    3: [2, 1] * 12,
+    4: [1, 2, 2, 0, 1, 1, 0, 0, 1, 0, 1, 1, 1, 2, 1, 0, 0, 1, 1, 1, 2, 1, 2, 2],
+    5: [0, 2, 2, 0, 0, 1, 1, 2, 0, 2, 0, 0, 2, 1, 0, 2, 2, 1, 2, 0, 0, 1, 1, 0],
+}
+
+
 @pytest.mark.parametrize("model", [0, 1, 2, 3, 4, 5])
 def test_random_realistic_catalogues_against_the_oracle(native, ctx, model):
     """Device results (whatever kernel family the guard picks) against the NumPy restatement of the reference on random
@@ -685,6 +699,7 @@ def test_random_realistic_catalogues_against_the_oracle(native, ctx, model):
     from oracle import lnprob_numpy as oracle
     rng = np.random.default_rng(7000 + model)
     families = set()
+    expected = REALISTIC_LEVELS[model]
     for trial in range(24):
         cat, sv = _realistic_case(rng)
         n = len(cat["v"])
@@ -715,6 +730,9 @@ def test_random_realistic_catalogues_against_the_oracle(native, ctx, model):
         g = native.Catalog(ctx, cat["ra"], cat["dec"], cat["v"], cat["verr"], model=model,
                            centre=None if free else (CENTRE_RA, CENTRE_DEC), **kw)
         got = g.loglike(params)
+        # the guard's verdict for this trial; a fast mixture kernel that met the reference's denormal regime hands the
+        # batch to the plain kernels (level 0, counted in rerun_count)
+        assert g.fast_level == expected[trial] or (g.rerun_count == 1 and g.fast_level == 0), (trial, g.fast_level, expected[trial])
         families.add(g.fast_level)
         g.close()
         want = np.empty(w)
@@ -737,7 +755,7 @@ def test_random_realistic_catalogues_against_the_oracle(native, ctx, model):
         assert np.array_equal(np.isfinite(got), np.isfinite(want)), (trial, got, want)
         ok = np.isfinite(want)
         assert np.max(np.abs(got[ok] - want[ok]) / np.maximum(np.abs(want[ok]), n), initial=0.0) < 1e-12, (trial, got, want)
-    assert families <= {0, 1, 2} and (model == 0 or len(families) >= 1)
+    assert families >= set(expected), (families, set(expected))      # every family the guard chose did run on the device
 
 
 @pytest.mark.parametrize("model,precision", [(0, "f64"), (1, "f64"), (2, "f64"), (5, "f64"), (0, "f32"), (1, "f32")])
