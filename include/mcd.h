@@ -324,6 +324,15 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      catalogue inside a bounded domain (no exponent argument below -700, 16 or 32 factors between two
  *                      rescales), the narrow-range kernel with prefetch runs its bounded loop -- fewer instructions per
  *                      term, the same bits; 0 never.  mcd_last_narrow_bounded tells which loop ran.
+ *   "verr_sorted"   the main kernel of an un-binned float64 fixed-centre MODEL_CONST_BGFIXED catalogue reads a second copy of
+ *                      the records ordered by verr (one more record array in device memory, made on first use); every
+ *                      per-star output keeps catalogue order.  -1 (default): from 8 MiB of records per device, unless an
+ *                      explicit "chunk_len" pins the chunks to catalogue stars; 0 never; 1 always.  A sum over the stars in another fixed order: results agree with catalogue order to
+ *                      rounding, not bit for bit.
+ *   "root_series"   1 (default): on verr-sorted records, a chunk whose verr^2 values lie within 2^-13 (relative to
+ *                      verr^2 + sigma^2) of their midpoint for every walker of a wave takes the reciprocal root from a
+ *                      four-term series about that midpoint instead of v_rsq_f64 and a Newton step (more accurate and
+ *                      fewer issue slots per term); 0 never.  mcd_last_series_chunks counts the chunks.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -361,6 +370,11 @@ int mcd_last_prefetch(const mcd_catalog* cat);
 /* Rescale interval R (16 or 32 factors) when the most recent main-kernel launch ran the bounded narrow-range loop (option
  * "narrow_bounded"), 0 when it ran another loop, -1 before the first launch.  mcd_last_fast_level reports 2 for it. */
 int mcd_last_narrow_bounded(const mcd_catalog* cat);
+/* Chunks of the most recent main-kernel launch (summed over this process' devices) in which every wave took the series
+ * root (option "root_series"): counted on the host from the chunk table and the smallest sigma of the call's parameter
+ * table.  0 when the launch did not read verr-sorted records or ran another kernel family (and for the launches of the
+ * resident stretch-move chain, whose tables never reach the host), -1 before the first launch. */
+int64_t mcd_last_series_chunks(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

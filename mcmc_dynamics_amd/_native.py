@@ -72,6 +72,7 @@ SYMBOLS = {
     "mcd_rerun_count": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_prefetch": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_narrow_bounded": (ctypes.c_int, [ctypes.c_void_p]),
+    "mcd_last_series_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
@@ -506,6 +507,12 @@ class Catalog(object):
         """R (16 or 32): the last main-kernel launch ran the bounded narrow-range BGFIXED loop with a rescale every R
         factors (option ``narrow_bounded``); 0 another loop; -1 before any launch."""
         return self.lib.mcd_last_narrow_bounded(self.handle)
+
+    @property
+    def last_series_chunks(self):
+        """Chunks of the last main-kernel launch in which every wave took the series reciprocal root (options
+        ``verr_sorted``, ``root_series``; counted on the host); 0 none; -1 before any launch."""
+        return self.lib.mcd_last_series_chunks(self.handle)
 
     def stretch_info(self):
         """Where the blocks of ``stretch_move`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks', 'last_discard_status'}

@@ -75,6 +75,45 @@ bool wants_prefetch(const mcd_catalog* cat, const Shard& sh) {
     return bytes >= ((size_t)8 << 20);
 }
 
+// Which shards the main kernel reads in verr order (option "verr_sorted").  By record volume alone -- the
+// threshold from which the prefetching instantiation is chosen by default -- and not by the "prefetch" option, so that
+// results do not depend on that option; smaller catalogues keep catalogue order and the bits they had.
+bool wants_sorted(const mcd_catalog* cat, const Shard& sh) {
+    if (cat->model != mcd::MODEL_BGFIXED || cat->free_centre || cat->precision != MCD_F64 || cat->n_psets != 1 || sh.n <= 0)
+        return false;
+    if (cat->verr_sorted >= 0) return cat->verr_sorted != 0;
+    // an explicit "chunk_len" pins which catalogue stars form a chunk (and keeps a parameter set of a binned catalogue
+    // bit for bit equal to a stand-alone catalogue of its stars): the order is then the caller's, unless forced
+    if (cat->chunk_len > 0) return false;
+    return (size_t)sh.n * (size_t)mcd::record_bytes(cat->model, cat->free_centre, cat->precision) >= ((size_t)8 << 20);
+}
+
+// The shard's records ordered by verr^2 ascending (ties in catalogue order: a fixed permutation), made once from the
+// packed records: one round trip through host memory at the first plan that wants them.
+int ensure_sorted_records(mcd_catalog* cat, Shard& sh) {
+    if (sh.records_sorted) return MCD_OK;
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    constexpr int ND = mcd::record_doubles(mcd::MODEL_BGFIXED, false);
+    const size_t n = (size_t)sh.n, bytes = n * ND * sizeof(double);
+    MCD_HIP(hipStreamSynchronize(slot.stream));
+    std::vector<double> rec(n * ND), out(n * ND);
+    MCD_HIP(hipMemcpy(rec.data(), sh.records, bytes, hipMemcpyDeviceToHost));
+    const std::vector<int64_t> perm = mcd::verr_order(rec.data(), (int64_t)n, ND);
+    sh.sorted_e2.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        std::memcpy(&out[i * ND], &rec[(size_t)perm[i] * ND], ND * sizeof(double));
+        sh.sorted_e2[i] = out[i * ND + 1];
+    }
+    sh.sorted_exceptions = mcd::permuted_exceptions(cat->stats.narrow_exceptions, perm, sh.star_begin);
+    void* d = nullptr;
+    MCD_HIP(hipMalloc(&d, bytes + 2048));                       // (the slack of `records`)
+    hipError_t e = hipMemset(d, 0, bytes + 2048);
+    if (e == hipSuccess) e = hipMemcpy(d, out.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); MCD_HIP(e); }
+    sh.records_sorted = d;
+    return MCD_OK;
+}
+
 // The catalogue options other than the timing ones.  mcd_set_option refuses a value outside min .. max (or one that
 // `accepts` turns down) with `message`, waits for whatever is in flight where `sync` is set, stores the value, and where
 // `replan` is set (the chunk tables depend on the option) drops the work sets, which are rebuilt lazily.
@@ -100,6 +139,8 @@ const Option kOptions[] = {
     {"posterior_pass", 1, kMax, "posterior_pass must be >= 1", false, false, MCD_SET(c->posterior_pass = v)},
     {"two_lanes", kMin, kMax, nullptr, true, false, MCD_SET(c->two_lanes = v != 0)},
     {"narrow_bounded", 0, 1, "narrow_bounded: 1 (where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->narrow_bounded = (int)v)},
+    {"verr_sorted", -1, 1, "verr_sorted: -1 (by record volume, default), 0 (catalogue order) or 1 (sorted by verr)", true, true, MCD_SET(c->verr_sorted = (int)v)},
+    {"root_series", 0, 1, "root_series: 1 (series root on the narrow chunks of verr-sorted records, default) or 0 (never)", false, false, MCD_SET(c->root_series = (int)v)},
     {"prefetch", -1, 1, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)", false, false, MCD_SET(c->prefetch = (int)v)},
     {"spin_us", 0, kMax, "spin_us must be >= 0", false, false, MCD_SET(c->spin_us = v)},
     {"tail_split", kMin, kMax, nullptr, true, true, MCD_SET(c->tail_split = (int)v)},
@@ -129,7 +170,21 @@ LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& 
     // launch (no reset needed).  Several ranks / devices: the kernels poison the affected partial sums with NaN
     // instead, which travels through the reduce kernel and the all-reduce to every rank.
     shape.rerun_flag = coll ? nullptr : out_buf + n_out;
+    shape.root_series = w.sorted && cat->root_series != 0;
     return shape;
+}
+
+// the record array the main kernel reads for work set `w` (the one its chunk table was planned on)
+const void* main_records(const Shard& sh, const WorkSet& w) { return w.sorted ? sh.records_sorted : sh.records; }
+
+// Chunks of a launch of work set `w` at kernel family `level` for the parameter table `params` in which EVERY wave takes
+// the series root: the vote passes in all lanes where it passes for the smallest sigma^2 of the table.  Counted from the
+// thresholds gathered at planning time (a chunk within a rounding error of its threshold may be counted either way).
+int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows) {
+    if (!w.sorted || !cat->root_series || level != 2 || w.series_need.empty()) return 0;
+    const mcd::ParamRanges pr = mcd::table_ranges(cat->model, cat->free_centre, cat->k, params, n_rows);
+    if (!pr.finite) return 0;
+    return (int64_t)(std::upper_bound(w.series_need.begin(), w.series_need.end(), pr.s2_min) - w.series_need.begin());
 }
 
 // the fast BGFIXED kernel leaves the walker-independent sum of lnL_bg to the reduction
@@ -153,10 +208,15 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
 
     // balanced single-round plan where it pays (option "balance": -1 by the rule above, 0 never, m forced); a catalogue
     // too small for m workgroups per CU (fewer than 16 stars per chunk) takes half as many, down to the multi-round table
+    // (the narrow-range exceptions and the series thresholds below belong to the array the kernel reads)
+    const bool sorted = wants_sorted(cat, sh);
+    if (sorted)
+        if (int rc = ensure_sorted_records(cat, sh)) return rc;
+    const std::vector<int64_t>& exceptions = sorted ? sh.sorted_exceptions : cat->stats.narrow_exceptions;
     mcd::ChunkPlan plan;
     for (int m = cat->balance < 0 ? balance_auto_m(cat, sh.n, n_walkers) : cat->balance;; m /= 2) {
         plan = mcd::plan_chunks(cat->bin_offsets, sh.star_begin, sh.n, n_walkers, cat->target_waves, cat->tail_split,
-                                cat->stats.narrow_exceptions, cat->chunk_len, m);
+                                exceptions, cat->chunk_len, m);
         if (m == 0 || plan.balanced_m > 0) break;
     }
     const std::vector<mcd::Chunk>& chunks = plan.chunks;
@@ -169,6 +229,8 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
     w.max_chunks_per_pset = plan.max_chunks_per_pset;
     w.uniform_len = plan.uniform_len;
     w.uniform_extra = plan.uniform_extra;
+    w.sorted = sorted;
+    if (sorted) w.series_need = mcd::series_thresholds(plan, sh.sorted_e2.data());
     {
         // balanced plans with an even number of workgroups per CU run as half as many 8-wave workgroups that add their
         // chunks' sums up themselves: half (to an eighth of) the partial sums per walker (mcd_kernels.hip: loglike_kernel)
@@ -356,6 +418,7 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
         (void)hipStreamSynchronize(cat->ctx->slots[sh.slot].stream2);
         for (auto& kv : sh.work) free_workset(kv.second);
         if (sh.records) (void)hipFree(sh.records);
+        if (sh.records_sorted) (void)hipFree(sh.records_sorted);
         if (sh.d_pset_const) (void)hipFree(sh.d_pset_const);
         if (sh.ev_begin) (void)hipEventDestroy(sh.ev_begin);
         if (sh.ev_k0) (void)hipEventDestroy(sh.ev_k0);
@@ -471,6 +534,8 @@ int mcd_stretch_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* ho
 }
 
 int mcd_last_prefetch(const mcd_catalog* cat) { return cat ? cat->last_prefetch : -1; }
+
+int64_t mcd_last_series_chunks(const mcd_catalog* cat) { return cat ? cat->last_series_chunks : -1; }
 
 int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
 

@@ -216,6 +216,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     double* const out_buf = w.d_out;
     mcd::LaunchShape shape = main_launch_shape(cat, sh, w, level, coll, out_buf, (int64_t)Bh);
     cat->last_narrow_bounded = 0;                      // (the resident chain keeps the narrow-range loop with its clamp)
+    cat->last_series_chunks = 0;                       // (its tables are built on the device: no host count)
     const double* pset_const = fast_pset_const(cat, sh, level);
     // launches with few partial sums per walker (balanced plans of small catalogues, radial bins of a few chunks): no
     // reduction kernel, the step kernel adds them up itself -- the same code in the same order (mcd_reduce.h), so the
@@ -250,7 +251,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
                 if (mark && i == i0 && h == 0) MCD_HIP(hipEventRecord(mark, slot.stream));
                 prev_tag = coll ? 0.0 : (double)(++cat->launch_seq);
                 shape.launch_tag = prev_tag;
-                MCD_HIP(mcd::launch_loglike(slot.stream, shape, sh.records, w.d_chunks, w.n_chunks, w.d_wpar, w.d_partials, half));
+                MCD_HIP(mcd::launch_loglike(slot.stream, shape, main_records(sh, w), w.d_chunks, w.n_chunks, w.d_wpar, w.d_partials, half));
                 if (!fused)
                     MCD_HIP(mcd::launch_reduce(slot.stream, w.d_partials, w.d_offsets, B, n_slots, max_slots, half, pset_const,
                                                out_buf));

@@ -109,6 +109,7 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
         w->lane1_knows_staging = false;
         w->fast = fast;
         w->narrow_rescale = narrow_rescale;
+        w->series_chunks = series_chunk_count(cat, *w, fast, params, n_rows);
         w->staged = true;
     }
     cat->cur_walkers = n_walkers;
@@ -170,6 +171,8 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         mcd::LaunchShape shape = main_launch_shape(cat, sh, w, w.fast, coll, out_buf, n_out);
         shape.narrow_rescale = cat->narrow_bounded ? w.narrow_rescale : 0;
         cat->last_narrow_bounded = mcd::narrow_bounded_launch(shape) ? shape.narrow_rescale : 0;
+        if (&sh == &cat->shards.front()) cat->last_series_chunks = 0;
+        cat->last_series_chunks += shape.root_series && shape.fast == 2 ? w.series_chunks : 0;
         w.launch_tag = coll ? 0.0 : (double)(++cat->launch_seq);
         shape.launch_tag = w.launch_tag;
         hipEvent_t k0 = sh.ev_k0, k1 = sh.ev_k1;
@@ -189,7 +192,7 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         }
         if (cat->timing && !cat->timing_all) MCD_HIP(hipEventRecord(sh.ev_begin, slot.stream));
         if (cat->timing && sampled) MCD_HIP(hipEventRecord(k0, lane_stream));
-        MCD_HIP(mcd::launch_loglike(lane_stream, shape, sh.records, w.d_chunks, w.n_chunks, w.d_wpar, lane_partials, W));
+        MCD_HIP(mcd::launch_loglike(lane_stream, shape, main_records(sh, w), w.d_chunks, w.n_chunks, w.d_wpar, lane_partials, W));
         if (cat->timing && sampled) MCD_HIP(hipEventRecord(k1, lane_stream));
         const double* pset_const = fast_pset_const(cat, sh, w.fast);
         // With a collective this step may only overwrite its result buffer once the all-reduce that last used it has

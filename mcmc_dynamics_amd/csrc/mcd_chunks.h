@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <vector>
 
 namespace mcd {
@@ -186,6 +187,54 @@ inline ChunkPlan plan_chunks(const std::vector<int64_t>& bin_offsets, int64_t st
         if (!any) plan.general.clear();
     }
     return plan;
+}
+
+// ---- verr-sorted record array of the main kernel (f64 MODEL_BGFIXED, fixed centre, one parameter set) ----
+// Order of the records by their verr^2 slot (slot 1 of `nd` doubles), ascending, ties in catalogue order (NaN last):
+// perm[i] = catalogue index (within the shard) of the i-th record of the sorted array.
+inline std::vector<int64_t> verr_order(const double* records, int64_t n, int nd) {
+    std::vector<int64_t> perm((size_t)n);
+    for (int64_t i = 0; i < n; ++i) perm[(size_t)i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
+        const double x = records[a * nd + 1], y = records[b * nd + 1];
+        return x < y || (y != y && x == x);
+    });
+    return perm;
+}
+
+// narrow_exceptions (ascending global star indices) of the shard starting at star_begin, as positions in its sorted
+// array + star_begin, ascending: what plan_chunks takes for a table planned on that array
+inline std::vector<int64_t> permuted_exceptions(const std::vector<int64_t>& narrow_exceptions, const std::vector<int64_t>& perm,
+                                                int64_t star_begin) {
+    std::vector<int64_t> out;
+    if (narrow_exceptions.empty()) return out;
+    const int64_t n = (int64_t)perm.size();
+    std::vector<int64_t> inverse((size_t)n);
+    for (int64_t i = 0; i < n; ++i) inverse[(size_t)perm[(size_t)i]] = i;
+    for (int64_t g : narrow_exceptions)
+        if (g >= star_begin && g < star_begin + n) out.push_back(star_begin + inverse[(size_t)(g - star_begin)]);
+    std::sort(out.begin(), out.end());
+    return out;
+}
+
+// Smallest sigma^2 with which a chunk whose verr^2 runs from e_first to e_last passes the series vote of the main kernel
+// (mcd_math.h: RootSeries::setup_chunk: half-width <= 2^-13 (centre + sigma^2)), up to rounding
+inline double series_threshold(double e_first, double e_last) {
+    const double need = 0.5 * (e_last - e_first) * 0x1p13 - (0.5 * e_first + 0.5 * e_last);
+    return need == need ? need : std::numeric_limits<double>::infinity();
+}
+
+// ... of every chunk of `plan` that is not flagged general, on the sorted verr^2 column the plan was made for; ascending
+inline std::vector<double> series_thresholds(const ChunkPlan& plan, const double* sorted_e2) {
+    std::vector<double> need;
+    need.reserve(plan.chunks.size());
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const Chunk& ch = plan.chunks[c];
+        if (ch.count <= 0 || (!plan.general.empty() && plan.general[c])) continue;
+        need.push_back(series_threshold(sorted_e2[ch.begin], sorted_e2[ch.begin + ch.count - 1]));
+    }
+    std::sort(need.begin(), need.end());
+    return need;
 }
 
 // Walker-independent part of the fixed-background likelihoods: sum of lnL_bg over the shard's stars of each parameter

@@ -127,6 +127,10 @@ struct WorkSet {
     int fast = 0;                      // mcd::LaunchShape::fast level of the staged batch
     int narrow_rescale = 0;            // its bounded narrow-range verdict (mcd_guard.h: bounded_rescale; R or 0)
     bool staged = false;
+    bool sorted = false;               // planned on, and launched with, the shard's verr-sorted records (Shard::records_sorted)
+    std::vector<double> series_need;   // sorted: per chunk outside chunk_general, the smallest sigma^2 with which its verr^2
+                                       // band passes the series vote (mcd_math.h: RootSeries), ascending
+    int64_t series_chunks = 0;         // chunks of the staged batch every wave of which takes the series root
 };
 
 // device arena of the resident stretch-move chain and its pinned host mirror (same layout, see stretch_block_device)
@@ -141,6 +145,12 @@ struct Shard {
     int64_t star_begin = 0;            // global index of the first star held here
     int64_t n = 0;
     void* records = nullptr;
+    // The same records ordered by verr ascending, read by the main kernel only (option "verr_sorted"; built on first use by
+    // ensure_sorted_records): every kernel that reports per star keeps `records`, i.e. catalogue order.
+    void* records_sorted = nullptr;
+    std::vector<double> sorted_e2;            // verr^2 of records_sorted, in its order
+    std::vector<int64_t> sorted_exceptions;   // CatalogStats::narrow_exceptions of this shard as positions in records_sorted
+                                              // (+ star_begin, ascending: what plan_chunks takes)
     double* d_pset_const = nullptr;    // BGFIXED: sum of lnlike_bg over this shard's stars of each parameter set
     std::map<int64_t, WorkSet> work;   // keyed by walker count
     hipEvent_t ev_begin = nullptr, ev_k0 = nullptr, ev_k1 = nullptr, ev_end = nullptr;
@@ -183,6 +193,8 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
 LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& w, int level, bool coll, double* out_buf,
                               int64_t n_out);
 const double* fast_pset_const(const mcd_catalog* cat, const Shard& sh, int level);
+const void* main_records(const Shard& sh, const WorkSet& w);
+int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
 // mcd_api_eval.hip
 int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
 int sync_all(mcd_catalog* cat);
@@ -231,6 +243,9 @@ struct mcd_catalog {
     int prefetch = -1;                 // option "prefetch": -1 by record volume (>= 8 MiB per device), 0 off, 1 on
     int narrow_bounded = 1;            // option "narrow_bounded": 1 the bounded narrow-range BGFIXED loop where the guard
                                        // admits it (mcd_guard.h: bounded_rescale), 0 never
+    int verr_sorted = -1;              // option "verr_sorted": the main kernel reads a verr-sorted copy of the records (f64
+                                       // MODEL_BGFIXED, fixed centre, one parameter set): -1 from 8 MiB of records per device, 0 never, 1 always
+    int root_series = 1;               // option "root_series": 1 the series root on the sorted records' narrow chunks, 0 never
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
                                        // small enough, 0 never, m > 0 forced with m workgroups per CU
     int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
@@ -261,6 +276,7 @@ struct mcd_catalog {
     int chain_last_status = 0;         // status word of the last discarded block (mcd::ChainStatus bits)
     std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
+    int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };
 

@@ -25,6 +25,8 @@ struct LaunchShape {
     bool prefetch = false;          // software prefetch of the next iteration's records (catalogues beyond the caches)
     int narrow_rescale = 0;         // fast == 2, MODEL_BGFIXED, fixed centre, f64: R = 16 or 32 runs the bounded loop of the
                                     // prefetching kernel (mcd_guard.h: bounded_rescale), 0 the narrow-range loop as is
+    bool root_series = false;       // the records are sorted by verr and the level-2 BGFIXED fixed-centre loops may take the
+                                    // per-chunk series root (mcd_math.h: RootSeries); f64 only
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };

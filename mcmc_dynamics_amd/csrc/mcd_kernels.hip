@@ -113,6 +113,7 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // BGGAUSS kernels (106 - 127 with 4 waves) and the occupancy drops from 4 to 3 waves per SIMD.
 // BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_loglike<.., BOUNDED>)
 // for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
+// root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries).
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
 __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
                                                                  const Chunk* __restrict__ chunks,
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
                                                                  int uniform_len, int uniform_extra, int64_t n_records,
                                                                  double* __restrict__ rerun_flag, double launch_tag,
                                                                  const uint8_t* __restrict__ chunk_general,
-                                                                 int64_t n_slots, int narrow_iters) {
+                                                                 int64_t n_slots, int narrow_iters, int root_series) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int kThreads = WAVES * kWave;
     constexpr bool kCombine = WAVES > kWavesPerBlock;
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
             if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
             else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(chunk_recs, ch.count, w, denormal,
-                                                                                         exptab_lds, narrow_iters);
+                                                                                         exptab_lds, narrow_iters, root_series != 0);
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }
@@ -336,7 +337,7 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
     hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
-                       sh.chunk_general, n_slots, narrow_iters)
+                       sh.chunk_general, n_slots, narrow_iters, (int)sh.root_series)
     if constexpr (kCanCombine) {
         if (combine && sh.waves == 8) {
             if (bounded) MCD_LAUNCH_MAIN(true, 8, kCanBound);

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "mcd_exp_table.h"
 
@@ -631,6 +632,60 @@ MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
     return add_hi_word(t, kh) * p;
 }
 
+// Rotate-free reciprocal root of the level-2 BGFIXED fixed-centre loops on a verr-sorted record array.
+//   g_i = (2 (e_i + s2))^(-1/2),  e_i = verr_i^2 (record, wave-uniform),  s2 = sigma^2 (per lane, constant over a chunk).
+// On a chunk whose e_i all lie within a narrow band around a centre eb (sorted array: the midpoint of its first and last
+// record), with m0 = 8 (eb + s2), delta = e_i - eb, t = 8 delta / m0 and G0 = 2 m0^(-1/2):
+//   g = G0 (1 - t/2 + 3 t^2/8 - 5 t^3/16) + R,  |R| <= 35/128 t^4 G0  (<= 6.1e-17 relative for |t| <= 2^-13),
+// i.e. a cubic in delta with four per-lane coefficients set up once per chunk: one subtraction and three fused
+// multiply-adds per term instead of the variance, v_rsq_f64 and the Newton step (8 issue slots).  Error: the rounding of
+// b0 and of the last FMA (2^-53 each) plus the truncation, < 2.9e-16 relative -- the one-step Newton form it replaces is low by up to
+// 4.1e-15.  The rounding error of m0 itself (an exact two-sum) is folded into b0.
+struct RootSeries {
+    static constexpr double kMaxT = 0x1p-13;
+    double eb, b0, b1, b2, b3;
+    // coefficients about the centre eb for this lane's s2; false when s2 puts a band of half-width `half` outside |t| <= 2^-13
+    MCD_HD bool setup(double eb_, double half, double s2) {
+        eb = eb_;
+        const double p = 8.0 * eb, s2x = 8.0 * s2;                 // exact
+        const double m0 = p + s2x;
+        const double bb = m0 - p;
+        const double err = (p - (m0 - bb)) + (s2x - bb);          // m0 + err = p + s2x exactly
+        const double inv = rcp_nr(m0);
+        // b0 = 2 (m0 + err)^(-1/2) with ONE rounding: y is within an ulp of m0^(-1/2), its residual 1 - m0 y^2 comes out
+        // exactly (h + eh = m0 y without rounding), and both first-order corrections enter through the last FMA
+        const double y = rsqrt_nr(m0);
+        const double h = m0 * y;
+        const double eh = fma_(m0, y, -h);
+        const double res = fma_(-h, y, 1.0) - eh * y;
+        const double G0 = 2.0 * y;
+        const double q = 8.0 * inv;                                // t = q delta
+        b0 = fma_(G0, 0.5 * (res - err * inv), G0);
+        b1 = -0.5 * (G0 * q);
+        b2 = -0.75 * (b1 * q);
+        b3 = (-5.0 / 6.0) * (b2 * q);
+        return half >= 0.0 && 8.0 * half <= kMaxT * m0;            // (false for NaN)
+    }
+    // the chunk's records run from e_first to e_last (ascending)
+    MCD_HD bool setup_chunk(double e_first, double e_last, double s2) {
+        return setup(0.5 * e_first + 0.5 * e_last, 0.5 * (e_last - e_first), s2);
+    }
+    MCD_HD double g(double e) const {
+        const double delta = e - eb;
+        return fma_(fma_(fma_(b3, delta, b2), delta, b1), delta, b0);
+    }
+};
+
+// true when `ok` holds in every active lane of the wave (one s_cmp on the ballot: callers branch on the scalar unit);
+// host build: the caller has combined the lanes (tests/emul)
+MCD_HD bool wave_all(bool ok) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(!ok) == 0;
+#else
+    return ok;
+#endif
+}
+
 // x == +-0 tested on the bit pattern: for a wave-uniform x (SGPR pair) this stays on the scalar unit.
 MCD_HD bool is_zero_bits(double x) {
     uint64_t b;
@@ -706,6 +761,11 @@ struct BgFixedAcc {
     MCD_HD void add(double d, double n, double omp, double nbp, const double* __restrict__ exptab) {
         // NARROW + HALVED: the caller passes 8 n and the one-step Newton form returns 2 (8 n)^-1/2 = (2 n)^-1/2
         const double g = (NARROW && HALVED) ? rsqrt2_newton(n) : rsqrt_nr(n);
+        add_g<UNIFORM_OMP, HALVED, NARROW, TAB_BIASED, CLAMP>(d, g, omp, nbp, exptab);
+    }
+    // the same with the reciprocal root g given (HALVED: (2 n)^-1/2; the series loops, RootSeries::g)
+    template <bool UNIFORM_OMP = true, bool HALVED = false, bool NARROW = false, bool TAB_BIASED = false, bool CLAMP = true>
+    MCD_HD void add_g(double d, double g, double omp, double nbp, const double* __restrict__ exptab) {
         const double dg = d * g;
         // u <= 1e5 by the host guard (|lnL_bg| <= 1e5); below -1100 e^u is an exact 0 in f64 (as in the reference),
         // and the clamp keeps u N / ln 2 inside the int range of exp_tab.
@@ -1024,9 +1084,11 @@ MCD_HD constexpr bool exp_table_is_sqrt2_scaled(int model) { return model == MOD
 // TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
 // BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
 // narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
+// `series` (MODEL_BGFIXED, fixed centre, FAST == 2, f64): the records are sorted by verr, so a chunk whose verr^2 band is
+// narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote.
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
-                            const double* __restrict__ exptab, int rescale_iters = 1) {
+                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false) {
     constexpr int ND = record_doubles(MODEL, FREE);
     denormal = false;
     constexpr int XB = geometry_doubles(MODEL, FREE);      // first background slot of a record
@@ -1212,18 +1274,26 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         const double scale = BOUNDED ? vgpr_constant(kScale) : kScale;
         BgFixedAcc acc;
         acc.init();
-        auto four = [&](RecPtr<double> r4) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                RecPtr<double> rr = r4 + j * ND;
-                double d, n;
-                star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-                if constexpr (HALVED) n = fma_(scale, rr[1], s2x);
+        // SERIES (a type: std::true_type / std::false_type): the reciprocal root from the chunk's RootSeries instead of
+        // v_rsq_f64 and the Newton step; everything after g is the same code
+        RootSeries sr;
+        auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
+            double d, n;
+            star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
+            if constexpr (decltype(SERIES)::value) {
+                acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, sr.g(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
+            } else {
+                if constexpr (HALVED) n = fma_(sc, rr[1], s2x);
                 acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
             }
         };
+        auto four = [&](RecPtr<double> r4, auto SERIES) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
+        };
         const int n4 = count >> 2;
         static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
+        auto run = [&](auto SERIES) {
         if constexpr (BOUNDED) {
             // bounded sub-variant: every mixture value lies in [y_lo, y_hi] with R log2(y_hi) <= 1000 and
             // 1 + R (-log2 y_lo) <= 1000 (mcd_guard.h: bounded_rescale), so R = 8 rescale_iters raw factors fit between
@@ -1235,14 +1305,14 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
                 RecordPrefetch<8 * ND * 8, PF> pf;
                 pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
-                four(r);
-                four(r + 4 * ND);
+                four(r, SERIES);
+                four(r + 4 * ND, SERIES);
                 pf.retire(acc.l.p);
                 if (--until == 0) { until = rescale_iters; MCD_KEEP_BRANCH(); acc.rescale_narrow(); }
             }
             acc.rescale_narrow();
             if (n4 & 1) {
-                four(r);
+                four(r, SERIES);
                 r += 4 * ND;
                 acc.rescale_narrow();
             }
@@ -1255,20 +1325,20 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
                 RecordPrefetch<8 * ND * 8, PF> pf;
                 pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
-                four(r);
-                four(r + 4 * ND);
+                four(r, SERIES);
+                four(r + 4 * ND, SERIES);
                 pf.retire(acc.l.p);
                 acc.rescale_narrow();
             }
             if (n4 & 1) {
-                four(r);
+                four(r, SERIES);
                 r += 4 * ND;
                 acc.rescale_narrow();
             }
         } else if constexpr (NARROW) {
             // eight raw factors per rescale: every second 4-star group (one scalar record-load batch each)
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
-                four(r);
+                four(r, SERIES);
                 if (g & 1) { MCD_KEEP_BRANCH(); acc.rescale_narrow(); }    // wave-uniform: a scalar branch, not a select
             }
             if (n4 & 1) acc.rescale_narrow();
@@ -1276,17 +1346,33 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
                 pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
-                four(r);
+                four(r, SERIES);
                 pf.retire(acc.l.p);
                 acc.rescale();
             }
         }
         for (int j = n4 * 4; j < count; ++j, r += ND) {
-            double d, n;
-            star_d_n<MODEL, double, FREE, true>(r, w, d, n);
-            if constexpr (HALVED) n = fma_(kScale, r[1], s2x);
-            acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, r[XB + 2], r[XB + 3], exptab);
+            one(r, SERIES, kScale);
             acc.rescale();
+        }
+        };
+        // The series form where every lane's sigma^2 keeps the chunk's verr^2 band inside |t| <= 2^-13 (RootSeries): the
+        // verdict depends on the chunk's first and last record and the wave's walkers alone, so the 4-star, the 8-star and
+        // the bounded loop decide alike and stay bitwise equal to each other.  `series`: the records are sorted by verr
+        // (host: LaunchShape::root_series).
+        constexpr bool kCanSeries = NARROW && MODEL == MODEL_BGFIXED && !FREE;
+        bool use_series = false;
+        if constexpr (kCanSeries) {
+            if (series && count > 0) {
+                const bool ok = sr.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], (double)w.s2);
+                use_series = wave_all(ok);
+            }
+        }
+        if constexpr (kCanSeries) {
+            if (use_series) { MCD_KEEP_BRANCH(); run(std::true_type()); }
+            else run(std::false_type());
+        } else {
+            run(std::false_type());
         }
         result = acc.finish();
         denormal = acc.denormal();

@@ -11,7 +11,10 @@ iteration (a block behind a scalar branch): their count is (2 x loop body + resc
 narrow-range instantiation runs 8-star iterations with the rescale inside the loop body; its bounded sub-variant (template
 parameter BOUNDED, the last one of the mangled name) rescales every fourth 8-star iteration at C3's R = 32, in a block the
 loop branches out to: (4 x loop body + rescale block) / 32.  That instantiation is what C3's timed launches run, so it
-gives the "bgfixed" key's prefetch fields; the level-2 prefetching loop keeps its row under "bgfixed_level2".
+keeps its row under "bgfixed_rsq"; the level-2 prefetching loop keeps its row under "bgfixed_level2".  Each of the three
+kernels also holds the series form of its loop (mcd_math.h: RootSeries; the chunks of a verr-sorted record array whose
+verr^2 band is narrow): rows "..., series".  The bounded series loop is what nearly all of C3's chunks run, so it gives the
+"bgfixed" key's prefetch fields.
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -60,7 +63,18 @@ KERNELS = [
 ]
 
 # the bounded narrow-range loop (prefetching instantiation only): full tag, name, key, stars, trips, selector
-BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded", "bgfixed", 8, 4, _sel(rsq=8, frexp=0))
+BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded", "bgfixed_rsq", 8, 4, _sel(rsq=8, frexp=0))
+
+# the series loops of the same three kernels (mcd_math.h: RootSeries; chunks of a verr-sorted record array whose verr^2
+# band is narrow): no v_rsq_f64 in the body.  Full tag, name, key, stars, trips, selector, prefetching, bounded
+SERIES = [
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, series", "bgfixed_series", 4, 2, _sel(rsq=0, frexp=0), False, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, series", "bgfixed_series", 8, 1, _sel(rsq=0, frexp=1),
+     True, False),
+    # what C3's timed launches run on the chunks that qualify (98 % of them): the "bgfixed" key's prefetch fields
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, series", "bgfixed", 8, 4, _sel(rsq=0, frexp=0),
+     True, True),
+]
 
 
 def _ops(lines):
@@ -121,8 +135,10 @@ def analyse(out="/tmp/isa_mix"):
     variants = [(row[0] + "Lb0ELi4ELb0EE", row[1], row[2], row[3], row[4], row[5], False) for row in KERNELS]
     variants += [(row[0] + "Lb1ELi4ELb0EE", row[1] + ", prefetch", row[7] if len(row) > 7 else row[2]) +
                  (row[6] if len(row) > 6 else row[3:6]) + (True,) for row in KERNELS]
-    variants.append(BOUNDED + (True,))
-    for tag, name, key, per, trips, selector, with_prefetch in variants:
+    variants = [v + (False,) for v in variants]
+    variants.append(BOUNDED + (True, True))
+    variants += SERIES
+    for tag, name, key, per, trips, selector, with_prefetch, bounded in variants:
         starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag)]
         if not starts:
             continue
@@ -139,13 +155,15 @@ def analyse(out="/tmp/isa_mix"):
         ranked = sorted(inner, key=lambda sp: sp[1] - sp[0], reverse=True)
         best = None
         if selector is not None:
-            hits = [sp for sp in ranked if selector(Counter(_ops(k[sp[0]:sp[1]])))]
+            # (the longest loop the selector accepts that does real work: the series loops share their kernels with short
+            # copy and tail loops without a v_rsq_f64 either)
+            hits = [sp for sp in ranked if selector(Counter(_ops(k[sp[0]:sp[1]]))) and sp[1] - sp[0] >= 8 * per]
             best = hits[0] if hits else None
         if best is None:
             best = ranked[0]
         body = Counter(_ops(k[best[0]:best[1] + 1]))
         extra = Counter()
-        blk = rescale_block(k, labels, best, tag == BOUNDED[0], trips)
+        blk = rescale_block(k, labels, best, bounded, trips)
         if blk:
             extra = Counter(_ops(k[blk[0]:blk[1]]))
         terms = per * trips
