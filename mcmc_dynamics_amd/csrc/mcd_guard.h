@@ -305,7 +305,7 @@ MCD_HD int level_verdict(const StatsScalars& st, int model, bool f32, int64_t n_
     return 1;
 }
 
-// Bounded sub-variant of the narrow-range BGFIXED loop (chunk_loglike<.., BOUNDED>): R = 32 or 16 raw factors between two
+// Bounded sub-variant of the narrow-range BGFIXED loop (chunk_bgfixed_fast<.., BOUNDED>): R = 32 or 16 raw factors between two
 // rescales and no exponent clamp in exp_tab_scaled; 0 = the level-2 loop as it is.  Only for level 2, MODEL_BGFIXED and
 // a fixed centre; the chunks flagged general still take the general form.  Same bits as level 2 wherever it is admitted.
 //   Clamp: the exponent argument is u = nbp - (d g)^2 (HALVED form, g = (2 n)^-1/2), so u >= nbp_min - d_max^2 / (2 n_min).

@@ -12,6 +12,8 @@
 //
 // The kernel is bound by the f64 VALU issue rate, not by HBM: the catalogue (32..64 B/star) is read
 // once per 64..256 walkers.  MFMA has nothing to offer here (no contraction).
+#include <type_traits>
+
 #include "mcd_internal.h"
 #include "mcd_math.h"
 #include "mcd_prep.h"
@@ -111,7 +113,7 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // add up itself (mcd_stretch.hip) and for a one-wave-per-group reduction.  The second launch bound (minimum waves per
 // SIMD) keeps the register budget of the 4-wave kernel: left alone, the compiler spends up to 150 VGPRs on the 8-wave
 // BGGAUSS kernels (106 - 127 with 4 waves) and the occupancy drops from 4 to 3 waves per SIMD.
-// BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_loglike<.., BOUNDED>)
+// BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_bgfixed_fast<.., BOUNDED>)
 // for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
 // root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries).
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
@@ -338,29 +340,24 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
                        sh.chunk_general, n_slots, narrow_iters, (int)sh.root_series)
+    // bounded, else prefetch, else plain -- once, for a workgroup of decltype(waves)::value waves
+    auto launch = [&](auto waves) {
+        constexpr int W = decltype(waves)::value;
+        if (bounded) MCD_LAUNCH_MAIN(true, W, kCanBound);
+        else if (FAST != 0 && sh.prefetch) MCD_LAUNCH_MAIN((FAST != 0), W, false);
+        else MCD_LAUNCH_MAIN(false, W, false);
+        return hipGetLastError();
+    };
+#undef MCD_LAUNCH_MAIN
     if constexpr (kCanCombine) {
-        if (combine && sh.waves == 8) {
-            if (bounded) MCD_LAUNCH_MAIN(true, 8, kCanBound);
-            else if (sh.prefetch) MCD_LAUNCH_MAIN(true, 8, false);
-            else MCD_LAUNCH_MAIN(false, 8, false);
-            return hipGetLastError();
-        }
+        if (combine && sh.waves == 8) return launch(std::integral_constant<int, 8>());
         // 16 waves: 1024 threads, at most 128 VGPRs -- the kernels of the per-walker Gaussian background need more
         if constexpr (bg_kind(MODEL) != BG_GAUSS) {
-            if (combine && sh.waves == 16) {
-                if (bounded) MCD_LAUNCH_MAIN(true, 16, kCanBound);
-                else if (sh.prefetch) MCD_LAUNCH_MAIN(true, 16, false);
-                else MCD_LAUNCH_MAIN(false, 16, false);
-                return hipGetLastError();
-            }
+            if (combine && sh.waves == 16) return launch(std::integral_constant<int, 16>());
         }
         if (combine) return hipErrorInvalidValue;
     }
-    if (bounded) MCD_LAUNCH_MAIN(true, kWavesPerBlock, kCanBound);
-    else if (FAST != 0 && sh.prefetch) MCD_LAUNCH_MAIN((FAST != 0), kWavesPerBlock, false);
-    else MCD_LAUNCH_MAIN(false, kWavesPerBlock, false);
-#undef MCD_LAUNCH_MAIN
-    return hipGetLastError();
+    return launch(std::integral_constant<int, kWavesPerBlock>());
 }
 
 template <int MODEL, bool FREE>

@@ -95,24 +95,48 @@ MCD_HD constexpr int record_doubles(int model, bool free_centre) {
 
 constexpr double kArcsecPerRad = 206264.80624709635516;   // 10800 / pi arcmin x 60: r0 of calc_xy_offset.py:11 in arcsec
 
-template <class T>
-MCD_HD T fma_(T a, T b, T c) {
+// ---------------------------------------------------------------------------------------------
+// Host/device shims, once each: the builtin (or HIP's overload) in the device pass, libm in the host pass (tests/emul).
 #if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_fma(a, b, c);
+#define MCD_ON_DEVICE(device_expr, host_expr) (device_expr)
 #else
-    return std::fma(a, b, c);
+#define MCD_ON_DEVICE(device_expr, host_expr) (host_expr)
 #endif
-}
-MCD_HD float fma_(float a, float b, float c) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_fmaf(a, b, c);
-#else
-    return std::fmaf(a, b, c);
-#endif
+template <class T> MCD_HD T fma_(T a, T b, T c) { return MCD_ON_DEVICE(__builtin_fma(a, b, c), std::fma(a, b, c)); }
+MCD_HD float fma_(float a, float b, float c) { return MCD_ON_DEVICE(__builtin_fmaf(a, b, c), std::fmaf(a, b, c)); }
+template <class T> MCD_HD T sqrt_(T x) { return MCD_ON_DEVICE(sqrt(x), std::sqrt(x)); }
+template <class T> MCD_HD T log_(T x) { return MCD_ON_DEVICE(log(x), std::log(x)); }
+template <class T> MCD_HD T exp_(T x) { return MCD_ON_DEVICE(exp(x), std::exp(x)); }
+MCD_HD double frexp_(double x, int* e) { return MCD_ON_DEVICE(__builtin_frexp(x, e), std::frexp(x, e)); }
+MCD_HD float frexp_(float x, int* e) { return MCD_ON_DEVICE(__builtin_frexpf(x, e), std::frexp(x, e)); }
+MCD_HD double ldexp_(double x, int k) { return MCD_ON_DEVICE(__builtin_ldexp(x, k), std::ldexp(x, k)); }
+MCD_HD double fmin_(double a, double b) { return MCD_ON_DEVICE(__builtin_fmin(a, b), std::fmin(a, b)); }     // v_min_f64
+MCD_HD double fmax_(double a, double b) { return MCD_ON_DEVICE(__builtin_fmax(a, b), std::fmax(a, b)); }     // v_max_f64
+MCD_HD double fabs_(double a) { return MCD_ON_DEVICE(__builtin_fabs(a), std::fabs(a)); }         // source modifier, no instruction
+template <class T> MCD_HD T max_(T a, T b) { return a > b ? a : b; }
+// the hardware estimates; measured max rel. error on gfx950 (tools/rsq_probe.hip): v_rsq_f64 2^-24.2, v_rcp_f64 2^-24.4
+MCD_HD double rsq_(double x) { return MCD_ON_DEVICE(__builtin_amdgcn_rsq(x), 1.0 / std::sqrt(x)); }
+MCD_HD double rcp_(double x) { return MCD_ON_DEVICE(__builtin_amdgcn_rcp(x), 1.0 / x); }
+MCD_HD float rsqf_(float x) { return MCD_ON_DEVICE(__builtin_amdgcn_rsqf(x), 1.0f / std::sqrt(x)); }
+// v_exp_f32; arguments below -126 / ln 2 flush to 0
+MCD_HD float expf_(float x) { return MCD_ON_DEVICE(__builtin_amdgcn_exp2f(x * 1.44269504088896340736f), std::exp(x)); }
+#undef MCD_ON_DEVICE          // textual selection: the other arm is never parsed -- for the one-line shims above only
+
+// n^(-1/2): v_rsq_f64 and one third-order step: with e = 1 - n y^2 (|e| <= 2^-23.2),  n^-1/2 = y (1 + e/2 + 3 e^2/8 + O(e^3)),
+// remaining error 5/16 e^3 < 2^-71: full f64 after the final rounding.  5 instructions.
+MCD_HD double rsqrt_nr(double n) {
+    const double y = rsq_(n);
+    const double e = fma_(-(n * y), y, 1.0);
+    const double t = fma_(0.375, e, 0.5);
+    return fma_(y, t * e, y);
 }
 
-MCD_HD double rsqrt_nr(double n);
-MCD_HD double rcp_nr(double x);
+// 1/x = y (1 + e + e^2 + O(e^3)),  y from v_rcp_f64,  e = 1 - x y
+MCD_HD double rcp_nr(double x) {
+    const double y = rcp_(x);
+    const double e = fma_(-x, y, 1.0);
+    return fma_(y, fma_(e, e, e), y);
+}
 
 // Free centre: tangent-plane offsets of calc_xy_offset.py:30-31 (in units of r0) from per-star products prepared at
 // upload, A = cos(dec) sin(ra), B = cos(dec) cos(ra), sd = sin(dec), and the walker's sin/cos of the centre:
@@ -139,11 +163,7 @@ MCD_HD T free_centre_residual(T A, T B, T sd, T sac, T cac, T sdc, T cdc, T vx, 
     if constexpr (FASTMATH && sizeof(T) == 8) {
         inv = (T)rsqrt_nr((double)r2);            // offsets are O(1e-9 .. 1) rad: r2 is a normal number (or exactly 0)
     } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-        inv = T(1) / sqrt(r2);
-#else
-        inv = T(1) / std::sqrt(r2);
-#endif
+        inv = T(1) / sqrt_(r2);
     }
     const T cross = fma_(vx, y, -(vy * x));
     const T general = fma_(-cross, inv, v_minus_vsys);
@@ -193,18 +213,7 @@ MCD_HD double fmax_raw(double x, double lo) {
 // wave's work at 100 stars per chunk).  The absolute error, ~1e-16, sits far below one ulp of what it is added to
 // (exponent x ln 2).  Anything else (0 from an underflowed product, inf, NaN) takes libm's log and its special cases.
 MCD_HD double log_unit(double m) {
-#ifdef MCD_LIBM_LOG_UNIT                     // A/B build (tools/ab_bench.sh): libm's logarithm as before round 3
-    const bool always_libm = true;
-#else
-    const bool always_libm = false;
-#endif
-    if (always_libm || !(m >= 0.5 && m < 1.0)) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        return log(m);
-#else
-        return std::log(m);
-#endif
-    }
+    if (!(m >= 0.5 && m < 1.0)) return log_(m);
     const bool low = m < 0.70710678118654752440;
     const double mm = low ? m + m : m;
     const double f = (mm - 1.0) / (mm + 1.0), s = f * f;
@@ -236,11 +245,7 @@ struct LogProduct {
     MCD_HD void mul(double x) { p *= x; }            // caller keeps |log2 p| < ~1000 between rescales
     MCD_HD void rescale() {
         int ex;
-#if defined(__HIP_DEVICE_COMPILE__)
-        p = __builtin_frexp(p, &ex);
-#else
-        p = std::frexp(p, &ex);
-#endif
+        p = frexp_(p, &ex);
         e += (int64_t)(e32 + ex);
         e32 = 0;
     }
@@ -248,21 +253,12 @@ struct LogProduct {
     // chunks hold <= 2^20 stars: mcd_chunks.h kMaxChunkLen), folded into e by value()
     MCD_HD void rescale_narrow() {
         int ex;
-#if defined(__HIP_DEVICE_COMPILE__)
-        p = __builtin_frexp(p, &ex);
-#else
-        p = std::frexp(p, &ex);
-#endif
+        p = frexp_(p, &ex);
         e32 += ex;
     }
     MCD_HD void mul_any(double x) {                  // any positive finite x: split first
         int ex;
-#if defined(__HIP_DEVICE_COMPILE__)
-        double m = __builtin_frexp(x, &ex);
-#else
-        double m = std::frexp(x, &ex);
-#endif
-        p *= m;
+        p *= frexp_(x, &ex);
         e32 += ex;
     }
     // as mul_any for x >= 0, additionally keeping the smallest BIASED exponent field seen (one v_min_i32): a field
@@ -295,18 +291,24 @@ struct LogProduct {
 //   sum_j q_j / n_j = NUM / DEN,  DEN = prod_j n_j,  built as a balanced tree of (num, den) pairs:
 //   (a, m) (+) (b, n) = (a n + b m, m n).
 // Valid while DEN and NUM stay in range: host guards 2^-60 <= n <= 2^60 and q < 2^120 for G = 8.
-struct Frac { double num, den; };
-MCD_HD Frac frac_leaf2(double q0, double n0, double q1, double n1) {
-    Frac f;
+template <class T> struct Frac { T num, den; };
+template <class T> MCD_HD Frac<T> frac_leaf2(T q0, T n0, T q1, T n1) {
+    Frac<T> f;
     f.den = n0 * n1;
     f.num = fma_(q1, n0, q0 * n1);
     return f;
 }
-MCD_HD Frac frac_join(Frac a, Frac b) {
-    Frac f;
+template <class T> MCD_HD Frac<T> frac_join(Frac<T> a, Frac<T> b) {
+    Frac<T> f;
     f.den = a.den * b.den;
     f.num = fma_(b.num, a.den, a.num * b.den);
     return f;
+}
+template <class T> MCD_HD Frac<T> frac_tree4(const T* qq, const T* nn) {
+    return frac_join(frac_leaf2(qq[0], nn[0], qq[1], nn[1]), frac_leaf2(qq[2], nn[2], qq[3], nn[3]));
+}
+template <class T> MCD_HD Frac<T> frac_tree8(const T* qq, const T* nn) {
+    return frac_join(frac_tree4(qq, nn), frac_tree4(qq + 4, nn + 4));
 }
 
 struct ConstAcc {          // accumulators of one walker over one chunk (MODEL_CONST)
@@ -314,8 +316,7 @@ struct ConstAcc {          // accumulators of one walker over one chunk (MODEL_C
     LogProduct l;          // sum log(norm)
     MCD_HD void init() { q = 0.0; l.init(); }
     MCD_HD void add8(const double* qq, const double* nn) {
-        Frac f = frac_join(frac_join(frac_leaf2(qq[0], nn[0], qq[1], nn[1]), frac_leaf2(qq[2], nn[2], qq[3], nn[3])),
-                           frac_join(frac_leaf2(qq[4], nn[4], qq[5], nn[5]), frac_leaf2(qq[6], nn[6], qq[7], nn[7])));
+        const Frac<double> f = frac_tree8(qq, nn);
         // DEN is a normal number far from the range limits (host guard), so the IEEE division's scaling and
         // fix-up instructions are not needed: reciprocal (v_rcp_f64 + one residual step, < 1 ulp) times NUM.
         q += f.num * rcp_nr(f.den);
@@ -324,11 +325,7 @@ struct ConstAcc {          // accumulators of one walker over one chunk (MODEL_C
     }
     // 16 stars: one more level of the tree, still ONE reciprocal (DEN = prod of 16 norms needs |log2 norm| <= 50)
     MCD_HD void add16(const double* qq, const double* nn) {
-        Frac a = frac_join(frac_join(frac_leaf2(qq[0], nn[0], qq[1], nn[1]), frac_leaf2(qq[2], nn[2], qq[3], nn[3])),
-                           frac_join(frac_leaf2(qq[4], nn[4], qq[5], nn[5]), frac_leaf2(qq[6], nn[6], qq[7], nn[7])));
-        Frac b = frac_join(frac_join(frac_leaf2(qq[8], nn[8], qq[9], nn[9]), frac_leaf2(qq[10], nn[10], qq[11], nn[11])),
-                           frac_join(frac_leaf2(qq[12], nn[12], qq[13], nn[13]), frac_leaf2(qq[14], nn[14], qq[15], nn[15])));
-        Frac f = frac_join(a, b);
+        const Frac<double> f = frac_join(frac_tree8(qq, nn), frac_tree8(qq + 8, nn + 8));
         q += f.num * rcp_nr(f.den);
         l.mul(f.den);
         l.rescale();
@@ -355,8 +352,7 @@ struct ProfileNarrowAcc {
     LogProduct lm;         // prod m_i
     MCD_HD void init() { q = 0.0; l.init(); lm.init(); }
     MCD_HD void add8(const double* qq, const double* nn, double m_prod) {
-        Frac f = frac_join(frac_join(frac_leaf2(qq[0], nn[0], qq[1], nn[1]), frac_leaf2(qq[2], nn[2], qq[3], nn[3])),
-                           frac_join(frac_leaf2(qq[4], nn[4], qq[5], nn[5]), frac_leaf2(qq[6], nn[6], qq[7], nn[7])));
+        const Frac<double> f = frac_tree8(qq, nn);
         q += f.num * rcp_nr(f.den);
         l.mul(f.den);
         l.rescale();
@@ -376,19 +372,6 @@ struct ProfileNarrowAcc {
 
 // float32 counterpart (MCD_F32 / MCD_F32_ACC64): groups of 4 stars so that DEN <= 2^60 and NUM <= 2^77 stay inside the
 // f32 range under the host guard 2^-15 <= n <= 2^15, q <= 2^30.  The quotient sum accumulates in A (float or double).
-struct FracF { float num, den; };
-MCD_HD FracF fracf_leaf2(float q0, float n0, float q1, float n1) {
-    FracF f;
-    f.den = n0 * n1;
-    f.num = fma_(q1, n0, q0 * n1);
-    return f;
-}
-MCD_HD FracF fracf_join(FracF a, FracF b) {
-    FracF f;
-    f.den = a.den * b.den;
-    f.num = fma_(b.num, a.den, a.num * b.den);
-    return f;
-}
 template <class A>
 struct ConstAccF {
     A q;
@@ -397,15 +380,11 @@ struct ConstAccF {
     MCD_HD void init() { q = 0; p = 1.0f; e = 0; }
     MCD_HD void fold(float x) {
         int ex;
-#if defined(__HIP_DEVICE_COMPILE__)
-        p = __builtin_frexpf(p * x, &ex);
-#else
-        p = std::frexp(p * x, &ex);
-#endif
+        p = frexp_(p * x, &ex);
         e += ex;
     }
     MCD_HD void add4(const float* qq, const float* nn) {
-        const FracF f = fracf_join(fracf_leaf2(qq[0], nn[0], qq[1], nn[1]), fracf_leaf2(qq[2], nn[2], qq[3], nn[3]));
+        const Frac<float> f = frac_tree4(qq, nn);
 #if defined(__HIP_DEVICE_COMPILE__)
         q += (A)(f.num * __builtin_amdgcn_rcpf(f.den));     // v_rcp_f32: 1 ulp
 #else
@@ -418,33 +397,13 @@ struct ConstAccF {
         fold(n1);
     }
     MCD_HD double finish(int64_t count) {
-#if defined(__HIP_DEVICE_COMPILE__)
-        const double lg = fma_((double)e, kLn2, log((double)p));
-#else
-        const double lg = fma_((double)e, kLn2, std::log((double)p));
-#endif
+        const double lg = fma_((double)e, kLn2, log_((double)p));
         return -0.5 * (fma_((double)count, kLn2Pi, lg) + (double)q);
     }
 };
 
 // ---------------------------------------------------------------------------------------------
 // Plain per-term forms (robust path and mixtures): one log / exp per term as written in the reference.
-template <class T> MCD_HD T log_(T x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return log(x);
-#else
-    return std::log(x);
-#endif
-}
-template <class T> MCD_HD T exp_(T x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return exp(x);
-#else
-    return std::exp(x);
-#endif
-}
-template <class T> MCD_HD T max_(T a, T b) { return a > b ? a : b; }
-
 // lnL_member of runner.py:280 / lnlike_cluster of constant.py:362
 template <class T>
 MCD_HD T gauss_lnl(T d, T n) {
@@ -464,30 +423,6 @@ MCD_HD T mixture_lnl(T m, T b, T p) {
 //   and one exp whose argument is <= 0 or exponent-clamped; the per-star mixture value y_i > 0 is
 //   folded into a LogProduct:  sum_i log y_i = log prod_i y_i.
 
-MCD_HD double rsqrt_nr(double n) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    double y = __builtin_amdgcn_rsq(n);      // v_rsq_f64: measured max rel. error 2^-24.2 on gfx950 (tools/rsq_probe.hip)
-#else
-    double y = 1.0 / std::sqrt(n);
-#endif
-    // one third-order step: with e = 1 - n y^2 (|e| <= 2^-23.2),  n^-1/2 = y (1 + e/2 + 3 e^2/8 + O(e^3)),
-    // remaining error 5/16 e^3 < 2^-71: full f64 after the final rounding.  5 instructions.
-    const double e = fma_(-(n * y), y, 1.0);
-    const double t = fma_(0.375, e, 0.5);
-    return fma_(y, t * e, y);
-}
-
-MCD_HD double rcp_nr(double x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    double y = __builtin_amdgcn_rcp(x);      // v_rcp_f64: measured max rel. error 2^-24.4 on gfx950
-#else
-    double y = 1.0 / x;
-#endif
-    // 1/x = y (1 + e + e^2 + O(e^3)),  e = 1 - x y
-    const double e = fma_(-x, y, 1.0);
-    return fma_(y, fma_(e, e, e), y);
-}
-
 // 2 m^(-1/2) from v_rsq_f64 and ONE Newton step in its three-instruction form,  y (3 - m y^2) = 2 y (1 + e/2),
 // e = 1 - m y^2 (|e| <= 2^-23.2):  m^-1/2 = y (1 + e/2 + 3 e^2/8 + ...), so the result is low by 3/8 e^2 <= 4.1e-15
 // relative (1.4e-15 on average) plus three roundings.  Used by the narrow-range mixture variants only, where a term's
@@ -495,14 +430,7 @@ MCD_HD double rcp_nr(double x) {
 // i.e. 1e-15 of |lnL| -- inside the rounding error of the reference's own float64 summation.  The factor 2 is free:
 // callers scale the variance they pass (m = 8 n gives (2 n)^-1/2).  Two instructions fewer than rsqrt_nr.
 MCD_HD double rsqrt2_newton(double m) {
-#if defined(MCD_AB_NEWTON3)                       // A/B builds only (csrc/Makefile: variant): the third-order form, for timing
-    return 2.0 * rsqrt_nr(m);
-#endif
-#if defined(__HIP_DEVICE_COMPILE__)
-    const double y = __builtin_amdgcn_rsq(m);
-#else
-    const double y = 1.0 / std::sqrt(m);
-#endif
+    const double y = rsq_(m);
     const double s = fma_(-m, y * y, 3.0);
     return y * s;
 }
@@ -534,6 +462,8 @@ constexpr int kExpTabHiShift = 20 - kExpTabBits;
 MCD_HD double exp_tab_bias(double t, int j) { return add_hi_word(t, -(j << kExpTabHiShift)); }
 
 // k of exp_tab and its reduced argument: k comes out of the low word of u * (N / ln 2) + 1.5 * 2^52 (round-to-nearest-even)
+// TWO_STEP = false, the one-constant reduction: ln 2 / N rounded to f64 is off by < 2^-53 of itself, so r is off by
+// < 1.1e-16 |k| ln 2 / N, i.e. a relative error of 8e-17 |u| in e^u -- for callers whose |u| is small wherever e^u matters
 template <bool TWO_STEP>
 MCD_HD double exp_tab_reduce(double u, int& k) {
     constexpr double kMagic = 6755399441055744.0;            // 1.5 * 2^52
@@ -549,44 +479,24 @@ MCD_HD double exp_tab_reduce(double u, int& k) {
         return fma_(-kf, kExpTabStepHi + kExpTabStepLo, u);
     }
 }
-
-template <bool TWO_STEP = true, bool BIASED = false>
-MCD_HD double exp_tab(double u, int& e_out, const double* __restrict__ tab) {
-    if constexpr (BIASED) {
-        // general form on the exponent-biased table: T[j] restored exactly (one integer instruction), then as below
-        int k;
-        const double r = exp_tab_reduce<TWO_STEP>(u, k);
-        double p;
-        if constexpr (kExpPolyDegree == 4) p = fma_(fma_(r, kExpPolyC4, kExpPolyC3), r, kExpPolyC2);
-        else p = fma_(r, kExpPolyC3, kExpPolyC2);
-        p = fma_(p, r, 1.0);
-        p = fma_(p, r, 1.0);
-        e_out = k >> kExpTabBits;
-        const int j = k & (kExpTabSize - 1);
-        return add_hi_word(tab[j], j << kExpTabHiShift) * p;
-    }
-    constexpr double kMagic = 6755399441055744.0;            // 1.5 * 2^52
-    const double shifted = fma_(u, kExpTabInvStep, kMagic);
-    const double kf = shifted - kMagic;
-    uint64_t bits;
-    std::memcpy(&bits, &shifted, sizeof bits);
-    const int k = (int)(uint32_t)bits;
-    double r;
-    if constexpr (TWO_STEP) {
-        r = fma_(-kf, kExpTabStepHi, u);
-        r = fma_(-kf, kExpTabStepLo, r);
-    } else {
-        // one-constant reduction: ln 2 / N rounded to f64 is off by < 2^-53 of itself, so r is off by < 1.1e-16 |k| ln 2 / N,
-        // i.e. a relative error of 8e-17 |u| in e^u -- for callers whose |u| is small wherever e^u matters
-        r = fma_(-kf, kExpTabStepHi + kExpTabStepLo, u);
-    }
+// e^r on the reduced argument, |r| <= ln 2 / 2N (degree and coefficients: mcd_exp_table.h)
+MCD_HD double exp_poly(double r) {
     double p;
     if constexpr (kExpPolyDegree == 4) p = fma_(fma_(r, kExpPolyC4, kExpPolyC3), r, kExpPolyC2);
     else p = fma_(r, kExpPolyC3, kExpPolyC2);
     p = fma_(p, r, 1.0);
-    p = fma_(p, r, 1.0);
+    return fma_(p, r, 1.0);
+}
+
+template <bool TWO_STEP = true, bool BIASED = false>
+MCD_HD double exp_tab(double u, int& e_out, const double* __restrict__ tab) {
+    int k;
+    const double p = exp_poly(exp_tab_reduce<TWO_STEP>(u, k));
     e_out = k >> kExpTabBits;
-    return tab[k & (kExpTabSize - 1)] * p;
+    const int j = k & (kExpTabSize - 1);
+    // the exponent-biased table: T[j] restored exactly (one integer instruction)
+    if constexpr (BIASED) return add_hi_word(tab[j], j << kExpTabHiShift) * p;
+    else return tab[j] * p;
 }
 
 // e^u = (T[j] 2^e) e^r from the exponent-biased table, with no v_ldexp_f64 and no k >> B: the integer part e is added
@@ -610,12 +520,7 @@ MCD_HD double vgpr_constant(double x) {
 template <bool TWO_STEP = false, bool CLAMP = true>
 MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
     int k;
-    const double r = exp_tab_reduce<TWO_STEP>(u, k);
-    double p;
-    if constexpr (kExpPolyDegree == 4) p = fma_(fma_(r, kExpPolyC4, kExpPolyC3), r, kExpPolyC2);
-    else p = fma_(r, kExpPolyC3, kExpPolyC2);
-    p = fma_(p, r, 1.0);
-    p = fma_(p, r, 1.0);
+    const double p = exp_poly(exp_tab_reduce<TWO_STEP>(u, k));
     if constexpr (CLAMP) k = k > kExpTabKMin ? k : kExpTabKMin;      // v_max_i32
     const double t = tab[k & (kExpTabSize - 1)];
     const int32_t kh = (int32_t)((uint32_t)k << kExpTabHiShift);
@@ -691,35 +596,6 @@ MCD_HD bool is_zero_bits(double x) {
     uint64_t b;
     __builtin_memcpy(&b, &x, sizeof b);
     return (b << 1) == 0;
-}
-
-MCD_HD double ldexp_(double x, int k) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_ldexp(x, k);
-#else
-    return std::ldexp(x, k);
-#endif
-}
-MCD_HD double fmin_(double a, double b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_fmin(a, b);              // v_min_f64
-#else
-    return std::fmin(a, b);
-#endif
-}
-MCD_HD double fabs_(double a) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_fabs(a);                 // source modifier, no instruction
-#else
-    return std::fabs(a);
-#endif
-}
-MCD_HD double fmax_(double a, double b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_fmax(a, b);              // v_max_f64
-#else
-    return std::fmax(a, b);
-#endif
 }
 
 // MODEL_BGFIXED: lnL_i = b_i + log((1 - p_i) + p_i t_i),  t_i = exp(m_i - b_i) = g exp(-1/2 q g^2 - b'_i),
@@ -857,20 +733,6 @@ struct BgGaussAcc {
 // float32 fast mixtures (MCD_F32 / MCD_F32_ACC64): the same formulations with v_rsq_f32 / v_exp_f32 (1 ulp each, no
 // Newton step, no table) and the running products in A = float or double.  Valid under the f32 conditions of
 // mcd_guard.h (fast_guard): every mixture value y lies in [2^-27, 2^31], so four factors fit between two rescales.
-MCD_HD float rsqf_(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_rsqf(x);
-#else
-    return 1.0f / std::sqrt(x);
-#endif
-}
-MCD_HD float expf_(float x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);      // v_exp_f32; arguments below -126 / ln 2 flush to 0
-#else
-    return std::exp(x);
-#endif
-}
 template <class A>
 struct LogProductF {                 // sum of logs as log of a product, mantissa in A, exponent in an int
     A p;
@@ -879,19 +741,7 @@ struct LogProductF {                 // sum of logs as log of a product, mantiss
     MCD_HD void mul(float x) { p *= (A)x; }
     MCD_HD void rescale() {
         int ex;
-        if constexpr (sizeof(A) == 8) {
-#if defined(__HIP_DEVICE_COMPILE__)
-            p = __builtin_frexp(p, &ex);
-#else
-            p = std::frexp(p, &ex);
-#endif
-        } else {
-#if defined(__HIP_DEVICE_COMPILE__)
-            p = __builtin_frexpf(p, &ex);
-#else
-            p = std::frexp(p, &ex);
-#endif
-        }
+        p = frexp_(p, &ex);
         e += ex;
     }
     MCD_HD double value() {
@@ -977,9 +827,6 @@ struct KdeLane {
 // 202.7 -> 200.1 us, 128 walkers 117.2 -> 107.4 us, 64 walkers 89.5 -> 61.5 us; with 256 walkers three of a chunk's four
 // waves find their records fetched by the first, with fewer walkers every wave waits for memory on its own (VALUBusy
 // 85 % / 67 % without the prefetch, tools/sq_w128.sh).
-#ifndef MCD_PREFETCH_DISTANCE
-#define MCD_PREFETCH_DISTANCE 1          // loop iterations ahead
-#endif
 template <int BYTES, bool ON>
 struct RecordPrefetch {
     static constexpr int kLines = (BYTES + 63) / 64 > 8 ? 8 : (BYTES + 63) / 64;
@@ -989,7 +836,7 @@ struct RecordPrefetch {
     // out).  Which launches get the prefetching instantiation: mcd_api_catalog.hip, wants_prefetch().
     template <class P>
     MCD_HD void issue(P next) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MCD_NO_PREFETCH)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (ON) {
             const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             typedef const uint32_t __attribute__((address_space(1)))* global_word_ptr;
@@ -1002,7 +849,7 @@ struct RecordPrefetch {
         t = 0;
     }
     MCD_HD void retire(double anchor) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(MCD_NO_PREFETCH)
+#if defined(__HIP_DEVICE_COMPILE__)
         if constexpr (ON) asm volatile("" :: "v"(t), "v"(anchor));
 #endif
         (void)anchor;
@@ -1022,14 +869,6 @@ template <class T> struct WalkerConsts {
         a2 = p[W_A2]; s2a = p[W_S2A]; rp2 = p[W_RP2]; rp_2 = p[W_2RP];
     }
 };
-
-template <class T> MCD_HD T sqrt_(T x) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return sqrt(x);
-#else
-    return std::sqrt(x);
-#endif
-}
 
 // Residual d = v - v_los and variance n = verr^2 + sigma_los^2 of one star for one walker.
 //   CONST   (constant.py:52-111): v_los = v_sys + v_maxx sin(theta) - v_maxy cos(theta), sigma_los = sigma_max
@@ -1078,222 +917,267 @@ MCD_HD void star_d_n(RecPtr<T> r, const WalkerConsts<T>& w, T& d, T& n) {
 // for MODEL_BGFIXED it is the sqrt(2)-scaled table (exp_table_is_sqrt2_scaled).
 MCD_HD constexpr bool exp_table_is_sqrt2_scaled(int model) { return model == MODEL_BGFIXED; }
 
-// FAST: 0 = plain (the reference's expressions term by term), 1 = fast formulation, 2 = fast formulation with the
-// narrow-range products of BgFixedAcc::add (MODEL_BGFIXED, MODEL_PROFILE_BGDENS) / BgGaussAcc::add (MODEL_BGGAUSS,
-// MODEL_PROFILE_BGGAUSS); for the models without background the same as 1.
-// TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
-// BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
-// narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
-// `series` (MODEL_BGFIXED, fixed centre, FAST == 2, f64): the records are sorted by verr, so a chunk whose verr^2 band is
-// narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote.
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
-MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
-                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false) {
+// ---------------------------------------------------------------------------------------------
+// One function per family of chunk_loglike (below).  The group loops (RecordPrefetch issue, body, retire, rescale) are
+// written out in each: behind a shared loop helper that takes the body as a lambda hipcc emits other vector code.
+
+// plain path without background: one log and one division per term (runner.py:269-270 keeps two sums as well)
+template <int MODEL, bool FREE, class T, class A>
+MCD_HD double chunk_plain(RecPtr<T> r, int count, const WalkerConsts<T>& w) {
     constexpr int ND = record_doubles(MODEL, FREE);
-    denormal = false;
+    A sum_log = 0, sum_q = 0;
+#pragma unroll 4
+    for (int j = 0; j < count; ++j, r += ND) {
+        T d, n;
+        star_d_n<MODEL, T, FREE>(r, w, d, n);
+        sum_log += (A)log_(n);
+        sum_q += (A)(d * d / n);
+    }
+    return -0.5 * ((double)count * kLn2Pi + (double)sum_log + (double)sum_q);
+}
+
+// plain mixtures: the reference's expressions term by term
+template <int MODEL, bool FREE, class T, class A>
+MCD_HD double chunk_plain_mixture(RecPtr<T> r, int count, const WalkerConsts<T>& w) {
+    constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int XB = geometry_doubles(MODEL, FREE);      // first background slot of a record
     constexpr int BG = bg_kind(MODEL);
-    double result;
-
-    if constexpr (BG != BG_NONE && FAST && sizeof(T) == 4) {
-        // float32 fast mixtures: four stars (one scalar record batch) per rescale; A = float or double
-        auto run4 = [&](auto& acc, auto&& one, auto&& rescale) {
-            const int n4 = count >> 2;
-            for (int g = 0; g < n4; ++g, r += 4 * ND) {
-                RecordPrefetch<4 * ND * 4, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) one(r + j * ND);
-                rescale();
-                pf.retire((double)acc.value_for_anchor());
-            }
-            for (int j = n4 * 4; j < count; ++j, r += ND) { one(r); rescale(); }
-        };
-        if constexpr (BG == BG_GAUSS) {
-            BgGaussAccF<A> acc;
-            acc.init();
-            run4(acc, [&](RecPtr<T> rr) {
-                T d, n;
-                star_d_n<MODEL, T, FREE, true>(rr, w, d, n);
-                acc.add(d, n, rr[0] - w.vb, rr[1] + w.sb2, rr[XB], w.fb);
-            }, [&]() { acc.rescale(); });
-            result = acc.finish(count);
-        } else if constexpr (BG == BG_FIXED) {
-            BgFixedAccF<A> acc;
-            acc.init();
-            run4(acc, [&](RecPtr<T> rr) {
-                T d, n;
-                star_d_n<MODEL, T, FREE, true>(rr, w, d, n);
-                acc.add(d, n, rr[XB + 2], rr[XB + 3]);
-            }, [&]() { acc.rescale(); });
-            result = acc.finish();
+    A sum = 0;
+#pragma unroll 2
+    for (int j = 0; j < count; ++j, r += ND) {
+        T d, n;
+        star_d_n<MODEL, T, FREE>(r, w, d, n);
+        const T m = gauss_lnl(d, n);
+        T b, p;
+        if (BG == BG_FIXED) {
+            b = r[XB];
+            p = r[XB + 1];
+        } else if (BG == BG_FIXED_DENSITY) {
+            b = r[XB];
+            const T rho = r[XB + 2];
+            p = rho / (rho + w.fb);                          // model.py:588
         } else {
-            BgFixedAccF<A> acc;
-            acc.init();
-            run4(acc, [&](RecPtr<T> rr) {
-                T d, n;
-                star_d_n<MODEL, T, FREE, true>(rr, w, d, n);
-                acc.add_density(d, n, rr[XB + 2], w.fb, rr[XB + 1]);
-            }, [&]() { acc.rescale_density(); });
-            result = acc.finish_density();
+            const T nb = r[1] + w.sb2;                       // constant.py:333, model.py:423
+            const T db = r[0] - w.vb;
+            b = gauss_lnl(db, nb);                           // constant.py:334-336
+            const T rho = r[XB];
+            p = rho / (rho + w.fb);                          // constant.py:339, model.py:429
         }
-    } else if constexpr (BG == BG_NONE && FAST && sizeof(T) == 4) {
-        // f32 fraction tree over 4 stars + f32 log-product.  One iteration covers 16 stars (four trees) so that four
-        // 64-byte scalar record loads are in flight per wave: a 4-star iteration is only ~40 ns of VALU work, far
-        // less than one load latency even with 8 waves per SIMD.
-        ConstAccF<A> acc;
-        acc.init();
-        // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
-        // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
-        constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
-        const int n16 = TREE16 ? count >> 4 : 0;
-        for (int g = 0; g < n16; ++g, r += 16 * ND) {
-            RecordPrefetch<16 * ND * 4, PF> pf;
-            pf.issue(r + MCD_PREFETCH_DISTANCE * 16 * ND);
-            float qq[16], nn[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                float d;
-                star_d_n<MODEL, float, FREE, true>(r + j * ND, w, d, nn[j]);
-                qq[j] = d * d;
-            }
-#pragma unroll
-            for (int t = 0; t < 4; ++t) acc.add4(qq + 4 * t, nn + 4 * t);
-            pf.retire((double)acc.p);
-        }
-        const int done = n16 << 4;
-        const int n4 = (count - done) >> 2;
-        for (int g = 0; g < n4; ++g, r += 4 * ND) {
-            float qq[4], nn[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float d;
-                star_d_n<MODEL, float, FREE, true>(r + j * ND, w, d, nn[j]);
-                qq[j] = d * d;
-            }
-            acc.add4(qq, nn);
-        }
-        for (int j = done + n4 * 4; j < count; ++j, r += ND) {
-            float d, n;
-            star_d_n<MODEL, float, FREE, true>(r, w, d, n);
-            acc.add1(d * d, n);
-        }
-        result = acc.finish(count);
-    } else if constexpr (BG == BG_NONE && FAST == 2 && MODEL == MODEL_PROFILE && !FREE) {
-        // narrow-range profile variant (ProfileNarrowAcc): no reciprocal per term, one-step Newton root for the Plummer
-        // dispersion (rsqrt2_newton returns 2 (a^2 + r^2)^-1/2: the factor goes into sigma_max^2 a / 2)
-        ProfileNarrowAcc acc;
-        acc.init();
-        const double hs2a = 0.5 * w.s2a;
-        auto one = [&](RecPtr<double> rr, double& q1, double& n1, double& m1) {
-            m1 = w.rp2 + rr[4];
-            const double t2 = rsqrt2_newton(w.a2 + rr[4]);
-            const double n = fma_(hs2a, t2, rr[1]);
-            const double cross = fma_(w.vx, rr[3], -(w.vy * rr[2]));
-            const double nd = fma_(rr[0] - w.vsys, m1, -(w.rp_2 * cross));
-            q1 = nd * nd;
-            n1 = (m1 * m1) * n;
-        };
-        const int n8 = count >> 3;
-        for (int g = 0; g < n8; ++g, r += 8 * ND) {
-            RecordPrefetch<8 * ND * 8, PF> pf;
-            pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
-            double qq[8], nn[8], mm[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) one(r + j * ND, qq[j], nn[j], mm[j]);
-            const double m_prod = ((mm[0] * mm[1]) * (mm[2] * mm[3])) * ((mm[4] * mm[5]) * (mm[6] * mm[7]));
-            acc.add8(qq, nn, m_prod);
-            pf.retire(acc.q);
-        }
-        for (int j = count & ~7; j < count; ++j, r += ND) {
-            double q1, n1, m1;
-            one(r, q1, n1, m1);
-            acc.add1(q1, n1, m1);
-        }
-        result = acc.finish(count);
-    } else if constexpr (BG == BG_NONE && FAST) {
-        // fraction-tree + log-product path (f64): 8 stars -> one division, one product factor
-        ConstAcc acc;
-        acc.init();
-        // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
-        // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
-        constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
-        const int n16 = TREE16 ? count >> 4 : 0;
-        for (int g = 0; g < n16; ++g, r += 16 * ND) {
-            RecordPrefetch<16 * ND * 8, PF> pf;
-            pf.issue(r + MCD_PREFETCH_DISTANCE * 16 * ND);
-            double qq[16], nn[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                double d;
-                star_d_n<MODEL, double, FREE, true>(r + j * ND, w, d, nn[j]);
-                qq[j] = d * d;
-            }
-            acc.add16(qq, nn);
-            pf.retire(acc.q);
-        }
-        const int n8 = TREE16 ? (count >> 3) & 1 : count >> 3;
-        for (int g = 0; g < n8; ++g, r += 8 * ND) {
-            RecordPrefetch<8 * ND * 8, PF> pf;
-            pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
-            double qq[8], nn[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                double d;
-                star_d_n<MODEL, double, FREE, true>(r + j * ND, w, d, nn[j]);
-                qq[j] = d * d;
-            }
-            acc.add8(qq, nn);
-            pf.retire(acc.q);
-        }
-        for (int j = count & ~7; j < count; ++j, r += ND) {
-            double d, n;
-            star_d_n<MODEL, double, FREE, true>(r, w, d, n);
-            acc.add1(d * d, n);
-        }
-        result = acc.finish(count);
-    } else if constexpr (BG == BG_NONE) {
-        // plain path: one log and one division per term (runner.py:269-270 keeps two sums as well)
-        A sum_log = 0, sum_q = 0;
-#pragma unroll 4
-        for (int j = 0; j < count; ++j, r += ND) {
-            T d, n;
-            star_d_n<MODEL, T, FREE>(r, w, d, n);
-            sum_log += (A)log_(n);
-            sum_q += (A)(d * d / n);
-        }
-        result = -0.5 * ((double)count * kLn2Pi + (double)sum_log + (double)sum_q);
-    } else if constexpr (BG == BG_FIXED && FAST) {
-        // MODEL_BGFIXED has norm = verr^2 + sigma^2 (constant.py:52-74): the accumulator takes 2 norm (HALVED form; 8 norm
-        // for the narrow-range variant's one-step Newton reciprocal root) and `exptab` is then the sqrt(2)-scaled table;
-        // star_d_n's own norm is dead code there.
-        constexpr bool HALVED = MODEL == MODEL_BGFIXED;
-        constexpr bool NARROW = FAST == 2 && MODEL == MODEL_BGFIXED;
-        constexpr double kScale = NARROW ? 8.0 : 2.0;
-        const double s2x = kScale * (double)w.s2;
-        const double scale = BOUNDED ? vgpr_constant(kScale) : kScale;
-        BgFixedAcc acc;
-        acc.init();
-        // SERIES (a type: std::true_type / std::false_type): the reciprocal root from the chunk's RootSeries instead of
-        // v_rsq_f64 and the Newton step; everything after g is the same code
-        RootSeries sr;
-        auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
-            double d, n;
-            star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-            if constexpr (decltype(SERIES)::value) {
-                acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, sr.g(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
-            } else {
-                if constexpr (HALVED) n = fma_(sc, rr[1], s2x);
-                acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
-            }
-        };
-        auto four = [&](RecPtr<double> r4, auto SERIES) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
-        };
+        sum += (A)mixture_lnl(m, b, p);                      // runner.py:282-284, constant.py:320-323
+    }
+    return (double)sum;
+}
+
+// float32 fast mixtures: four stars (one scalar record batch) per rescale; A = float or double
+template <int MODEL, bool FREE, class A, bool PF>
+MCD_HD double chunk_mixture_f32(RecPtr<float> r, int count, const WalkerConsts<float>& w) {
+    constexpr int ND = record_doubles(MODEL, FREE);
+    constexpr int XB = geometry_doubles(MODEL, FREE);
+    constexpr int BG = bg_kind(MODEL);
+    auto run4 = [&](auto& acc, auto&& one, auto&& rescale) {
         const int n4 = count >> 2;
-        static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
-        auto run = [&](auto SERIES) {
+        for (int g = 0; g < n4; ++g, r += 4 * ND) {
+            RecordPrefetch<4 * ND * 4, PF> pf;
+            pf.issue(r + 4 * ND);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) one(r + j * ND);
+            rescale();
+            pf.retire((double)acc.value_for_anchor());
+        }
+        for (int j = n4 * 4; j < count; ++j, r += ND) { one(r); rescale(); }
+    };
+    if constexpr (BG == BG_GAUSS) {
+        BgGaussAccF<A> acc;
+        acc.init();
+        run4(acc, [&](RecPtr<float> rr) {
+            float d, n;
+            star_d_n<MODEL, float, FREE, true>(rr, w, d, n);
+            acc.add(d, n, rr[0] - w.vb, rr[1] + w.sb2, rr[XB], w.fb);
+        }, [&]() { acc.rescale(); });
+        return acc.finish(count);
+    } else if constexpr (BG == BG_FIXED) {
+        BgFixedAccF<A> acc;
+        acc.init();
+        run4(acc, [&](RecPtr<float> rr) {
+            float d, n;
+            star_d_n<MODEL, float, FREE, true>(rr, w, d, n);
+            acc.add(d, n, rr[XB + 2], rr[XB + 3]);
+        }, [&]() { acc.rescale(); });
+        return acc.finish();
+    } else {
+        BgFixedAccF<A> acc;
+        acc.init();
+        run4(acc, [&](RecPtr<float> rr) {
+            float d, n;
+            star_d_n<MODEL, float, FREE, true>(rr, w, d, n);
+            acc.add_density(d, n, rr[XB + 2], w.fb, rr[XB + 1]);
+        }, [&]() { acc.rescale_density(); });
+        return acc.finish_density();
+    }
+}
+
+// f32 fraction tree over 4 stars + f32 log-product.  One iteration covers 16 stars (four trees) so that four
+// 64-byte scalar record loads are in flight per wave: a 4-star iteration is only ~40 ns of VALU work, far
+// less than one load latency even with 8 waves per SIMD.
+template <int MODEL, bool FREE, class A, bool PF>
+MCD_HD double chunk_const_f32(RecPtr<float> r, int count, const WalkerConsts<float>& w) {
+    constexpr int ND = record_doubles(MODEL, FREE);
+    ConstAccF<A> acc;
+    acc.init();
+    // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
+    // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
+    constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
+    const int n16 = TREE16 ? count >> 4 : 0;
+    for (int g = 0; g < n16; ++g, r += 16 * ND) {
+        RecordPrefetch<16 * ND * 4, PF> pf;
+        pf.issue(r + 16 * ND);
+        float qq[16], nn[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            float d;
+            star_d_n<MODEL, float, FREE, true>(r + j * ND, w, d, nn[j]);
+            qq[j] = d * d;
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc.add4(qq + 4 * t, nn + 4 * t);
+        pf.retire((double)acc.p);
+    }
+    const int done = n16 << 4;
+    const int n4 = (count - done) >> 2;
+    for (int g = 0; g < n4; ++g, r += 4 * ND) {
+        float qq[4], nn[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float d;
+            star_d_n<MODEL, float, FREE, true>(r + j * ND, w, d, nn[j]);
+            qq[j] = d * d;
+        }
+        acc.add4(qq, nn);
+    }
+    for (int j = done + n4 * 4; j < count; ++j, r += ND) {
+        float d, n;
+        star_d_n<MODEL, float, FREE, true>(r, w, d, n);
+        acc.add1(d * d, n);
+    }
+    return acc.finish(count);
+}
+
+// narrow-range profile variant (ProfileNarrowAcc): no reciprocal per term, one-step Newton root for the Plummer
+// dispersion (rsqrt2_newton returns 2 (a^2 + r^2)^-1/2: the factor goes into sigma_max^2 a / 2)
+template <bool PF>
+MCD_HD double chunk_profile_narrow(RecPtr<double> r, int count, const WalkerConsts<double>& w) {
+    constexpr int ND = record_doubles(MODEL_PROFILE, false);
+    ProfileNarrowAcc acc;
+    acc.init();
+    const double hs2a = 0.5 * w.s2a;
+    auto one = [&](RecPtr<double> rr, double& q1, double& n1, double& m1) {
+        m1 = w.rp2 + rr[4];
+        const double t2 = rsqrt2_newton(w.a2 + rr[4]);
+        const double n = fma_(hs2a, t2, rr[1]);
+        const double cross = fma_(w.vx, rr[3], -(w.vy * rr[2]));
+        const double nd = fma_(rr[0] - w.vsys, m1, -(w.rp_2 * cross));
+        q1 = nd * nd;
+        n1 = (m1 * m1) * n;
+    };
+    const int n8 = count >> 3;
+    for (int g = 0; g < n8; ++g, r += 8 * ND) {
+        RecordPrefetch<8 * ND * 8, PF> pf;
+        pf.issue(r + 8 * ND);
+        double qq[8], nn[8], mm[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) one(r + j * ND, qq[j], nn[j], mm[j]);
+        const double m_prod = ((mm[0] * mm[1]) * (mm[2] * mm[3])) * ((mm[4] * mm[5]) * (mm[6] * mm[7]));
+        acc.add8(qq, nn, m_prod);
+        pf.retire(acc.q);
+    }
+    for (int j = count & ~7; j < count; ++j, r += ND) {
+        double q1, n1, m1;
+        one(r, q1, n1, m1);
+        acc.add1(q1, n1, m1);
+    }
+    return acc.finish(count);
+}
+
+// fraction-tree + log-product path (f64): 8 stars -> one division, one product factor
+template <int MODEL, bool FREE, bool PF>
+MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w) {
+    constexpr int ND = record_doubles(MODEL, FREE);
+    ConstAcc acc;
+    acc.init();
+    // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
+    // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
+    constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
+    const int n16 = TREE16 ? count >> 4 : 0;
+    for (int g = 0; g < n16; ++g, r += 16 * ND) {
+        RecordPrefetch<16 * ND * 8, PF> pf;
+        pf.issue(r + 16 * ND);
+        double qq[16], nn[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            double d;
+            star_d_n<MODEL, double, FREE, true>(r + j * ND, w, d, nn[j]);
+            qq[j] = d * d;
+        }
+        acc.add16(qq, nn);
+        pf.retire(acc.q);
+    }
+    const int n8 = TREE16 ? (count >> 3) & 1 : count >> 3;
+    for (int g = 0; g < n8; ++g, r += 8 * ND) {
+        RecordPrefetch<8 * ND * 8, PF> pf;
+        pf.issue(r + 8 * ND);
+        double qq[8], nn[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            double d;
+            star_d_n<MODEL, double, FREE, true>(r + j * ND, w, d, nn[j]);
+            qq[j] = d * d;
+        }
+        acc.add8(qq, nn);
+        pf.retire(acc.q);
+    }
+    for (int j = count & ~7; j < count; ++j, r += ND) {
+        double d, n;
+        star_d_n<MODEL, double, FREE, true>(r, w, d, n);
+        acc.add1(d * d, n);
+    }
+    return acc.finish(count);
+}
+
+// BG_FIXED, f64 fast forms.  MODEL_BGFIXED has norm = verr^2 + sigma^2 (constant.py:52-74): the accumulator takes 2 norm
+// (HALVED form; 8 norm for the narrow-range variant's one-step Newton reciprocal root) and `exptab` is then the
+// sqrt(2)-scaled table; star_d_n's own norm is dead code there.
+template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED>
+MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w, bool& denormal,
+                                 const double* __restrict__ exptab, int rescale_iters, bool series) {
+    constexpr int ND = record_doubles(MODEL, FREE);
+    constexpr int XB = geometry_doubles(MODEL, FREE);
+    constexpr bool HALVED = MODEL == MODEL_BGFIXED;
+    constexpr bool NARROW = FAST == 2 && MODEL == MODEL_BGFIXED;
+    constexpr double kScale = NARROW ? 8.0 : 2.0;
+    const double s2x = kScale * w.s2;
+    const double scale = BOUNDED ? vgpr_constant(kScale) : kScale;
+    BgFixedAcc acc;
+    acc.init();
+    // SERIES (a type: std::true_type / std::false_type): the reciprocal root from the chunk's RootSeries instead of
+    // v_rsq_f64 and the Newton step; everything after g is the same code
+    RootSeries sr;
+    auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
+        double d, n;
+        star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
+        if constexpr (decltype(SERIES)::value) {
+            acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, sr.g(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
+        } else {
+            if constexpr (HALVED) n = fma_(sc, rr[1], s2x);
+            acc.add<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, n, rr[XB + 2], rr[XB + 3], exptab);
+        }
+    };
+    const int n4 = count >> 2;
+    static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
+    auto four = [&](RecPtr<double> r4, auto SERIES) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
+    };
+    auto run = [&](auto SERIES) {
         if constexpr (BOUNDED) {
             // bounded sub-variant: every mixture value lies in [y_lo, y_hi] with R log2(y_hi) <= 1000 and
             // 1 + R (-log2 y_lo) <= 1000 (mcd_guard.h: bounded_rescale), so R = 8 rescale_iters raw factors fit between
@@ -1304,7 +1188,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             int until = rescale_iters;
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
                 RecordPrefetch<8 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
+                pf.issue(r + 8 * ND);
                 four(r, SERIES);
                 four(r + 4 * ND, SERIES);
                 pf.retire(acc.l.p);
@@ -1324,7 +1208,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             // group's record loads and takes 76 VGPRs, i.e. 6 waves per SIMD: that instantiation keeps 4-star groups.)
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
                 RecordPrefetch<8 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 8 * ND);
+                pf.issue(r + 8 * ND);
                 four(r, SERIES);
                 four(r + 4 * ND, SERIES);
                 pf.retire(acc.l.p);
@@ -1345,7 +1229,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         } else {
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
+                pf.issue(r + 4 * ND);
                 four(r, SERIES);
                 pf.retire(acc.l.p);
                 acc.rescale();
@@ -1355,28 +1239,61 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             one(r, SERIES, kScale);
             acc.rescale();
         }
-        };
-        // The series form where every lane's sigma^2 keeps the chunk's verr^2 band inside |t| <= 2^-13 (RootSeries): the
-        // verdict depends on the chunk's first and last record and the wave's walkers alone, so the 4-star, the 8-star and
-        // the bounded loop decide alike and stay bitwise equal to each other.  `series`: the records are sorted by verr
-        // (host: LaunchShape::root_series).
-        constexpr bool kCanSeries = NARROW && MODEL == MODEL_BGFIXED && !FREE;
-        bool use_series = false;
-        if constexpr (kCanSeries) {
-            if (series && count > 0) {
-                const bool ok = sr.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], (double)w.s2);
-                use_series = wave_all(ok);
-            }
+    };
+    // The series form where every lane's sigma^2 keeps the chunk's verr^2 band inside |t| <= 2^-13 (RootSeries): the
+    // verdict depends on the chunk's first and last record and the wave's walkers alone, so the 4-star, the 8-star and
+    // the bounded loop decide alike and stay bitwise equal to each other.  `series`: the records are sorted by verr
+    // (host: LaunchShape::root_series).
+    constexpr bool kCanSeries = NARROW && MODEL == MODEL_BGFIXED && !FREE;
+    bool use_series = false;
+    if constexpr (kCanSeries) {
+        if (series && count > 0) {
+            const bool ok = sr.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], w.s2);
+            use_series = wave_all(ok);
         }
-        if constexpr (kCanSeries) {
-            if (use_series) { MCD_KEEP_BRANCH(); run(std::true_type()); }
-            else run(std::false_type());
-        } else {
-            run(std::false_type());
-        }
-        result = acc.finish();
-        denormal = acc.denormal();
-    } else if constexpr (BG == BG_FIXED_DENSITY && FAST) {
+    }
+    if constexpr (kCanSeries) {
+        if (use_series) { MCD_KEEP_BRANCH(); run(std::true_type()); }
+        else run(std::false_type());
+    } else {
+        run(std::false_type());
+    }
+    const double result = acc.finish();
+    denormal = acc.denormal();
+    return result;
+}
+
+// One chunk of stars for one walker: selects the family.  The two f64 mixtures with two running products (BG_FIXED_DENSITY,
+// BG_GAUSS) stay inline at the end: as functions of their own, hipcc issues the two frexp of their narrow-range rescale
+// in the other order.
+// FAST: 0 = plain (the reference's expressions term by term), 1 = fast formulation, 2 = fast formulation with the
+// narrow-range products of BgFixedAcc::add (MODEL_BGFIXED, MODEL_PROFILE_BGDENS) / BgGaussAcc::add (MODEL_BGGAUSS,
+// MODEL_PROFILE_BGGAUSS); for the models without background the same as 1.
+// TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
+// BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
+// narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
+// `series` (MODEL_BGFIXED, fixed centre, FAST == 2, f64): the records are sorted by verr, so a chunk whose verr^2 band is
+// narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote.
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
+MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
+                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false) {
+    constexpr int BG = bg_kind(MODEL);
+    denormal = false;
+    if constexpr (!FAST) {
+        if constexpr (BG == BG_NONE) return chunk_plain<MODEL, FREE, T, A>(r, count, w);
+        else return chunk_plain_mixture<MODEL, FREE, T, A>(r, count, w);
+    } else if constexpr (sizeof(T) == 4) {
+        if constexpr (BG == BG_NONE) return chunk_const_f32<MODEL, FREE, A, PF>(r, count, w);
+        else return chunk_mixture_f32<MODEL, FREE, A, PF>(r, count, w);
+    } else if constexpr (BG == BG_NONE) {
+        if constexpr (FAST == 2 && MODEL == MODEL_PROFILE && !FREE) return chunk_profile_narrow<PF>(r, count, w);
+        else return chunk_const_fast<MODEL, FREE, PF>(r, count, w);
+    } else if constexpr (BG == BG_FIXED) {
+        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series);
+    } else if constexpr (BG == BG_FIXED_DENSITY) {
+        // BG_FIXED_DENSITY, f64 fast forms
+        constexpr int ND = record_doubles(MODEL, FREE);
+        constexpr int XB = geometry_doubles(MODEL, FREE);
         constexpr bool NARROW = FAST == 2;          // f_back >= 2^-20 bounds every mixture value from below (mcd_guard.h)
         BgFixedAcc acc;
         acc.init();
@@ -1393,7 +1310,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (NARROW) {
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
+                pf.issue(r + 4 * ND);
                 four(r);
                 pf.retire(acc.l.p);
                 if (g & 1) { MCD_KEEP_BRANCH(); acc.rescale_density_narrow(); }    // wave-uniform: a scalar branch, not a select
@@ -1402,7 +1319,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         } else {
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
+                pf.issue(r + 4 * ND);
                 four(r);
                 pf.retire(acc.l.p);
                 acc.rescale_density();
@@ -1414,15 +1331,18 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             acc.add_density<NARROW>(d, n, r[XB + 2], w.fb, r[XB + 1], exptab);
             acc.rescale_density();
         }
-        result = acc.finish_density();
+        const double result = acc.finish_density();
         denormal = acc.denormal();
-    } else if constexpr (BG == BG_GAUSS && FAST) {
-        // MODEL_BGGAUSS has norm = verr^2 + sigma^2 and verr^2 + sigma_back^2: doubled norms are one FMA each (HALVED form;
-        // 8 norm for the narrow-range variant's one-step Newton reciprocal roots)
+        return result;
+    } else {
+        // BG_GAUSS, f64 fast forms.  MODEL_BGGAUSS has norm = verr^2 + sigma^2 and verr^2 + sigma_back^2: doubled norms are one
+        // FMA each (HALVED form; 8 norm for the narrow-range variant's one-step Newton reciprocal roots)
+        constexpr int ND = record_doubles(MODEL, FREE);
+        constexpr int XB = geometry_doubles(MODEL, FREE);
         constexpr bool HALVED = MODEL == MODEL_BGGAUSS;
         constexpr bool NARROW = FAST == 2;
         constexpr double kScale = NARROW ? 8.0 : 2.0;
-        const double s2x = kScale * (double)w.s2, sb2x = kScale * (double)w.sb2;
+        const double s2x = kScale * w.s2, sb2x = kScale * w.sb2;
         BgGaussAcc acc;
         acc.init();
         auto one = [&](RecPtr<double> rr) {
@@ -1439,7 +1359,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (NARROW) {
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
+                pf.issue(r + 4 * ND);
                 four(r);
                 pf.retire(acc.ly.p);
                 if (g & 1) { MCD_KEEP_BRANCH(); acc.rescale_narrow(); }    // wave-uniform: a scalar branch, not a select
@@ -1448,7 +1368,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         } else {
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
                 RecordPrefetch<4 * ND * 8, PF> pf;
-                pf.issue(r + MCD_PREFETCH_DISTANCE * 4 * ND);
+                pf.issue(r + 4 * ND);
                 four(r);
                 pf.retire(acc.ly.p);
                 acc.rescale();
@@ -1458,35 +1378,10 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
             one(r);
             acc.rescale();
         }
-        result = acc.finish<HALVED>(count);
+        const double result = acc.finish<HALVED>(count);
         denormal = acc.denormal();
-    } else {
-        A sum = 0;
-#pragma unroll 2
-        for (int j = 0; j < count; ++j, r += ND) {
-            T d, n;
-            star_d_n<MODEL, T, FREE>(r, w, d, n);
-            const T m = gauss_lnl(d, n);
-            T b, p;
-            if (BG == BG_FIXED) {
-                b = r[XB];
-                p = r[XB + 1];
-            } else if (BG == BG_FIXED_DENSITY) {
-                b = r[XB];
-                const T rho = r[XB + 2];
-                p = rho / (rho + w.fb);                          // model.py:588
-            } else {
-                const T nb = r[1] + w.sb2;                       // constant.py:333, model.py:423
-                const T db = r[0] - w.vb;
-                b = gauss_lnl(db, nb);                           // constant.py:334-336
-                const T rho = r[XB];
-                p = rho / (rho + w.fb);                          // constant.py:339, model.py:429
-            }
-            sum += (A)mixture_lnl(m, b, p);                      // runner.py:282-284, constant.py:320-323
-        }
-        result = (double)sum;
+        return result;
     }
-    return result;
 }
 
 // Per-star log-likelihood pieces for the membership / no_sum outputs: cluster lnL, background lnL, prior m.

@@ -1,4 +1,4 @@
-// CPU build of the bounded sub-variant of the narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_loglike<.., BOUNDED>,
+// CPU build of the bounded sub-variant of the narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_bgfixed_fast<.., BOUNDED>,
 // exp_tab_scaled<.., false>) and of its host guard (csrc/mcd_guard.h: bounded_rescale), next to the level-2 loop it replaces.
 // Test infrastructure only (tests/test_bgfixed_bounded.py).
 #include <cstdint>

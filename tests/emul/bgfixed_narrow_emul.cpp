@@ -1,5 +1,5 @@
 // CPU build of the narrow-range MODEL_BGFIXED chunk arithmetic on the exponent-biased table (csrc/mcd_math.h:
-// exp_tab_bias, exp_tab_scaled, chunk_loglike<.., TAB_BIASED>), next to the same chunk on the plain sqrt(2) table.
+// exp_tab_bias, exp_tab_scaled, chunk_bgfixed_fast<.., TAB_BIASED>), next to the same chunk on the plain sqrt(2) table.
 // Test infrastructure only (tests/test_bgfixed_narrow_loop.py).
 #include <cstdint>
 

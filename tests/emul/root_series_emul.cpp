@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- the verr-sorted record array and the series reciprocal root of the level-2 BGFIXED
-// fixed-centre loops (csrc/mcd_math.h: RootSeries, chunk_loglike; csrc/mcd_chunks.h: verr_order, permuted_exceptions,
+// fixed-centre loops (csrc/mcd_math.h: RootSeries, chunk_bgfixed_fast; csrc/mcd_chunks.h: verr_order, permuted_exceptions,
 // series_thresholds) compiled for the CPU, so that the series, the wave's vote, the sort and the plan on a sorted shard
 // can be checked without a GPU (tests/root_series_helper.py).  Never loaded by the product package.
 #include <algorithm>

@@ -1,4 +1,4 @@
-"""The bounded sub-variant of the narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_loglike<.., BOUNDED>; host guard
+"""The bounded sub-variant of the narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_bgfixed_fast<.., BOUNDED>; host guard
 csrc/mcd_guard.h: bounded_rescale): no exponent clamp and a rescale every R = 16 or 32 factors.  Wherever the guard admits
 it, every term stays inside the domain it was derived for and the loop gives the level-2 loop's bits; C3's exact shape
 runs it on the device with the same bits as the forced level-2 loop."""

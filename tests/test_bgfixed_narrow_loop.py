@@ -1,4 +1,4 @@
-"""The narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_loglike, 8-star iterations with one rescale each, then an
+"""The narrow-range MODEL_BGFIXED loop (csrc/mcd_math.h: chunk_bgfixed_fast, 8-star iterations with one rescale each, then an
 optional 4-star group and single stars): chunk lengths that exercise every part of it agree with the plain formulation
 on the CPU build, and C3's exact shape (1e6 stars x 256 walkers) agrees with the plain kernel and the NumPy oracle on
 the device."""

@@ -58,8 +58,7 @@ __global__ __launch_bounds__(kBlock) void lane_star_kernel(const double* __restr
             qq[j] = ok ? d * d : 0.0;
             nn[j] = ok ? se[j] + s2 : 1.0;
         }
-        const Frac f = frac_join(frac_join(frac_leaf2(qq[0], nn[0], qq[1], nn[1]), frac_leaf2(qq[2], nn[2], qq[3], nn[3])),
-                                 frac_join(frac_leaf2(qq[4], nn[4], qq[5], nn[5]), frac_leaf2(qq[6], nn[6], qq[7], nn[7])));
+        const Frac<double> f = frac_tree8(qq, nn);
         double q = f.num * rcp_nr(f.den);
         // product of 64 lane denominators would overflow: reduce log-domain pieces (mantissa product + exponent sum)
         int ex;
