@@ -333,6 +333,11 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      verr^2 + sigma^2) of their midpoint for every walker of a wave takes the reciprocal root from a
  *                      four-term series about that midpoint instead of v_rsq_f64 and a Newton step (more accurate and
  *                      fewer issue slots per term); 0 never.  mcd_last_series_chunks counts the chunks.
+ *   "root_direct"   1 (default): a chunk that takes the series root, and whose midpoint verr^2 is at most 1/8 of
+ *                      verr^2 + sigma^2 for every walker of the wave, evaluates the same cubic in verr^2 itself, with
+ *                      coefficients re-centred once per chunk: one float64 instruction per term fewer, relative error of
+ *                      the root <= 4.6e-16; 0: every series chunk keeps the form about the midpoint (the results of a
+ *                      library without this option, bit for bit).  mcd_last_direct_chunks counts the chunks.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -375,6 +380,9 @@ int mcd_last_narrow_bounded(const mcd_catalog* cat);
  * table.  0 when the launch did not read verr-sorted records or ran another kernel family (and for the launches of the
  * resident stretch-move chain, whose tables never reach the host), -1 before the first launch. */
 int64_t mcd_last_series_chunks(const mcd_catalog* cat);
+/* ... of which chunks in which every wave took the direct form of the series (option "root_direct"), counted the same way:
+ * never more than mcd_last_series_chunks, whose meaning it does not change; 0 and -1 as there. */
+int64_t mcd_last_direct_chunks(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

@@ -73,6 +73,7 @@ SYMBOLS = {
     "mcd_last_prefetch": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_narrow_bounded": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_series_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
+    "mcd_last_direct_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
@@ -514,6 +515,12 @@ class Catalog(object):
         ``verr_sorted``, ``root_series``; counted on the host); 0 none; -1 before any launch."""
         return self.lib.mcd_last_series_chunks(self.handle)
 
+    @property
+    def last_direct_chunks(self):
+        """... of which chunks in which every wave took the direct form of the series (option ``root_direct``; counted on
+        the host); 0 none; -1 before any launch."""
+        return self.lib.mcd_last_direct_chunks(self.handle)
+
     def stretch_info(self):
         """Where the blocks of ``stretch_move`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks', 'last_discard_status'}
         (``mcd_stretch_info``: resident on the device / host-driven / discarded by the device and re-run host-driven)."""
@@ -567,7 +574,8 @@ class Catalog(object):
         tile, rb = ctypes.c_int32(), ctypes.c_int32()
         _check(self.lib, self.lib.mcd_last_launch_info(self.handle, ctypes.byref(wg), ctypes.byref(tile),
                                                        ctypes.byref(ch), ctypes.byref(rb)), "mcd_last_launch_info")
-        return {"workgroups": wg.value, "walker_tile": tile.value, "chunks": ch.value, "record_bytes": rb.value}
+        return {"workgroups": wg.value, "walker_tile": tile.value, "chunks": ch.value, "record_bytes": rb.value,
+                "series_chunks": self.last_series_chunks, "direct_chunks": self.last_direct_chunks}
 
     def close(self):
         if getattr(self, "handle", None):

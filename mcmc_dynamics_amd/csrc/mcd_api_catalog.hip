@@ -141,6 +141,7 @@ const Option kOptions[] = {
     {"narrow_bounded", 0, 1, "narrow_bounded: 1 (where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->narrow_bounded = (int)v)},
     {"verr_sorted", -1, 1, "verr_sorted: -1 (by record volume, default), 0 (catalogue order) or 1 (sorted by verr)", true, true, MCD_SET(c->verr_sorted = (int)v)},
     {"root_series", 0, 1, "root_series: 1 (series root on the narrow chunks of verr-sorted records, default) or 0 (never)", false, false, MCD_SET(c->root_series = (int)v)},
+    {"root_direct", 0, 1, "root_direct: 1 (direct form of the series root where a chunk admits it, default) or 0 (delta form only)", false, false, MCD_SET(c->root_direct = (int)v)},
     {"prefetch", -1, 1, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)", false, false, MCD_SET(c->prefetch = (int)v)},
     {"spin_us", 0, kMax, "spin_us must be >= 0", false, false, MCD_SET(c->spin_us = v)},
     {"tail_split", kMin, kMax, nullptr, true, true, MCD_SET(c->tail_split = (int)v)},
@@ -171,6 +172,7 @@ LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& 
     // instead, which travels through the reduce kernel and the all-reduce to every rank.
     shape.rerun_flag = coll ? nullptr : out_buf + n_out;
     shape.root_series = w.sorted && cat->root_series != 0;
+    shape.root_direct = shape.root_series && cat->root_direct != 0;
     return shape;
 }
 
@@ -185,6 +187,15 @@ int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, 
     const mcd::ParamRanges pr = mcd::table_ranges(cat->model, cat->free_centre, cat->k, params, n_rows);
     if (!pr.finite) return 0;
     return (int64_t)(std::upper_bound(w.series_need.begin(), w.series_need.end(), pr.s2_min) - w.series_need.begin());
+}
+
+// ... of which in the direct form of the series (option "root_direct"): both votes pass in all lanes where they pass for the
+// smallest sigma^2 of the table (either condition only loosens as sigma^2 grows, so the largest passes with it)
+int64_t direct_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows) {
+    if (!w.sorted || !cat->root_series || !cat->root_direct || level != 2 || w.direct_need.empty()) return 0;
+    const mcd::ParamRanges pr = mcd::table_ranges(cat->model, cat->free_centre, cat->k, params, n_rows);
+    if (!pr.finite) return 0;
+    return (int64_t)(std::upper_bound(w.direct_need.begin(), w.direct_need.end(), pr.s2_min) - w.direct_need.begin());
 }
 
 // the fast BGFIXED kernel leaves the walker-independent sum of lnL_bg to the reduction
@@ -230,7 +241,10 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
     w.uniform_len = plan.uniform_len;
     w.uniform_extra = plan.uniform_extra;
     w.sorted = sorted;
-    if (sorted) w.series_need = mcd::series_thresholds(plan, sh.sorted_e2.data());
+    if (sorted) {
+        w.series_need = mcd::series_thresholds(plan, sh.sorted_e2.data());
+        w.direct_need = mcd::direct_thresholds(plan, sh.sorted_e2.data());
+    }
     {
         // balanced plans with an even number of workgroups per CU run as half as many 8-wave workgroups that add their
         // chunks' sums up themselves: half (to an eighth of) the partial sums per walker (mcd_kernels.hip: loglike_kernel)
@@ -536,6 +550,7 @@ int mcd_stretch_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* ho
 int mcd_last_prefetch(const mcd_catalog* cat) { return cat ? cat->last_prefetch : -1; }
 
 int64_t mcd_last_series_chunks(const mcd_catalog* cat) { return cat ? cat->last_series_chunks : -1; }
+int64_t mcd_last_direct_chunks(const mcd_catalog* cat) { return cat ? cat->last_direct_chunks : -1; }
 
 int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
 

@@ -110,6 +110,7 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
         w->fast = fast;
         w->narrow_rescale = narrow_rescale;
         w->series_chunks = series_chunk_count(cat, *w, fast, params, n_rows);
+        w->direct_chunks = direct_chunk_count(cat, *w, fast, params, n_rows);
         w->staged = true;
     }
     cat->cur_walkers = n_walkers;
@@ -171,8 +172,9 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         mcd::LaunchShape shape = main_launch_shape(cat, sh, w, w.fast, coll, out_buf, n_out);
         shape.narrow_rescale = cat->narrow_bounded ? w.narrow_rescale : 0;
         cat->last_narrow_bounded = mcd::narrow_bounded_launch(shape) ? shape.narrow_rescale : 0;
-        if (&sh == &cat->shards.front()) cat->last_series_chunks = 0;
+        if (&sh == &cat->shards.front()) cat->last_series_chunks = cat->last_direct_chunks = 0;
         cat->last_series_chunks += shape.root_series && shape.fast == 2 ? w.series_chunks : 0;
+        cat->last_direct_chunks += shape.root_direct && shape.fast == 2 ? w.direct_chunks : 0;
         w.launch_tag = coll ? 0.0 : (double)(++cat->launch_seq);
         shape.launch_tag = w.launch_tag;
         hipEvent_t k0 = sh.ev_k0, k1 = sh.ev_k1;

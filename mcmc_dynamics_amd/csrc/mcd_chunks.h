@@ -237,6 +237,26 @@ inline std::vector<double> series_thresholds(const ChunkPlan& plan, const double
     return need;
 }
 
+// Smallest sigma^2 with which such a chunk also takes the direct form of the series (mcd_math.h: RootDirect::direct_ok on
+// the chunk's centre: 7 centre <= sigma^2), up to rounding
+inline double direct_threshold(double e_first, double e_last) {
+    const double need = std::max(series_threshold(e_first, e_last), 7.0 * (0.5 * e_first + 0.5 * e_last));
+    return need == need ? need : std::numeric_limits<double>::infinity();
+}
+
+// ... of every chunk of `plan` that is not flagged general; ascending
+inline std::vector<double> direct_thresholds(const ChunkPlan& plan, const double* sorted_e2) {
+    std::vector<double> need;
+    need.reserve(plan.chunks.size());
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const Chunk& ch = plan.chunks[c];
+        if (ch.count <= 0 || (!plan.general.empty() && plan.general[c])) continue;
+        need.push_back(direct_threshold(sorted_e2[ch.begin], sorted_e2[ch.begin + ch.count - 1]));
+    }
+    std::sort(need.begin(), need.end());
+    return need;
+}
+
 // Walker-independent part of the fixed-background likelihoods: sum of lnL_bg over the shard's stars of each parameter
 // set (Neumaier-compensated).  Added once per output by the reduce kernel when a fast mixture kernel ran.
 inline std::vector<double> pset_background_sums(const double* lnlike_bg, const std::vector<int64_t>& bin_offsets,

@@ -131,6 +131,9 @@ struct WorkSet {
     std::vector<double> series_need;   // sorted: per chunk outside chunk_general, the smallest sigma^2 with which its verr^2
                                        // band passes the series vote (mcd_math.h: RootSeries), ascending
     int64_t series_chunks = 0;         // chunks of the staged batch every wave of which takes the series root
+    std::vector<double> direct_need;   // sorted: ... and the smallest sigma^2 with which the chunk also passes the vote on the
+                                       // direct form of the series (mcd_math.h: RootDirect)
+    int64_t direct_chunks = 0;         // chunks of the staged batch every wave of which takes the direct form
 };
 
 // device arena of the resident stretch-move chain and its pinned host mirror (same layout, see stretch_block_device)
@@ -195,6 +198,7 @@ LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& 
 const double* fast_pset_const(const mcd_catalog* cat, const Shard& sh, int level);
 const void* main_records(const Shard& sh, const WorkSet& w);
 int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
+int64_t direct_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
 // mcd_api_eval.hip
 int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
 int sync_all(mcd_catalog* cat);
@@ -246,6 +250,8 @@ struct mcd_catalog {
     int verr_sorted = -1;              // option "verr_sorted": the main kernel reads a verr-sorted copy of the records (f64
                                        // MODEL_BGFIXED, fixed centre, one parameter set): -1 from 8 MiB of records per device, 0 never, 1 always
     int root_series = 1;               // option "root_series": 1 the series root on the sorted records' narrow chunks, 0 never
+    int root_direct = 1;               // option "root_direct": 1 the direct form of the series where a chunk admits it, 0 the
+                                       // delta form on every series chunk
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
                                        // small enough, 0 never, m > 0 forced with m workgroups per CU
     int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
@@ -277,6 +283,7 @@ struct mcd_catalog {
     std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
+    int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
     int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };
 

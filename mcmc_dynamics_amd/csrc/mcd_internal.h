@@ -27,6 +27,7 @@ struct LaunchShape {
                                     // prefetching kernel (mcd_guard.h: bounded_rescale), 0 the narrow-range loop as is
     bool root_series = false;       // the records are sorted by verr and the level-2 BGFIXED fixed-centre loops may take the
                                     // per-chunk series root (mcd_math.h: RootSeries); f64 only
+    bool root_direct = false;       // ... and its direct form where a chunk admits it (mcd_math.h: RootDirect)
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };

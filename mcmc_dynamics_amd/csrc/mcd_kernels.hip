@@ -115,7 +115,8 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // BGGAUSS kernels (106 - 127 with 4 waves) and the occupancy drops from 4 to 3 waves per SIMD.
 // BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_bgfixed_fast<.., BOUNDED>)
 // for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
-// root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries).
+// root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries): 1
+// its delta form only, 2 the direct form where a chunk admits it (RootDirect).
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
 __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
                                                                  const Chunk* __restrict__ chunks,
@@ -208,7 +209,8 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
             if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
             else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(chunk_recs, ch.count, w, denormal,
-                                                                                         exptab_lds, narrow_iters, root_series != 0);
+                                                                                         exptab_lds, narrow_iters, root_series != 0,
+                                                                                         root_series > 1);
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }
@@ -339,7 +341,7 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
     hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
-                       sh.chunk_general, n_slots, narrow_iters, (int)sh.root_series)
+                       sh.chunk_general, n_slots, narrow_iters, sh.root_series ? (sh.root_direct ? 2 : 1) : 0)
     // bounded, else prefetch, else plain -- once, for a workgroup of decltype(waves)::value waves
     auto launch = [&](auto waves) {
         constexpr int W = decltype(waves)::value;

@@ -517,6 +517,14 @@ MCD_HD double vgpr_constant(double x) {
 #endif
     return x;
 }
+// x, opaque to the optimiser AND tied to its place in the program (a volatile asm, no instruction): what is computed
+// from it is neither shared with an equal computation elsewhere nor moved out of the branch it stands in
+MCD_HD double vgpr_pinned(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
 template <bool TWO_STEP = false, bool CLAMP = true>
 MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
     int k;
@@ -546,26 +554,40 @@ MCD_HD double exp_tab_scaled(double u, const double* __restrict__ tab) {
 // multiply-adds per term instead of the variance, v_rsq_f64 and the Newton step (8 issue slots).  Error: the rounding of
 // b0 and of the last FMA (2^-53 each) plus the truncation, < 2.9e-16 relative -- the one-step Newton form it replaces is low by up to
 // 4.1e-15.  The rounding error of m0 itself (an exact two-sum) is folded into b0.
+// What both forms of the series (RootSeries, RootDirect) start from at a chunk's centre eb for a lane's s2 -- one place, so
+// that the two stay in step
+struct RootCentre {
+    double p, m0, inv, G0, q, corr;
+    MCD_HD void setup(double eb, double s2) {
+        p = 8.0 * eb;
+        const double s2x = 8.0 * s2;                               // exact, both
+        m0 = p + s2x;
+        const double bb = m0 - p;
+        const double err = (p - (m0 - bb)) + (s2x - bb);          // m0 + err = p + s2x exactly
+        inv = rcp_nr(m0);
+        // 2 (m0 + err)^(-1/2) = G0 (1 + corr) to second order: y is within an ulp of m0^(-1/2), its residual 1 - m0 y^2
+        // comes out exactly (h + eh = m0 y without rounding); callers let both first-order corrections enter through ONE
+        // last FMA, fma(G0, corr [+ ...], G0), which then carries one rounding
+        const double y = rsqrt_nr(m0);
+        const double h = m0 * y;
+        const double eh = fma_(m0, y, -h);
+        const double res = fma_(-h, y, 1.0) - eh * y;
+        G0 = 2.0 * y;
+        q = 8.0 * inv;                                             // t = q delta
+        corr = 0.5 * (res - err * inv);
+    }
+};
+
 struct RootSeries {
     static constexpr double kMaxT = 0x1p-13;
     double eb, b0, b1, b2, b3;
     // coefficients about the centre eb for this lane's s2; false when s2 puts a band of half-width `half` outside |t| <= 2^-13
     MCD_HD bool setup(double eb_, double half, double s2) {
         eb = eb_;
-        const double p = 8.0 * eb, s2x = 8.0 * s2;                 // exact
-        const double m0 = p + s2x;
-        const double bb = m0 - p;
-        const double err = (p - (m0 - bb)) + (s2x - bb);          // m0 + err = p + s2x exactly
-        const double inv = rcp_nr(m0);
-        // b0 = 2 (m0 + err)^(-1/2) with ONE rounding: y is within an ulp of m0^(-1/2), its residual 1 - m0 y^2 comes out
-        // exactly (h + eh = m0 y without rounding), and both first-order corrections enter through the last FMA
-        const double y = rsqrt_nr(m0);
-        const double h = m0 * y;
-        const double eh = fma_(m0, y, -h);
-        const double res = fma_(-h, y, 1.0) - eh * y;
-        const double G0 = 2.0 * y;
-        const double q = 8.0 * inv;                                // t = q delta
-        b0 = fma_(G0, 0.5 * (res - err * inv), G0);
+        RootCentre c;
+        c.setup(eb, s2);
+        const double m0 = c.m0, G0 = c.G0, q = c.q;
+        b0 = fma_(G0, c.corr, G0);                                 // ONE rounding (RootCentre)
         b1 = -0.5 * (G0 * q);
         b2 = -0.75 * (b1 * q);
         b3 = (-5.0 / 6.0) * (b2 * q);
@@ -578,6 +600,68 @@ struct RootSeries {
     MCD_HD double g(double e) const {
         const double delta = e - eb;
         return fma_(fma_(fma_(b3, delta, b2), delta, b1), delta, b0);
+    }
+};
+
+// a * s + c with the factor s known to be wave-uniform (a star-record value held in an SGPR pair): the three-address
+// form with the SGPR pair as its one scalar operand, whatever the register allocator would have preferred
+MCD_HD double fma_sgpr_factor(double a, double s, double c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    double r;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(s), "v"(c));
+    return r;
+#else
+    return std::fma(a, s, c);
+#endif
+}
+
+// The same cubic as RootSeries::g written in e itself: g = c0 + e (c1 + e (c2 + e c3)).  delta = e - eb is
+// wave-uniform (record value and chunk centre), yet gfx950 has no scalar f64 add, so RootSeries::g pays the subtraction
+// on the vector pipe once per term; here the coefficients are re-centred to 0 once per chunk and the three FMAs take the
+// record value as their SGPR operand: one f64 instruction per term fewer.  With G = 2 (8 (eb + s2))^(-1/2), q = 1 / (eb + s2)
+// and rho = q eb (the weight of the centre in the variance) the Taylor cubic about eb, expanded about 0, is
+//   c0 =  G     (1   + rho/2   + 3 rho^2/8 + 5 rho^3/16)        c2 =  G q^2 (3/8 + 15 rho/16)
+//   c1 = -G q   (1/2 + 3 rho/4 + 15 rho^2/16)                   c3 = -G q^3  5/16
+// The price is conditioning: the terms no longer shrink with |t| <= 2^-13 but with x = q e <= rho + 2^-13, and c0's
+// rounding is not damped, so the form is admitted for rho <= kRhoMax = 1/8 only (direct_ok; a wave-wide vote like the
+// series').  Worst-case relative error against (2 (e + s2))^(-1/2) for |t| <= 2^-13 and rho <= 1/8, in units of
+// u = 2^-53 = 1.11e-16 and relative to G (g / G lies within 1 +- 2^-14):
+//   last FMA                                                                                   1.00
+//   c0: ONE rounding of the value, |c0| <= 1.0690 G.  It is built as b0 is, G0 + G0 A in one FMA, where
+//       A = (res - err inv) / 2 + P takes up G0's own error exactly (RootSeries::setup) and P = rho/2 + 3 rho^2/8 +
+//       5 rho^3/16 <= 0.0690 carries rho's error (inv 1.5, m0 against m0 + err 1, the product 1: 3.5, times
+//       rho P'/P <= 1.2) and three Horner roundings, 7.2 in all, plus the rounding of the sum: 0.0690 x 8.2 = 0.57    1.64
+//   c1 e: |c1 e| <= x (1/2 + 3 rho/4 + 15 rho^2/16) G <= 0.0762 G.  c1: G0 2 (y 1.5, m0 0.5), q 2.5, G0 q 1, the bracket
+//       2.7 (rho's 3.5 x 0.2, two roundings), the product 1: 9.2; the FMA that forms c1 + e (..) 1: 0.0762 x 10.2      0.78
+//   c2 e^2: <= x^2 (3/8 + 15 rho/16) G <= 0.0077 G, coefficient and FMA <= 15: 0.0077 x 15                            0.12
+//   c3 e^3: <= 5/16 x^3 G <= 0.00062 G, coefficient <= 12                                                             0.01
+//   truncation 35/128 t^4 = 6.1e-17                                                                                   0.55
+// 4.10 u (1 + 2^-14) = 4.6e-16 = kErrorBound (the issue's ceiling: 5e-16, an eighth of what the one-step Newton form is
+// low by).  A bound, not an estimate: the roundings do not line up, and over 4e5 samples the largest error met is
+// 2.9e-16, against 2.7e-16 for the delta form on the same inputs (tests/test_root_direct_cpu.py).
+struct RootDirect {
+    static constexpr double kRhoMax = 0.125;
+    static constexpr double kErrorBound = 4.6e-16;
+    double c0, c1, c2, c3;
+    // rho = eb / (eb + s2) <= 1/8, without a division (false for NaN)
+    static MCD_HD bool direct_ok(double eb, double s2) { return (1.0 / kRhoMax - 1.0) * eb <= s2; }
+    // coefficients for this lane's s2 on the chunk with centre eb (the eb of RootSeries::setup)
+    MCD_HD void setup(double eb, double s2) {
+        RootCentre c;
+        c.setup(eb, s2);
+        const double G0 = c.G0, q = c.q;
+        const double rho = c.p * c.inv;
+        const double P = rho * fma_(rho, fma_(rho, 0.3125, 0.375), 0.5);
+        c0 = fma_(G0, c.corr + P, G0);
+        const double gq = G0 * q;
+        c1 = -gq * fma_(rho, fma_(rho, 0.9375, 0.75), 0.5);
+        const double gq2 = gq * q;
+        c2 = gq2 * fma_(rho, 0.9375, 0.375);
+        c3 = -0.3125 * (gq2 * q);
+    }
+    // e: the record's verr^2 (wave-uniform, an SGPR pair on the device)
+    MCD_HD double g_direct(double e) const {
+        return fma_sgpr_factor(fma_sgpr_factor(fma_sgpr_factor(c3, e, c2), e, c1), e, c0);
     }
 };
 
@@ -1148,7 +1232,7 @@ MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<d
 // sqrt(2)-scaled table; star_d_n's own norm is dead code there.
 template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED>
 MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w, bool& denormal,
-                                 const double* __restrict__ exptab, int rescale_iters, bool series) {
+                                 const double* __restrict__ exptab, int rescale_iters, bool series, bool direct) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int XB = geometry_doubles(MODEL, FREE);
     constexpr bool HALVED = MODEL == MODEL_BGFIXED;
@@ -1158,13 +1242,16 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     const double scale = BOUNDED ? vgpr_constant(kScale) : kScale;
     BgFixedAcc acc;
     acc.init();
-    // SERIES (a type: std::true_type / std::false_type): the reciprocal root from the chunk's RootSeries instead of
-    // v_rsq_f64 and the Newton step; everything after g is the same code
+    // SERIES (std::false_type / std::true_type / a RootDirect): the reciprocal root from the chunk's RootSeries (or from
+    // the RootDirect passed along, the same cubic in verr^2 itself) instead of v_rsq_f64 and the Newton step; everything
+    // after g is the same code
     RootSeries sr;
     auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
         double d, n;
         star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-        if constexpr (decltype(SERIES)::value) {
+        if constexpr (std::is_same<decltype(SERIES), RootDirect>::value) {
+            acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, SERIES.g_direct(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
+        } else if constexpr (decltype(SERIES)::value) {
             acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, sr.g(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
         } else {
             if constexpr (HALVED) n = fma_(sc, rr[1], s2x);
@@ -1243,17 +1330,38 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     // The series form where every lane's sigma^2 keeps the chunk's verr^2 band inside |t| <= 2^-13 (RootSeries): the
     // verdict depends on the chunk's first and last record and the wave's walkers alone, so the 4-star, the 8-star and
     // the bounded loop decide alike and stay bitwise equal to each other.  `series`: the records are sorted by verr
-    // (host: LaunchShape::root_series).
+    // (host: LaunchShape::root_series).  A second vote, on the weight of the chunk's centre in every lane's variance
+    // (RootDirect::direct_ok), sends a series chunk to the direct form of the cubic: it too depends on the end records and
+    // the walkers alone.  `direct`: the second vote is held (option "root_direct"); without it every series chunk keeps
+    // the delta form.
     constexpr bool kCanSeries = NARROW && MODEL == MODEL_BGFIXED && !FREE;
-    bool use_series = false;
+    bool use_series = false, use_direct = false;
     if constexpr (kCanSeries) {
         if (series && count > 0) {
-            const bool ok = sr.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], w.s2);
+            RootSeries vote;                                         // (its verdict and centre only: the rest is dead code)
+            const bool ok = vote.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], w.s2);
             use_series = wave_all(ok);
+            if (use_series && direct) use_direct = wave_all(RootDirect::direct_ok(vote.eb, w.s2));
         }
     }
     if constexpr (kCanSeries) {
-        if (use_series) { MCD_KEEP_BRANCH(); run(std::true_type()); }
+        // The three copies follow one another in the kernel, each behind its own test, and whatever a later copy takes
+        // over from here stays in registers across the earlier ones: a series copy therefore forms its coefficients
+        // itself, from the end records and from s2x (which the rsq loops keep anyway), behind vgpr_pinned so that
+        // nothing of it is shared with the vote or moves out of the copy's own branch -- the same values as the
+        // vote's, bit for bit, BECAUSE s2x = 8 s2 and (1/8) s2x are exact: scaling by a power of two rounds nothing as
+        // long as 8 s2 is finite (and the way back lands on s2, which is representable, subnormal or not); the range
+        // guard admits no fast mixture kernel for a variance beyond 2^200 (mcd_guard.h: guard_verdict).
+        if (use_direct) {
+            const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
+            RootDirect sd;
+            sd.setup(0.5 * e_first + 0.5 * e_last, vgpr_pinned((1.0 / kScale) * s2x));
+            run(sd);
+        } else if (use_series) {
+            const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
+            sr.setup_chunk(e_first, e_last, vgpr_pinned((1.0 / kScale) * s2x));
+            run(std::true_type());
+        }
         else run(std::false_type());
     } else {
         run(std::false_type());
@@ -1273,10 +1381,12 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
 // BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
 // narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
 // `series` (MODEL_BGFIXED, fixed centre, FAST == 2, f64): the records are sorted by verr, so a chunk whose verr^2 band is
-// narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote.
+// narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote;
+// with `direct` (option "root_direct") such a chunk takes the direct form of the series (RootDirect) where the chunk's
+// verr^2 is at most 1/8 of every walker's variance -- a second vote.
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
-                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false) {
+                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false, bool direct = false) {
     constexpr int BG = bg_kind(MODEL);
     denormal = false;
     if constexpr (!FAST) {
@@ -1289,7 +1399,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (FAST == 2 && MODEL == MODEL_PROFILE && !FREE) return chunk_profile_narrow<PF>(r, count, w);
         else return chunk_const_fast<MODEL, FREE, PF>(r, count, w);
     } else if constexpr (BG == BG_FIXED) {
-        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series);
+        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct);
     } else if constexpr (BG == BG_FIXED_DENSITY) {
         // BG_FIXED_DENSITY, f64 fast forms
         constexpr int ND = record_doubles(MODEL, FREE);

@@ -12,9 +12,10 @@ narrow-range instantiation runs 8-star iterations with the rescale inside the lo
 parameter BOUNDED, the last one of the mangled name) rescales every fourth 8-star iteration at C3's R = 32, in a block the
 loop branches out to: (4 x loop body + rescale block) / 32.  That instantiation is what C3's timed launches run, so it
 keeps its row under "bgfixed_rsq"; the level-2 prefetching loop keeps its row under "bgfixed_level2".  Each of the three
-kernels also holds the series form of its loop (mcd_math.h: RootSeries; the chunks of a verr-sorted record array whose
-verr^2 band is narrow): rows "..., series".  The bounded series loop is what nearly all of C3's chunks run, so it gives the
-"bgfixed" key's prefetch fields.
+kernels also holds the two series forms of its loop (mcd_math.h: RootSeries about the chunk's centre, RootDirect in
+verr^2 itself; the chunks of a verr-sorted record array whose verr^2 band is narrow): rows "..., series" and "..., direct".
+The bounded direct loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded
+delta series loop keeps its row under "bgfixed_series_bounded".
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -37,10 +38,10 @@ SLOT_NS = 2.33
 #  [, (stars, trips, selector) of the instantiation with the prefetch when its loop differs
 #   [, model key of the instantiation with the prefetch when it differs]])
 #   selector(Counter of the loop body) -> bool picks the loop among the kernel's innermost loops
-def _sel(rsq=None, frexp=None, rcp=None):
+def _sel(rsq=None, frexp=None, rcp=None, add=None):
     def f(c):
         return ((rsq is None or c["v_rsq_f64_e32"] == rsq) and (frexp is None or c["v_frexp_mant_f64_e32"] == frexp)
-                and (rcp is None or c["v_rcp_f64_e32"] == rcp))
+                and (rcp is None or c["v_rcp_f64_e32"] == rcp) and (add is None or c["v_add_f64"] == add))
     return f
 
 
@@ -66,14 +67,24 @@ KERNELS = [
 BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded", "bgfixed_rsq", 8, 4, _sel(rsq=8, frexp=0))
 
 # the series loops of the same three kernels (mcd_math.h: RootSeries; chunks of a verr-sorted record array whose verr^2
-# band is narrow): no v_rsq_f64 in the body.  Full tag, name, key, stars, trips, selector, prefetching, bounded
+# band is narrow): no v_rsq_f64 in the body.  Each kernel holds two of them, told apart by their v_add_f64 per term: the
+# delta form (about the chunk's centre) has three -- v - v_sys, the exponent's rounding constant and delta = e - eb, which
+# feeds the first FMA of the cubic -- the direct form (RootDirect: the cubic in verr^2 itself) the first two only.
+# Full tag, name, key, stars, trips, selector, prefetching, bounded
 SERIES = [
-    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, series", "bgfixed_series", 4, 2, _sel(rsq=0, frexp=0), False, False),
-    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, series", "bgfixed_series", 8, 1, _sel(rsq=0, frexp=1),
-     True, False),
-    # what C3's timed launches run on the chunks that qualify (98 % of them): the "bgfixed" key's prefetch fields
-    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, series", "bgfixed", 8, 4, _sel(rsq=0, frexp=0),
-     True, True),
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, series", "bgfixed_series", 4, 2, _sel(rsq=0, frexp=0, add=12),
+     False, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, series", "bgfixed_series", 8, 1,
+     _sel(rsq=0, frexp=1, add=24), True, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, series", "bgfixed_series_bounded", 8, 4,
+     _sel(rsq=0, frexp=0, add=24), True, True),
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, direct", "bgfixed_direct", 4, 2, _sel(rsq=0, frexp=0, add=8),
+     False, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, direct", "bgfixed_direct", 8, 1,
+     _sel(rsq=0, frexp=1, add=16), True, False),
+    # what C3's timed launches run on the chunks that qualify (98.2 % of the stars): the "bgfixed" key's prefetch fields
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, direct", "bgfixed", 8, 4,
+     _sel(rsq=0, frexp=0, add=16), True, True),
 ]
 
 
