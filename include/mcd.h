@@ -178,6 +178,15 @@ int mcd_membership(mcd_catalog* cat, int32_t k, const double* params, double* ou
 /* Per-star mixture log-likelihood for ONE parameter row, `lnlike(values, no_sum=True)` of
  * ModelFitConstantBackground (analysis/model.py:565-623); defined for every background model. */
 int mcd_loglike_per_star(mcd_catalog* cat, int32_t k, const double* params, double* out);
+/* Log-likelihood AND its gradient with respect to the K kernel columns (units of the kernel: km/s, arcsec for a and
+ * r_peak, degrees for the centre).  params [max(1,B)][W][K]; out [max(1,B)][W] (may be NULL); grad [max(1,B)][W][K].
+ * out equals mcd_loglike_batch with option "fast_path" = 0 to rounding.  A star exactly on a walker's free centre
+ * contributes 0 to the centre columns of the constant-rotation models (theta is undefined there).  float64 catalogues only
+ * (MCD_ERR_INVALID otherwise).  Synchronous, deterministic (fixed-order sums: bit-identical from run to run); device and
+ * rank shards are summed by one all-reduce of the 1 + K fields under the collective deadline.  Honours option "timing"
+ * (mcd_last_kernel_ms: the gradient kernel, as the main kernel for values). */
+int mcd_loglike_grad_batch(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* params, double* out,
+                           double* grad);
 /* Per-star summaries over S posterior samples (params: row-major [S][K], the kernel columns of mcd_loglike_batch).
  * lppd[i]    = log( (1/S) sum_s exp(lnL_is) )      lnl_var[i] = sample variance (S-1) of lnL_is (0 when S == 1)
  * pmem_mean[i], pmem_std[i]: mean and standard deviation (S-1; 0 when S == 1) of the membership probability

@@ -43,6 +43,8 @@ SYMBOLS = {
     "mcd_catalog_n_stars": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_catalog_n_outputs": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "mcd_loglike_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p]),
+    "mcd_loglike_grad_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p,
+                                              _c_double_p]),
     "mcd_params_upload": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p]),
     "mcd_loglike_enqueue": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_loglike_fetch": (ctypes.c_int, [ctypes.c_void_p, _c_double_p]),
@@ -370,6 +372,20 @@ class Catalog(object):
         _check(self.lib, rc, "mcd_loglike_batch")
         self._walkers = w
         return out
+
+    def loglike_grad(self, params, want_value=True):
+        """Value and gradient with respect to the K kernel columns (kernel units: km/s, arcsec, degrees):
+        (W, K) -> ((W,), (W, K))   [binned: (B, W, K) -> ((B, W), (B, W, K))].  float64 catalogues only; synchronous and
+        bit-identical from run to run.  ``want_value=False`` passes a null value pointer and returns (None, grad)."""
+        self._alive()
+        p, w = self._params(params)
+        lead = (self.n_sets, w) if self.n_sets > 1 else (w,)
+        out = np.empty(lead, dtype=np.float64) if want_value else None
+        grad = np.empty(lead + (self.k,), dtype=np.float64)
+        rc = self.lib.mcd_loglike_grad_batch(self.handle, w, self.k, _ptr(p), _ptr(out), _ptr(grad))
+        _check(self.lib, rc, "mcd_loglike_grad_batch")
+        self._walkers = w
+        return out, grad
 
     def upload_params(self, params):
         p, w = self._params(params)

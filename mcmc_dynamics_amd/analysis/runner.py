@@ -389,6 +389,124 @@ class Runner(object):
         out[ok] = ll[ok] + lp[ok]
         return out
 
+    # ------------------------------------------------------------------ first-order methods (new)
+    def _grad_plan(self):
+        """The plan, refused unless every parameter is a plain box-bounded one: the chain rule below has no term for an
+        ``expr`` constraint or an ``lnprior`` expression."""
+        plan = self._plan()
+        if not plan.simple:
+            for name, par in self.parameters.items():
+                if par._expr is not None:
+                    raise NotImplementedError("gradients through the expr constraint of parameter '{0}' are not "
+                                              "implemented".format(name))
+                if par._lnprior is not None:
+                    raise NotImplementedError("gradients through the lnprior expression of parameter '{0}' are not "
+                                              "implemented".format(name))
+        return plan
+
+    def lnlike_grad_batch(self, values):
+        """(W, P) free-parameter vectors -> ((W,) log-likelihoods, (W, P) gradients with respect to the FREE parameters, in
+        their own units), one launch of the device's value-and-gradient kernel.  The chain rule of the batch plan is
+        applied on the host: a kernel column fed by free parameter j contributes its unit factor times the column's
+        partial derivative, columns fed by fixed parameters are dropped.  Rows outside the prior get (-inf, zero row)."""
+        values = np.atleast_2d(np.asarray(values, dtype=np.float64))
+        plan = self._grad_plan()
+        if values.shape[1] != plan.free_idx.size:
+            raise ValueError("expected {0} free parameters per row, got {1}".format(plan.free_idx.size, values.shape[1]))
+        if self._context is not None and getattr(self._context, "n_ranks", 1) > 1:
+            self._check_ranks_agree(values)
+        n = values.shape[0]
+        out, grad = np.full(n, -np.inf), np.zeros((n, plan.free_idx.size))
+        full = plan.full(values)
+        ok = plan.prior_ok(full)
+        if not ok.any():
+            return out, grad
+        if not ok.all():
+            full[~ok] = full[int(np.flatnonzero(ok)[0])]
+        cat = self._catalog
+        if cat is None or plan.catalog_key != self._catalog_key:
+            cat = self._ensure_catalog()
+        if cat.n_sets != 1:
+            raise NotImplementedError("gradients are defined for un-binned analyses")
+        ll, g_cols = cat.loglike_grad(plan.table(full))
+        if plan.kernel_fac is not None:
+            g_cols = g_cols * plan.kernel_fac
+        free_pos = {int(i): j for j, i in enumerate(plan.free_idx)}
+        g_free = np.zeros((n, plan.free_idx.size))
+        for c, i in enumerate(plan.kernel_idx):
+            if int(i) in free_pos:
+                g_free[:, free_pos[int(i)]] += g_cols[:, c]
+        out[ok] = ll[ok]
+        grad[ok] = g_free[ok]
+        return out, grad
+
+    def lnprob_grad_batch(self, values):
+        """As ``lnlike_grad_batch`` for the log-posterior: the box priors are flat, so inside them value and gradient are
+        those of the likelihood, outside (-inf, zero row)."""
+        return self.lnlike_grad_batch(values)
+
+    def maximize(self, n_starts=64, x0=None, max_iter=200, gtol=1e-8):
+        """Maximum of the log-posterior inside the prior box (MAP; with flat boxes the maximum-likelihood estimate), by a
+        batched projected BFGS on the device gradient (``optimize.maximize_batch``) from ``n_starts`` rows of
+        ``get_initials`` or from the rows of ``x0``.
+
+        The default of 64 starts fills a wavefront: the kernel's lane = walker layout evaluates 64 parameter rows per
+        wave for the price of one, and idles the lanes below that.
+
+        Returns a dict: ``x`` the best start's position, ``lnprob`` and ``grad`` there, ``n_iter`` and ``converged`` of that
+        start, and ``all_x`` (W, P), ``all_lnprob`` (W,), ``all_converged`` (W,) for every start."""
+        from ..optimize import maximize_batch
+        plan = self._grad_plan()
+        starts = self.get_initials(int(n_starts)) if x0 is None else np.atleast_2d(np.asarray(x0, dtype=np.float64))
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        res = maximize_batch(self.lnprob_grad_batch, starts, lo, hi, max_iter=max_iter, gtol=gtol)
+        f = np.where(np.isfinite(res["f"]), res["f"], -np.inf)
+        # the best converged start, or the best of all when none converged
+        pool = np.flatnonzero(res["converged"]) if res["converged"].any() else np.arange(f.size)
+        best = int(pool[np.argmax(f[pool])])
+        return {"x": res["x"][best].copy(), "lnprob": float(f[best]), "grad": res["grad"][best].copy(),
+                "n_iter": int(res["n_iter"][best]), "converged": bool(res["converged"][best]), "all_x": res["x"],
+                "all_lnprob": f, "all_converged": res["converged"]}
+
+    def laplace(self, x, rel_step=1e-4):
+        """Laplace approximation at ``x`` (a maximum inside the box): the Hessian of the log-posterior by central
+        differences of the device gradient -- all 2 P displaced rows in ONE ``lnprob_grad_batch`` call -- symmetrised, and
+        ``covariance = inv(-H)``.  The step of parameter j is ``rel_step * max(|x_j|, width of a finite prior box / 100,
+        1e-3)``.  ValueError when ``x`` sits on a bound or when -H is not positive definite (not a maximum)."""
+        plan = self._grad_plan()
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        n_p = x.size
+        if np.any(x <= lo) or np.any(x >= hi):
+            raise ValueError("laplace: x sits on a bound of the prior in parameter(s) {0}".format(
+                [plan.names[int(plan.free_idx[j])] for j in np.flatnonzero((x <= lo) | (x >= hi))]))
+        width = np.where(np.isfinite(hi - lo), (hi - lo) / 100.0, 0.0)
+        h = rel_step * np.maximum(np.maximum(np.abs(x), width), 1e-3)
+        h = np.minimum(h, 0.5 * np.minimum(x - lo, hi - x))
+        rows = np.tile(x, (2 * n_p, 1))
+        rows[np.arange(n_p), np.arange(n_p)] += h
+        rows[n_p + np.arange(n_p), np.arange(n_p)] -= h
+        step = rows[:n_p].diagonal() - rows[n_p:].diagonal()          # the steps as represented
+        value, grad = self.lnprob_grad_batch(rows)
+        if not np.all(np.isfinite(value)):
+            raise ValueError("laplace: a displaced point left the prior")
+        hess = (grad[:n_p] - grad[n_p:]) / step[:, None]              # row j: d grad / d x_j
+        hess = 0.5 * (hess + hess.T)
+        try:
+            np.linalg.cholesky(-hess)
+        except np.linalg.LinAlgError:
+            raise ValueError("laplace: -H is not positive definite at x (not a maximum)")
+        return {"hessian": hess, "covariance": np.linalg.inv(-hess)}
+
+    def get_initials_laplace(self, n_walkers, x, covariance):
+        """(n_walkers, P) start positions drawn from the Gaussian N(x, covariance) of ``laplace`` and clipped into the
+        prior box."""
+        plan = self._grad_plan()
+        x = np.asarray(x, dtype=np.float64).reshape(-1)
+        chol = np.linalg.cholesky(np.asarray(covariance, dtype=np.float64))
+        draws = x + np.random.standard_normal((int(n_walkers), x.size)) @ chol.T      # (NumPy's global generator, as get_initials)
+        return np.clip(draws, plan.lo[plan.free_idx], plan.hi[plan.free_idx])
+
     # ------------------------------------------------------------------ several ranks (one process per GPU)
     RANK_CHECK_EVERY = 256
 

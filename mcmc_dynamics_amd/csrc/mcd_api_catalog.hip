@@ -25,6 +25,9 @@ void free_workset(WorkSet& w) {
     if (w.d_out) (void)hipFree(w.d_out);
     if (w.d_out2) (void)hipFree(w.d_out2);
     if (w.d_partials2) (void)hipFree(w.d_partials2);
+    if (w.d_grad_partials) (void)hipFree(w.d_grad_partials);
+    if (w.d_grad_out) (void)hipFree(w.d_grad_out);
+    if (w.h_grad_out) (void)hipHostFree(w.h_grad_out);
     if (w.ev_staged) (void)hipEventDestroy(w.ev_staged);
     for (int b = 0; b < 2; ++b) {
         if (w.ev_reduced[b]) (void)hipEventDestroy(w.ev_reduced[b]);

@@ -1,8 +1,10 @@
 // mcd_api_eval.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host units):
 // the per-call launch sequence
 //   params H2D -> walker prep -> main kernel -> fixed-order reduce -> [RCCL all-reduce] -> D2H,
-// blocking and pipelined, with its HIP-event timing, and the per-star outputs of one parameter row.
+// blocking and pipelined, with its HIP-event timing, the per-star outputs of one parameter row, and the same sequence
+// for the value-and-gradient kernel (mcd_loglike_grad_batch).
 #include "mcd_host.h"
+#include "mcd_grad.h"
 
 using namespace mcd::host;
 
@@ -348,9 +350,110 @@ int per_star(mcd_catalog* cat, int32_t k, const double* params, int mode, double
     return MCD_OK;
 }
 
+// Value and gradient of one parameter table: the staging of the value path (params H2D, walker prep), the gradient kernel
+// and the fixed-order reduction of its 1 + K fields on every shard, one all-reduce of the fields where the stars are
+// spread over devices or ranks, D2H, and the transposition into the caller's [.][W] and [.][W][K] arrays.
+int loglike_grad(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* params, double* out, double* grad) {
+    if (!cat || !params || !grad) return fail(MCD_ERR_INVALID, "mcd_loglike_grad_batch: null catalogue, params or grad");
+    if (int rc = ctx_usable(cat->ctx)) return rc;
+    if (cat->precision != MCD_F64) return fail(MCD_ERR_INVALID, "gradients need an MCD_F64 catalogue");
+    int rc = stage_params(cat, n_walkers, k, params, false);
+    if (rc != MCD_OK) return rc;
+    mcd_ctx* ctx = cat->ctx;
+    const int64_t W = n_walkers;
+    const int64_t fields = 1 + k;
+    const int64_t padded = (W + 63) / 64 * 64;
+    const size_t n_res = (size_t)(cat->n_psets * fields * padded);       // doubles of a result buffer
+    const bool coll = ctx->has_comm();
+    for (Shard& sh : cat->shards) {
+        WorkSet& w = (*find_work(sh, W));
+        const DeviceSlot& slot = ctx->slots[sh.slot];
+        MCD_HIP(hipSetDevice(slot.device));
+        // (each buffer on its own: a call that failed half-way leaves what it got for the next one, nothing is allocated twice)
+        if (!w.d_grad_partials)
+            MCD_HIP(hipMalloc(&w.d_grad_partials, std::max<size_t>(1, (size_t)(fields * padded * w.n_chunks)) * sizeof(double)));
+        if (!w.h_grad_out) MCD_HIP(hipHostMalloc(&w.h_grad_out, n_res * sizeof(double), hipHostMallocDefault));
+        if (!w.d_grad_out) MCD_HIP(hipMalloc(&w.d_grad_out, n_res * sizeof(double)));
+        mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+        hipEvent_t k0 = sh.ev_k0, k1 = sh.ev_k1;
+        if (cat->timing_all) {
+            if (sh.ring_used >= (size_t)1 << 16) sh.ring_used = 0;
+            if (sh.ring_used == sh.ring.size()) {
+                hipEvent_t a, b;
+                MCD_HIP(hipEventCreate(&a));
+                MCD_HIP(hipEventCreate(&b));
+                sh.ring.emplace_back(a, b);
+            }
+            k0 = sh.ring[sh.ring_used].first;
+            k1 = sh.ring[sh.ring_used].second;
+            ++sh.ring_used;
+        }
+        // (timing: as for values, the inner event pair brackets the main kernel alone, the outer one the device sequence)
+        if (cat->timing && !cat->timing_all) MCD_HIP(hipEventRecord(sh.ev_begin, slot.stream));
+        if (cat->timing) MCD_HIP(hipEventRecord(k0, slot.stream));
+        MCD_HIP(mcd::launch_loglike_grad(slot.stream, shape, main_records(sh, w), w.d_chunks, w.n_chunks, w.d_params, w.d_wpar,
+                                         w.d_grad_partials, W));
+        if (cat->timing) MCD_HIP(hipEventRecord(k1, slot.stream));
+        MCD_HIP(mcd::launch_grad_reduce(slot.stream, shape, w.d_grad_partials, w.n_chunks, w.d_offsets, cat->n_psets,
+                                        w.max_chunks_per_pset, W, w.d_grad_out));
+    }
+    if (coll) {
+        // sum the shards' fields: one all-reduce of (1 + K) x outputs doubles (rows padded to whole walker tiles), on the
+        // compute stream behind any collective still pending on the communication stream
+        if (!ctx->multi_process) MCD_NCCL(g_rccl.GroupStart());
+        for (Shard& sh : cat->shards) {
+            WorkSet& w = (*find_work(sh, W));
+            const DeviceSlot& slot = ctx->slots[sh.slot];
+            MCD_HIP(hipSetDevice(slot.device));
+            for (int b = 0; b < 2; ++b) {
+                if (!w.comm_pending[b]) continue;
+                MCD_HIP(hipStreamWaitEvent(slot.stream, w.ev_comm[b], 0));
+                w.comm_pending[b] = false;
+            }
+            MCD_NCCL(g_rccl.AllReduce(w.d_grad_out, w.d_grad_out, n_res, ncclDouble, ncclSum, slot.comm, slot.stream));
+        }
+        if (!ctx->multi_process) MCD_NCCL(g_rccl.GroupEnd());
+    }
+    {
+        // after the all-reduce every device holds the same results: only the first shard's are copied
+        Shard& sh = cat->shards[0];
+        WorkSet& w = (*find_work(sh, W));
+        const DeviceSlot& slot = ctx->slots[sh.slot];
+        MCD_HIP(hipSetDevice(slot.device));
+        MCD_HIP(hipMemcpyAsync(w.h_grad_out, w.d_grad_out, n_res * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+    }
+    if (cat->timing_all) ++cat->timing_launches;
+    if (cat->timing) {
+        if (!cat->timing_all) {
+            for (Shard& sh : cat->shards) {
+                const DeviceSlot& slot = ctx->slots[sh.slot];
+                MCD_HIP(hipSetDevice(slot.device));
+                MCD_HIP(hipEventRecord(sh.ev_end, slot.stream));
+            }
+        }
+        cat->timing_pending = true;
+    }
+    rc = sync_all(cat);                       // (waits under the collective deadline, collects the timing)
+    if (rc != MCD_OK) return rc;
+    const double* res = (*find_work(cat->shards[0], W)).h_grad_out;
+    for (int64_t b = 0; b < cat->n_psets; ++b) {
+        const double* block = res + b * fields * padded;
+        if (out) std::memcpy(out + b * W, block, (size_t)W * sizeof(double));
+        for (int64_t j = 0; j < k; ++j) {
+            const double* col = block + (1 + j) * padded;
+            for (int64_t i = 0; i < W; ++i) grad[(b * W + i) * k + j] = col[i];
+        }
+    }
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int mcd_loglike_grad_batch(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* params, double* out, double* grad) {
+    try { return loglike_grad(cat, n_walkers, k, params, out, grad); } catch (...) { return on_exception("mcd_loglike_grad_batch"); }
+}
 
 int mcd_params_upload(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* params) {
     try { return stage_params(cat, n_walkers, k, params, false); } catch (...) { return on_exception("mcd_params_upload"); }

@@ -112,6 +112,11 @@ struct WorkSet {
     // independent (each has its parameters staged), so the reduction and the launch ramp of one overlap the main kernel
     // of the next instead of sitting between two main kernels on one stream (enqueue(): two_lanes).
     double* d_partials2 = nullptr;
+    // mcd_loglike_grad_batch (sized on first use): partial sums [1 + K][roundup64(W) / 8][n_chunks][8], results
+    // [n_psets][1 + K][roundup64(W)] on the device and in pinned host memory
+    double* d_grad_partials = nullptr;
+    double* d_grad_out = nullptr;
+    double* h_grad_out = nullptr;
     hipEvent_t ev_staged = nullptr;    // parameters staged (on the compute stream): lane 1 waits for it once per staging
     bool lane1_knows_staging = false;
     bool lane1_used = false;           // something may be in flight on the second stream
