@@ -267,7 +267,6 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
             if (cat->combine == 1 && plan.balanced_m == 4 && can16) w.waves = 16;
         }
     }
-    const int64_t padded_walkers = (n_walkers + 63) / 64 * 64;       // partial sums: whole walker tiles (mcd_kernels.hip)
     const int64_t n_out = cat->n_psets * n_walkers;
     const size_t term_bytes = cat->precision == MCD_F64 ? 8 : 4;
     auto allocate = [&]() -> hipError_t {
@@ -280,7 +279,7 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
         if ((e = hipMalloc(&w.d_offsets, offs.size() * sizeof(int64_t))) != hipSuccess) return e;
         if ((e = hipMalloc(&w.d_params, (size_t)n_out * cat->k * sizeof(double))) != hipSuccess) return e;
         if ((e = hipMalloc(&w.d_wpar, (size_t)n_out * mcd::KD * term_bytes)) != hipSuccess) return e;
-        if ((e = hipMalloc(&w.d_partials, std::max<size_t>(1, (size_t)padded_walkers * w.n_chunks) * sizeof(double))) != hipSuccess) return e;
+        if ((e = hipMalloc(&w.d_partials, std::max<size_t>(1, (size_t)mcd::padded_walkers(n_walkers) * w.n_chunks) * sizeof(double))) != hipSuccess) return e;
         if ((e = hipMalloc(&w.d_out, (size_t)(n_out + 1) * sizeof(double))) != hipSuccess) return e;   // + re-run flag word
         if ((e = hipMemset(w.d_out, 0, (size_t)(n_out + 1) * sizeof(double))) != hipSuccess) return e;
         if ((e = hipMalloc(&w.d_out2, (size_t)(n_out + 1) * sizeof(double))) != hipSuccess) return e;

@@ -127,6 +127,40 @@ int stage_params(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* p
     return rc;
 }
 
+// The event pair that brackets a shard's main kernel: the shard's own pair, or with per-launch timing ("timing" = 2) and a
+// sampled launch the next pair of its ring (grown on demand).
+int timing_pair(const mcd_catalog* cat, Shard& sh, bool sampled, hipEvent_t* k0, hipEvent_t* k1) {
+    *k0 = sh.ev_k0;
+    *k1 = sh.ev_k1;
+    if (!(cat->timing_all && sampled)) return MCD_OK;
+    if (sh.ring_used >= (size_t)1 << 16) sh.ring_used = 0;        // harness option left on: recycle, never grow without bound
+    if (sh.ring_used == sh.ring.size()) {
+        hipEvent_t a, b;
+        MCD_HIP(hipEventCreate(&a));
+        MCD_HIP(hipEventCreate(&b));
+        sh.ring.emplace_back(a, b);
+    }
+    *k0 = sh.ring[sh.ring_used].first;
+    *k1 = sh.ring[sh.ring_used].second;
+    ++sh.ring_used;
+    return MCD_OK;
+}
+
+// End of a timed launch sequence: the outer event of every shard, and the timing left for sync_all to collect
+int timing_end(mcd_catalog* cat) {
+    if (cat->timing_all) ++cat->timing_launches;
+    if (!cat->timing) return MCD_OK;
+    if (!cat->timing_all) {
+        for (Shard& sh : cat->shards) {
+            const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+            MCD_HIP(hipSetDevice(slot.device));
+            MCD_HIP(hipEventRecord(sh.ev_end, slot.stream));
+        }
+    }
+    cat->timing_pending = true;
+    return MCD_OK;
+}
+
 // pipelined (mcd_loglike_enqueue): the all-reduce goes to the communication stream and overlaps the next step's kernels.
 // A blocking call gains nothing from that hop: its all-reduce stays on the compute stream (after any collective still
 // pending on the communication stream, so that operations on one communicator never run concurrently).
@@ -142,7 +176,7 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         WorkSet& w = (*find_work(sh, W));
         const DeviceSlot& slot = ctx->slots[sh.slot];
         MCD_HIP(hipSetDevice(slot.device));
-        const bool coll = ctx->n_ranks > 1 || ctx->slots.size() > 1 || ctx->force_collective;
+        const bool coll = ctx->has_comm();
         double* out_buf = w.mapped ? w.m_out : w.d_out;
         // two lanes: see WorkSet.  (Not with per-launch timing of the harness' plain mode, whose begin / end events
         // bracket ONE stream; the sampled per-kernel events of "timing" = 2 are recorded on the lane's stream.)
@@ -157,8 +191,7 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
             out_buf = w.buf ? w.d_out2 : w.d_out;
             if (two_lanes && w.buf) {
                 if (!w.d_partials2) {
-                    const int64_t padded_walkers = (W + 63) / 64 * 64;
-                    MCD_HIP(hipMalloc(&w.d_partials2, std::max<size_t>(1, (size_t)padded_walkers * w.n_chunks) * sizeof(double)));
+                    MCD_HIP(hipMalloc(&w.d_partials2, std::max<size_t>(1, (size_t)mcd::padded_walkers(W) * w.n_chunks) * sizeof(double)));
                 }
                 if (!w.lane1_knows_staging) {
                     MCD_HIP(hipStreamWaitEvent(slot.stream2, w.ev_staged, 0));
@@ -179,21 +212,10 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         cat->last_direct_chunks += shape.root_direct && shape.fast == 2 ? w.direct_chunks : 0;
         w.launch_tag = coll ? 0.0 : (double)(++cat->launch_seq);
         shape.launch_tag = w.launch_tag;
-        hipEvent_t k0 = sh.ev_k0, k1 = sh.ev_k1;
         // per-launch events cost a signal packet each (~3 us per pair between back-to-back kernels): a harness may sample
         const bool sampled = !cat->timing_all || (cat->timing_launches % cat->timing_stride) == 0;
-        if (cat->timing_all && sampled) {
-            if (sh.ring_used >= (size_t)1 << 16) sh.ring_used = 0;        // harness option left on: recycle, never grow without bound
-            if (sh.ring_used == sh.ring.size()) {
-                hipEvent_t a, b;
-                MCD_HIP(hipEventCreate(&a));
-                MCD_HIP(hipEventCreate(&b));
-                sh.ring.emplace_back(a, b);
-            }
-            k0 = sh.ring[sh.ring_used].first;
-            k1 = sh.ring[sh.ring_used].second;
-            ++sh.ring_used;
-        }
+        hipEvent_t k0, k1;
+        if (int rc = timing_pair(cat, sh, sampled, &k0, &k1)) return rc;
         if (cat->timing && !cat->timing_all) MCD_HIP(hipEventRecord(sh.ev_begin, slot.stream));
         if (cat->timing && sampled) MCD_HIP(hipEventRecord(k0, lane_stream));
         MCD_HIP(mcd::launch_loglike(lane_stream, shape, main_records(sh, w), w.d_chunks, w.n_chunks, w.d_wpar, lane_partials, W));
@@ -215,8 +237,7 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         if (coll && pipelined) MCD_HIP(hipEventRecord(w.ev_reduced[w.buf], lane_stream));
     }
     // sum the per-device / per-rank partial log-likelihoods: one all-reduce of n_out doubles
-    const bool collective = ctx->n_ranks > 1 || ctx->slots.size() > 1 || ctx->force_collective;
-    if (collective) {
+    if (ctx->has_comm()) {
         if (!ctx->multi_process) MCD_NCCL(g_rccl.GroupStart());
         for (Shard& sh : cat->shards) {
             WorkSet& w = (*find_work(sh, W));
@@ -245,17 +266,7 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
             }
         }
     }
-    if (cat->timing_all) ++cat->timing_launches;
-    if (cat->timing) {
-        if (!cat->timing_all) {
-            for (Shard& sh : cat->shards) {
-                const DeviceSlot& slot = ctx->slots[sh.slot];
-                MCD_HIP(hipSetDevice(slot.device));
-                MCD_HIP(hipEventRecord(sh.ev_end, slot.stream));
-            }
-        }
-        cat->timing_pending = true;
-    }
+    if (int rc = timing_end(cat)) return rc;
     {
         WorkSet& w0 = (*find_work(cat->shards[0], W));
         cat->last_chunks = w0.n_chunks;
@@ -271,7 +282,7 @@ int fetch_once(mcd_catalog* cat, bool* rerun) {
     const int64_t W = cat->cur_walkers;
     const int64_t n_out = cat->n_psets * W;
     *rerun = false;
-    const bool coll = cat->ctx->n_ranks > 1 || cat->ctx->slots.size() > 1 || cat->ctx->force_collective;
+    const bool coll = cat->ctx->has_comm();
     bool any_fast = false;
     for (Shard& sh : cat->shards) {
         WorkSet& w = (*find_work(sh, W));
@@ -362,7 +373,7 @@ int loglike_grad(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* p
     mcd_ctx* ctx = cat->ctx;
     const int64_t W = n_walkers;
     const int64_t fields = 1 + k;
-    const int64_t padded = (W + 63) / 64 * 64;
+    const int64_t padded = mcd::padded_walkers(W);
     const size_t n_res = (size_t)(cat->n_psets * fields * padded);       // doubles of a result buffer
     const bool coll = ctx->has_comm();
     for (Shard& sh : cat->shards) {
@@ -375,19 +386,8 @@ int loglike_grad(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* p
         if (!w.h_grad_out) MCD_HIP(hipHostMalloc(&w.h_grad_out, n_res * sizeof(double), hipHostMallocDefault));
         if (!w.d_grad_out) MCD_HIP(hipMalloc(&w.d_grad_out, n_res * sizeof(double)));
         mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
-        hipEvent_t k0 = sh.ev_k0, k1 = sh.ev_k1;
-        if (cat->timing_all) {
-            if (sh.ring_used >= (size_t)1 << 16) sh.ring_used = 0;
-            if (sh.ring_used == sh.ring.size()) {
-                hipEvent_t a, b;
-                MCD_HIP(hipEventCreate(&a));
-                MCD_HIP(hipEventCreate(&b));
-                sh.ring.emplace_back(a, b);
-            }
-            k0 = sh.ring[sh.ring_used].first;
-            k1 = sh.ring[sh.ring_used].second;
-            ++sh.ring_used;
-        }
+        hipEvent_t k0, k1;
+        if (int rc = timing_pair(cat, sh, true, &k0, &k1)) return rc;      // (a pair on every call, whatever the stride)
         // (timing: as for values, the inner event pair brackets the main kernel alone, the outer one the device sequence)
         if (cat->timing && !cat->timing_all) MCD_HIP(hipEventRecord(sh.ev_begin, slot.stream));
         if (cat->timing) MCD_HIP(hipEventRecord(k0, slot.stream));
@@ -422,17 +422,8 @@ int loglike_grad(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* p
         MCD_HIP(hipSetDevice(slot.device));
         MCD_HIP(hipMemcpyAsync(w.h_grad_out, w.d_grad_out, n_res * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
     }
-    if (cat->timing_all) ++cat->timing_launches;
-    if (cat->timing) {
-        if (!cat->timing_all) {
-            for (Shard& sh : cat->shards) {
-                const DeviceSlot& slot = ctx->slots[sh.slot];
-                MCD_HIP(hipSetDevice(slot.device));
-                MCD_HIP(hipEventRecord(sh.ev_end, slot.stream));
-            }
-        }
-        cat->timing_pending = true;
-    }
+    rc = timing_end(cat);
+    if (rc != MCD_OK) return rc;
     rc = sync_all(cat);                       // (waits under the collective deadline, collects the timing)
     if (rc != MCD_OK) return rc;
     const double* res = (*find_work(cat->shards[0], W)).h_grad_out;
@@ -472,7 +463,7 @@ int mcd_sync(mcd_catalog* cat) {
 int mcd_loglike_batch(mcd_catalog* cat, int64_t n_walkers, int32_t k, const double* params, double* out) {
     try {
     if (!out) return fail(MCD_ERR_INVALID, "null output");
-    const bool collective = cat && (cat->ctx->n_ranks > 1 || cat->ctx->slots.size() > 1 || cat->ctx->force_collective);
+    const bool collective = cat && cat->ctx->has_comm();
     int rc = stage_params(cat, n_walkers, k, params, !collective && cat && cat->zero_copy);
     if (rc != MCD_OK) return rc;
     rc = enqueue(cat, false);

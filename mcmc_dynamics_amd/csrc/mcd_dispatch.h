@@ -1,0 +1,39 @@
+// mcd_dispatch.h -- runtime (model, free_centre) and term precision -> compile-time constants, written once for every
+// launcher of the library and for the host builds of the same arithmetic (tests/emul).  No HIP types.
+#pragma once
+
+#include <type_traits>
+
+#include "mcd_math.h"
+
+namespace mcd {
+
+// THE list of models: a new one is added here (and to mcd_math.h: Model, kNumModels) and reaches every launcher
+#define MCD_MODEL_LIST(X)                                                                                           \
+    X(MODEL_CONST) X(MODEL_BGFIXED) X(MODEL_BGGAUSS) X(MODEL_PROFILE) X(MODEL_PROFILE_BGGAUSS) X(MODEL_PROFILE_BGDENS) \
+    X(MODEL_PROFILE_BGFIXED)
+
+// f(std::integral_constant<int, M>{}, std::bool_constant<FREE>{}) of the matching pair; `fallback`, without a call of f,
+// for a model outside [0, kNumModels).  What a model or a centre lacks is an `if constexpr` inside f.
+template <class F, class R>
+R dispatch_model(int model, bool free_centre, F&& f, R fallback) {
+#define MCD_MODEL_COUNT(M) +1
+    static_assert(0 MCD_MODEL_LIST(MCD_MODEL_COUNT) == kNumModels, "MCD_MODEL_LIST names every model");
+#undef MCD_MODEL_COUNT
+#define MCD_MODEL_CASE(M)                                                                   \
+    case M:                                                                                 \
+        return free_centre ? f(std::integral_constant<int, M>{}, std::true_type{})          \
+                           : f(std::integral_constant<int, M>{}, std::false_type{});
+    switch (model) { MCD_MODEL_LIST(MCD_MODEL_CASE) }
+#undef MCD_MODEL_CASE
+    return fallback;
+}
+#undef MCD_MODEL_LIST
+
+// f(T{}) with the type of the terms: double for precision 0 (MCD_F64), float for the float32 catalogues
+template <class F>
+auto dispatch_term_type(int precision, F&& f) {
+    return precision == 0 ? f(double{}) : f(float{});
+}
+
+}  // namespace mcd

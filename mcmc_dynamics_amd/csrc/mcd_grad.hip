@@ -1,7 +1,8 @@
 // mcd_grad.hip -- gfx950 kernel of mcd_loglike_grad_batch: the log-likelihood and its gradient with respect to the K
 // kernel columns, per walker (mcd_grad.h holds the per-term arithmetic).
 //
-// Work decomposition: that of loglike_kernel (mcd_kernels.hip).  lane = walker; a wave evaluates 64 walkers against one
+// Work decomposition: the value kernel's (mcd_kernels.hip: loglike_kernel; mcd_launch.h has the shared mapping and the
+// partial-sum address).  lane = walker; a wave evaluates 64 walkers against one
 // chunk of the catalogue's chunk table; the record pointer is wave-uniform, so records arrive by scalar loads and are SGPR
 // operands of the f64 vector ops.  Each lane keeps 1 + K float64 sums (at most 12) in registers over its chunk and
 // stores them as partials[field][walker / 8][chunk][walker % 8] -- per field the layout of the value kernel's partial
@@ -13,16 +14,13 @@
 // expected to be bound by f64 VALU issue, which three resident waves should saturate as well -- not measured).  DESIGN 3.9
 // lists the compiler's resource usage per family.
 #include "mcd_internal.h"
+#include "mcd_dispatch.h"
 #include "mcd_grad.h"
 #include "mcd_reduce.h"
 
 namespace mcd {
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
 
 template <int MODEL, bool FREE>
 __global__ __launch_bounds__(kBlock) void loglike_grad_kernel(const double* __restrict__ recs,
@@ -38,21 +36,7 @@ __global__ __launch_bounds__(kBlock) void loglike_grad_kernel(const double* __re
     const int lane = threadIdx.x & (kWave - 1);
     int64_t chunk_id;
     int wtile;
-    if (n_wtiles <= kWavesPerBlock) {
-        // <= 256 walkers: consecutive waves share a chunk
-        const int64_t task = (int64_t)blockIdx.x * kWavesPerBlock + wave;    // wave-uniform
-        if (task >= n_tasks) return;
-        chunk_id = task / n_wtiles;
-        wtile = (int)(task - chunk_id * n_wtiles);
-    } else {
-        // > 256 walkers: the XCD-aware grouping of loglike_kernel (placement only, never results)
-        const int m = (n_wtiles + kWavesPerBlock - 1) / kWavesPerBlock;
-        const int64_t group = blockIdx.x / (8 * m);
-        const int j = (int)(blockIdx.x - group * (8 * m));
-        chunk_id = group * 8 + (j & 7);
-        wtile = (j >> 3) * kWavesPerBlock + wave;
-        if (chunk_id >= n_chunks || wtile >= n_wtiles) return;
-    }
+    if (!wave_task(wave, n_tasks, n_wtiles, n_chunks, chunk_id, wtile)) return;
     const Chunk ch = chunks[chunk_id];                                       // scalar load
     const int64_t w_raw = (int64_t)wtile * kWave + lane;
     const int64_t w_idx = w_raw < n_walkers ? w_raw : n_walkers - 1;        // idle lanes shadow the last walker
@@ -69,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void loglike_grad_kernel(const double* __re
 
     // rows are padded to whole walker tiles: idle lanes store their shadow sums into padding
     const int64_t n_groups = (int64_t)n_wtiles * (kWave / kPartialGroup);
-    const int64_t at = ((w_raw >> 3) * n_chunks + chunk_id) * kPartialGroup + (w_raw & (kPartialGroup - 1));
+    const int64_t at = partial_index(w_raw, n_chunks, chunk_id);
     const int64_t field_stride = n_groups * n_chunks * kPartialGroup;
 #pragma unroll
     for (int f = 0; f <= K; ++f) partials[f * field_stride + at] = acc[f];
@@ -92,23 +76,10 @@ hipError_t launch_loglike_grad(hipStream_t s, const LaunchShape& sh, const void*
                                int64_t n_chunks, const double* params, const void* wpar, double* partials,
                                int64_t n_walkers) {
     if (sh.precision != 0) return hipErrorInvalidValue;
-    hipError_t e = hipErrorInvalidValue;
-#define MCD_DISPATCH(M)                                                                                                \
-    case M:                                                                                                            \
-        e = sh.free_centre ? launch_grad_main<M, true>(s, records, chunks, n_chunks, params, wpar, partials, n_walkers) \
-                           : launch_grad_main<M, false>(s, records, chunks, n_chunks, params, wpar, partials, n_walkers); \
-        break;
-    switch (sh.model) {
-        MCD_DISPATCH(MODEL_CONST)
-        MCD_DISPATCH(MODEL_BGFIXED)
-        MCD_DISPATCH(MODEL_BGGAUSS)
-        MCD_DISPATCH(MODEL_PROFILE)
-        MCD_DISPATCH(MODEL_PROFILE_BGGAUSS)
-        MCD_DISPATCH(MODEL_PROFILE_BGDENS)
-        MCD_DISPATCH(MODEL_PROFILE_BGFIXED)
-    }
-#undef MCD_DISPATCH
-    return e;
+    return dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+        return launch_grad_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, params, wpar, partials,
+                                                                           n_walkers);
+    }, hipErrorInvalidValue);
 }
 
 // the value path's reduction over (1 + K) x roundup64(W) "walkers": the same tree for every field, no constant added (the
@@ -117,9 +88,8 @@ hipError_t launch_grad_reduce(hipStream_t s, const LaunchShape& sh, const double
                               const int64_t* pset_slot_offsets, int64_t n_psets, int64_t max_chunks_per_pset,
                               int64_t n_walkers, double* out) {
     const int64_t fields = 1 + grad_columns(sh.model, sh.free_centre);
-    const int64_t padded = (n_walkers + kWave - 1) / kWave * kWave;
     return launch_reduce(s, partials, pset_slot_offsets, n_psets, n_chunks, n_psets == 1 ? n_chunks : max_chunks_per_pset,
-                         fields * padded, nullptr, out);
+                         fields * padded_walkers(n_walkers), nullptr, out);
 }
 
 }  // namespace mcd

@@ -6,6 +6,7 @@
 
 #include "mcd_chunks.h"   // Chunk, chunk-table planning (host-only, shared with the CPU tests)
 #include "mcd_guard.h"    // StatsScalars: the range guard's catalogue statistics travel to the device by value
+#include "mcd_launch.h"   // kWave, kBlock, padded_walkers: the launch vocabulary of the device units
 
 namespace mcd {
 

@@ -19,10 +19,6 @@
 namespace mcd {
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
-
 __device__ const double kExpTabDevice[kExpTabSize] = {MCD_EXP_TABLE_VALUES};
 
 __global__ __launch_bounds__(kBlock) void kde_slice_kernel(const double* __restrict__ comp, int64_t m,

@@ -14,7 +14,8 @@
 // once per 64..256 walkers.  MFMA has nothing to offer here (no contraction).
 #include <type_traits>
 
-#include "mcd_internal.h"
+#include "mcd_internal.h"   // first: <hip/hip_runtime.h> before the MCD_HD headers
+#include "mcd_dispatch.h"
 #include "mcd_math.h"
 #include "mcd_prep.h"
 #include "mcd_reduce.h"
@@ -22,10 +23,6 @@
 namespace mcd {
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kBlock = 256;               // 4 waves: one per SIMD of a CU
-constexpr int kWavesPerBlock = kBlock / kWave;
 
 constexpr double kR0Arcmin = 3437.7467707849392526;   // 10800 / pi, calc_xy_offset.py:11
 
@@ -151,11 +148,12 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
     }
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & (kWave - 1);
+    // wave -> (chunk_id, wtile): the mapping of mcd_launch.h: wave_task (its comments; loglike_grad_kernel calls it), written
+    // out here because the call changes this kernel's vector code.  A change to either is a change to both.
     int64_t chunk_id;
     int wtile;
     bool live = true;                                                        // (combining workgroups keep idle waves for the barrier)
     if (kCombine || n_wtiles <= kWavesPerBlock) {
-        // <= 256 walkers: consecutive waves share a chunk, so every chunk is read by one workgroup (one CU, one XCD)
         const int64_t task = (int64_t)blockIdx.x * WAVES + wave;            // wave-uniform
         if (task >= n_tasks) {
             if constexpr (!kCombine) return;
@@ -165,10 +163,6 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
         wtile = (int)(task - chunk_id * n_wtiles);
         if (!live) { chunk_id = 0; wtile = wave % n_wtiles; }
     } else {
-        // > 256 walkers: a chunk needs m = ceil(n_wtiles / 4) workgroups.  Workgroups are dealt round-robin over the
-        // 8 XCDs, so workgroups b and b + 8 share an XCD (and its L2): within a group of 8 m workgroups, workgroup j
-        // takes chunk j % 8 and walker-tile quartet j / 8 -- all m readers of a chunk sit on one XCD and the chunk is
-        // fetched from HBM once.  (Placement only affects traffic, never results.)
         const int m = (n_wtiles + kWavesPerBlock - 1) / kWavesPerBlock;
         const int64_t group = blockIdx.x / (8 * m);
         const int j = (int)(blockIdx.x - group * (8 * m));
@@ -223,19 +217,17 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             else result = __builtin_nan("");
         }
     }
-    // partials[walker group of 8][slot][walker in group]: eight full 64-byte segments per wave store (the rows are
-    // padded to whole walker tiles, so idle lanes store their shadow value into padding), and the reduce kernel streams
-    // one contiguous [slot][8] block per walker group.  slot = chunk, or the workgroup when its chunks are combined.
+    // (mcd_launch.h: partial_index has the layout; slot = chunk, or the workgroup when its chunks are combined)
     if constexpr (kCombine) {
         combine_lds[wave][lane] = result;
         __syncthreads();
         if (wave < n_wtiles) {                                    // (wave == wtile for the workgroup's first chunk)
             double sum = combine_lds[wave][lane];
             for (int c = n_wtiles; c < WAVES; c += n_wtiles) sum += combine_lds[c + wave][lane];     // chunk order
-            partials[((w_raw >> 3) * n_slots + blockIdx.x) * kPartialGroup + (w_raw & (kPartialGroup - 1))] = sum;
+            partials[partial_index(w_raw, n_slots, blockIdx.x)] = sum;
         }
     } else {
-        partials[((w_raw >> 3) * n_slots + chunk_id) * kPartialGroup + (w_raw & (kPartialGroup - 1))] = result;
+        partials[partial_index(w_raw, n_slots, chunk_id)] = result;
     }
 #ifdef MCD_MAIN_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < kStampBlocks) {
@@ -400,45 +392,32 @@ hipError_t launch_prepare_records(hipStream_t s, const RawColumns& raw, int64_t 
                                   int precision, double ra_c_deg, double dec_c_deg, void* records) {
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    if (precision == 0)
-        hipLaunchKernelGGL(prepare_records_kernel<double>, dim3(grid), dim3(kBlock), 0, s, raw, n, model,
-                           (int)free_centre, ra_c_deg, dec_c_deg, (double*)records);
-    else
-        hipLaunchKernelGGL(prepare_records_kernel<float>, dim3(grid), dim3(kBlock), 0, s, raw, n, model,
-                           (int)free_centre, ra_c_deg, dec_c_deg, (float*)records);
-    return hipGetLastError();
+    return dispatch_term_type(precision, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(prepare_records_kernel<T>, dim3(grid), dim3(kBlock), 0, s, raw, n, model, (int)free_centre,
+                           ra_c_deg, dec_c_deg, (T*)records);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_prepare_walkers(hipStream_t s, const double* params, int64_t n_rows, int k, int model,
                                   bool free_centre, int precision, void* wpar) {
     if (n_rows <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((n_rows + kBlock - 1) / kBlock);
-    if (precision == 0)
-        hipLaunchKernelGGL(prepare_walkers_kernel<double>, dim3(grid), dim3(kBlock), 0, s, params, n_rows, k, model,
-                           (int)free_centre, (double*)wpar);
-    else
-        hipLaunchKernelGGL(prepare_walkers_kernel<float>, dim3(grid), dim3(kBlock), 0, s, params, n_rows, k, model,
-                           (int)free_centre, (float*)wpar);
-    return hipGetLastError();
+    return dispatch_term_type(precision, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(prepare_walkers_kernel<T>, dim3(grid), dim3(kBlock), 0, s, params, n_rows, k, model,
+                           (int)free_centre, (T*)wpar);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& sh, const void* records, const Chunk* chunks,
                           int64_t n_chunks, const void* wpar, double* partials, int64_t n_walkers) {
-#define MCD_DISPATCH(M)                                                                                          \
-    case M:                                                                                                      \
-        return sh.free_centre ? launch_precision<M, true>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers) \
-                              : launch_precision<M, false>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
-    switch (sh.model) {
-        MCD_DISPATCH(MODEL_CONST)
-        MCD_DISPATCH(MODEL_BGFIXED)
-        MCD_DISPATCH(MODEL_BGGAUSS)
-        MCD_DISPATCH(MODEL_PROFILE)
-        MCD_DISPATCH(MODEL_PROFILE_BGGAUSS)
-        MCD_DISPATCH(MODEL_PROFILE_BGDENS)
-        MCD_DISPATCH(MODEL_PROFILE_BGFIXED)
-    }
-#undef MCD_DISPATCH
-    return hipErrorInvalidValue;
+    return dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+        return launch_precision<decltype(M)::value, decltype(FREE)::value>(s, sh, records, chunks, n_chunks, wpar, partials,
+                                                                           n_walkers);
+    }, hipErrorInvalidValue);
 }
 
 // Partial-sum slots per walker of a launch (what the reduction reads): the chunks, or the workgroups when they combine
@@ -472,41 +451,20 @@ hipError_t launch_reduce(hipStream_t s, const double* partials, const int64_t* o
     return hipGetLastError();
 }
 
-namespace {
-template <int MODEL>
-hipError_t per_star_model(hipStream_t s, const LaunchShape& sh, const void* records, int64_t n, const void* wpar_row,
-                          int mode, double* out) {
-    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    if (sh.precision == 0) {
-        if (sh.free_centre)
-            hipLaunchKernelGGL((per_star_kernel<MODEL, true, double>), dim3(grid), dim3(kBlock), 0, s,
-                               (const double*)records, n, (const double*)wpar_row, mode, out);
-        else
-            hipLaunchKernelGGL((per_star_kernel<MODEL, false, double>), dim3(grid), dim3(kBlock), 0, s,
-                               (const double*)records, n, (const double*)wpar_row, mode, out);
-    } else {
-        if (sh.free_centre)
-            hipLaunchKernelGGL((per_star_kernel<MODEL, true, float>), dim3(grid), dim3(kBlock), 0, s,
-                               (const float*)records, n, (const float*)wpar_row, mode, out);
-        else
-            hipLaunchKernelGGL((per_star_kernel<MODEL, false, float>), dim3(grid), dim3(kBlock), 0, s,
-                               (const float*)records, n, (const float*)wpar_row, mode, out);
-    }
-    return hipGetLastError();
-}
-}  // namespace
-
 hipError_t launch_per_star(hipStream_t s, const LaunchShape& sh, const void* records, int64_t n,
                            const void* wpar_row, int mode, double* out) {
     if (n <= 0) return hipSuccess;
-    switch (sh.model) {
-        case MODEL_BGFIXED: return per_star_model<MODEL_BGFIXED>(s, sh, records, n, wpar_row, mode, out);
-        case MODEL_BGGAUSS: return per_star_model<MODEL_BGGAUSS>(s, sh, records, n, wpar_row, mode, out);
-        case MODEL_PROFILE_BGGAUSS: return per_star_model<MODEL_PROFILE_BGGAUSS>(s, sh, records, n, wpar_row, mode, out);
-        case MODEL_PROFILE_BGDENS: return per_star_model<MODEL_PROFILE_BGDENS>(s, sh, records, n, wpar_row, mode, out);
-        case MODEL_PROFILE_BGFIXED: return per_star_model<MODEL_PROFILE_BGFIXED>(s, sh, records, n, wpar_row, mode, out);
-    }
-    return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
+    return dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+        // the models without a background have no components to tell apart: no kernel for them
+        if constexpr (bg_kind(decltype(M)::value) == BG_NONE) return hipErrorInvalidValue;
+        else return dispatch_term_type(sh.precision, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL((per_star_kernel<decltype(M)::value, decltype(FREE)::value, T>), dim3(grid), dim3(kBlock), 0, s,
+                               (const T*)records, n, (const T*)wpar_row, mode, out);
+            return hipGetLastError();
+        });
+    }, hipErrorInvalidValue);
 }
 
 }  // namespace mcd

@@ -12,14 +12,11 @@
 #include <cstdint>
 
 #include "mcd_internal.h"
+#include "mcd_dispatch.h"
 #include "mcd_posterior.h"
 
 namespace mcd {
 namespace {
-
-constexpr int kBlock = 256;
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 
 // part: [n_slices][post_fields(MEM)][n]   inv: 1 / (j + 1) for j < slice_len
 template <int MODEL, bool FREE, bool MEM, class T>
@@ -128,30 +125,12 @@ hipError_t slice_launch(hipStream_t s, int precision, const void* records, int64
                         const double* inv, int64_t slice_len, int64_t n_slices, double* part) {
     const int64_t n_tasks = (n + kWave - 1) / kWave * n_slices;
     const dim3 grid((unsigned)((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock));
-    if (precision == 0)
-        hipLaunchKernelGGL((posterior_slice_kernel<MODEL, FREE, MEM, double>), grid, dim3(kBlock), 0, s,
-                           (const double*)records, n, (const double*)wpar, n_samples, inv, slice_len, n_slices, part);
-    else
-        hipLaunchKernelGGL((posterior_slice_kernel<MODEL, FREE, MEM, float>), grid, dim3(kBlock), 0, s,
-                           (const float*)records, n, (const float*)wpar, n_samples, inv, slice_len, n_slices, part);
-    return hipGetLastError();
-}
-
-template <int MODEL>
-hipError_t slice_model(hipStream_t s, bool free_centre, bool mem, int precision, const void* records, int64_t n,
-                       const void* wpar, int64_t n_samples, const double* inv, int64_t slice_len, int64_t n_slices,
-                       double* part) {
-    if constexpr (bg_kind(MODEL) == BG_NONE) {
-        if (mem) return hipErrorInvalidValue;
-        return free_centre ? slice_launch<MODEL, true, false>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part)
-                           : slice_launch<MODEL, false, false>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part);
-    } else {
-        if (mem)
-            return free_centre ? slice_launch<MODEL, true, true>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part)
-                               : slice_launch<MODEL, false, true>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part);
-        return free_centre ? slice_launch<MODEL, true, false>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part)
-                           : slice_launch<MODEL, false, false>(s, precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part);
-    }
+    return dispatch_term_type(precision, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((posterior_slice_kernel<MODEL, FREE, MEM, T>), grid, dim3(kBlock), 0, s, (const T*)records, n,
+                           (const T*)wpar, n_samples, inv, slice_len, n_slices, part);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace
@@ -160,22 +139,16 @@ hipError_t launch_posterior(hipStream_t s, const LaunchShape& sh, bool mem, cons
                             const void* wpar, int64_t n_samples, const double* inv, int64_t slice_len, int64_t n_slices,
                             double* part, double* state, int64_t n_prev, int64_t n_total, double* out) {
     if (n <= 0 || n_samples <= 0) return hipSuccess;
-    hipError_t e = hipErrorInvalidValue;
-#define MCD_POST_CASE(M)                                                                                             \
-    case M:                                                                                                          \
-        e = slice_model<M>(s, sh.free_centre, mem, sh.precision, records, n, wpar, n_samples, inv, slice_len,       \
-                           n_slices, part);                                                                          \
-        break;
-    switch (sh.model) {
-        MCD_POST_CASE(MODEL_CONST)
-        MCD_POST_CASE(MODEL_BGFIXED)
-        MCD_POST_CASE(MODEL_BGGAUSS)
-        MCD_POST_CASE(MODEL_PROFILE)
-        MCD_POST_CASE(MODEL_PROFILE_BGGAUSS)
-        MCD_POST_CASE(MODEL_PROFILE_BGDENS)
-        MCD_POST_CASE(MODEL_PROFILE_BGFIXED)
-    }
-#undef MCD_POST_CASE
+    const hipError_t e = dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+        constexpr int MODEL = decltype(M)::value;
+        constexpr bool kFree = decltype(FREE)::value;
+        // the membership fields exist for the models with a background only
+        if constexpr (bg_kind(MODEL) != BG_NONE) {
+            if (mem) return slice_launch<MODEL, kFree, true>(s, sh.precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part);
+        }
+        if (mem) return hipErrorInvalidValue;
+        return slice_launch<MODEL, kFree, false>(s, sh.precision, records, n, wpar, n_samples, inv, slice_len, n_slices, part);
+    }, hipErrorInvalidValue);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((n + kBlock - 1) / kBlock));
     if (mem)

@@ -15,13 +15,13 @@
 #include <cstdint>
 
 #include "mcd_internal.h"
+#include "mcd_dispatch.h"
 #include "mcd_posterior.h"
 #include "mcd_psis.h"
 
 namespace mcd {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kChunk = 16;                 // samples per LDS transpose of the term kernel
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -311,13 +311,12 @@ hipError_t term_launch(hipStream_t s, int precision, const void* records, int64_
     int64_t slice_len = 0;
     const int64_t n_slices = posterior_slices(n, S, &slice_len);
     const dim3 grid((unsigned)((n + kWave - 1) / kWave * n_slices));
-    if (precision == 0)
-        hipLaunchKernelGGL((psis_term_kernel<MODEL, FREE, double>), grid, dim3(kWave), 0, s, (const double*)records, n,
-                           (const double*)wpar, S, slice_len, n_slices, terms);
-    else
-        hipLaunchKernelGGL((psis_term_kernel<MODEL, FREE, float>), grid, dim3(kWave), 0, s, (const float*)records, n,
-                           (const float*)wpar, S, slice_len, n_slices, terms);
-    return hipGetLastError();
+    return dispatch_term_type(precision, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((psis_term_kernel<MODEL, FREE, T>), grid, dim3(kWave), 0, s, (const T*)records, n, (const T*)wpar,
+                           S, slice_len, n_slices, terms);
+        return hipGetLastError();
+    });
 }
 
 size_t psis_tail_lds_bytes(int64_t M) { return 256 * 4 + (size_t)M * (8 + 8 + 4 + 4) + 2 * kPsisMaxGrid * 8; }
@@ -328,22 +327,9 @@ hipError_t launch_psis(hipStream_t s, const LaunchShape& sh, const void* records
                        int64_t M, double r_eff, double* terms, double* out, int64_t out_stride) {
     if (n <= 0 || S <= 0) return hipSuccess;
     if (M > kPsisMaxTail) return hipErrorInvalidValue;
-    hipError_t e = hipErrorInvalidValue;
-#define MCD_PSIS_CASE(MD)                                                                                            \
-    case MD:                                                                                                         \
-        e = sh.free_centre ? term_launch<MD, true>(s, sh.precision, records, n, wpar, S, terms)                      \
-                           : term_launch<MD, false>(s, sh.precision, records, n, wpar, S, terms);                    \
-        break;
-    switch (sh.model) {
-        MCD_PSIS_CASE(MODEL_CONST)
-        MCD_PSIS_CASE(MODEL_BGFIXED)
-        MCD_PSIS_CASE(MODEL_BGGAUSS)
-        MCD_PSIS_CASE(MODEL_PROFILE)
-        MCD_PSIS_CASE(MODEL_PROFILE_BGGAUSS)
-        MCD_PSIS_CASE(MODEL_PROFILE_BGDENS)
-        MCD_PSIS_CASE(MODEL_PROFILE_BGFIXED)
-    }
-#undef MCD_PSIS_CASE
+    const hipError_t e = dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+        return term_launch<decltype(M)::value, decltype(FREE)::value>(s, sh.precision, records, n, wpar, S, terms);
+    }, hipErrorInvalidValue);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(psis_tail_kernel, dim3((unsigned)n), dim3(kWave), psis_tail_lds_bytes(M), s, terms, S, M, r_eff,
                        out, out_stride);

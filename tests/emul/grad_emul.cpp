@@ -3,6 +3,7 @@
 // product package.
 #include <cstdint>
 
+#include "mcd_dispatch.h"
 #include "mcd_grad.h"
 
 using namespace mcd;
@@ -34,8 +35,8 @@ extern "C" int emul_grad_columns(int model, int free_centre) { return grad_colum
 
 extern "C" int emul_grad(int model, int free_centre, int64_t n, const double* recs, const double* wpar, const double* params,
                          int64_t W, int64_t chunk_len, double* out) {
-#define CASE(M) if (model == M) { if (free_centre) run<M, true>(n, recs, wpar, params, W, chunk_len, out); else run<M, false>(n, recs, wpar, params, W, chunk_len, out); return 0; }
-    CASE(0) CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6)
-#undef CASE
-    return -1;
+    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+        run<decltype(M)::value, decltype(FREE)::value>(n, recs, wpar, params, W, chunk_len, out);
+        return 0;
+    }, -1);
 }

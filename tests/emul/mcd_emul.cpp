@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mcd_chunks.h"
+#include "mcd_dispatch.h"
 #include "mcd_guard.h"
 #include "mcd_math.h"
 #include "mcd_rng.h"
@@ -87,27 +88,30 @@ extern "C" int emul_record_doubles(int model, int free_centre) { return record_d
 extern "C" int emul_geometry_doubles(int model, int free_centre) { return geometry_doubles(model, free_centre != 0); }
 extern "C" int emul_kd() { return KD; }
 
-#define FOR_ALL(M) CASE(M, false, false) CASE(M, false, true) CASE(M, true, false) CASE(M, true, true)
 extern "C" int emul_loglike(int model, int free_centre, int fast, int64_t n, const double* recs, const double* wpar,
                             int64_t W, int64_t chunk_len, double* out) {
-#define CASE(M, F, X) if (model == M && (free_centre != 0) == F && (fast != 0) == X && fast != 2) { run<M, F, X ? 1 : 0>(n, recs, wpar, W, chunk_len, out); return 0; }
-    FOR_ALL(0) FOR_ALL(1) FOR_ALL(2) FOR_ALL(3) FOR_ALL(4) FOR_ALL(5) FOR_ALL(6)
-#undef CASE
-    if (fast == 2) {                          // narrow-range variants
-#define NARROW_CASE(M) if (model == M) { if (free_centre) run<M, true, 2>(n, recs, wpar, W, chunk_len, out); else run<M, false, 2>(n, recs, wpar, W, chunk_len, out); return 0; }
-        NARROW_CASE(1) NARROW_CASE(2) NARROW_CASE(4) NARROW_CASE(5) NARROW_CASE(6)
-        if (model == 3 && !free_centre) { run<3, false, 2>(n, recs, wpar, W, chunk_len, out); return 0; }   // ProfileNarrowAcc
-#undef NARROW_CASE
-    }
-    return -1;
+    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+        constexpr int MODEL = decltype(M)::value;
+        constexpr bool kFree = decltype(FREE)::value;
+        if (fast == 2) {
+            // the narrow-range variants: the mixtures, and MODEL_PROFILE with a fixed centre (ProfileNarrowAcc)
+            if constexpr (bg_kind(MODEL) != BG_NONE || (MODEL == MODEL_PROFILE && !kFree)) run<MODEL, kFree, 2>(n, recs, wpar, W, chunk_len, out);
+            else return -1;
+        } else if (fast) {
+            run<MODEL, kFree, 1>(n, recs, wpar, W, chunk_len, out);
+        } else {
+            run<MODEL, kFree, 0>(n, recs, wpar, W, chunk_len, out);
+        }
+        return 0;
+    }, -1);
 }
 
 extern "C" int emul_per_star(int model, int free_centre, int mode, int64_t n, const double* recs, const double* wrow,
                              double* out) {
-#define CASE(M, F, X) if (X && model == M && (free_centre != 0) == F) { per_star<M, F>(n, recs, wrow, mode, out); return 0; }
-    FOR_ALL(1) FOR_ALL(2) FOR_ALL(4) FOR_ALL(5) FOR_ALL(6)
-#undef CASE
-    return -1;
+    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+        if constexpr (bg_kind(decltype(M)::value) == BG_NONE) return -1;
+        else { per_star<decltype(M)::value, decltype(FREE)::value>(n, recs, wrow, mode, out); return 0; }
+    }, -1);
 }
 
 // the library's own range guard (csrc/mcd_guard.h) on raw host columns and a C-ABI-ordered parameter table
@@ -258,10 +262,11 @@ extern "C" int emul_sharded_loglike(int model, int free_centre, int level, int64
                                     const int64_t* exc, int64_t W, const double* wpar, int n_shards,
                                     int64_t target_waves, int tail_split, double* out, int64_t* n_general) {
     const std::vector<int64_t> ex(exc, exc + n_exc);
-#define CASE(M, F, X) if (X && model == M && (free_centre != 0) == F) { sharded<M, F>(level, n, recs, n_psets, bin_offsets, lnbg, ex, W, wpar, n_shards, target_waves, tail_split, out, n_general); return 0; }
-    FOR_ALL(0) FOR_ALL(1) FOR_ALL(2) FOR_ALL(3) FOR_ALL(4) FOR_ALL(5) FOR_ALL(6)
-#undef CASE
-    return -1;
+    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+        sharded<decltype(M)::value, decltype(FREE)::value>(level, n, recs, n_psets, bin_offsets, lnbg, ex, W, wpar, n_shards,
+                                                           target_waves, tail_split, out, n_general);
+        return 0;
+    }, -1);
 }
 
 // narrow_exception star list of a catalogue (mcd_guard.h: compute_stats), ascending global indices

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "mcd_dispatch.h"
 #include "mcd_posterior.h"
 
 using namespace mcd;
@@ -66,14 +67,16 @@ void run(int64_t n, const double* recs, const double* wrows, int64_t S, int64_t 
 // out[4][n] = lppd, lnl_var, pmem_mean, pmem_std; n_slices <= 0: the library's slice plan
 extern "C" int emul_posterior(int model, int free_centre, int mem, int64_t n, const double* recs, const double* wrows,
                               int64_t S, int64_t n_slices, double* out) {
-#define CASE(M, F, X) if (model == M && (free_centre != 0) == F && (mem != 0) == X) { run<M, F, X>(n, recs, wrows, S, n_slices, out); return 0; }
-#define NOMEM(M) CASE(M, false, false) CASE(M, true, false)
-#define BOTH(M) NOMEM(M) CASE(M, false, true) CASE(M, true, true)
-    NOMEM(0) BOTH(1) BOTH(2) NOMEM(3) BOTH(4) BOTH(5) BOTH(6)
-#undef BOTH
-#undef NOMEM
-#undef CASE
-    return -1;
+    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+        constexpr int MODEL = decltype(M)::value;
+        constexpr bool kFree = decltype(FREE)::value;
+        if constexpr (bg_kind(MODEL) != BG_NONE) {
+            if (mem) { run<MODEL, kFree, true>(n, recs, wrows, S, n_slices, out); return 0; }
+        }
+        if (mem) return -1;
+        run<MODEL, kFree, false>(n, recs, wrows, S, n_slices, out);
+        return 0;
+    }, -1);
 }
 
 // The same reduction over given terms: x, p [n][S] -> out[4][n]

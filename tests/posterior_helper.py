@@ -21,7 +21,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC] + [os.path.join(INC, f) for f in ("mcd_posterior.h", "mcd_math.h", "mcd_exp_table.h")]
+        deps = [SRC] + [os.path.join(INC, f) for f in ("mcd_posterior.h", "mcd_math.h", "mcd_exp_table.h", "mcd_dispatch.h")]
         if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", INC, SRC,
                             "-o", OUT], check=True)

@@ -28,7 +28,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        deps = [SRC] + [os.path.join(eh.INC, h) for h in ("mcd_grad.h", "mcd_math.h", "mcd_exp_table.h")]
+        deps = [SRC] + [os.path.join(eh.INC, h) for h in ("mcd_grad.h", "mcd_math.h", "mcd_exp_table.h", "mcd_dispatch.h")]
         if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", eh.INC, SRC,
                             "-o", OUT], check=True)

@@ -31,7 +31,8 @@ from collections import Counter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
-SOURCES = ("mcd_kernels.hip", "mcd_math.h", "mcd_exp_table.h", "mcd_internal.h", "mcd_chunks.h", "mcd_reduce.h")
+SOURCES = ("mcd_kernels.hip", "mcd_math.h", "mcd_exp_table.h", "mcd_internal.h", "mcd_launch.h", "mcd_dispatch.h", "mcd_chunks.h",
+           "mcd_reduce.h")
 SLOT_NS = 2.33
 
 # (template tag, name, bench model key, stars per inner iteration, inner trips per outer iteration, selector
