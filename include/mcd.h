@@ -295,6 +295,55 @@ int mcd_chain_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_b
 int mcd_stretch_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks, int64_t* discarded_blocks,
                      int32_t* last_discard_status);
 
+/* One block of Hamiltonian Monte Carlo steps (Duane et al. 1987; Neal 2011) on the gradient of mcd_loglike_grad_batch:
+ * W independent chains, each step n_leap leapfrog points, i.e. n_leap value-and-gradient evaluations of W rows.  The
+ * reference has no gradient-based sampler -- this stands beside mcd_stretch_move_seeded as a second way to drive the chain
+ * that emcee's stretch move drives for it (analysis/runner.py:403-419), for posteriors on which that move mixes slowly.
+ * The algebra is mcmc_dynamics_amd/csrc/mcd_hmc.h, one text for host and device:
+ *   map     the column map, bounds and fixed_ok of mcd_stretch_move; n_walkers = W >= 1 (odd allowed), n_dim = P <= 12,
+ *           n_bins 0 or 1
+ *   chol    [P][P] row-major LOWER Cholesky factor L of the INVERSE mass matrix, M^-1 = L L^T -- the factor of an estimate
+ *           of the posterior covariance (entries above the diagonal must be 0, the diagonal positive).  Momenta are
+ *           p = L^-T z with z standard normal, the kinetic energy is 1/2 |L^T p|^2, a drift is q += eps L L^T p.
+ *   step    eps = step_size (1 + jitter r), r uniform in [-1, 1), drawn per walker and step
+ *   prior   the box lo <= q <= hi (inclusive).  With a DIAGONAL chol a coordinate that leaves the box after a drift is
+ *           mirrored at the bound and its momentum component negated (a hard wall: exact, reversible).  With a DENSE chol a
+ *           trajectory that leaves the box is ended and its proposal rejected.  Detailed balance holds either way.
+ *   accept  iff log(u) < H0 - H1, H = -lnlike + kinetic.  A non-finite value or gradient on the way rejects the proposal (a
+ *           divergent trajectory is no error); fixed_ok == 0 rejects everything.
+ * Every number of a step is a function of (seed, step0 + i, walker) alone (Philox4x64-10 with a key of its own, normals by
+ * Marsaglia's polar method with det_log: no libm call), so blocks of any length continue each other through step0, and
+ * mcd_hmc_numbers returns them: z [n_steps][W][P], thr [n_steps][W] = log(u), eps_factor [n_steps][W] = r.
+ *   pos [W][P]           in: where the block starts; out: where it ends
+ *   lnp [W]              out only: the log-likelihood at pos (the block evaluates its own starting point)
+ *   chain [n_steps][W][P], lnprob_chain [n_steps][W], energy_error [n_steps][W]   the state after every step and
+ *                        |H1 - H0| of its proposal (+inf for a trajectory that ended early); each may be NULL
+ *   accepted [W]         incremented; may be NULL
+ * pos, lnp and accepted are only ever written with final values.  Returns MCD_ERR_NONFINITE when a walker STARTS outside
+ * the box or with a non-finite log-likelihood or gradient, MCD_ERR_INVALID (pos untouched) for a binned or a float32
+ * catalogue: lock-stepped ensembles have no HMC block, and the gradient is float64.
+ *
+ * Where it runs.  One device per process without a communicator: RESIDENT -- the starting point costs one host round
+ * trip, then begin / (walker prep, gradient kernel, reduction, leap) x n_leap per step are one chain of launches on the
+ * catalogue's stream, the trajectory state stays in a device scratch that is released with the catalogue, and the host
+ * waits once under the context's deadline (csrc/mcd_hmc.hip).  Everything else -- option "device_chain" = 0, several
+ * devices or ranks, option "timing", more than 65536 walkers or more than 512 MB of rows per block -- runs HOST-DRIVEN: the
+ * same loop around mcd_loglike_grad_batch, whose all-reduce makes it multi-rank.  Both give the same chain bit for bit;
+ * mcd_hmc_info counts the blocks of either kind. */
+typedef struct {
+    mcd_stretch_desc map;
+    const double* chol;     /* [n_dim][n_dim] lower Cholesky factor of the inverse mass matrix */
+    double step_size;       /* eps > 0 */
+    double jitter;          /* 0 <= j < 1 */
+    int32_t n_leap;         /* L >= 1 */
+} mcd_hmc_desc;
+
+int mcd_hmc_block(mcd_catalog* cat, const mcd_hmc_desc* desc, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
+                  int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error);
+int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_walkers, int32_t n_dim, double* z, double* thr,
+                    double* eps_factor);
+int mcd_hmc_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);
+
 /* ---- introspection for the measurement harness ------------------------------------------- */
 
 const char* mcd_last_error(void);
@@ -321,8 +370,8 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *   "spin_us"       microseconds mcd_sync / fetch / batch poll the stream (hipStreamQuery) before they fall back to the
  *                      blocking hipStreamSynchronize, whose interrupt wake-up adds 50 - 500 us of jitter to waits longer
  *                      than a fraction of a millisecond (default 20000; 0: always block)
- *   "device_chain"  1 (default): mcd_stretch_move keeps the ensemble resident on the device where it can (see there);
- *                      0: host-driven blocks only
+ *   "device_chain"  1 (default): mcd_stretch_move and mcd_hmc_block keep the ensemble resident on the device where
+ *                      they can (see there); 0: host-driven blocks only
  *   "prefetch"      software prefetch of the star records of the next loop iteration (a second instantiation of the fast
  *                      kernels): -1 (default) by shape -- mixture models from 8 MiB of records per device up (it hides
  *                      the memory latency there: +8 % at 256 walkers to +45 % at 64 on 1e6 stars), models without

@@ -66,6 +66,11 @@ SYMBOLS = {
                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p,
                                          ctypes.POINTER(ctypes.c_int32)]),
     "mcd_stretch_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p, _c_int64_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mcd_hmc_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
+                                     ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p]),
+    "mcd_hmc_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
+                                       _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_hmc_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p]),
     "mcd_last_error": (ctypes.c_char_p, []),
     "mcd_abi_version": (ctypes.c_int, []),
     "mcd_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
@@ -108,6 +113,12 @@ class StretchDesc(ctypes.Structure):
         ("col_source", ctypes.POINTER(ctypes.c_int32)), ("col_const", _c_double_p), ("col_factor", _c_double_p),
         ("lo", _c_double_p), ("hi", _c_double_p), ("fixed_ok", ctypes.c_int32), ("n_bins", ctypes.c_int32),
     ]
+
+
+class HmcDesc(ctypes.Structure):
+    """Mirror of ``mcd_hmc_desc``."""
+    _fields_ = [("map", StretchDesc), ("chol", _c_double_p), ("step_size", ctypes.c_double), ("jitter", ctypes.c_double),
+                ("n_leap", ctypes.c_int32)]
 
 
 # Environment switches the library or this binding reads (INTEGRATION.md lists them).  None is needed in production: they
@@ -296,6 +307,20 @@ def chain_numbers(seed, step0, n_steps, n_bins, n_walkers, n_dim, squeeze=False)
     if squeeze:
         return order[:, 0], zz[:, :, 0], thr[:, :, 0], pick[:, :, 0]
     return order, zz, thr, pick
+
+
+def hmc_numbers(seed, step0, n_steps, n_walkers, n_dim):
+    """``mcd_hmc_numbers``: the numbers of steps ``step0 .. step0 + n_steps - 1`` of the HMC chain that ``seed`` names (host
+    code, no device involved): standard normals z (steps, W, P), acceptance thresholds thr = log(u) (steps, W) and the
+    step-size jitter variables r in [-1, 1) (steps, W); a step runs with eps = step_size (1 + jitter r)."""
+    lib = load_library()
+    z = np.empty((int(n_steps), int(n_walkers), int(n_dim)), dtype=np.float64)
+    thr = np.empty((int(n_steps), int(n_walkers)), dtype=np.float64)
+    r = np.empty_like(thr)
+    rc = lib.mcd_hmc_numbers(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(n_steps), int(n_walkers), int(n_dim), _ptr(z),
+                             _ptr(thr), _ptr(r))
+    _check(lib, rc, "mcd_hmc_numbers")
+    return z, thr, r
 
 
 class Catalog(object):
@@ -536,6 +561,35 @@ class Catalog(object):
         """... of which chunks in which every wave took the direct form of the series (option ``root_direct``; counted on
         the host); 0 none; -1 before any launch."""
         return self.lib.mcd_last_direct_chunks(self.handle)
+
+    def hmc_block(self, plan, chol, step_size, n_leap, pos, lnp, seed, step0, n_steps, chain=None, lnprob_chain=None,
+                  accepted=None, energy_error=None, jitter=0.1):
+        """``mcd_hmc_block``: advance W independent chains by ``n_steps`` Hamiltonian Monte Carlo steps of ``n_leap``
+        leapfrog points on the device gradient.  ``plan`` as for ``stretch_move``; ``chol`` (P, P): lower Cholesky factor
+        of the inverse mass matrix (a posterior covariance estimate).  ``pos`` (W, P) is updated in place, ``lnp`` (W,) is
+        written; ``chain`` (steps, W, P), ``lnprob_chain`` (steps, W), ``energy_error`` (steps, W) and ``accepted`` (W,)
+        int64 (incremented) are optional.  Steps ``step0 .. step0 + n_steps - 1`` of the chain that ``seed`` names."""
+        if n_steps < 0 or step0 < 0 or pos.ndim != 2:
+            raise ValueError("hmc_block: inconsistent array shapes")
+        head, tail, _keep = self._stretch_args("hmc_block", plan, pos, lnp, n_steps, chain, lnprob_chain, accepted)
+        chol = np.ascontiguousarray(chol, dtype=np.float64)
+        if chol.shape != (pos.shape[1], pos.shape[1]):
+            raise ValueError("hmc_block: chol must have shape (P, P)")
+        if energy_error is not None and (energy_error.dtype != np.float64 or not energy_error.flags.c_contiguous or
+                                         energy_error.shape != (n_steps, pos.shape[0])):
+            raise ValueError("hmc_block: energy_error must be a C-contiguous float64 array of shape (steps, W)")
+        d = HmcDesc()
+        d.map = head[1]._obj
+        d.chol, d.step_size, d.jitter, d.n_leap = _ptr(chol), float(step_size), float(jitter), int(n_leap)
+        rc = self.lib.mcd_hmc_block(self.handle, ctypes.byref(d), int(n_steps), head[3], head[4],
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail, _ptr(energy_error))
+        _check(self.lib, rc, "mcd_hmc_block")
+
+    def hmc_info(self):
+        """Where the blocks of ``hmc_block`` ran: {'device_blocks', 'host_blocks'} (``mcd_hmc_info``)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        _check(self.lib, self.lib.mcd_hmc_info(self.handle, ctypes.byref(a), ctypes.byref(b)), "mcd_hmc_info")
+        return {"device_blocks": a.value, "host_blocks": b.value}
 
     def stretch_info(self):
         """Where the blocks of ``stretch_move`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks', 'last_discard_status'}

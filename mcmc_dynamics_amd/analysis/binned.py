@@ -249,6 +249,10 @@ class BinnedConstantFit(ConstantFit):
         raise NotImplementedError("BinnedConstantFit: PSIS-LOO is defined for un-binned fits only; fit the bins' stars "
                                   "with ConstantFit to compare models")
 
+    def hmc(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
+                                  "lock-stepped ensembles of the bins have no HMC block)")
+
     def compute_bestfit_values(self, chain, n_burn):
         """List of per-bin result tables (median / uperr / loerr), as the per-bin loop of
         bin/run_tests.py:105-113 collects them."""

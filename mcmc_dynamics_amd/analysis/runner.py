@@ -507,6 +507,87 @@ class Runner(object):
         draws = x + np.random.standard_normal((int(n_walkers), x.size)) @ chol.T      # (NumPy's global generator, as get_initials)
         return np.clip(draws, plan.lo[plan.free_idx], plan.hi[plan.free_idx])
 
+    # ------------------------------------------------------------------ Hamiltonian Monte Carlo (new)
+    HMC_TARGET_ACCEPT = 0.8
+
+    def _hmc_block(self, pos, lnp, chol, step_size, n_leap, jitter, seed, step0, n_steps, chain, lnprob_chain, accepted,
+                   energy_error):
+        """One block of HMC steps inside the library (``_native.Catalog.hmc_block``)."""
+        self._stretch_catalog(pos).hmc_block(self._stretch_plan(), chol, step_size, n_leap, pos, lnp, seed, step0, n_steps,
+                                             chain, lnprob_chain, accepted, energy_error, jitter=jitter)
+
+    def hmc(self, n_walkers=64, n_steps=500, pos=None, covariance=None, step_size=None, n_leap=8, n_warmup=None, seed=None,
+            jitter=0.1, warmup_block=10):
+        """Sample the posterior with Hamiltonian Monte Carlo on the device gradient (``sampler.HMCSampler``; csrc/mcd_hmc.h):
+        ``n_walkers`` independent chains of ``n_steps`` steps of ``n_leap`` leapfrog points each, after ``n_warmup`` steps
+        (default ``min(200, n_steps // 2)``) that are not kept.  Returns the sampler; its chain holds the ``n_steps`` steps.
+
+        ``covariance`` (P, P) defines the metric: its lower Cholesky factor is the factor of the inverse mass matrix.  When
+        ``pos`` or ``covariance`` is None, ``maximize`` + ``laplace`` supply the covariance and ``get_initials_laplace`` the
+        start positions; when ``laplace`` raises (the maximum sits on a bound, or -H is not positive definite there) the
+        metric falls back to a DIAGONAL one, (prior width / 10)^2 or (max(|x|, 1) / 10)^2 for an unbounded parameter, with
+        a warning.  A diagonal metric reflects at the prior box, a dense one rejects trajectories that leave it.
+
+        Step size: ``step_size`` or, by default, ``1.5 * P ** -0.25`` in the units of the metric (a leapfrog step in a
+        well-estimated metric is stable below 2 and the optimal step shrinks as P^(-1/4), Neal 2011).  During warm-up the
+        step size is adapted BETWEEN blocks of ``warmup_block`` steps by a plain multiplicative rule on the host,
+        ``eps *= exp(acceptance of the block - HMC_TARGET_ACCEPT)``: a block that accepts everything grows eps by 22 %, one
+        that accepts nothing shrinks it by 55 %, and the rule is stationary at an acceptance of 0.8.  After warm-up eps
+        is frozen (``sampler.step_size``; the adaptation's path is in ``sampler.warmup_step_sizes``).
+
+        ``expr`` / ``lnprior``-expression parameters and binned or non-float64 catalogues raise NotImplementedError: the
+        gradient's own limits."""
+        plan = self._grad_plan()
+        ok, why_not = self.resident_ok()
+        if not ok:
+            raise NotImplementedError("Runner.hmc: " + why_not)
+        if self._precision != "f64":
+            raise NotImplementedError("Runner.hmc: gradients need a float64 catalogue")
+        n_p = int(plan.free_idx.size)
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        x_map = None
+        if covariance is None:
+            x_map = self.maximize()["x"]
+            try:
+                covariance = self.laplace(x_map)["covariance"]
+            except ValueError as exc:
+                width = np.where(np.isfinite(hi - lo), hi - lo, np.maximum(np.abs(x_map), 1.0))
+                covariance = np.diag((width / 10.0) ** 2)
+                warnings.warn("Runner.hmc: no Laplace covariance ({0}); using a diagonal metric from the prior widths".format(exc))
+        covariance = np.asarray(covariance, dtype=np.float64)
+        if covariance.shape != (n_p, n_p):
+            raise ValueError("covariance must have shape ({0}, {0})".format(n_p))
+        chol = np.linalg.cholesky(covariance)
+        if pos is None:
+            if x_map is None:
+                x_map = self.maximize()["x"]
+            pos = self.get_initials_laplace(n_walkers, x_map, covariance)
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.shape != (n_walkers, n_p):
+            raise ValueError("Array with starting values has invalid shape.")
+        if np.any(pos < lo) or np.any(pos > hi):
+            raise ValueError("Runner.hmc: a start position lies outside the prior box")
+        from ..sampler import HMCSampler
+        eps = float(step_size) if step_size is not None else 1.5 * n_p ** -0.25
+        sampler = HMCSampler(n_walkers, n_p, self._hmc_block, chol, eps, n_leap=n_leap, jitter=jitter, seed=seed)
+        n_warmup = min(200, int(n_steps) // 2) if n_warmup is None else int(n_warmup)
+        logger.info("MCMC driver: Hamiltonian Monte Carlo, %d chains, %d leapfrog points per step, %d warm-up steps",
+                    n_walkers, n_leap, n_warmup)
+        sampler.warmup_step_sizes = [sampler.step_size]
+        done = 0
+        while done < n_warmup:
+            n = min(max(1, int(warmup_block)), n_warmup - done)
+            before = sampler._accepted.sum()
+            pos, _, _ = sampler.run_mcmc(pos, n)
+            rate = float(sampler._accepted.sum() - before) / (n * n_walkers)
+            sampler.step_size *= float(np.exp(rate - self.HMC_TARGET_ACCEPT))
+            sampler.warmup_step_sizes.append(sampler.step_size)
+            done += n
+        sampler.reset()                                               # (the generator's step counter is not rewound)
+        sampler.reserve(n_steps)
+        sampler.run_mcmc(pos, n_steps)
+        return sampler
+
     # ------------------------------------------------------------------ several ranks (one process per GPU)
     RANK_CHECK_EVERY = 256
 

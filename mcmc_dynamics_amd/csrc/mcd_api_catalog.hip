@@ -445,6 +445,8 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
     for (hipEvent_t e : cat->chain_events) (void)hipEventDestroy(e);
     if (cat->chain.d) (void)hipFree(cat->chain.d);
     if (cat->chain.h) (void)hipHostFree(cat->chain.h);
+    if (cat->hmc.d) (void)hipFree(cat->hmc.d);
+    if (cat->hmc.h) (void)hipHostFree(cat->hmc.h);
     delete cat;
     return MCD_OK;
 }

@@ -1,9 +1,12 @@
 // mcd_api_chain.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host units):
 // mcd_stretch_move / mcd_stretch_move_seeded as a block resident on the device (kernels: mcd_stretch.hip) or driven from
-// the host (mcd_stretch.h), and mcd_chain_numbers.
+// the host (mcd_stretch.h), and mcd_chain_numbers; mcd_hmc_block in the same two forms (kernels: mcd_hmc.hip, algebra and
+// host-driven loop: mcd_hmc.h), and mcd_hmc_numbers.
 #include "mcd_host.h"
 #include "mcd_rng.h"
 #include "mcd_stretch.h"
+#include "mcd_grad.h"
+#include "mcd_hmc.h"
 
 using namespace mcd::host;
 
@@ -497,6 +500,179 @@ int run_stretch(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, do
     return MCD_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// mcd_hmc_block resident on the device: the starting point is evaluated through mcd_loglike_grad_batch (which also
+// stages the work set of W walkers and sizes its gradient scratch), then n_steps x n_leap gradient evaluations with the
+// two kernels of mcd_hmc.hip between them run as ONE chain of launches on the shard's stream, and the host waits once
+// under the context's deadline.  Nothing on the device needs the host: a divergent trajectory is a rejection.
+// *done = false (nothing written) when the trajectory scratch cannot be had: the caller runs the block host-driven.
+constexpr int64_t kHmcResidentMaxWalkers = 65536;              // what the trajectory scratch is sized for
+constexpr size_t kHmcResidentMaxBytes = (size_t)512 << 20;     // ... and a block's chain rows with it
+
+bool hmc_resident_covers(const mcd_catalog* cat, int64_t W, int P, int64_t n_steps) {
+    if (!cat->device_chain || cat->shards.size() != 1 || cat->ctx->has_comm() || cat->timing || n_steps < 1) return false;
+    if (W > kHmcResidentMaxWalkers) return false;
+    return (size_t)n_steps * W * (P + 2) * 8 <= kHmcResidentMaxBytes;
+}
+
+int hmc_block_device(mcd_catalog* cat, const mcd::HmcShared& hs, int64_t W, int64_t n_steps, double* pos, double* lnp,
+                     uint64_t seed, int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted,
+                     double* energy_error, bool* done) {
+    *done = false;
+    mcd_ctx* ctx = cat->ctx;
+    const int P = hs.n_dim, K = hs.k;
+    // ---- the starting point (host round trip, once per block): values, column derivatives, chain rule, checks
+    std::vector<double> table((size_t)W * K), ll((size_t)W), gcols((size_t)W * K), grad((size_t)W * P), lnp0((size_t)W);
+    for (int64_t w = 0; w < W; ++w) mcd::hmc_row(hs, pos + w * P, table.data() + w * K);
+    int rc = mcd_loglike_grad_batch(cat, W, K, table.data(), ll.data(), gcols.data());
+    if (rc != MCD_OK) return rc;
+    if (mcd::hmc_start(hs, W, pos, ll.data(), gcols.data(), lnp0.data(), grad.data()) != mcd::HMC_OK)
+        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior box or with a non-finite log-likelihood or gradient");
+    Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = ctx->slots[sh.slot];
+    MCD_HIP(hipSetDevice(slot.device));
+    const auto it = sh.work.find(W);
+    if (it == sh.work.end() || !it->second.d_grad_out || !it->second.d_grad_partials)
+        return fail(MCD_ERR_INVALID, "mcd_hmc_block: the gradient work set of this walker count is gone");
+    WorkSet& w = it->second;
+
+    // ---- arena: [state, both ways | column map, bounds, factor: in | trajectory scratch | rows of the block: out]
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off += (bytes + 63) / 64 * 64; return at; };
+    const size_t WP = (size_t)W * P;
+    const size_t o_pos = take(WP * 8), o_lnp = take((size_t)W * 8), o_grad = take(WP * 8), o_acc = take((size_t)W * 8);
+    const size_t state_end = off;
+    const size_t o_src = take((size_t)K * 4), o_const = take((size_t)K * 8), o_fac = take((size_t)K * 8);
+    const size_t o_lo = take((size_t)P * 8), o_hi = take((size_t)P * 8), o_chol = take((size_t)P * P * 8);
+    const size_t input_end = off;
+    const size_t o_q = take(WP * 8), o_p = take(WP * 8), o_h0 = take((size_t)W * 8), o_eps = take((size_t)W * 8);
+    const size_t o_alive = take((size_t)W * 4);
+    const size_t o_rows = off;
+    const size_t o_chain = take(chain ? (size_t)n_steps * WP * 8 : 0);
+    const size_t o_lnpc = take(lnprob_chain ? (size_t)n_steps * W * 8 : 0);
+    const size_t o_err = take(energy_error ? (size_t)n_steps * W * 8 : 0);
+    const size_t total = off;
+    ChainArena& a = cat->hmc;
+    if (a.bytes < total) {
+        if (a.d) (void)hipFree(a.d);
+        if (a.h) (void)hipHostFree(a.h);
+        a = ChainArena();
+        const size_t want = total + total / 2;
+        // (one device, no collective: a block too large for the scratch simply runs host-driven)
+        if (hipMalloc((void**)&a.d, want) != hipSuccess) { (void)hipGetLastError(); a = ChainArena(); return MCD_OK; }
+        if (hipHostMalloc((void**)&a.h, want, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(a.d);
+            a = ChainArena();
+            return MCD_OK;
+        }
+        a.bytes = want;
+    }
+    std::memcpy(a.h + o_pos, pos, WP * 8);
+    std::memcpy(a.h + o_lnp, lnp0.data(), (size_t)W * 8);
+    std::memcpy(a.h + o_grad, grad.data(), WP * 8);
+    std::memset(a.h + o_acc, 0, (size_t)W * 8);
+    std::memcpy(a.h + o_src, hs.col_source, (size_t)K * 4);
+    std::memcpy(a.h + o_const, hs.col_const, (size_t)K * 8);
+    std::memcpy(a.h + o_fac, hs.col_factor, (size_t)K * 8);
+    std::memcpy(a.h + o_lo, hs.lo, (size_t)P * 8);
+    std::memcpy(a.h + o_hi, hs.hi, (size_t)P * 8);
+    std::memcpy(a.h + o_chol, hs.chol, (size_t)P * P * 8);
+
+    mcd::HmcDevice hd;
+    hd.s = hs;
+    hd.s.col_source = (const int32_t*)(a.d + o_src); hd.s.col_const = (const double*)(a.d + o_const);
+    hd.s.col_factor = (const double*)(a.d + o_fac); hd.s.lo = (const double*)(a.d + o_lo); hd.s.hi = (const double*)(a.d + o_hi);
+    hd.s.chol = (const double*)(a.d + o_chol);
+    hd.n_walkers = W; hd.seed = seed;
+    hd.pos = (double*)(a.d + o_pos); hd.lnp = (double*)(a.d + o_lnp); hd.grad = (double*)(a.d + o_grad);
+    hd.accepted = (long long*)(a.d + o_acc);
+    hd.q = (double*)(a.d + o_q); hd.p = (double*)(a.d + o_p); hd.h0 = (double*)(a.d + o_h0); hd.eps = (double*)(a.d + o_eps);
+    hd.alive = (int32_t*)(a.d + o_alive);
+    hd.chain = chain ? (double*)(a.d + o_chain) : nullptr;
+    hd.lnprob_chain = lnprob_chain ? (double*)(a.d + o_lnpc) : nullptr;
+    hd.energy_error = energy_error ? (double*)(a.d + o_err) : nullptr;
+    hd.table = w.d_params;
+    hd.fields = w.d_grad_out;
+    hd.padded = mcd::padded_walkers(W);
+
+    // (mcd_loglike_grad_batch has waited for the stream: nothing of an earlier call uses the work buffers)
+    w.staged = false;                     // the parameter table and the walker constants are about to be overwritten
+    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+    MCD_HIP(hipMemcpyAsync(a.d, a.h, input_end, hipMemcpyHostToDevice, slot.stream));
+    for (int64_t i = 0; i < n_steps; ++i) {
+        MCD_HIP(mcd::launch_hmc_begin(slot.stream, hd, step0 + i));
+        for (int leap = 1; leap <= hs.n_leap; ++leap) {
+            MCD_HIP(mcd::launch_prepare_walkers(slot.stream, w.d_params, W, K, cat->model, cat->free_centre, cat->precision, w.d_wpar));
+            MCD_HIP(mcd::launch_loglike_grad(slot.stream, shape, main_records(sh, w), w.d_chunks, w.n_chunks, w.d_params, w.d_wpar,
+                                             w.d_grad_partials, W));
+            MCD_HIP(mcd::launch_grad_reduce(slot.stream, shape, w.d_grad_partials, w.n_chunks, w.d_offsets, cat->n_psets,
+                                            w.max_chunks_per_pset, W, w.d_grad_out));
+            MCD_HIP(mcd::launch_hmc_leap(slot.stream, hd, step0 + i, i, leap));
+        }
+    }
+    MCD_HIP(hipMemcpyAsync(a.h, a.d, state_end, hipMemcpyDeviceToHost, slot.stream));
+    if (total > o_rows) MCD_HIP(hipMemcpyAsync(a.h + o_rows, a.d + o_rows, total - o_rows, hipMemcpyDeviceToHost, slot.stream));
+    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, "mcd_hmc_block (resident block)");
+
+    ++cat->hmc_device_blocks;
+    std::memcpy(pos, a.h + o_pos, WP * 8);
+    std::memcpy(lnp, a.h + o_lnp, (size_t)W * 8);
+    if (accepted) {
+        const int64_t* acc = (const int64_t*)(a.h + o_acc);
+        for (int64_t x = 0; x < W; ++x) accepted[x] += acc[x];
+    }
+    if (chain) big_copy(chain, a.h + o_chain, (size_t)n_steps * WP * 8);
+    if (lnprob_chain) std::memcpy(lnprob_chain, a.h + o_lnpc, (size_t)n_steps * W * 8);
+    if (energy_error) std::memcpy(energy_error, a.h + o_err, (size_t)n_steps * W * 8);
+    *done = true;
+    return MCD_OK;
+}
+
+int run_hmc(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* pos, double* lnp, uint64_t seed, int64_t step0,
+            double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error) {
+    if (!cat || !d || !pos || !lnp) return fail(MCD_ERR_INVALID, "mcd_hmc_block: null argument");
+    if (int urc = ctx_usable(cat->ctx)) return urc;
+    const mcd_stretch_desc& m = d->map;
+    if (m.n_bins > 1 || cat->n_psets != 1)
+        return fail(MCD_ERR_INVALID, "mcd_hmc_block: binned catalogues are not covered (lock-stepped ensembles have no HMC block)");
+    if (cat->precision != MCD_F64) return fail(MCD_ERR_INVALID, "mcd_hmc_block: gradients need an MCD_F64 catalogue");
+    if (m.k != cat->k) return fail(MCD_ERR_INVALID, "mcd_hmc_block: descriptor has the wrong number of kernel columns");
+    if (m.n_walkers < 1 || m.n_dim < 1 || m.n_dim > mcd::kHmcMaxDim || n_steps < 0 || step0 < 0)
+        return fail(MCD_ERR_INVALID, "mcd_hmc_block: n_walkers >= 1, 1 <= n_dim <= 12, steps non-negative");
+    if (!m.col_source || !m.col_const || !m.col_factor || !m.lo || !m.hi || !d->chol) return fail(MCD_ERR_INVALID, "mcd_hmc_block: null descriptor array");
+    for (int c = 0; c < m.k; ++c)
+        if (m.col_source[c] >= m.n_dim) return fail(MCD_ERR_INVALID, "mcd_hmc_block: col_source outside the free parameters");
+    mcd::HmcShared hs;
+    hs.n_dim = m.n_dim; hs.k = m.k; hs.col_source = m.col_source; hs.col_const = m.col_const; hs.col_factor = m.col_factor;
+    hs.lo = m.lo; hs.hi = m.hi; hs.chol = d->chol; hs.fixed_ok = m.fixed_ok; hs.n_leap = d->n_leap;
+    hs.step_size = d->step_size; hs.jitter = d->jitter;
+    hs.diagonal = mcd::hmc_is_diagonal(d->chol, m.n_dim) ? 1 : 0;
+    if (!mcd::hmc_args_ok(hs, m.n_walkers))
+        return fail(MCD_ERR_INVALID, "mcd_hmc_block: step_size > 0, 0 <= jitter < 1, n_leap >= 1 and a finite lower-triangular chol with a positive diagonal");
+    const int64_t W = m.n_walkers;
+    if (hmc_resident_covers(cat, W, hs.n_dim, n_steps)) {
+        bool done = false;
+        const int rc = hmc_block_device(cat, hs, W, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error, &done);
+        if (rc != MCD_OK) return rc;
+        if (done) return MCD_OK;
+    }
+    // host-driven block: the same loop (mcd_hmc.h) around mcd_loglike_grad_batch, whose all-reduce makes it work on
+    // several devices and ranks
+    ++cat->hmc_host_blocks;
+    int eval_rc = MCD_OK;
+    const int rc = mcd::hmc_block(hs, W, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error,
+                                  [&](const double* table, int64_t n, double* out, double* grad) {
+                                      eval_rc = mcd_loglike_grad_batch(cat, n, m.k, table, out, grad);
+                                      return eval_rc;
+                                  });
+    if (rc == mcd::HMC_EVAL_FAILED) return eval_rc;                      // message already set
+    if (rc == mcd::HMC_NONFINITE)
+        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior box or with a non-finite log-likelihood or gradient");
+    if (rc != mcd::HMC_OK) return fail(MCD_ERR_INVALID, "mcd_hmc_block: bad arguments");
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -529,6 +705,34 @@ int mcd_chain_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_b
                                    thr + (size_t)i * 2 * B * half, pick + (size_t)i * 2 * B * half, sorter);
     return MCD_OK;
     } catch (...) { return on_exception("mcd_chain_numbers"); }
+}
+
+int mcd_hmc_block(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
+                  int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error) {
+    try {
+    return run_hmc(cat, d, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error);
+    } catch (...) { return on_exception("mcd_hmc_block"); }
+}
+
+int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_walkers, int32_t n_dim, double* z, double* thr,
+                    double* eps_factor) {
+    try {
+    if (!z || !thr || !eps_factor || n_steps < 0 || step0 < 0 || n_walkers < 1 || n_dim < 1 || n_dim > mcd::kHmcMaxDim)
+        return fail(MCD_ERR_INVALID, "mcd_hmc_numbers: bad arguments");
+    for (int64_t i = 0; i < n_steps; ++i)
+        for (int64_t w = 0; w < n_walkers; ++w) {
+            for (int c = 0; c < n_dim; ++c) z[((size_t)i * n_walkers + w) * n_dim + c] = mcd::hmc_normal(seed, step0 + i, w, c);
+            mcd::hmc_aux(seed, step0 + i, w, thr[(size_t)i * n_walkers + w], eps_factor[(size_t)i * n_walkers + w]);
+        }
+    return MCD_OK;
+    } catch (...) { return on_exception("mcd_hmc_numbers"); }
+}
+
+int mcd_hmc_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks) {
+    if (!cat) return fail(MCD_ERR_INVALID, "null catalogue");
+    if (device_blocks) *device_blocks = cat->hmc_device_blocks;
+    if (host_blocks) *host_blocks = cat->hmc_host_blocks;
+    return MCD_OK;
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 //   mcd_api_ctx.hip        error state, RCCL loading, contexts, the failure / abort protocol, waits on a context's streams
 //   mcd_api_catalog.hip    catalogues, work sets and chunk plans, the main kernel's launch shape, options, mcd_last_* queries
 //   mcd_api_eval.hip       staging, enqueue, sync, fetch; the per-star outputs of one parameter row
-//   mcd_api_chain.hip      the stretch-move block, resident on the device or host-driven
+//   mcd_api_chain.hip      the stretch-move block and the HMC block, each resident on the device or host-driven
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -288,6 +288,9 @@ struct mcd_catalog {
     int64_t chain_device_blocks = 0, chain_host_blocks = 0, chain_discarded = 0;
     int chain_last_status = 0;         // status word of the last discarded block (mcd::ChainStatus bits)
     std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
+    // Hamiltonian Monte Carlo blocks (mcd_hmc_block): trajectory state and chain rows of the resident block, its pinned mirror
+    mcd::host::ChainArena hmc;
+    int64_t hmc_device_blocks = 0, hmc_host_blocks = 0;
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet

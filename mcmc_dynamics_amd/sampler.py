@@ -305,3 +305,110 @@ class EnsembleSampler(object):
         _run_blocks(self, pos, lnp, nsteps, first, chunk, self._draw,
                     lambda proposal: self._log_prob(proposal, checked=not self.vectorize), store=store)
         return pos, lnp, self._random.get_state()
+
+
+class HMCSampler(object):
+    """Hamiltonian Monte Carlo on the device gradient: ``nwalkers`` independent chains, each step ``n_leap`` leapfrog
+    points with step size ``step_size`` (jittered by ``jitter`` per walker and step) in the metric whose INVERSE mass
+    matrix is ``chol @ chol.T`` -- the lower Cholesky factor of a posterior covariance estimate (csrc/mcd_hmc.h; the
+    reference has no gradient-based sampler).  A sampler the user asks for by name (``Runner.hmc``), with the attributes
+    the other samplers expose plus ``energy_error``.
+
+    ``block_fn(pos, lnp, chol, step_size, n_leap, jitter, seed, step0, n_steps, chain, lnprob_chain, accepted,
+    energy_error)`` advances ``pos`` (W, P) in place by a block of steps and writes ``lnp`` (``Runner._hmc_block``:
+    ``mcd_hmc_block``, resident on the device where it can be).
+
+    The numbers of a step are a function of (seed, step counter, walker).  The step counter ``rng_step`` only ever grows:
+    ``reset()`` empties the chain and the acceptance counts and leaves it alone, so a production run after a burn-in
+    never replays the numbers that produced its own starting point."""
+
+    def __init__(self, nwalkers, ndim, block_fn, chol, step_size, n_leap=8, jitter=0.1, seed=None):
+        chol = np.array(chol, dtype=np.float64)
+        if chol.shape != (ndim, ndim):
+            raise ValueError("chol must have shape (ndim, ndim)")
+        if np.any(np.triu(chol, 1) != 0.0) or np.any(np.diag(chol) <= 0.0) or not np.isfinite(chol).all():
+            raise ValueError("chol must be a finite lower-triangular matrix with a positive diagonal")
+        if not (step_size > 0.0) or not (0.0 <= jitter < 1.0) or int(n_leap) < 1 or int(nwalkers) < 1:
+            raise ValueError("step_size > 0, 0 <= jitter < 1, n_leap >= 1 and nwalkers >= 1")
+        self.nwalkers, self.ndim, self.block_fn = int(nwalkers), int(ndim), block_fn
+        self.chol, self.step_size, self.n_leap, self.jitter = chol, float(step_size), int(n_leap), float(jitter)
+        self.seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else \
+            (int(np.random.randint(0, 2 ** 32)) << 32) | int(np.random.randint(0, 2 ** 32))
+        self.block_steps = 64                    # steps per library call (NOT part of the stream's definition)
+        self.rng_step = 0                        # the generator's step counter: never rewound
+        self.reset()
+
+    def reset(self):
+        """Drop the chain, the acceptance counts and the energy errors.  The generator's step counter stays."""
+        self.iteration = 0
+        self._chain = np.empty((0, self.nwalkers, self.ndim))
+        self._lnprob = np.empty((0, self.nwalkers))
+        self._energy = np.empty((0, self.nwalkers))
+        self._accepted = np.zeros(self.nwalkers)
+        self.n_calls = 0                         # value-and-gradient evaluations of W rows
+
+    def reserve(self, total_steps):
+        """Chain storage for ``total_steps`` steps in all; the rows already held are kept."""
+        total = int(total_steps)
+        if total > self._chain.shape[0]:
+            for name in ("_chain", "_lnprob", "_energy"):
+                old = getattr(self, name)
+                new = np.empty((total,) + old.shape[1:])
+                new[:self.iteration] = old[:self.iteration]
+                setattr(self, name, new)
+
+    @property
+    def chain(self):
+        """(nwalkers, nsteps, ndim), the layout the reference pickles (runner.py:471-472)."""
+        return np.swapaxes(self._chain[:self.iteration], 0, 1)
+
+    @property
+    def lnprobability(self):
+        return np.swapaxes(self._lnprob[:self.iteration], 0, 1)
+
+    @property
+    def energy_error(self):
+        """(nwalkers, nsteps): |H1 - H0| of every proposal, +inf for a trajectory that ended early (left the box in a
+        dense metric, or met a non-finite value)."""
+        return np.swapaxes(self._energy[:self.iteration], 0, 1)
+
+    @property
+    def flatchain(self):
+        return self._chain[:self.iteration].reshape(-1, self.ndim)
+
+    @property
+    def acceptance_fraction(self):
+        return self._accepted / max(1, self.iteration)
+
+    def get_chain(self, discard=0, flat=False):
+        c = self._chain[discard:self.iteration]
+        return c.reshape(-1, self.ndim) if flat else c
+
+    def get_log_prob(self, discard=0, flat=False):
+        lp = self._lnprob[discard:self.iteration]
+        return lp.reshape(-1) if flat else lp
+
+    def run_mcmc(self, initial_state, nsteps, **kwargs):
+        """Advance the chains by ``nsteps``.  Returns ``(pos, log_prob, None)``."""
+        pos = np.array(initial_state, dtype=np.float64)
+        if pos.shape != (self.nwalkers, self.ndim):
+            raise ValueError("incompatible input dimensions {0}".format(pos.shape))
+        if not np.isfinite(pos).all():
+            raise ValueError("At least one parameter value was infinite or NaN")
+        nsteps = int(nsteps)
+        if self.iteration + nsteps > self._chain.shape[0]:
+            self.reserve(max(self.iteration + nsteps, 2 * self._chain.shape[0]))
+        lnp = np.full(self.nwalkers, np.nan)
+        done = 0
+        while done < nsteps:
+            n = min(max(1, int(self.block_steps)), nsteps - done)
+            it = self.iteration
+            accepted = np.zeros(self.nwalkers, dtype=np.int64)
+            self.block_fn(pos, lnp, self.chol, self.step_size, self.n_leap, self.jitter, self.seed64, self.rng_step, n,
+                          self._chain[it:it + n], self._lnprob[it:it + n], accepted, self._energy[it:it + n])
+            self._accepted += accepted
+            self.iteration += n
+            self.rng_step += n
+            self.n_calls += 1 + n * self.n_leap
+            done += n
+        return pos, lnp, None
