@@ -396,6 +396,12 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      coefficients re-centred once per chunk: one float64 instruction per term fewer, relative error of
  *                      the root <= 4.6e-16; 0: every series chunk keeps the form about the midpoint (the results of a
  *                      library without this option, bit for bit).  mcd_last_direct_chunks counts the chunks.
+ *   "exp_split"     1 (default): the chunks in the direct form evaluate the exponent with the record's offset split once per
+ *                      star by the record preparation (integer table steps in the rounding constant, the fraction in the
+ *                      record's 1 - pmember; a third verr-ordered array of 64 bytes per star in device memory): one float64
+ *                      instruction per term fewer, results equal to rounding; refused per call where the range guard
+ *                      cannot place every mixture value, scaled by up to 1.2016, inside the rescale interval.  0: never
+ *                      (the results of a library without this option, bit for bit).  mcd_last_exp_split tells.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -441,6 +447,9 @@ int64_t mcd_last_series_chunks(const mcd_catalog* cat);
 /* ... of which chunks in which every wave took the direct form of the series (option "root_direct"), counted the same way:
  * never more than mcd_last_series_chunks, whose meaning it does not change; 0 and -1 as there. */
 int64_t mcd_last_direct_chunks(const mcd_catalog* cat);
+/* 1 when the direct chunks of the most recent main-kernel launch ran with the split exponent offset (option "exp_split"), 0
+ * when not (option off, refused by the guard, another kernel family, the resident chain), -1 before the first launch. */
+int mcd_last_exp_split(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

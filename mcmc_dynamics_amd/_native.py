@@ -81,6 +81,7 @@ SYMBOLS = {
     "mcd_last_narrow_bounded": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_series_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_direct_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
+    "mcd_last_exp_split": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
@@ -562,6 +563,12 @@ class Catalog(object):
         the host); 0 none; -1 before any launch."""
         return self.lib.mcd_last_direct_chunks(self.handle)
 
+    @property
+    def last_exp_split(self):
+        """1: the direct chunks of the last main-kernel launch ran with the split exponent offset (option ``exp_split``);
+        0 not; -1 before any launch."""
+        return self.lib.mcd_last_exp_split(self.handle)
+
     def hmc_block(self, plan, chol, step_size, n_leap, pos, lnp, seed, step0, n_steps, chain=None, lnprob_chain=None,
                   accepted=None, energy_error=None, jitter=0.1):
         """``mcd_hmc_block``: advance W independent chains by ``n_steps`` Hamiltonian Monte Carlo steps of ``n_leap``
@@ -645,7 +652,8 @@ class Catalog(object):
         _check(self.lib, self.lib.mcd_last_launch_info(self.handle, ctypes.byref(wg), ctypes.byref(tile),
                                                        ctypes.byref(ch), ctypes.byref(rb)), "mcd_last_launch_info")
         return {"workgroups": wg.value, "walker_tile": tile.value, "chunks": ch.value, "record_bytes": rb.value,
-                "series_chunks": self.last_series_chunks, "direct_chunks": self.last_direct_chunks}
+                "series_chunks": self.last_series_chunks, "direct_chunks": self.last_direct_chunks,
+                "exp_split": self.last_exp_split}
 
     def close(self):
         if getattr(self, "handle", None):

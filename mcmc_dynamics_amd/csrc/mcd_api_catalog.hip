@@ -19,6 +19,7 @@ void free_workset(WorkSet& w) {
     if (w.d_chunks) (void)hipFree(w.d_chunks);
     if (w.d_offsets) (void)hipFree(w.d_offsets);
     if (w.d_chunk_general) (void)hipFree(w.d_chunk_general);
+    if (w.d_split_const) (void)hipFree(w.d_split_const);
     if (w.d_params) (void)hipFree(w.d_params);
     if (w.d_wpar) (void)hipFree(w.d_wpar);
     if (w.d_partials) (void)hipFree(w.d_partials);
@@ -108,12 +109,23 @@ int ensure_sorted_records(mcd_catalog* cat, Shard& sh) {
         sh.sorted_e2[i] = out[i * ND + 1];
     }
     sh.sorted_exceptions = mcd::permuted_exceptions(cat->stats.narrow_exceptions, perm, sh.star_begin);
-    void* d = nullptr;
-    MCD_HIP(hipMalloc(&d, bytes + 2048));                       // (the slack of `records`)
-    hipError_t e = hipMemset(d, 0, bytes + 2048);
-    if (e == hipSuccess) e = hipMemcpy(d, out.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); MCD_HIP(e); }
-    sh.records_sorted = d;
+    // ... and the same stars with the split exponent offset (rec is free again: it takes them)
+    sh.sorted_nbf.resize(n);
+    mcd::exp_split_records(out.data(), (int64_t)n, rec.data(), sh.sorted_nbf.data());
+    void* d[2] = {nullptr, nullptr};
+    const double* src[2] = {out.data(), rec.data()};
+    for (int a = 0; a < 2; ++a) {
+        hipError_t e = hipMalloc(&d[a], bytes + 2048);          // (the slack of `records`)
+        if (e == hipSuccess) e = hipMemset(d[a], 0, bytes + 2048);
+        if (e == hipSuccess) e = hipMemcpy(d[a], src[a], bytes, hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            for (int b = 0; b <= a; ++b)
+                if (d[b]) (void)hipFree(d[b]);
+            MCD_HIP(e);
+        }
+    }
+    sh.records_sorted = d[0];
+    sh.records_split = d[1];
     return MCD_OK;
 }
 
@@ -144,6 +156,7 @@ const Option kOptions[] = {
     {"narrow_bounded", 0, 1, "narrow_bounded: 1 (where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->narrow_bounded = (int)v)},
     {"verr_sorted", -1, 1, "verr_sorted: -1 (by record volume, default), 0 (catalogue order) or 1 (sorted by verr)", true, true, MCD_SET(c->verr_sorted = (int)v)},
     {"root_series", 0, 1, "root_series: 1 (series root on the narrow chunks of verr-sorted records, default) or 0 (never)", false, false, MCD_SET(c->root_series = (int)v)},
+    {"exp_split", 0, 1, "exp_split: 1 (split exponent offset in the direct chunks where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->exp_split = (int)v)},
     {"root_direct", 0, 1, "root_direct: 1 (direct form of the series root where a chunk admits it, default) or 0 (delta form only)", false, false, MCD_SET(c->root_direct = (int)v)},
     {"prefetch", -1, 1, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)", false, false, MCD_SET(c->prefetch = (int)v)},
     {"spin_us", 0, kMax, "spin_us must be >= 0", false, false, MCD_SET(c->spin_us = v)},
@@ -248,6 +261,7 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
         w.series_need = mcd::series_thresholds(plan, sh.sorted_e2.data());
         w.direct_need = mcd::direct_thresholds(plan, sh.sorted_e2.data());
     }
+    const std::vector<double> split_const = sorted ? mcd::exp_split_chunk_consts(plan, sh.sorted_nbf.data()) : std::vector<double>();
     {
         // balanced plans with an even number of workgroups per CU run as half as many 8-wave workgroups that add their
         // chunks' sums up themselves: half (to an eighth of) the partial sums per walker (mcd_kernels.hip: loglike_kernel)
@@ -274,6 +288,10 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
         if (!general.empty()) {
             if ((e = hipMalloc(&w.d_chunk_general, general.size())) != hipSuccess) return e;
             if ((e = hipMemcpy(w.d_chunk_general, general.data(), general.size(), hipMemcpyHostToDevice)) != hipSuccess) return e;
+        }
+        if (!split_const.empty()) {
+            if ((e = hipMalloc(&w.d_split_const, split_const.size() * sizeof(double))) != hipSuccess) return e;
+            if ((e = hipMemcpy(w.d_split_const, split_const.data(), split_const.size() * sizeof(double), hipMemcpyHostToDevice)) != hipSuccess) return e;
         }
         if ((e = hipMalloc(&w.d_chunks, std::max<size_t>(1, chunks.size()) * sizeof(mcd::Chunk))) != hipSuccess) return e;
         if ((e = hipMalloc(&w.d_offsets, offs.size() * sizeof(int64_t))) != hipSuccess) return e;
@@ -435,6 +453,7 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
         for (auto& kv : sh.work) free_workset(kv.second);
         if (sh.records) (void)hipFree(sh.records);
         if (sh.records_sorted) (void)hipFree(sh.records_sorted);
+        if (sh.records_split) (void)hipFree(sh.records_split);
         if (sh.d_pset_const) (void)hipFree(sh.d_pset_const);
         if (sh.ev_begin) (void)hipEventDestroy(sh.ev_begin);
         if (sh.ev_k0) (void)hipEventDestroy(sh.ev_k0);
@@ -557,6 +576,7 @@ int64_t mcd_last_series_chunks(const mcd_catalog* cat) { return cat ? cat->last_
 int64_t mcd_last_direct_chunks(const mcd_catalog* cat) { return cat ? cat->last_direct_chunks : -1; }
 
 int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
+int mcd_last_exp_split(const mcd_catalog* cat) { return cat ? cat->last_exp_split : -1; }
 
 int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_theta) {
     if (!cat) return -1;

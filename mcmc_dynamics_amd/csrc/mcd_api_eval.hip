@@ -111,6 +111,10 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
         w->lane1_knows_staging = false;
         w->fast = fast;
         w->narrow_rescale = narrow_rescale;
+        for (int b = 0; b < 2; ++b)
+            w->exp_split[b] = fast == 2 && cat->precision == MCD_F64 && (b == 0 || narrow_rescale != 0) &&
+                              mcd::exp_split_admitted(cat->stats, cat->model, cat->free_centre, cat->k, params, n_rows,
+                                                      b ? narrow_rescale : 0);
         w->series_chunks = series_chunk_count(cat, *w, fast, params, n_rows);
         w->direct_chunks = direct_chunk_count(cat, *w, fast, params, n_rows);
         w->staged = true;
@@ -207,6 +211,13 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         mcd::LaunchShape shape = main_launch_shape(cat, sh, w, w.fast, coll, out_buf, n_out);
         shape.narrow_rescale = cat->narrow_bounded ? w.narrow_rescale : 0;
         cat->last_narrow_bounded = mcd::narrow_bounded_launch(shape) ? shape.narrow_rescale : 0;
+        // the direct chunks with the split exponent offset (option "exp_split"), where the guard admits it for the loop
+        // this launch runs; refused: the direct form as it is
+        if (cat->exp_split && w.sorted && w.d_split_const && w.exp_split[cat->last_narrow_bounded ? 1 : 0]) {
+            shape.records_split = sh.records_split;
+            shape.split_const = w.d_split_const;
+        }
+        cat->last_exp_split = mcd::exp_split_launch(shape) ? 1 : 0;
         if (&sh == &cat->shards.front()) cat->last_series_chunks = cat->last_direct_chunks = 0;
         cat->last_series_chunks += shape.root_series && shape.fast == 2 ? w.series_chunks : 0;
         cat->last_direct_chunks += shape.root_direct && shape.fast == 2 ? w.direct_chunks : 0;

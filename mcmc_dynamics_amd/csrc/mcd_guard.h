@@ -332,6 +332,28 @@ MCD_HD int bounded_rescale(const StatsScalars& st, int model, bool free_centre, 
     return 0;
 }
 
+// Split exponent offset of the direct chunks (option "exp_split"; mcd_math.h: kExpSplitC, BgFixedAcc::add_gs): every
+// mixture value of such a chunk is y' = kappa y with kappa = (c / 32) e^{-nbf ln2/N}, 1 < kappa <= kappa_max = (c / 32) e^{ln2/2N}
+// = 1.20153 (log2: 0.264872), and the table index is lower by 5 N.  `rescale` is bounded_rescale's verdict for the launch.
+//   Bounded loop (rescale = R): R factors of at most kappa_max y_hi must still fit, R (hi2 + log2 kappa_max) <= 1000 with
+//   bounded_rescale's hi2; the lower side only loosens (kappa > 1).  Clamp: u >= -700 now gives k >= -1034127 - 5120 =
+//   -1039247, still above kExpTabKMin = -1045504, so the loop stays without its v_max_i32.
+//   Other level-2 loops (rescale = 0): eight factors of at most 2^120 kappa_max < 2^961 fit as before, the clamp is in place
+//   and what it lets through (< 2^-1019 2^-5, times gs <= 2^31 c) is absorbed by omp' >= 2^-53 exactly as before.
+// Where this refuses, the launch runs the direct form without the split.
+constexpr double kExpSplitLog2KappaMax = 0.264872;            // log2((c / 32) e^{ln2/2N}) = 0.26487147, rounded up
+constexpr int kExpSplitKMinBounded = -1034127 - 5 * 1024;     // k at u = -700 in the split form (N = 1024)
+MCD_HD bool exp_split_admitted(const StatsScalars& st, int model, bool free_centre, int64_t n_rows, const ParamRanges& pr,
+                               int rescale) {
+    if (model != MODEL_BGFIXED || free_centre) return false;
+    if (level_verdict(st, model, false, n_rows, pr) != 2) return false;
+    if (rescale == 0) return true;
+    GuardRanges g;
+    if (!guard_verdict(st, model, false, n_rows, pr, &g)) return false;
+    const double hi2 = log2(1.0 + exp(st.nbp_max) / sqrt(g.n_min));    // (bounded_rescale's)
+    return rescale * (hi2 + kExpSplitLog2KappaMax) <= 1000.0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // float32 accuracy domain (MCD_F32, MCD_F32_ACC64; host only -- the resident chain is float64).  The float32 kernels round
 // every record field and every walker constant to 24 bits before the first operation, so what they can deliver is set by
@@ -418,6 +440,10 @@ inline int fast_level(const CatalogStats& st, int model, bool free_centre, bool 
 
 inline int bounded_rescale(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows) {
     return bounded_rescale(st, model, free_centre, n_rows, table_ranges(model, free_centre, k, params, n_rows));
+}
+inline bool exp_split_admitted(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows,
+                               int rescale) {
+    return exp_split_admitted(st, model, free_centre, n_rows, table_ranges(model, free_centre, k, params, n_rows), rescale);
 }
 
 }  // namespace mcd

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../include/mcd.h"
+#include "mcd_exp_split.h"
 #include "mcd_internal.h"
 #include "mcd_guard.h"
 #include "mcd_math.h"
@@ -102,6 +103,8 @@ struct WorkSet {
     mcd::Chunk* d_chunks = nullptr;
     int64_t* d_offsets = nullptr;      // [n_psets + 1] chunk offsets
     uint8_t* d_chunk_general = nullptr;   // [n_chunks] chunks excluded from the narrow-range variant; null when there are none
+    double* d_split_const = nullptr;      // [n_chunks] sorted: what a direct chunk run with the split exponent offset adds to
+                                          // its sum (mcd_exp_split.h: exp_split_chunk_consts)
     double* d_params = nullptr;        // [n_psets][W][K]
     void* d_wpar = nullptr;            // [n_psets][W][KD]
     double* d_partials = nullptr;      // [roundup64(W) / 8][n_chunks][8]
@@ -133,6 +136,8 @@ struct WorkSet {
     double launch_tag = 0.0;           // tag of the last fast-path launch (written to out[n_out] by a kernel that wants a re-run)
     int fast = 0;                      // mcd::LaunchShape::fast level of the staged batch
     int narrow_rescale = 0;            // its bounded narrow-range verdict (mcd_guard.h: bounded_rescale; R or 0)
+    bool exp_split[2] = {false, false};   // mcd_guard.h: exp_split_admitted for the staged batch: [0] in the loops that keep the
+                                          // clamp, [1] in the bounded loop with R = narrow_rescale
     bool staged = false;
     bool sorted = false;               // planned on, and launched with, the shard's verr-sorted records (Shard::records_sorted)
     std::vector<double> series_need;   // sorted: per chunk outside chunk_general, the smallest sigma^2 with which its verr^2
@@ -159,6 +164,10 @@ struct Shard {
     // ensure_sorted_records): every kernel that reports per star keeps `records`, i.e. catalogue order.
     void* records_sorted = nullptr;
     std::vector<double> sorted_e2;            // verr^2 of records_sorted, in its order
+    // records_sorted with the split exponent offset, [v, verr^2, cx, cy, M, omp', 0, 0] per star (mcd_exp_split.h; made with
+    // records_sorted, read by the direct chunks of a launch with option "exp_split"), and the stars' nbf on the host
+    void* records_split = nullptr;
+    std::vector<double> sorted_nbf;
     std::vector<int64_t> sorted_exceptions;   // CatalogStats::narrow_exceptions of this shard as positions in records_sorted
                                               // (+ star_begin, ascending: what plan_chunks takes)
     double* d_pset_const = nullptr;    // BGFIXED: sum of lnlike_bg over this shard's stars of each parameter set
@@ -257,6 +266,8 @@ struct mcd_catalog {
     int verr_sorted = -1;              // option "verr_sorted": the main kernel reads a verr-sorted copy of the records (f64
                                        // MODEL_BGFIXED, fixed centre, one parameter set): -1 from 8 MiB of records per device, 0 never, 1 always
     int root_series = 1;               // option "root_series": 1 the series root on the sorted records' narrow chunks, 0 never
+    int exp_split = 1;                 // option "exp_split": 1 the direct chunks run with the split exponent offset where the
+                                       // guard admits it (mcd_guard.h: exp_split_admitted), 0 never
     int root_direct = 1;               // option "root_direct": 1 the direct form of the series where a chunk admits it, 0 the
                                        // delta form on every series chunk
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
@@ -294,6 +305,8 @@ struct mcd_catalog {
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
+    int last_exp_split = -1;           // 1: the direct chunks of the last main-kernel launch ran with the split exponent offset,
+                                       // 0 not (-1: no launch yet)
     int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };
 

@@ -29,6 +29,9 @@ struct LaunchShape {
     bool root_series = false;       // the records are sorted by verr and the level-2 BGFIXED fixed-centre loops may take the
                                     // per-chunk series root (mcd_math.h: RootSeries); f64 only
     bool root_direct = false;       // ... and its direct form where a chunk admits it (mcd_math.h: RootDirect)
+    const void* records_split = nullptr;    // ... with the split exponent offset (option "exp_split"): the direct chunks read
+    const double* split_const = nullptr;    // this array in place of the records and add split_const[chunk] (mcd_exp_split.h);
+                                            // null: the direct form as it is
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };
@@ -55,6 +58,12 @@ hipError_t launch_prepare_walkers(hipStream_t s, const double* params, int64_t n
 inline bool narrow_bounded_launch(const LaunchShape& sh) {
     return sh.fast == 2 && sh.model == MODEL_BGFIXED && !sh.free_centre && sh.precision == 0 && sh.prefetch &&
            (sh.narrow_rescale == 16 || sh.narrow_rescale == 32);
+}
+
+// The main-kernel launch of `shape` runs its direct chunks with the split exponent offset (what mcd_last_exp_split reports)
+inline bool exp_split_launch(const LaunchShape& sh) {
+    return sh.fast == 2 && sh.model == MODEL_BGFIXED && !sh.free_centre && sh.precision == 0 && sh.root_series &&
+           sh.root_direct && sh.records_split != nullptr && sh.split_const != nullptr;
 }
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& shape, const void* records, const Chunk* chunks,

@@ -114,6 +114,8 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
 // root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries): 1
 // its delta form only, 2 the direct form where a chunk admits it (RootDirect).
+// recs_split (null: none): the split-offset records of a launch with option "exp_split" (mcd_exp_split.h), in the order and
+// stride of `recs`, read by the direct chunks in its place; split_const[chunk]: what such a chunk adds to its sum.
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
 __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
                                                                  const Chunk* __restrict__ chunks,
@@ -123,7 +125,9 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
                                                                  int uniform_len, int uniform_extra, int64_t n_records,
                                                                  double* __restrict__ rerun_flag, double launch_tag,
                                                                  const uint8_t* __restrict__ chunk_general,
-                                                                 int64_t n_slots, int narrow_iters, int root_series) {
+                                                                 int64_t n_slots, int narrow_iters, int root_series,
+                                                                 const T* __restrict__ recs_split,
+                                                                 const double* __restrict__ split_const) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int kThreads = WAVES * kWave;
     constexpr bool kCombine = WAVES > kWavesPerBlock;
@@ -202,9 +206,9 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             // (the narrow-range profile variant without background has no per-star conditions: no flags, one form)
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
             if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
-            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(chunk_recs, ch.count, w, denormal,
-                                                                                         exptab_lds, narrow_iters, root_series != 0,
-                                                                                         root_series > 1);
+            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(
+                     chunk_recs, ch.count, w, denormal, exptab_lds, narrow_iters, root_series != 0, root_series > 1,
+                     recs_split ? (RecPtr<T>)(recs_split + ch.begin * ND) : (RecPtr<T>) nullptr, split_const + chunk_id);
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }
@@ -333,7 +337,8 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
     hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
-                       sh.chunk_general, n_slots, narrow_iters, sh.root_series ? (sh.root_direct ? 2 : 1) : 0)
+                       sh.chunk_general, n_slots, narrow_iters, sh.root_series ? (sh.root_direct ? 2 : 1) : 0,                \
+                       (const T*)(exp_split_launch(sh) ? sh.records_split : nullptr), sh.split_const)
     // bounded, else prefetch, else plain -- once, for a workgroup of decltype(waves)::value waves
     auto launch = [&](auto waves) {
         constexpr int W = decltype(waves)::value;

@@ -665,6 +665,81 @@ struct RootDirect {
     }
 };
 
+// Split exponent offset of the direct loops (option "exp_split").  The record's nbp enters k = rint(u N / ln 2)
+// additively and is the same for every walker, so the record preparation converts it into table steps once per star
+// (mcd_exp_split.h: exp_split_record): nbp N / ln 2 = nbi + nbf, nbi an integer, |nbf| <= 1/2.  With the root scaled by
+// c = sqrt(N / ln 2) (gs = c g: the scale sits in RootDirect's four per-chunk coefficients) and dgs = d gs,
+//   shifted = fma(-dgs, dgs, M)     M = 1.5 2^52 + nbi - 5 N, an exact double from the record; k = low word of shifted
+//   w       = shifted - M           exact, an integer
+//   rv      = fma(-dgs, dgs, -w)    the reduced argument in table steps, |rv| <= 1/2, ONE rounding
+// replace the parent's four instructions (u, shifted, kf, r).  e^u = 2^((w + nbi) / N) e^{rv ln2/N} e^{nbf ln2/N}: the
+// polynomial runs in rv with its coefficients scaled by powers of ln 2 / N, the table supplies 2^(k / N) = 2^-5 2^((w + nbi) / N),
+// and the walker-independent factor e^{nbf ln2/N} goes into the record's omp' = kappa (1 - p),
+// kappa = (c / 32) e^{-nbf ln2/N} in 1.2011 (1 +- 3.4e-4), so that y' = fma(gs, es, omp') = kappa y.  Sum log kappa of a chunk is a constant
+// of the plan, which the wave adds once per chunk (exp_split_chunk_const).  The 2^-5 keeps c = 38.4 out of the rescale
+// headroom (mcd_guard.h: exp_split_admitted).
+// Error of y' / kappa against (1 - p) + g e^u, in units of 2^-53 of the cluster term g e^u (the parent's direct form in
+// brackets), on top of RootDirect's own budget for g, which both forms share:
+//   scaled coefficients: the scale enters through G0 and its rounding error through c0's last FMA
+//       (RootDirectSplit), so gs carries the roundings g does                                                   0     [0]
+//   c as a double is off by delta = c^2 ln2/N - 1 = 4.9e-17 relative: a factor e^{-dg^2 delta}           0.44 dg^2  [0]
+//   reduced argument: rv has ONE rounding, at most 2^-54 of a table step, times ln 2 / N                      4e-4  [0.72 |u|:
+//       the parent's one-constant reduction is off by 8e-17 |u|]
+//   rounding of dgs = d gs, doubled by the square and carried into the exponent                         2.0 dg^2  [the same]
+//   polynomial: coefficients scaled at compile time (C2 s^2, C3 s^3, s: each within 2^-52 of a term <= 3.4e-4,
+//       negligible), its last FMA                                                                              1.00  [1.00]
+//   table entry, the product T[j] p, the last FMA of y                                                         2.50  [2.50]
+//   record: omp' = kappa (1 - p) rounded ONCE from long double (1/2 ulp of the (1 - p) term); M is exact;
+//       nbf is held as a double, 2^-54 of a table step off at most (4e-20 relative)                           0.50  [0]
+// i.e. half an ulp more than the parent where |u| is small and less where |u| > 1.  Measured over 4.5e5 (star, walker) terms
+// of a C3 catalogue through this code: largest relative error 8.6e-16 against the parent's 9.0e-16, both set by the root's
+// error amplified by 1 + 2 dg^2 (tests/test_exp_split_cpu.py).
+static_assert(kExpTabBits == 10 || kExpTabBits == 8, "kExpSplitC is written for N = 1024 (and halved exactly for N = 256)");
+constexpr double kExpSplitC = 0x1.337cc2183b050p+5 / (kExpTabBits == 10 ? 1.0 : 2.0);   // sqrt(1024 / ln 2) = 38.4359170811663934...
+constexpr int kExpSplitShift = 5;                                         // es comes out smaller by 2^-5
+constexpr double kExpSplitS1 = kExpTabStepHi + kExpTabStepLo;             // ln 2 / N
+constexpr double kExpSplitS2 = kExpPolyC2 * kExpSplitS1 * kExpSplitS1;
+constexpr double kExpSplitS3 = kExpPolyC3 * kExpSplitS1 * kExpSplitS1 * kExpSplitS1;
+constexpr double kExpSplitS4 = kExpPolyC4 * kExpSplitS1 * kExpSplitS1 * kExpSplitS1 * kExpSplitS1;
+// k and the reduced argument rv (in table steps) of the split form for dgs = d gs and the record's M (wave-uniform)
+MCD_HD double exp_split_reduce(double dgs, double M, int& k) {
+    const double shifted = fnma_sgpr_addend(dgs, dgs, M);
+    const double w = shifted - M;
+    uint64_t bits;
+    std::memcpy(&bits, &shifted, sizeof bits);
+    k = (int)(uint32_t)bits;
+    return fma_(-dgs, dgs, -w);
+}
+// e^{rv ln2/N}, |rv| <= 1/2: exp_poly with its coefficients scaled; s1 = kExpSplitS1, held in an SGPR pair on the device
+MCD_HD double exp_poly_steps(double rv, double s1) {
+    double p;
+    if constexpr (kExpPolyDegree == 4) p = fma_(fma_(rv, kExpSplitS4, kExpSplitS3), rv, kExpSplitS2);
+    else p = fma_(rv, kExpSplitS3, kExpSplitS2);
+    p = fma_sgpr_addend(p, rv, s1);                            // (three-address: a VGPR addend is copied for a v_fmac_f64)
+    return fma_(p, rv, 1.0);
+}
+
+// RootDirect with its coefficients scaled by `scale` (c): g_direct returns gs = c g.  The scale enters through G0, so every
+// coefficient is rounded as often as RootDirect's: G0s = fl(c G0) is off by eg = c G0 - G0s, which comes out exactly and
+// joins G0's own error in the one last FMA of c0 (eg / G0s to first order, with 1 / G0 = m0 G0 / 4 since G0^2 = 4 / m0)
+struct RootDirectSplit : RootDirect {
+    MCD_HD void setup_scaled(double eb, double s2, double scale) {
+        RootCentre c;
+        c.setup(eb, s2);
+        const double q = c.q;
+        const double G0s = c.G0 * scale;
+        const double eg = fma_(c.G0, scale, -G0s);
+        const double rho = c.p * c.inv;
+        const double P = rho * fma_(rho, fma_(rho, 0.3125, 0.375), 0.5);
+        c0 = fma_(G0s, (c.corr + P) + eg * ((0.25 / scale) * (c.m0 * c.G0)), G0s);
+        const double gq = G0s * q;
+        c1 = -gq * fma_(rho, fma_(rho, 0.9375, 0.75), 0.5);
+        const double gq2 = gq * q;
+        c2 = gq2 * fma_(rho, 0.9375, 0.375);
+        c3 = -0.3125 * (gq2 * q);
+    }
+};
+
 // true when `ok` holds in every active lane of the wave (one s_cmp on the ballot: callers branch on the scalar unit);
 // host build: the caller has combined the lanes (tests/emul)
 MCD_HD bool wave_all(bool ok) {
@@ -754,6 +829,32 @@ struct BgFixedAcc {
         const double y = UNIFORM_OMP ? fma_sgpr_addend(g, ldexp_(er, kc), omp) : fma_(g, ldexp_(er, kc), omp);
         l.mul_any_track(y, emin);
         l.e32 += k - kc;
+    }
+    // The narrow-range term with the split exponent offset (see kExpSplitC): gs = c g, M and ompk = omp' from the split
+    // record (wave-uniform), s1 = kExpSplitS1.  Multiplies the product by y' = kappa y.
+    template <bool TAB_BIASED = false, bool CLAMP = true>
+    MCD_HD void add_gs(double d, double gs, double M, double ompk, double s1, const double* __restrict__ exptab) {
+        int k;
+        const double p = exp_poly_steps(exp_split_reduce(d * gs, M, k), s1);
+        if constexpr (CLAMP) k = k > kExpTabKMin ? k : kExpTabKMin;      // v_max_i32
+        double es;
+        if constexpr (TAB_BIASED) {
+            const double t = exptab[k & (kExpTabSize - 1)];
+            const int32_t kh = (int32_t)((uint32_t)k << kExpTabHiShift);
+#if defined(__HIP_DEVICE_COMPILE__)
+            // (the add on a two-word vector, as exp_tab_scaled<.., false>: here the compiler splits add_hi_word's byte copies
+            // into byte-mask operations with the clamp in place too)
+            typedef uint32_t word2 __attribute__((ext_vector_type(2)));
+            word2 tw = __builtin_bit_cast(word2, t);
+            tw.y += (uint32_t)kh;
+            es = __builtin_bit_cast(double, tw) * p;
+#else
+            es = add_hi_word(t, kh) * p;
+#endif
+        } else {
+            es = ldexp_(exptab[k & (kExpTabSize - 1)] * p, k >> kExpTabBits);
+        }
+        l.mul(fma_sgpr_addend(gs, es, ompk));
     }
     MCD_HD void rescale() { l.rescale(); }
     MCD_HD void rescale_density() { l.rescale(); lden.rescale(); }
@@ -1232,7 +1333,8 @@ MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<d
 // sqrt(2)-scaled table; star_d_n's own norm is dead code there.
 template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED>
 MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w, bool& denormal,
-                                 const double* __restrict__ exptab, int rescale_iters, bool series, bool direct) {
+                                 const double* __restrict__ exptab, int rescale_iters, bool series, bool direct,
+                                 RecPtr<double> r_split, const double* __restrict__ split_const) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int XB = geometry_doubles(MODEL, FREE);
     constexpr bool HALVED = MODEL == MODEL_BGFIXED;
@@ -1249,7 +1351,10 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
         double d, n;
         star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-        if constexpr (std::is_same<decltype(SERIES), RootDirect>::value) {
+        if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value) {
+            // the split record [v, verr^2, cx, cy, M, omp', 0, 0]; sc: kExpSplitS1 here
+            acc.add_gs<TAB_BIASED, !BOUNDED>(d, SERIES.g_direct(rr[1]), rr[XB], rr[XB + 1], sc, exptab);
+        } else if constexpr (std::is_same<decltype(SERIES), RootDirect>::value) {
             acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, SERIES.g_direct(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
         } else if constexpr (decltype(SERIES)::value) {
             acc.add_g<true, HALVED, NARROW, TAB_BIASED, !BOUNDED>(d, sr.g(rr[1]), rr[XB + 2], rr[XB + 3], exptab);
@@ -1261,8 +1366,14 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     const int n4 = count >> 2;
     static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
     auto four = [&](RecPtr<double> r4, auto SERIES) {
+        if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value) {
+            // (the linear coefficient of the scaled polynomial in place of the rsq loops' variance scale)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
+            for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, kExpSplitS1);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
+        }
     };
     auto run = [&](auto SERIES) {
         if constexpr (BOUNDED) {
@@ -1323,7 +1434,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             }
         }
         for (int j = n4 * 4; j < count; ++j, r += ND) {
-            one(r, SERIES, kScale);
+            one(r, SERIES, std::is_same<decltype(SERIES), RootDirectSplit>::value ? kExpSplitS1 : kScale);
             acc.rescale();
         }
     };
@@ -1335,11 +1446,16 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     // the walkers alone.  `direct`: the second vote is held (option "root_direct"); without it every series chunk keeps
     // the delta form.
     constexpr bool kCanSeries = NARROW && MODEL == MODEL_BGFIXED && !FREE;
+    // `r_split` (a launch with the split exponent offset, option "exp_split"): the chunk's records in the split array, which
+    // a direct chunk then reads INSTEAD of `r` -- the vote's two records included (the same verr^2 in both arrays), so that
+    // such a chunk touches one array only
     bool use_series = false, use_direct = false;
+    const bool split = kCanSeries && r_split != nullptr;
     if constexpr (kCanSeries) {
         if (series && count > 0) {
             RootSeries vote;                                         // (its verdict and centre only: the rest is dead code)
-            const bool ok = vote.setup_chunk(r[1], r[(int64_t)(count - 1) * ND + 1], w.s2);
+            const RecPtr<double> rv = split ? r_split : r;
+            const bool ok = vote.setup_chunk(rv[1], rv[(int64_t)(count - 1) * ND + 1], w.s2);
             use_series = wave_all(ok);
             if (use_series && direct) use_direct = wave_all(RootDirect::direct_ok(vote.eb, w.s2));
         }
@@ -1352,7 +1468,18 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
         // vote's, bit for bit, BECAUSE s2x = 8 s2 and (1/8) s2x are exact: scaling by a power of two rounds nothing as
         // long as 8 s2 is finite (and the way back lands on s2, which is representable, subnormal or not); the range
         // guard admits no fast mixture kernel for a variance beyond 2^200 (mcd_guard.h: guard_verdict).
-        if (use_direct) {
+        if (use_direct && split) {
+            r = r_split;
+            const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
+            RootDirectSplit sd;
+            sd.setup_scaled(0.5 * e_first + 0.5 * e_last, vgpr_pinned((1.0 / kScale) * s2x), kExpSplitC);
+            run(sd);
+            // sum of log kappa over the chunk's stars, a constant of the plan (mcd_exp_split.h: exp_split_chunk_const): read
+            // on this branch only, so it can never reach a chunk that ran another loop
+            const double result = acc.finish() + *split_const;
+            denormal = acc.denormal();
+            return result;
+        } else if (use_direct) {
             const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
             RootDirect sd;
             sd.setup(0.5 * e_first + 0.5 * e_last, vgpr_pinned((1.0 / kScale) * s2x));
@@ -1386,7 +1513,8 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
 // verr^2 is at most 1/8 of every walker's variance -- a second vote.
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
-                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false, bool direct = false) {
+                            const double* __restrict__ exptab, int rescale_iters = 1, bool series = false, bool direct = false,
+                            RecPtr<T> r_split = nullptr, const double* __restrict__ split_const = nullptr) {
     constexpr int BG = bg_kind(MODEL);
     denormal = false;
     if constexpr (!FAST) {
@@ -1399,7 +1527,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (FAST == 2 && MODEL == MODEL_PROFILE && !FREE) return chunk_profile_narrow<PF>(r, count, w);
         else return chunk_const_fast<MODEL, FREE, PF>(r, count, w);
     } else if constexpr (BG == BG_FIXED) {
-        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct);
+        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct, r_split, split_const);
     } else if constexpr (BG == BG_FIXED_DENSITY) {
         // BG_FIXED_DENSITY, f64 fast forms
         constexpr int ND = record_doubles(MODEL, FREE);

@@ -13,9 +13,11 @@ parameter BOUNDED, the last one of the mangled name) rescales every fourth 8-sta
 loop branches out to: (4 x loop body + rescale block) / 32.  That instantiation is what C3's timed launches run, so it
 keeps its row under "bgfixed_rsq"; the level-2 prefetching loop keeps its row under "bgfixed_level2".  Each of the three
 kernels also holds the two series forms of its loop (mcd_math.h: RootSeries about the chunk's centre, RootDirect in
-verr^2 itself; the chunks of a verr-sorted record array whose verr^2 band is narrow): rows "..., series" and "..., direct".
-The bounded direct loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded
-delta series loop keeps its row under "bgfixed_series_bounded".
+verr^2 itself; the chunks of a verr-sorted record array whose verr^2 band is narrow): rows "..., series" and "..., direct",
+and the direct loop once more with the split exponent offset (option "exp_split", BgFixedAcc::add_gs): rows "..., split".
+The bounded split loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded
+direct loop without the split keeps its row under "bgfixed_direct_bounded", the bounded delta series loop under
+"bgfixed_series_bounded".
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -39,10 +41,11 @@ SLOT_NS = 2.33
 #  [, (stars, trips, selector) of the instantiation with the prefetch when its loop differs
 #   [, model key of the instantiation with the prefetch when it differs]])
 #   selector(Counter of the loop body) -> bool picks the loop among the kernel's innermost loops
-def _sel(rsq=None, frexp=None, rcp=None, add=None):
+def _sel(rsq=None, frexp=None, rcp=None, add=None, fma=None):
     def f(c):
         return ((rsq is None or c["v_rsq_f64_e32"] == rsq) and (frexp is None or c["v_frexp_mant_f64_e32"] == frexp)
-                and (rcp is None or c["v_rcp_f64_e32"] == rcp) and (add is None or c["v_add_f64"] == add))
+                and (rcp is None or c["v_rcp_f64_e32"] == rcp) and (add is None or c["v_add_f64"] == add)
+                and (fma is None or c["v_fma_f64"] + c["v_fmac_f64_e32"] == fma))
     return f
 
 
@@ -70,7 +73,9 @@ BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bou
 # the series loops of the same three kernels (mcd_math.h: RootSeries; chunks of a verr-sorted record array whose verr^2
 # band is narrow): no v_rsq_f64 in the body.  Each kernel holds two of them, told apart by their v_add_f64 per term: the
 # delta form (about the chunk's centre) has three -- v - v_sys, the exponent's rounding constant and delta = e - eb, which
-# feeds the first FMA of the cubic -- the direct form (RootDirect: the cubic in verr^2 itself) the first two only.
+# feeds the first FMA of the cubic -- the direct form (RootDirect: the cubic in verr^2 itself) the first two only.  The
+# direct loop with the split exponent offset has two as well (v - v_sys and shifted - M): it is told from the direct loop
+# without the split by its fused multiply-adds (v_fma_f64 + v_fmac_f64) per term, 11 instead of 12.
 # Full tag, name, key, stars, trips, selector, prefetching, bounded
 SERIES = [
     ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, series", "bgfixed_series", 4, 2, _sel(rsq=0, frexp=0, add=12),
@@ -79,13 +84,19 @@ SERIES = [
      _sel(rsq=0, frexp=1, add=24), True, False),
     ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, series", "bgfixed_series_bounded", 8, 4,
      _sel(rsq=0, frexp=0, add=24), True, True),
-    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, direct", "bgfixed_direct", 4, 2, _sel(rsq=0, frexp=0, add=8),
-     False, False),
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, direct", "bgfixed_direct", 4, 2,
+     _sel(rsq=0, frexp=0, add=8, fma=48), False, False),
     ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, direct", "bgfixed_direct", 8, 1,
-     _sel(rsq=0, frexp=1, add=16), True, False),
+     _sel(rsq=0, frexp=1, add=16, fma=96), True, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, direct", "bgfixed_direct_bounded", 8, 4,
+     _sel(rsq=0, frexp=0, add=16, fma=96), True, True),
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, split", "bgfixed_split", 4, 2,
+     _sel(rsq=0, frexp=0, add=8, fma=44), False, False),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, split", "bgfixed_split", 8, 1,
+     _sel(rsq=0, frexp=1, add=16, fma=88), True, False),
     # what C3's timed launches run on the chunks that qualify (98.2 % of the stars): the "bgfixed" key's prefetch fields
-    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, direct", "bgfixed", 8, 4,
-     _sel(rsq=0, frexp=0, add=16), True, True),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, split", "bgfixed", 8, 4,
+     _sel(rsq=0, frexp=0, add=16, fma=88), True, True),
 ]
 
 
