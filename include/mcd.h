@@ -295,6 +295,39 @@ int mcd_chain_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_b
 int mcd_stretch_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks, int64_t* discarded_blocks,
                      int32_t* last_discard_status);
 
+/* Structured priors on the free parameters, on top of the inclusive box lo / hi of the descriptor (the reference writes
+ * them as `lnprior` expressions over scipy's norm / lognorm, parameter.py:64-74, 684-705).  Per free parameter:
+ *   kind 0  flat        --                     0
+ *   kind 1  normal      p0 = loc, p1 = scale   -log(scale) - 1/2 log(2 pi) - 1/2 ((x - loc) / scale)^2
+ *   kind 2  lognormal   p0 = mu,  p1 = s       -log(s) - 1/2 log(2 pi) - log(x) - 1/2 ((log(x) - mu) / s)^2
+ *                       (scipy's lognorm(s, scale=exp(mu))); x <= 0 is outside the prior
+ * i.e. the un-truncated log-density, evaluated at the full float64 value by one text of code on host and device
+ * (mcmc_dynamics_amd/csrc/mcd_prior.h; the logarithm is det_log, no libm call per proposal): resident and host-driven
+ * blocks give the same chain bit for bit.  A proposal is inside the prior when it is inside the box and every lognormal
+ * coordinate is > 0; one that is not is treated as a proposal outside the box is.  lnp / lnprob_chain of the *_prior
+ * entry points hold log-likelihood plus log-prior (lnp of mcd_stretch_move*_prior is the caller's on entry, as before).
+ * prior == NULL, or all kinds 0, is the entry point without `_prior`, bit for bit.  p1 <= 0, a non-finite p0 / p1 of a
+ * non-flat kind, an unknown kind or n_dim different from the descriptor's: MCD_ERR_INVALID, nothing written.  In
+ * mcd_hmc_block_prior the potential is -(lnlike + lnprior) and the prior's derivative joins the gradient; a lognormal
+ * coordinate <= 0 on a trajectory rejects the proposal, at the block's start it is MCD_ERR_NONFINITE. */
+typedef struct {
+    int32_t n_dim;          /* free parameters: must equal the descriptor's n_dim */
+    const int32_t* kind;    /* [n_dim] 0 flat, 1 normal, 2 lognormal */
+    const double* p0;       /* [n_dim] loc / mu (ignored for kind 0) */
+    const double* p1;       /* [n_dim] scale / s > 0 (ignored for kind 0) */
+} mcd_prior_desc;
+
+/* value [n_rows] = log-prior of the rows x [n_rows][n_dim] WITHOUT the box (-inf where a lognormal coordinate is <= 0),
+ * grad [n_rows][n_dim] (may be NULL) its derivatives (0 for such a row): the host compilation of the header the blocks
+ * use, so that a caller can reproduce their numbers bit for bit.  Needs no device. */
+int mcd_prior_eval(const mcd_prior_desc* prior, int64_t n_rows, const double* x, double* value, double* grad);
+int mcd_stretch_move_prior(mcd_catalog* cat, const mcd_stretch_desc* desc, int64_t n_steps, double* pos, double* lnp,
+                           const int32_t* order, const double* zz, const double* thr, const int32_t* pick, double* chain,
+                           double* lnprob_chain, int64_t* accepted, const mcd_prior_desc* prior);
+int mcd_stretch_move_seeded_prior(mcd_catalog* cat, const mcd_stretch_desc* desc, int64_t n_steps, double* pos, double* lnp,
+                                  uint64_t seed, int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted,
+                                  const mcd_prior_desc* prior);
+
 /* One block of Hamiltonian Monte Carlo steps (Duane et al. 1987; Neal 2011) on the gradient of mcd_loglike_grad_batch:
  * W independent chains, each step n_leap leapfrog points, i.e. n_leap value-and-gradient evaluations of W rows.  The
  * reference has no gradient-based sampler -- this stands beside mcd_stretch_move_seeded as a second way to drive the chain
@@ -340,6 +373,9 @@ typedef struct {
 
 int mcd_hmc_block(mcd_catalog* cat, const mcd_hmc_desc* desc, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
                   int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error);
+int mcd_hmc_block_prior(mcd_catalog* cat, const mcd_hmc_desc* desc, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
+                        int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error,
+                        const mcd_prior_desc* prior);      /* mcd_prior_desc: above, with mcd_stretch_move_prior */
 int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_walkers, int32_t n_dim, double* z, double* thr,
                     double* eps_factor);
 int mcd_hmc_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);

@@ -71,6 +71,17 @@ SYMBOLS = {
     "mcd_hmc_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        _c_double_p, _c_double_p, _c_double_p]),
     "mcd_hmc_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p]),
+    "mcd_prior_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_stretch_move_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
+                                              ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p,
+                                              ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p, _c_int64_p,
+                                              ctypes.c_void_p]),
+    "mcd_stretch_move_seeded_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
+                                                     _c_double_p, ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p,
+                                                     _c_int64_p, ctypes.c_void_p]),
+    "mcd_hmc_block_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
+                                           ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p,
+                                           ctypes.c_void_p]),
     "mcd_last_error": (ctypes.c_char_p, []),
     "mcd_abi_version": (ctypes.c_int, []),
     "mcd_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
@@ -114,6 +125,42 @@ class StretchDesc(ctypes.Structure):
         ("col_source", ctypes.POINTER(ctypes.c_int32)), ("col_const", _c_double_p), ("col_factor", _c_double_p),
         ("lo", _c_double_p), ("hi", _c_double_p), ("fixed_ok", ctypes.c_int32), ("n_bins", ctypes.c_int32),
     ]
+
+
+class PriorDesc(ctypes.Structure):
+    """Mirror of ``mcd_prior_desc``."""
+    _fields_ = [("n_dim", ctypes.c_int32), ("kind", ctypes.POINTER(ctypes.c_int32)), ("p0", _c_double_p), ("p1", _c_double_p)]
+
+
+PRIOR_FLAT, PRIOR_NORMAL, PRIOR_LOGNORMAL = 0, 1, 2
+
+
+def _prior_desc(prior):
+    """``prior``: (kind int32 [P], p0 float64 [P], p1 float64 [P]) -> (PriorDesc, the arrays it points to)."""
+    kind = np.ascontiguousarray(prior[0], dtype=np.int32)
+    p0, p1 = _f64(prior[1]), _f64(prior[2])
+    if kind.ndim != 1 or p0.shape != kind.shape or p1.shape != kind.shape:
+        raise ValueError("a prior is three arrays of one length: kind, p0, p1")
+    d = PriorDesc()
+    d.n_dim = kind.size
+    d.kind, d.p0, d.p1 = kind.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(p0), _ptr(p1)
+    return d, (kind, p0, p1)
+
+
+def prior_eval(prior, x, want_grad=False):
+    """``mcd_prior_eval``: the log-prior of the rows ``x`` (n, P) under the structured priors ``prior`` = (kind, p0, p1)
+    (include/mcd.h: 0 flat, 1 normal (loc, scale), 2 lognormal (mu, s)), WITHOUT the box: -inf where a lognormal coordinate
+    is <= 0.  Host code of the library (csrc/mcd_prior.h, the text the device kernels compile): the library's own bits, no
+    device involved.  -> values (n,) [, derivatives (n, P)]"""
+    lib = load_library()
+    x = _f64(np.atleast_2d(x))
+    d, _keep = _prior_desc(prior)
+    if x.shape[1] != d.n_dim:
+        raise ValueError("prior_eval: x must have shape (n, {0})".format(d.n_dim))
+    value = np.empty(x.shape[0])
+    grad = np.empty(x.shape) if want_grad else None
+    _check(lib, lib.mcd_prior_eval(ctypes.byref(d), x.shape[0], _ptr(x), _ptr(value), _ptr(grad)), "mcd_prior_eval")
+    return (value, grad) if want_grad else value
 
 
 class HmcDesc(ctypes.Structure):
@@ -504,13 +551,23 @@ class Catalog(object):
                 raise ValueError("stretch_move: chain buffers must be C-contiguous float64 of shape (steps, [B,] W, P) / (steps, [B,] W)")
         if accepted is not None and (accepted.dtype != np.int64 or accepted.shape != lead + (w,) or not accepted.flags.c_contiguous):
             raise ValueError("stretch_move: accepted must be a C-contiguous int64 array of shape ([B,] W)")
+        # a plan with a "prior" entry ((kind, p0, p1) over the free parameters, or None) takes the *_prior entry points
+        self._prior_arg = None
+        if "prior" in plan:
+            pd = None
+            if plan["prior"] is not None:
+                pd, keep = _prior_desc(plan["prior"])
+                cols.append(keep)
+            self._prior_arg = (ctypes.byref(pd) if pd is not None else None,)
         return ((self.handle, ctypes.byref(d), n_steps, _ptr(pos), _ptr(lnp)),
                 (_ptr(chain), _ptr(lnprob_chain), accepted.ctypes.data_as(_c_int64_p) if accepted is not None else None), cols)
 
     def stretch_move(self, plan, pos, lnp, order, zz, thr, pick, chain=None, lnprob_chain=None, accepted=None):
         """``mcd_stretch_move``: advance the ensemble by ``len(order)`` stretch-move steps with the half-step loop inside
         the library.  ``plan``: dict with ``col_source`` (int32 [K]), ``col_const``, ``col_factor`` (float64 [K]), ``lo``,
-        ``hi`` (float64 [P]) and ``fixed_ok``.  ``pos`` (W, P) and ``lnp`` (W,) are C-contiguous float64 arrays updated
+        ``hi`` (float64 [P]) and ``fixed_ok``; an entry ``prior`` -- ``(kind, p0, p1)`` over the free parameters
+        (``prior_eval``) or None -- selects ``mcd_stretch_move_prior`` (and the ``_prior`` form of the seeded and the HMC
+        block), whose ``lnp`` is log-likelihood plus log-prior.  ``pos`` (W, P) and ``lnp`` (W,) are C-contiguous float64 arrays updated
         in place; random numbers as drawn by ``sampler.EnsembleSampler``.
 
         Binned catalogues: ``pos`` (B, W, P), ``lnp`` (B, W), ``order`` (steps, B, W), ``zz`` / ``thr`` / ``pick``
@@ -524,8 +581,12 @@ class Catalog(object):
         if order.shape != order.shape[:1] + lnp.shape or zz.shape != half_shape or thr.shape != half_shape or \
                 pick.shape != half_shape:
             raise ValueError("stretch_move: inconsistent array shapes")
-        rc = self.lib.mcd_stretch_move(*head, order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(zz), _ptr(thr),
-                                       pick.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), *tail)
+        numbers = (order.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(zz), _ptr(thr),
+                   pick.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        if self._prior_arg is not None:
+            rc = self.lib.mcd_stretch_move_prior(*head, *numbers, *tail, *self._prior_arg)
+        else:
+            rc = self.lib.mcd_stretch_move(*head, *numbers, *tail)
         _check(self.lib, rc, "mcd_stretch_move")
         self._walkers = pos.shape[-2] // 2
 
@@ -536,7 +597,10 @@ class Catalog(object):
         if n_steps < 0 or step0 < 0:
             raise ValueError("stretch_move_seeded: inconsistent array shapes")
         head, tail, _keep = self._stretch_args("stretch_move_seeded", plan, pos, lnp, n_steps, chain, lnprob_chain, accepted)
-        rc = self.lib.mcd_stretch_move_seeded(*head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail)
+        if self._prior_arg is not None:
+            rc = self.lib.mcd_stretch_move_seeded_prior(*head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail, *self._prior_arg)
+        else:
+            rc = self.lib.mcd_stretch_move_seeded(*head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail)
         _check(self.lib, rc, "mcd_stretch_move_seeded")
         self._walkers = pos.shape[-2] // 2
 
@@ -588,8 +652,13 @@ class Catalog(object):
         d = HmcDesc()
         d.map = head[1]._obj
         d.chol, d.step_size, d.jitter, d.n_leap = _ptr(chol), float(step_size), float(jitter), int(n_leap)
-        rc = self.lib.mcd_hmc_block(self.handle, ctypes.byref(d), int(n_steps), head[3], head[4],
-                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail, _ptr(energy_error))
+        if self._prior_arg is not None:
+            rc = self.lib.mcd_hmc_block_prior(self.handle, ctypes.byref(d), int(n_steps), head[3], head[4],
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail, _ptr(energy_error),
+                                              *self._prior_arg)
+        else:
+            rc = self.lib.mcd_hmc_block(self.handle, ctypes.byref(d), int(n_steps), head[3], head[4],
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail, _ptr(energy_error))
         _check(self.lib, rc, "mcd_hmc_block")
 
     def hmc_info(self):

@@ -182,8 +182,9 @@ class BinnedConstantFit(ConstantFit):
         if plan.simple and values.ndim == 3 and values.shape[0] == self.n_bins and values.shape[2] == plan.free_idx.size:
             # flat bounds, no expression priors / constraints: the vectorised plan of Runner.lnprob_batch over all bins
             w = values.shape[1]
-            full = plan.full(values.reshape(-1, values.shape[2]))
-            ok = plan.prior_ok(full)
+            free = values.reshape(-1, values.shape[2])
+            full = plan.full(free)
+            lp, ok = plan.prior_free(free, plan.prior_ok(full))          # (structured priors: shared by the bins)
             out = np.full(self.n_bins * w, -np.inf)
             if ok.any():
                 if not ok.all():
@@ -192,7 +193,7 @@ class BinnedConstantFit(ConstantFit):
                 table = plan.table(full)
                 ll = (cat.loglike(table.reshape(self.n_bins, w, -1)) if self.n_bins > 1 else
                       cat.loglike(table.reshape(w, -1))[None, :]).reshape(-1)
-                out[ok] = ll[ok]
+                out[ok] = ll[ok] if lp is None else ll[ok] + lp[ok]
             return out.reshape(self.n_bins, w)
         w, flat = self._resolve(values)
         lp = self.parameters.lnprior_batch(flat)

@@ -42,6 +42,9 @@ class _BatchPlan(object):
         self.fixed_idx = np.array([i for i, _ in fixed], dtype=np.intp)
         self.fixed_val = np.array([float(p._value) for _, p in fixed], dtype=np.float64)
         self.simple = all(p._expr is None and p._lnprior is None for p in pars.values())
+        # structured priors (Parameter.prior) over the FREE parameters: (kind, p0, p1) arrays, or None.  They do not end
+        # `simple`: the library evaluates them, on the device inside resident blocks (csrc/mcd_prior.h).
+        self.prior = pars.structured_prior()
         self.lo, self.hi = pars.bounds()
         self.unbounded = bool(np.all(np.isneginf(self.lo)) and np.all(np.isposinf(self.hi)))
         # kernel table columns (C-ABI order) and unit factors
@@ -72,8 +75,16 @@ class _BatchPlan(object):
 
     @staticmethod
     def signature(runner):
-        return tuple((p.fixed, p._value if p.fixed else None, p.min, p.max, p._expr, p._lnprior, p.unit)
+        return tuple((p.fixed, p._value if p.fixed else None, p.min, p.max, p._expr, p._lnprior, p.unit, p._prior)
                      for p in runner.parameters.values())
+
+    def prior_free(self, values, ok):
+        """Structured priors of the (W, P) free-parameter rows: (log-prior (W,), `ok` without the rows whose prior is -inf
+        -- a log-normal coordinate <= 0), by one ``mcd_prior_eval`` call; (None, ok) without structured priors."""
+        if self.prior is None:
+            return None, ok
+        lp = _native.prior_eval(self.prior, values)
+        return lp, ok & (lp > -np.inf)
 
     def full(self, values):
         out = np.empty((values.shape[0], self.n_all), dtype=np.float64)
@@ -343,6 +354,7 @@ class Runner(object):
         plan = self._plan()
         if plan.direct_cols is not None and values.shape[1] == plan.free_idx.size:
             ok = plan.prior_ok_free(values)
+            lp, ok = plan.prior_free(values, ok)
             n_ok = int(np.count_nonzero(ok))
             if n_ok == 0:
                 return np.full(values.shape[0], -np.inf)
@@ -353,6 +365,8 @@ class Runner(object):
             if cat is None or plan.catalog_key != self._catalog_key:
                 cat = self._ensure_catalog()
             ll = cat.loglike(plan.table_direct(values))
+            if lp is not None:
+                ll = ll + lp
             if n_ok == ok.size:
                 return ll
             out = np.full(values.shape[0], -np.inf)
@@ -361,7 +375,7 @@ class Runner(object):
         if plan.simple and values.shape[1] == plan.free_idx.size:
             # fast host path: flat bounds, no expression priors / constraints
             full = plan.full(values)
-            ok = plan.prior_ok(full)
+            lp, ok = plan.prior_free(values, plan.prior_ok(full))
             out = np.full(values.shape[0], -np.inf)
             n_ok = int(ok.sum())
             if n_ok == 0:
@@ -372,6 +386,8 @@ class Runner(object):
             if cat is None or plan.catalog_key != self._catalog_key:
                 cat = self._ensure_catalog()
             ll = cat.loglike(plan.table(full))
+            if lp is not None:
+                ll = ll + lp
             if n_ok == ok.size:
                 return ll
             out[ok] = ll[ok]
@@ -391,8 +407,8 @@ class Runner(object):
 
     # ------------------------------------------------------------------ first-order methods (new)
     def _grad_plan(self):
-        """The plan, refused unless every parameter is a plain box-bounded one: the chain rule below has no term for an
-        ``expr`` constraint or an ``lnprior`` expression."""
+        """The plan, refused unless every parameter is a box-bounded one with a flat or a structured prior: the chain rule
+        below has no term for an ``expr`` constraint or an ``lnprior`` expression."""
         plan = self._plan()
         if not plan.simple:
             for name, par in self.parameters.items():
@@ -441,12 +457,32 @@ class Runner(object):
         return out, grad
 
     def lnprob_grad_batch(self, values):
-        """As ``lnlike_grad_batch`` for the log-posterior: the box priors are flat, so inside them value and gradient are
-        those of the likelihood, outside (-inf, zero row)."""
-        return self.lnlike_grad_batch(values)
+        """As ``lnlike_grad_batch`` for the log-posterior: inside the box, value and gradient of the likelihood plus those of
+        the structured priors (``Parameter.prior``; one ``mcd_prior_eval`` call) -- with flat priors the likelihood's own --
+        and (-inf, zero row) outside the box or where a log-normal coordinate is <= 0."""
+        values = np.atleast_2d(np.asarray(values, dtype=np.float64))
+        plan = self._grad_plan()
+        if plan.prior is None:
+            return self.lnlike_grad_batch(values)
+        if values.shape[1] != plan.free_idx.size:
+            raise ValueError("expected {0} free parameters per row, got {1}".format(plan.free_idx.size, values.shape[1]))
+        lp, g_lp = _native.prior_eval(plan.prior, values, want_grad=True)
+        inside = lp > -np.inf
+        if not inside.any():
+            return np.full(values.shape[0], -np.inf), np.zeros(values.shape)
+        rows = values
+        if not inside.all():                       # such a row takes a valid row's place in the launch and is masked
+            rows = values.copy()
+            rows[~inside] = values[int(np.flatnonzero(inside)[0])]
+        out, grad = self.lnlike_grad_batch(rows)
+        ok = inside & np.isfinite(out)
+        out = np.where(ok, out + np.where(inside, lp, 0.0), -np.inf)
+        grad = np.where(ok[:, None], grad + np.where(inside[:, None], g_lp, 0.0), 0.0)
+        return out, grad
 
     def maximize(self, n_starts=64, x0=None, max_iter=200, gtol=1e-8):
-        """Maximum of the log-posterior inside the prior box (MAP; with flat boxes the maximum-likelihood estimate), by a
+        """Maximum of the log-posterior inside the prior box (MAP: structured priors count; with flat boxes the
+        maximum-likelihood estimate), by a
         batched projected BFGS on the device gradient (``optimize.maximize_batch``) from ``n_starts`` rows of
         ``get_initials`` or from the rows of ``x0``.
 
@@ -469,7 +505,8 @@ class Runner(object):
                 "all_lnprob": f, "all_converged": res["converged"]}
 
     def laplace(self, x, rel_step=1e-4):
-        """Laplace approximation at ``x`` (a maximum inside the box): the Hessian of the log-posterior by central
+        """Laplace approximation at ``x`` (a maximum inside the box): the Hessian of the log-posterior (likelihood plus
+        structured priors) by central
         differences of the device gradient -- all 2 P displaced rows in ONE ``lnprob_grad_batch`` call -- symmetrised, and
         ``covariance = inv(-H)``.  The step of parameter j is ``rel_step * max(|x_j|, width of a finite prior box / 100,
         1e-3)``.  ValueError when ``x`` sits on a bound or when -H is not positive definite (not a maximum)."""
@@ -535,6 +572,7 @@ class Runner(object):
         that accepts nothing shrinks it by 55 %, and the rule is stationary at an acceptance of 0.8.  After warm-up eps
         is frozen (``sampler.step_size``; the adaptation's path is in ``sampler.warmup_step_sizes``).
 
+        Structured priors (``Parameter.prior``) are part of the target: the potential is -(lnlike + lnprior), on the device.
         ``expr`` / ``lnprior``-expression parameters and binned or non-float64 catalogues raise NotImplementedError: the
         gradient's own limits."""
         plan = self._grad_plan()
@@ -655,7 +693,7 @@ class Runner(object):
             if fn is not None and not module.startswith(__name__.rsplit(".", 2)[0] + "."):
                 return False, "{0}.{1} overrides the posterior outside the package".format(type(self).__name__, name)
         if not self._plan().simple:
-            return False, "the priors are not plain boxes (expression priors / constrained parameters)"
+            return False, "the priors are not plain boxes with flat / normal / log-normal priors (expression priors / constrained parameters)"
         return True, ""
 
     def _make_sampler(self, n_walkers, seed=None):
@@ -694,8 +732,9 @@ class Runner(object):
     NATIVE_STRETCH = True          # sub-classes whose posterior is not ONE un-binned catalogue switch this off
 
     def _stretch_plan(self):
-        """Arguments of ``mcd_stretch_move`` for the current parameter configuration (box priors only: ``plan.simple``):
-        which free parameter feeds each kernel column, constants for fixed parameters, unit factors, bounds."""
+        """Arguments of ``mcd_stretch_move_prior`` for the current parameter configuration (``plan.simple``: boxes with
+        flat or structured priors): which free parameter feeds each kernel column, constants for fixed parameters, unit
+        factors, bounds, and the structured priors (None without one)."""
         plan = self._plan()
         cached = getattr(self, "_stretch_cache", None)
         if cached is not None and cached[0] is plan:
@@ -713,7 +752,7 @@ class Runner(object):
         fixed_ok = bool(np.all((plan.fixed_val >= plan.lo[plan.fixed_idx]) & (plan.fixed_val <= plan.hi[plan.fixed_idx]))) \
             if plan.fixed_idx.size else True
         out = {"col_source": src, "col_const": const, "col_factor": fac, "lo": plan.lo[plan.free_idx].copy(),
-               "hi": plan.hi[plan.free_idx].copy(), "fixed_ok": fixed_ok}
+               "hi": plan.hi[plan.free_idx].copy(), "fixed_ok": fixed_ok, "prior": plan.prior}
         self._stretch_cache = (plan, out)
         return out
 

@@ -1,8 +1,9 @@
 // mcd_api_chain.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host units):
 // mcd_stretch_move / mcd_stretch_move_seeded as a block resident on the device (kernels: mcd_stretch.hip) or driven from
 // the host (mcd_stretch.h), and mcd_chain_numbers; mcd_hmc_block in the same two forms (kernels: mcd_hmc.hip, algebra and
-// host-driven loop: mcd_hmc.h), and mcd_hmc_numbers.
+// host-driven loop: mcd_hmc.h), and mcd_hmc_numbers; the *_prior forms of the three blocks and mcd_prior_eval (mcd_prior.h).
 #include "mcd_host.h"
+#include "mcd_prior.h"
 #include "mcd_rng.h"
 #include "mcd_stretch.h"
 #include "mcd_grad.h"
@@ -20,6 +21,31 @@ namespace {
 // host-driven re-run overwrites (and which stay if that re-run fails).
 // user <-> pinned copies of tens of MB (a binned block: 40 MB of random numbers in, 70 MB of chain rows out) on four
 // threads: one core moves ~10 GB/s, the copies would otherwise cost as much as the block's device time
+// The structured priors of a call: mcd_prior_desc checked and its derived constants (mcd_prior.h: prior_derive, libm, once
+// per call).  table.any() is false for a null descriptor and for one whose kinds are all flat: the call is then the
+// prior-free one, bit for bit.
+struct PriorHost {
+    std::vector<int32_t> kind;
+    std::vector<double> loc, scale, c0;
+    mcd::PriorTable table;
+};
+
+int prior_of(const mcd_prior_desc* p, int32_t n_dim, const char* who, PriorHost& out) {
+    out.table = mcd::PriorTable();
+    if (!p) return MCD_OK;
+    if (p->n_dim != n_dim) return fail(MCD_ERR_INVALID, std::string(who) + ": the prior's n_dim differs from the descriptor's");
+    if (n_dim < 1 || !p->kind || !p->p0 || !p->p1) return fail(MCD_ERR_INVALID, std::string(who) + ": null prior array");
+    out.kind.assign(p->kind, p->kind + n_dim);
+    out.loc.resize((size_t)n_dim); out.scale.resize((size_t)n_dim); out.c0.resize((size_t)n_dim);
+    bool structured = false;
+    if (!mcd::prior_derive(n_dim, p->kind, p->p0, p->p1, out.loc.data(), out.scale.data(), out.c0.data(), &structured))
+        return fail(MCD_ERR_INVALID, std::string(who) + ": prior kinds are 0 (flat), 1 (normal: loc, scale > 0) or 2 (lognormal: mu, s > 0) with finite parameters");
+    if (structured) {
+        out.table.kind = out.kind.data(); out.table.loc = out.loc.data(); out.table.scale = out.scale.data(); out.table.c0 = out.c0.data();
+    }
+    return MCD_OK;
+}
+
 void big_copy(void* dst, const void* src, size_t bytes) {
     constexpr size_t kSerial = (size_t)4 << 20;
     if (bytes < kSerial) { std::memcpy(dst, src, bytes); return; }
@@ -51,8 +77,8 @@ void big_copy(void* dst, const void* src, size_t bytes) {
 // numbers of absolute steps step0 .. step0 + n_steps - 1 on the device (mcd_rng.h, mcd_stretch.hip: chain_numbers_kernel)
 int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,
                          const int32_t* order, const double* zz, const double* thr, const int32_t* pick, double* chain,
-                         double* lnprob_chain, int64_t* accepted, bool* done, const uint64_t* seed = nullptr,
-                         int64_t step0 = 0) {
+                         double* lnprob_chain, int64_t* accepted, bool* done, const mcd::PriorTable& prior,
+                         const uint64_t* seed = nullptr, int64_t step0 = 0) {
     *done = false;
     mcd_ctx* ctx = cat->ctx;
     if (int urc = ctx_usable(ctx)) return urc;
@@ -100,6 +126,9 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     const size_t state_end = off;
     const size_t o_src = take((size_t)K * 4), o_const = take((size_t)K * 8), o_fac = take((size_t)K * 8);
     const size_t o_lo = take((size_t)P * 8), o_hi = take((size_t)P * 8);
+    const bool with_prior = prior.any();                        // (without: no bytes, the layout of a prior-free block)
+    const size_t o_pkind = take(with_prior ? (size_t)P * 4 : 0), o_ploc = take(with_prior ? (size_t)P * 8 : 0);
+    const size_t o_pscale = take(with_prior ? (size_t)P * 8 : 0), o_pc0 = take(with_prior ? (size_t)P * 8 : 0);
     const bool seeded = seed != nullptr;
     // seeded blocks: a kernel writes the numbers where the upload would have put them (ensembles too large for it: the host
     // build of the same functions fills the pinned copy, uploaded as usual)
@@ -109,6 +138,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     const size_t o_thr = take(n_in * BW * 8), o_pick = take(n_in * BW * 4);
     const size_t input_end = off;
     const size_t o_prop = take(Bh * P * 8), o_ok = take(Bh), o_nok = take((size_t)2 * B * 4), o_ranges = take((size_t)2 * B * 10 * 8);
+    const size_t o_pval = take(with_prior ? Bh * 8 : 0);
     const size_t o_nok_log = take(defer ? n_launches * 4 : 0), o_table_log = take(defer ? n_launches * half * K * 8 : 0);
     const size_t o_chain = take(chain ? (size_t)n_steps * BW * P * 8 : 0);
     const size_t o_lnpc = take(lnprob_chain ? (size_t)n_steps * BW * 8 : 0);
@@ -150,6 +180,12 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     std::memcpy(a.h + o_fac, d->col_factor, (size_t)K * 8);
     std::memcpy(a.h + o_lo, d->lo, (size_t)P * 8);
     std::memcpy(a.h + o_hi, d->hi, (size_t)P * 8);
+    if (with_prior) {
+        std::memcpy(a.h + o_pkind, prior.kind, (size_t)P * 4);
+        std::memcpy(a.h + o_ploc, prior.loc, (size_t)P * 8);
+        std::memcpy(a.h + o_pscale, prior.scale, (size_t)P * 8);
+        std::memcpy(a.h + o_pc0, prior.c0, (size_t)P * 8);
+    }
     // Blocks that move tens of MB (binned catalogues: the random numbers of 64 steps of 55 x 512 walkers are 40 MB, their
     // chain rows 70 MB -- a third of the block's device time in copies) are cut into parts: the host copies and the PCIe
     // transfers of one part overlap the device work of another (copies on the second stream, joined by events).
@@ -210,6 +246,11 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     sd.proposal = (double*)(a.d + o_prop); sd.ok = (uint8_t*)(a.d + o_ok); sd.meta = (int32_t*)(a.d + o_meta);
     sd.n_ok = (int32_t*)(a.d + o_nok); sd.ranges = (double*)(a.d + o_ranges);
     sd.table = w.d_params; sd.wpar = (double*)w.d_wpar;
+    if (with_prior) {
+        sd.prior.kind = (const int32_t*)(a.d + o_pkind); sd.prior.loc = (const double*)(a.d + o_ploc);
+        sd.prior.scale = (const double*)(a.d + o_pscale); sd.prior.c0 = (const double*)(a.d + o_pc0);
+        sd.prior_val = (double*)(a.d + o_pval);
+    }
     if (defer) {
         sd.defer_guard = 1;
         sd.table_log = (double*)(a.d + o_table_log); sd.n_ok_log = (int32_t*)(a.d + o_nok_log); sd.level_log = (int32_t*)(a.d + o_levels);
@@ -437,7 +478,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
 // common part of mcd_stretch_move / mcd_stretch_move_seeded: argument checks, the resident block, else the host-driven one
 int run_stretch(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,
                 const int32_t* order, const double* zz, const double* thr, const int32_t* pick, double* chain,
-                double* lnprob_chain, int64_t* accepted, const uint64_t* seed, int64_t step0) {
+                double* lnprob_chain, int64_t* accepted, const uint64_t* seed, int64_t step0, const mcd_prior_desc* prior) {
     const char* who = seed ? "mcd_stretch_move_seeded" : "mcd_stretch_move";
     if (!cat || !d || !pos || !lnp) return fail(MCD_ERR_INVALID, std::string(who) + ": null argument");
     if (!seed && (!order || !zz || !thr || !pick)) return fail(MCD_ERR_INVALID, std::string(who) + ": null argument");
@@ -452,6 +493,8 @@ int run_stretch(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, do
     if (!d->col_source || !d->col_const || !d->col_factor || !d->lo || !d->hi) return fail(MCD_ERR_INVALID, std::string(who) + ": null descriptor array");
     for (int c = 0; c < d->k; ++c)
         if (d->col_source[c] >= d->n_dim) return fail(MCD_ERR_INVALID, std::string(who) + ": col_source outside the free parameters");
+    PriorHost ph;
+    if (int prc = prior_of(prior, d->n_dim, who, ph)) return prc;
     const int64_t W = d->n_walkers, half = W / 2;
     if (!seed) {
         // (range checks as min / max reductions: branch-free, vectorised -- a binned block holds millions of indices)
@@ -467,9 +510,10 @@ int run_stretch(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, do
     sd.n_bins = B;
     sd.n_walkers = W; sd.n_dim = d->n_dim; sd.k = d->k; sd.col_source = d->col_source; sd.col_const = d->col_const;
     sd.col_factor = d->col_factor; sd.lo = d->lo; sd.hi = d->hi; sd.fixed_ok = d->fixed_ok;
+    sd.prior = ph.table;
     bool done = false;
     const int dev_rc = stretch_block_device(cat, d, n_steps, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted, &done,
-                                            seed, step0);
+                                            ph.table, seed, step0);
     if (dev_rc != MCD_OK) return dev_rc;
     if (done) return MCD_OK;
     ++cat->chain_host_blocks;
@@ -496,7 +540,7 @@ int run_stretch(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, do
         }
     }
     if (rc == mcd::STRETCH_EVAL_FAILED) return eval_rc;                  // message already set by mcd_loglike_batch
-    if (rc == mcd::STRETCH_NAN) return fail(MCD_ERR_NONFINITE, std::string(who) + ": the log-likelihood returned NaN");
+    if (rc == mcd::STRETCH_NAN) return fail(MCD_ERR_NONFINITE, std::string(who) + ": the log-probability returned NaN");
     if (rc != mcd::STRETCH_OK) return fail(MCD_ERR_INVALID, std::string(who) + ": bad arguments");
     return MCD_OK;
 }
@@ -528,7 +572,7 @@ int hmc_block_device(mcd_catalog* cat, const mcd::HmcShared& hs, int64_t W, int6
     int rc = mcd_loglike_grad_batch(cat, W, K, table.data(), ll.data(), gcols.data());
     if (rc != MCD_OK) return rc;
     if (mcd::hmc_start(hs, W, pos, ll.data(), gcols.data(), lnp0.data(), grad.data()) != mcd::HMC_OK)
-        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior box or with a non-finite log-likelihood or gradient");
+        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior or with a non-finite log-likelihood or gradient");
     Shard& sh = cat->shards[0];
     const DeviceSlot& slot = ctx->slots[sh.slot];
     MCD_HIP(hipSetDevice(slot.device));
@@ -545,6 +589,9 @@ int hmc_block_device(mcd_catalog* cat, const mcd::HmcShared& hs, int64_t W, int6
     const size_t state_end = off;
     const size_t o_src = take((size_t)K * 4), o_const = take((size_t)K * 8), o_fac = take((size_t)K * 8);
     const size_t o_lo = take((size_t)P * 8), o_hi = take((size_t)P * 8), o_chol = take((size_t)P * P * 8);
+    const bool with_prior = hs.prior.any();
+    const size_t o_pkind = take(with_prior ? (size_t)P * 4 : 0), o_ploc = take(with_prior ? (size_t)P * 8 : 0);
+    const size_t o_pscale = take(with_prior ? (size_t)P * 8 : 0), o_pc0 = take(with_prior ? (size_t)P * 8 : 0);
     const size_t input_end = off;
     const size_t o_q = take(WP * 8), o_p = take(WP * 8), o_h0 = take((size_t)W * 8), o_eps = take((size_t)W * 8);
     const size_t o_alive = take((size_t)W * 4);
@@ -579,12 +626,22 @@ int hmc_block_device(mcd_catalog* cat, const mcd::HmcShared& hs, int64_t W, int6
     std::memcpy(a.h + o_lo, hs.lo, (size_t)P * 8);
     std::memcpy(a.h + o_hi, hs.hi, (size_t)P * 8);
     std::memcpy(a.h + o_chol, hs.chol, (size_t)P * P * 8);
+    if (with_prior) {
+        std::memcpy(a.h + o_pkind, hs.prior.kind, (size_t)P * 4);
+        std::memcpy(a.h + o_ploc, hs.prior.loc, (size_t)P * 8);
+        std::memcpy(a.h + o_pscale, hs.prior.scale, (size_t)P * 8);
+        std::memcpy(a.h + o_pc0, hs.prior.c0, (size_t)P * 8);
+    }
 
     mcd::HmcDevice hd;
     hd.s = hs;
     hd.s.col_source = (const int32_t*)(a.d + o_src); hd.s.col_const = (const double*)(a.d + o_const);
     hd.s.col_factor = (const double*)(a.d + o_fac); hd.s.lo = (const double*)(a.d + o_lo); hd.s.hi = (const double*)(a.d + o_hi);
     hd.s.chol = (const double*)(a.d + o_chol);
+    if (with_prior) {
+        hd.s.prior.kind = (const int32_t*)(a.d + o_pkind); hd.s.prior.loc = (const double*)(a.d + o_ploc);
+        hd.s.prior.scale = (const double*)(a.d + o_pscale); hd.s.prior.c0 = (const double*)(a.d + o_pc0);
+    }
     hd.n_walkers = W; hd.seed = seed;
     hd.pos = (double*)(a.d + o_pos); hd.lnp = (double*)(a.d + o_lnp); hd.grad = (double*)(a.d + o_grad);
     hd.accepted = (long long*)(a.d + o_acc);
@@ -631,7 +688,7 @@ int hmc_block_device(mcd_catalog* cat, const mcd::HmcShared& hs, int64_t W, int6
 }
 
 int run_hmc(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* pos, double* lnp, uint64_t seed, int64_t step0,
-            double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error) {
+            double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error, const mcd_prior_desc* prior) {
     if (!cat || !d || !pos || !lnp) return fail(MCD_ERR_INVALID, "mcd_hmc_block: null argument");
     if (int urc = ctx_usable(cat->ctx)) return urc;
     const mcd_stretch_desc& m = d->map;
@@ -649,6 +706,9 @@ int run_hmc(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* po
     hs.lo = m.lo; hs.hi = m.hi; hs.chol = d->chol; hs.fixed_ok = m.fixed_ok; hs.n_leap = d->n_leap;
     hs.step_size = d->step_size; hs.jitter = d->jitter;
     hs.diagonal = mcd::hmc_is_diagonal(d->chol, m.n_dim) ? 1 : 0;
+    PriorHost ph;
+    if (int prc = prior_of(prior, m.n_dim, "mcd_hmc_block", ph)) return prc;
+    hs.prior = ph.table;
     if (!mcd::hmc_args_ok(hs, m.n_walkers))
         return fail(MCD_ERR_INVALID, "mcd_hmc_block: step_size > 0, 0 <= jitter < 1, n_leap >= 1 and a finite lower-triangular chol with a positive diagonal");
     const int64_t W = m.n_walkers;
@@ -669,7 +729,7 @@ int run_hmc(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* po
                                   });
     if (rc == mcd::HMC_EVAL_FAILED) return eval_rc;                      // message already set
     if (rc == mcd::HMC_NONFINITE)
-        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior box or with a non-finite log-likelihood or gradient");
+        return fail(MCD_ERR_NONFINITE, "mcd_hmc_block: a walker starts outside the prior or with a non-finite log-likelihood or gradient");
     if (rc != mcd::HMC_OK) return fail(MCD_ERR_INVALID, "mcd_hmc_block: bad arguments");
     return MCD_OK;
 }
@@ -682,15 +742,51 @@ int mcd_stretch_move(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_step
                      const int32_t* order, const double* zz, const double* thr, const int32_t* pick, double* chain,
                      double* lnprob_chain, int64_t* accepted) {
     try {
-    return run_stretch(cat, d, n_steps, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted, nullptr, 0);
+    return run_stretch(cat, d, n_steps, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted, nullptr, 0, nullptr);
     } catch (...) { return on_exception("mcd_stretch_move"); }
+}
+
+int mcd_stretch_move_prior(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,
+                           const int32_t* order, const double* zz, const double* thr, const int32_t* pick, double* chain,
+                           double* lnprob_chain, int64_t* accepted, const mcd_prior_desc* prior) {
+    try {
+    return run_stretch(cat, d, n_steps, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted, nullptr, 0, prior);
+    } catch (...) { return on_exception("mcd_stretch_move_prior"); }
 }
 
 int mcd_stretch_move_seeded(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,
                             uint64_t seed, int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted) {
     try {
-    return run_stretch(cat, d, n_steps, pos, lnp, nullptr, nullptr, nullptr, nullptr, chain, lnprob_chain, accepted, &seed, step0);
+    return run_stretch(cat, d, n_steps, pos, lnp, nullptr, nullptr, nullptr, nullptr, chain, lnprob_chain, accepted, &seed, step0,
+                       nullptr);
     } catch (...) { return on_exception("mcd_stretch_move_seeded"); }
+}
+
+int mcd_stretch_move_seeded_prior(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,
+                                  uint64_t seed, int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted,
+                                  const mcd_prior_desc* prior) {
+    try {
+    return run_stretch(cat, d, n_steps, pos, lnp, nullptr, nullptr, nullptr, nullptr, chain, lnprob_chain, accepted, &seed, step0,
+                       prior);
+    } catch (...) { return on_exception("mcd_stretch_move_seeded_prior"); }
+}
+
+int mcd_prior_eval(const mcd_prior_desc* prior, int64_t n_rows, const double* x, double* value, double* grad) {
+    try {
+    if (!prior || n_rows < 0 || (n_rows > 0 && (!x || !value))) return fail(MCD_ERR_INVALID, "mcd_prior_eval: null argument");
+    PriorHost ph;
+    if (int prc = prior_of(prior, prior->n_dim, "mcd_prior_eval", ph)) return prc;
+    const int P = prior->n_dim;
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const double* row = x + r * P;
+        double* g = grad ? grad + r * P : nullptr;
+        if (g) for (int c = 0; c < P; ++c) g[c] = 0.0;
+        if (!ph.table.any()) { value[r] = 0.0; continue; }
+        if (!mcd::prior_row_inside(ph.table, P, row)) { value[r] = -INFINITY; continue; }
+        value[r] = g ? mcd::prior_row_grad(ph.table, P, row, g) : mcd::prior_row(ph.table, P, row);
+    }
+    return MCD_OK;
+    } catch (...) { return on_exception("mcd_prior_eval"); }
 }
 
 int mcd_chain_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_bins, int64_t n_walkers, int32_t n_dim,
@@ -711,8 +807,16 @@ int mcd_chain_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_b
 int mcd_hmc_block(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
                   int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error) {
     try {
-    return run_hmc(cat, d, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error);
+    return run_hmc(cat, d, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error, nullptr);
     } catch (...) { return on_exception("mcd_hmc_block"); }
+}
+
+int mcd_hmc_block_prior(mcd_catalog* cat, const mcd_hmc_desc* d, int64_t n_steps, double* pos, double* lnp, uint64_t seed,
+                        int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted, double* energy_error,
+                        const mcd_prior_desc* prior) {
+    try {
+    return run_hmc(cat, d, n_steps, pos, lnp, seed, step0, chain, lnprob_chain, accepted, energy_error, prior);
+    } catch (...) { return on_exception("mcd_hmc_block_prior"); }
 }
 
 int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_walkers, int32_t n_dim, double* z, double* thr,

@@ -20,7 +20,11 @@
 //             a trajectory that leaves the box is ENDED and its proposal rejected.  That is the Metropolis rule for a
 //             target that is zero outside the box: the proposal map stays the reversible, volume-preserving leapfrog, only
 //             its acceptance probability is zero there.  Detailed balance holds either way.
-//   accept    iff thr < H0 - H1, H = -lnlike + kinetic (inside the box the priors are flat: lnprob = lnlike)
+//   accept    iff thr < H0 - H1, H = -(lnlike + lnprior) + kinetic
+//   priors    the structured priors of mcd_prior.h (HmcShared::prior; none: lnprior = 0 inside the box): their value is added
+//             to the log-likelihood and their derivative to the chain rule's result at every evaluated point.  A log-normal
+//             coordinate <= 0 on a trajectory is a non-finite value: the proposal is rejected; at the block's start it is
+//             HMC_NONFINITE like a walker outside the box
 //   rejected  also: a non-finite lnlike or gradient at any leapfrog point (a divergent trajectory), and everything when
 //             fixed_ok == 0 (a fixed parameter violates its own bounds: every lnprob is -inf, as in the stretch move)
 // A rejected trajectory keeps being "evaluated" at its start point (the launch needs a valid row for every walker) and
@@ -29,6 +33,7 @@
 
 #include <cstdint>
 
+#include "mcd_prior.h"
 #include "mcd_rng.h"
 
 namespace mcd {
@@ -86,6 +91,7 @@ struct HmcShared {
     int32_t diagonal = 1;                      // hmc_is_diagonal(chol): reflection; 0: leaving the box ends the trajectory
     int32_t n_leap = 1;
     double step_size = 0.0, jitter = 0.0;
+    PriorTable prior;                          // structured priors of the free parameters, or none
 };
 
 inline bool hmc_is_diagonal(const double* chol, int P) {
@@ -185,7 +191,7 @@ MCD_HD void hmc_kick(const HmcShared& s, double eps, const double* g, double* p)
 
 // Start of a step: momenta, H0, the step size, the first half kick and the first drift; row = the kernel row to evaluate
 // next (the start point's when the trajectory has already ended).  pos / lnp / grad: the walker's current point, its
-// log-likelihood and its free-parameter gradient (all finite: the block checked its starting point).
+// log-probability (likelihood plus prior) and its free-parameter gradient (all finite: the block checked its starting point).
 MCD_HD void hmc_begin(const HmcShared& s, uint64_t seed, int64_t step, int64_t walker, const double* pos, double lnp,
                       const double* grad, HmcWalker t, double* row) {
     const int P = s.n_dim;
@@ -208,7 +214,8 @@ MCD_HD void hmc_begin(const HmcShared& s, uint64_t seed, int64_t step, int64_t w
 // What the last point of a trajectory leaves behind.
 struct HmcOutcome { bool accepted; double energy_error; };
 
-// Leapfrog point `leap` (1 .. n_leap) has been evaluated: l = lnlike at t.q, gcol the K column derivatives there.
+// Leapfrog point `leap` (1 .. n_leap) has been evaluated: l = lnlike at t.q, gcol the K column derivatives there (the
+// prior's value and derivative at t.q are added here).
 //   leap < n_leap : full kick, drift, row = the next point
 //   leap == n_leap: half kick, H1, accept / reject: pos, *lnp, grad take the new point when accepted; row is not written.
 // energy_error = |H1 - H0|, +inf for a trajectory that ended early.
@@ -221,6 +228,10 @@ MCD_HD HmcOutcome hmc_leap(const HmcShared& s, uint64_t seed, int64_t step, int6
     if (alive) {
         const bool ok = hmc_chain_rule(s, gcol, stride, g);
         if (!ok || !hmc_finite(l)) alive = 0;                      // a divergent trajectory is a rejection
+        if (alive && s.prior.any()) {
+            if (prior_row_inside(s.prior, s.n_dim, t.q)) l += prior_row_grad(s.prior, s.n_dim, t.q, g);
+            else alive = 0;                                        // a log-normal coordinate <= 0: lnprior = -inf
+        }
     }
     if (leap < s.n_leap) {
         if (alive) {
@@ -262,8 +273,9 @@ inline bool hmc_args_ok(const HmcShared& s, int64_t W) {
     return true;
 }
 
-// The block's starting point: table [W][K] of pos, and after the evaluation lnp [W] and the free-parameter gradients
-// [W][P].  HMC_NONFINITE: a walker starts outside the box, or with a non-finite value or gradient.  (With fixed_ok == 0
+// The block's starting point: table [W][K] of pos, and after the evaluation lnp [W] (likelihood plus prior) and the
+// free-parameter gradients [W][P].  HMC_NONFINITE: a walker starts outside the box or on a log-normal coordinate <= 0, or
+// with a non-finite value or gradient.  (With fixed_ok == 0
 // nothing is ever accepted and nothing needs to be finite.)
 inline int hmc_start(const HmcShared& s, int64_t W, const double* pos, const double* ll, const double* gcols, double* lnp,
                      double* grad) {
@@ -271,8 +283,10 @@ inline int hmc_start(const HmcShared& s, int64_t W, const double* pos, const dou
     for (int64_t w = 0; w < W; ++w) {
         bool ok = hmc_chain_rule(s, gcols + w * K, 1, grad + w * P) && hmc_finite(ll[w]);
         for (int c = 0; c < P; ++c) ok = ok && pos[w * P + c] >= s.lo[c] && pos[w * P + c] <= s.hi[c];
+        if (ok && s.prior.any()) ok = prior_row_inside(s.prior, P, pos + w * P);
         if (!ok && s.fixed_ok) return HMC_NONFINITE;
         lnp[w] = ll[w];
+        if (ok && s.prior.any()) lnp[w] = ll[w] + prior_row_grad(s.prior, P, pos + w * P, grad + w * P);
     }
     return HMC_OK;
 }

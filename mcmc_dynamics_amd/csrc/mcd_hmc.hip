@@ -8,7 +8,8 @@
 //                      on the trajectory's last point half kick, accept / reject, and the step's chain rows
 //
 // One thread per walker: a handful of float64 operations over P <= 12 coordinates, plain C++ on per-walker rows
-// (mcd_launch.h's workgroup of 256 threads, wave64; no LDS, no atomics, vector stores only).  Built with
+// (mcd_launch.h's workgroup of 256 threads, wave64; no LDS, no atomics, vector stores only).  Structured priors
+// (mcd_prior.h) arrive through HmcShared::prior and the shared hmc_* functions; nothing here names them.  Built with
 // -ffp-contract=off like the host: the chain is the host-driven block's bit for bit.
 #include "mcd_internal.h"
 #include "mcd_launch.h"

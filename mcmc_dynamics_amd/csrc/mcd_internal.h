@@ -7,6 +7,7 @@
 #include "mcd_chunks.h"   // Chunk, chunk-table planning (host-only, shared with the CPU tests)
 #include "mcd_guard.h"    // StatsScalars: the range guard's catalogue statistics travel to the device by value
 #include "mcd_launch.h"   // kWave, kBlock, padded_walkers: the launch vocabulary of the device units
+#include "mcd_prior.h"    // PriorTable: the structured priors of a resident block
 
 namespace mcd {
 
@@ -117,6 +118,11 @@ struct StretchDevice {
     const double* col_factor = nullptr;    // [k]
     const double* lo = nullptr;            // [P]
     const double* hi = nullptr;            // [P]
+    // structured priors (mcd_prior.h), or none: the kernels are instantiated with and without them, and a block without
+    // priors runs the instantiation that knows nothing of these two members
+    PriorTable prior;                      // [P] each, shared by the ensembles like the bounds
+    double* prior_val = nullptr;           // [B][W/2] log-prior of each proposal inside the prior (written when proposed,
+                                           // added to the reduced sum when accepted)
     double* pos = nullptr;                 // [W][P]  ensemble, updated in place
     double* lnp = nullptr;                 // [W]
     long long* accepted = nullptr;         // [W]

@@ -1,7 +1,9 @@
 // mcd_stretch.h -- host-only: one block of affine-invariant stretch-move steps (Goodman & Weare 2010, the default move of
 // emcee's EnsembleSampler that the reference hands Runner.lnprob to, analysis/runner.py:403-419) with the per-half-step
 // host work in C++: proposals from the complementary half of the ensemble, the box prior of Runner.lnprior
-// (runner.py:182-217: inclusive bounds, NaN outside), the resolved kernel parameter table, accept / reject.  Between two
+// (runner.py:182-217: inclusive bounds, NaN outside) with the structured priors of mcd_prior.h on top of it (a proposal
+// is inside the prior when it is inside the box and every log-normal coordinate is > 0; its log-probability is the
+// log-likelihood plus the log-prior), the resolved kernel parameter table, accept / reject.  Between two
 // kernel launches the host then spends a few microseconds instead of ~50 us of NumPy.
 //
 // Every random number comes from the caller, in the layout mcmc_dynamics_amd/sampler.py draws them, and the arithmetic is
@@ -13,6 +15,8 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
+
+#include "mcd_prior.h"
 
 namespace mcd {
 
@@ -27,6 +31,7 @@ struct StretchDesc {
     const double* lo = nullptr;            // [P] inclusive lower prior bounds (-inf: none)
     const double* hi = nullptr;            // [P] inclusive upper prior bounds
     int32_t fixed_ok = 1;                  // 0: a fixed parameter violates its own bounds, every lnprob is -inf (runner.py:207-214)
+    PriorTable prior;                      // structured priors of the free parameters (mcd_prior.h), or none
 };
 
 enum StretchStatus : int { STRETCH_OK = 0, STRETCH_NAN = 1, STRETCH_EVAL_FAILED = 2, STRETCH_BAD_ARGS = 3 };
@@ -66,6 +71,8 @@ int stretch_block(const StretchDesc& d, int64_t n_steps, double* pos, double* ln
                         p[c] = q[c] - (q[c] - s[c]) * z[j];
                         good = good && (p[c] >= d.lo[c]) && (p[c] <= d.hi[c]);        // false for NaN as well
                     }
+                    if (d.prior.any()) good = good && prior_row_inside(d.prior, P, p);   // a log-normal coordinate <= 0
+
                     ok[b * half + j] = good;
                     if (good) { ++n_ok; if (donor < 0) donor = b * half + j; }
                 }
@@ -85,6 +92,7 @@ int stretch_block(const StretchDesc& d, int64_t n_steps, double* pos, double* ln
             }
             for (int64_t r = 0; r < rows; ++r) {
                 new_lnp[r] = (n_ok > 0 && ok[r]) ? ll[r] : -INFINITY;
+                if (d.prior.any() && n_ok > 0 && ok[r]) new_lnp[r] = ll[r] + prior_row(d.prior, P, proposal.data() + r * P);
                 if (new_lnp[r] != new_lnp[r]) return STRETCH_NAN;                 // "Probability function returned NaN"
             }
             // accept iff thr < new_lnp - old_lnp   (thr = log(u) - (P - 1) log(z), drawn by the caller)

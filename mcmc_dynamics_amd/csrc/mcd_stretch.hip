@@ -21,6 +21,7 @@
 #include "mcd_guard.h"
 #include "mcd_math.h"
 #include "mcd_prep.h"
+#include "mcd_prior.h"
 #include "mcd_reduce.h"
 #include "mcd_rng.h"
 
@@ -76,6 +77,10 @@ __device__ __forceinline__ ParamRanges load_ranges(const double* o) {
 
 // One workgroup.  acc_step >= 0: accept / reject half step (acc_step, acc_h) from the sums `ll` (written by the reduction
 // [+ all-reduce] that precedes this launch on the stream).  prop_step >= 0: propose half step (prop_step, prop_h).
+// kPrior: the block has structured priors (mcd_prior.h) -- a proposal's log-prior is evaluated when it is proposed, kept in
+// d.prior_val and added to the reduced sum when the proposal is accepted or rejected; a log-normal coordinate <= 0 counts
+// as outside the prior.  Without priors the instantiation is the kernel as it was.
+template <bool kPrior>
 __global__ __launch_bounds__(kStepBlock) void stretch_step_kernel(StretchDevice d, int64_t acc_step, int acc_h,
                                                                    int64_t prop_step, int prop_h,
                                                                    const double* __restrict__ ll, double rerun_tag) {
@@ -92,7 +97,8 @@ __global__ __launch_bounds__(kStepBlock) void stretch_step_kernel(StretchDevice 
         // single device: the fast mixture kernels write the launch's tag behind the sums when they want the plain kernels
         if (tid == 0 && rerun_tag != 0.0 && ll[half] == rerun_tag) atomicOr(&d.meta[META_STATUS], CHAIN_RERUN);
         for (int64_t j = tid; j < half; j += kStepBlock) {
-            const double new_lnp = (n_ok > 0 && d.ok[j]) ? ll[j] : -kInfinity;
+            double new_lnp = (n_ok > 0 && d.ok[j]) ? ll[j] : -kInfinity;
+            if constexpr (kPrior) { if (n_ok > 0 && d.ok[j]) new_lnp = ll[j] + d.prior_val[j]; }
             if (new_lnp != new_lnp) atomicOr(&d.meta[META_STATUS], CHAIN_NAN);   // genuine, or the multi-rank re-run signal
             const int64_t w = first[j];
             if (t[j] < new_lnp - d.lnp[w]) {                                     // accept iff thr < new_lnp - old_lnp
@@ -126,6 +132,10 @@ __global__ __launch_bounds__(kStepBlock) void stretch_step_kernel(StretchDevice 
             const double v = q[c] - (q[c] - s[c]) * z[j];
             p[c] = v;
             good = good && (v >= d.lo[c]) && (v <= d.hi[c]);
+        }
+        if constexpr (kPrior) {
+            good = good && prior_row_inside(d.prior, P, p);
+            d.prior_val[j] = good ? prior_row(d.prior, P, p) : 0.0;
         }
         d.ok[j] = good;
         if (good) { atomicAdd(&s_n_ok, 1); atomicMin(&s_donor, (int)j); }
@@ -187,13 +197,17 @@ __global__ __launch_bounds__(kStepBlock) void stretch_step_kernel(StretchDevice 
 constexpr int kSmallPosBytes = 32 << 10;
 
 extern __shared__ double s_dynamic[];     // [W * P] positions | [W] log-probabilities | [W / 2] int32: the partner half
+                                          // | kPrior: [kMaxCols] loc, scale, c0, int32 kind: the prior table
+constexpr size_t kPriorLdsBytes = 8 + 12 * (3 * 8 + 4);      // (what the launch adds for it, after rounding up to a double)
 
 // kFused: the kernel runs with kFusedThreads threads; all of its waves first add up the main kernel's partial sums of this
 // ensemble (one wave per group of 8 walkers at a time, the reduction kernel's own code and order: mcd_reduce.h) into LDS,
 // then the waves beyond the first kStepBlock threads leave and the step proceeds as below with the sums read from LDS.
 constexpr int kFusedThreads = 1024;
 
-template <int kMaxCols, bool kBinned, bool kFused>
+// kPrior: structured priors, as in the general kernel -- the table sits behind the ensemble in dynamic LDS, so the
+// instantiations without priors keep their code, their registers and their LDS.
+template <int kMaxCols, bool kBinned, bool kFused, bool kPrior>
 __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_step_small_kernel(
     StretchDevice d, int64_t acc_step, int acc_h, int64_t prop_step, int prop_h, const double* __restrict__ ll,
     double rerun_tag) {
@@ -230,6 +244,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
     double* const proposal_b = d.proposal + b * half * P;
     uint8_t* const ok_b = d.ok + b * half;
     const double* const ll_b = ll + b * half;
+    double* const prior_val_b = kPrior ? d.prior_val + b * half : nullptr;
     // n_ok and the guard's ranges are kept per half-step parity: workgroup 0 judges the PREVIOUS table of all ensembles
     // while the other workgroups already write the next one's
     const int64_t slot_acc = ((acc_step * 2 + acc_h) & 1) * B, slot_prop = ((prop_step * 2 + prop_h) & 1) * B;
@@ -243,6 +258,10 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
     double* const s_pos = s_dynamic;
     double* const s_lnp = s_dynamic + W * P;
     int* const s_second = reinterpret_cast<int*>(s_lnp + W);
+    double* const s_ploc = s_lnp + W + (half + 1) / 2;          // (kPrior only)
+    double* const s_pscale = s_ploc + kMaxCols;
+    double* const s_pc0 = s_pscale + kMaxCols;
+    int* const s_pkind = reinterpret_cast<int*>(s_pc0 + kMaxCols);
 
     MCD_STAMP(0);
     // ---- the one round of loads: nothing here depends on this kernel's own stores ----
@@ -269,7 +288,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
     }
     int n_ok_prev = 0, w_acc = 0;
     bool ok_prev = false;
-    double ll_j = 0.0, thr_j = 0.0, flag_word = 0.0;
+    double ll_j = 0.0, thr_j = 0.0, flag_word = 0.0, prior_prev = 0.0;
     double prev[kMaxCols];
     if (do_acc) {
         n_ok_prev = d.n_ok[slot_acc + b];
@@ -277,6 +296,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
         if (active) {
             ok_prev = ok_b[j] != 0;
             if constexpr (!kFused) ll_j = ll_b[j];
+            if constexpr (kPrior) prior_prev = prior_val_b[j];
             w_acc = d.order[(acc_step * B + b) * W + (acc_h == 0 ? 0 : half) + j];
             thr_j = d.thr[((acc_step * 2 + acc_h) * B + b) * half + j];
 #pragma unroll
@@ -306,6 +326,12 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
         s_source[j] = j < K ? d.col_source[j] : -1;
         s_const[j] = j < K ? d.col_const[j] : 0.0;
         s_factor[j] = j < K ? d.col_factor[j] : 1.0;
+        if constexpr (kPrior) {
+            s_pkind[j] = j < P ? d.prior.kind[j] : (int)PRIOR_FLAT;
+            s_ploc[j] = j < P ? d.prior.loc[j] : 0.0;
+            s_pscale[j] = j < P ? d.prior.scale[j] : 0.0;
+            s_pc0[j] = j < P ? d.prior.c0[j] : 0.0;
+        }
     }
     __syncthreads();
     MCD_STAMP(1);
@@ -340,7 +366,8 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
             __syncthreads();                           // (s_ranges is used again by the propose phase)
         }
         if (active) {
-            const double new_lnp = (n_ok_prev > 0 && ok_prev) ? ll_j : -kInfinity;
+            double new_lnp = (n_ok_prev > 0 && ok_prev) ? ll_j : -kInfinity;
+            if constexpr (kPrior) { if (n_ok_prev > 0 && ok_prev) new_lnp = ll_j + prior_prev; }
             if (new_lnp != new_lnp) atomicOr(&d.meta[META_STATUS], CHAIN_NAN);
             if (thr_j < new_lnp - s_lnp[w_acc]) {
 #pragma unroll
@@ -373,9 +400,20 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
                 mine_prop[c] = v;
                 proposal_b[j * P + c] = v;
                 good = good && (v >= s_lo[c]) && (v <= s_hi[c]);
+                if constexpr (kPrior) good = good && prior_inside(s_pkind[c], v);
             } else {
                 mine_prop[c] = 0.0;
             }
+        }
+        if constexpr (kPrior) {
+            // the proposal's log-prior: mcd_prior.h's terms in ascending coordinate order, as prior_row adds them
+            double sum = 0.0;
+            if (good) {
+#pragma unroll
+                for (int c = 0; c < kMaxCols; ++c)
+                    if (c < P && s_pkind[c] != PRIOR_FLAT) sum += prior_term(s_pkind[c], s_ploc[c], s_pscale[c], s_pc0[c], mine_prop[c]);
+            }
+            prior_val_b[j] = sum;
         }
         ok_b[j] = good;
     }
@@ -564,18 +602,25 @@ bool stretch_step_fuses(const StretchDevice& d) { return small_step(d); }
 hipError_t launch_stretch_step(hipStream_t s, const StretchDevice& d, int64_t acc_step, int acc_h, int64_t prop_step,
                                int prop_h, const double* ll, double rerun_tag) {
     const size_t pos_bytes = (size_t)d.n_walkers * d.n_dim * sizeof(double);
-    const size_t lds = pos_bytes + (size_t)d.n_walkers * sizeof(double) + (size_t)(d.n_walkers / 2) * sizeof(int32_t);
+    const bool prior = d.prior.any();
+    if (prior && !d.prior_val) return hipErrorInvalidValue;
+    const size_t lds = pos_bytes + (size_t)d.n_walkers * sizeof(double) + (size_t)(d.n_walkers / 2) * sizeof(int32_t) +
+                       (prior ? kPriorLdsBytes : 0);
     const int cols = d.k > d.n_dim ? d.k : d.n_dim;
     const bool small = small_step(d);
     if (!small && d.n_bins != 1) return hipErrorInvalidValue;
+#define MCD_LAUNCH_SMALL_(C, BINNED, PRIOR)                                                                                    \
+    do {                                                                                                                        \
+        if (d.fused)                                                                                                            \
+            hipLaunchKernelGGL((stretch_step_small_kernel<C, BINNED, true, PRIOR>), dim3((unsigned)d.n_bins),                   \
+                               dim3(kFusedThreads), lds, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);              \
+        else                                                                                                                    \
+            hipLaunchKernelGGL((stretch_step_small_kernel<C, BINNED, false, PRIOR>), dim3((unsigned)d.n_bins),                  \
+                               dim3(kStepBlock), lds, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);                 \
+    } while (0)
 #define MCD_LAUNCH_SMALL(C, BINNED)                                                                                            \
     do {                                                                                                                       \
-        if (d.fused)                                                                                                           \
-            hipLaunchKernelGGL((stretch_step_small_kernel<C, BINNED, true>), dim3((unsigned)d.n_bins), dim3(kFusedThreads),    \
-                               lds, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);                                  \
-        else                                                                                                                   \
-            hipLaunchKernelGGL((stretch_step_small_kernel<C, BINNED, false>), dim3((unsigned)d.n_bins), dim3(kStepBlock), lds, \
-                               s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);                                       \
+        if (prior) MCD_LAUNCH_SMALL_(C, BINNED, true); else MCD_LAUNCH_SMALL_(C, BINNED, false);                               \
     } while (0)
     if ((d.fused || d.defer_guard) && (!small || (d.defer_guard && d.n_bins != 1))) return hipErrorInvalidValue;
     const bool binned = d.n_bins > 1;
@@ -583,8 +628,11 @@ hipError_t launch_stretch_step(hipStream_t s, const StretchDevice& d, int64_t ac
     else if (small && cols <= 8) { if (binned) MCD_LAUNCH_SMALL(8, true); else MCD_LAUNCH_SMALL(8, false); }
     else if (small) { if (binned) MCD_LAUNCH_SMALL(12, true); else MCD_LAUNCH_SMALL(12, false); }
 #undef MCD_LAUNCH_SMALL
+#undef MCD_LAUNCH_SMALL_
+    else if (prior)
+        hipLaunchKernelGGL(stretch_step_kernel<true>, dim3(1), dim3(kStepBlock), 0, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);
     else
-        hipLaunchKernelGGL(stretch_step_kernel, dim3(1), dim3(kStepBlock), 0, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);
+        hipLaunchKernelGGL(stretch_step_kernel<false>, dim3(1), dim3(kStepBlock), 0, s, d, acc_step, acc_h, prop_step, prop_h, ll, rerun_tag);
     return hipGetLastError();
 }
 

@@ -24,6 +24,44 @@ logger = logging.getLogger(__name__)
 
 _STATE_FIELDS = ("name", "value", "unit", "fixed", "min", "max", "label", "initials", "lnprior", "user_data", "expr")
 
+# Structured priors (``Parameter.prior``): the closed set the library evaluates on the device (csrc/mcd_prior.h), at the full
+# float64 value.  The reference writes priors as ``lnprior`` expressions over scipy's norm / lognorm (parameter.py:64-74,
+# 684-705) and hands them the value rounded to six decimals; those keep working here, on the Python-loop drivers only.
+PRIOR_KINDS = {"normal": 1, "lognormal": 2}
+
+
+def check_prior(prior, minimum=-np.inf, name=""):
+    """None, or ``(kind, p0, p1)`` with kind 'normal' (loc, scale) / 'lognormal' (mu, s; scipy's ``lognorm(s,
+    scale=exp(mu))``) -> None or the normalised tuple.  ValueError for an unknown kind, non-finite values, a scale <= 0, or a
+    log-normal prior on a parameter whose lower bound is negative."""
+    if prior is None:
+        return None
+    try:
+        kind, p0, p1 = prior
+        kind, p0, p1 = str(kind), float(p0), float(p1)
+    except (TypeError, ValueError):
+        raise ValueError("prior of parameter '{0}' must be None or (kind, p0, p1), got {1!r}".format(name, prior))
+    if kind not in PRIOR_KINDS:
+        raise ValueError("prior of parameter '{0}': unknown kind '{1}' (known: {2})".format(name, kind, sorted(PRIOR_KINDS)))
+    if not (np.isfinite(p0) and np.isfinite(p1)):
+        raise ValueError("prior of parameter '{0}': non-finite value in {1!r}".format(name, prior))
+    if not p1 > 0.0:
+        raise ValueError("prior of parameter '{0}': the scale must be positive, got {1}".format(name, p1))
+    if kind == "lognormal" and not minimum >= 0.0:
+        raise ValueError("prior of parameter '{0}': a log-normal prior needs min >= 0 (min is {1})".format(name, minimum))
+    return (kind, p0, p1)
+
+
+def prior_arrays(priors):
+    """List of ``Parameter.prior`` values -> the (kind int32, p0, p1) arrays ``_native.prior_eval`` and the library's
+    ``*_prior`` entry points take, or None when every entry is None."""
+    if all(p is None for p in priors):
+        return None
+    kind = np.array([0 if p is None else PRIOR_KINDS[p[0]] for p in priors], dtype=np.int32)
+    p0 = np.array([0.0 if p is None else p[1] for p in priors], dtype=np.float64)
+    p1 = np.array([1.0 if p is None else p[2] for p in priors], dtype=np.float64)
+    return kind, p0, p1
+
 
 def _expression_namespace():
     ns = {}
@@ -159,7 +197,7 @@ class Parameter(object):
     """One model parameter (reference: parameter.py:558-1007)."""
 
     def __init__(self, name, value=None, unit=None, fixed=False, min=-np.inf, max=np.inf, label=None,
-                 initials=None, lnprior=None, expr=None, user_data=None):
+                 initials=None, lnprior=None, expr=None, user_data=None, prior=None):
         self.name = name
         self.fixed = bool(fixed)
         self.min = min
@@ -171,6 +209,7 @@ class Parameter(object):
         self._eval = None            # set by Parameters.__setitem__
         self._initials = None
         self._lnprior = None
+        self._prior = None
         self._expr = None
         self._codes = {}
         self._set_unit(unit)
@@ -179,10 +218,13 @@ class Parameter(object):
         self.initials = initials
         self.lnprior = lnprior
         self.expr = expr
+        if prior is None and isinstance(user_data, dict) and user_data.get("prior") is not None:
+            prior = user_data["prior"]           # how a structured prior travels through the reference's file format
+        self.prior = prior
 
     # ------------------------------------------------------------------ attribute plumbing
     def set(self, value=None, unit=None, fixed=None, min=None, max=None, label=None, initials=None, lnprior=None,
-            expr=None):
+            expr=None, prior=None):
         """Update selected attributes (reference: parameter.py:589-619)."""
         if unit is not None:
             self._set_unit(unit)
@@ -203,6 +245,10 @@ class Parameter(object):
             self.expr = expr
         if label is not None:
             self._label = label
+        if prior is not None:
+            self.prior = prior
+        else:
+            check_prior(self._prior, self.min, self.name)        # (the bounds may have changed under a log-normal prior)
 
     def _set_unit(self, unit):
         name = units.unit_name(unit)
@@ -279,8 +325,25 @@ class Parameter(object):
 
     @lnprior.setter
     def lnprior(self, val):
+        if val and self._prior is not None:
+            raise ValueError("parameter '{0}' has a structured prior: it cannot have an lnprior expression as well".format(self.name))
         self._lnprior = val or None
         self._code("lnprior", self._lnprior)
+
+    @property
+    def prior(self):
+        """Structured prior on top of the bounds: None (flat), ``("normal", loc, scale)`` or ``("lognormal", mu, s)``
+        (``check_prior``), in the parameter's own unit.  The un-truncated log-density, evaluated at the full float64 value
+        by the library (csrc/mcd_prior.h) on host and device alike: every sampler, the gradients, ``maximize``, ``laplace``
+        and ``hmc`` take it.  Applies to a FREE parameter; on a fixed one it is a constant of the posterior and left out."""
+        return self._prior
+
+    @prior.setter
+    def prior(self, val):
+        val = check_prior(val, self.min, self.name)
+        if val is not None and self._lnprior is not None:
+            raise ValueError("parameter '{0}' has an lnprior expression: it cannot have a structured prior as well".format(self.name))
+        self._prior = val
 
     @property
     def expr(self):
@@ -324,6 +387,11 @@ class Parameter(object):
         val = float(units.to_unit(val, self.unit))
         if val < self.min or val > self.max:
             return -np.inf
+        if self._prior is not None:
+            if self.fixed:
+                return 0
+            from . import _native                  # the library's own bits: what lnprior_batch and the blocks add
+            return float(_native.prior_eval(prior_arrays([self._prior]), [[val]])[0])
         if self._lnprior is None:
             return 0
         if self._eval is None:
@@ -342,8 +410,15 @@ class Parameter(object):
         self._label = val
 
     def __getstate__(self):
+        # _STATE_FIELDS is the reference's file format and does not grow: a structured prior travels in user_data["prior"]
+        user_data = self.user_data
+        if self._prior is not None:
+            user_data = dict(user_data) if isinstance(user_data, dict) else ({} if user_data is None else {"user_data": user_data})
+            user_data["prior"] = list(self._prior)
+        elif isinstance(user_data, dict) and "prior" in user_data:
+            user_data = {k: v for k, v in user_data.items() if k != "prior"} or None
         return (self.name, self._value, self.unit, self.fixed, self.min, self.max, self._label, self._initials,
-                self._lnprior, self.user_data, self._expr)
+                self._lnprior, user_data, self._expr)
 
     @classmethod
     def from_state(cls, state):
@@ -363,6 +438,8 @@ class Parameter(object):
         for key in ("initials", "expr", "lnprior"):
             if getattr(self, "_" + key) is not None:
                 bits.append("{0}='{1}'".format(key, getattr(self, "_" + key)))
+        if self._prior is not None:
+            bits.append("prior={0!r}".format(self._prior))
         return "<Parameter '{0}', {1}>".format(self.name, ", ".join(bits))
 
 
@@ -390,12 +467,12 @@ class Parameters(OrderedDict):
         self._asteval.symtable[key] = par._value
 
     def add(self, name, value=None, unit=None, fixed=False, min=-np.inf, max=np.inf, label=None, initials=None,
-            lnprior=None, expr=None):
+            lnprior=None, expr=None, prior=None):
         if isinstance(name, Parameter):
             self[name.name] = name
         else:
             self[name] = Parameter(name, value=value, unit=unit, fixed=fixed, min=min, max=max, label=label,
-                                   initials=initials, lnprior=lnprior, expr=expr)
+                                   initials=initials, lnprior=lnprior, expr=expr, prior=prior)
 
     def add_many(self, *parlist):
         for par in parlist:
@@ -522,11 +599,21 @@ class Parameters(OrderedDict):
             pending = rest
         return OrderedDict((name, out[name]) for name in self)
 
+    def structured_prior(self):
+        """(kind, p0, p1) arrays over the FREE parameters in iteration order (``prior_arrays``), or None without one."""
+        return prior_arrays([p._prior for p in self.values() if not p.fixed])
+
     def lnprior_batch(self, resolved):
         """Vectorised ``Runner.lnprior``: sum of per-parameter priors, -inf outside inclusive bounds
-        (runner.py:206-217: every parameter is checked, fixed ones included)."""
+        (runner.py:206-217: every parameter is checked, fixed ones included).  Structured priors (``Parameter.prior``) are
+        added in one ``mcd_prior_eval`` call over all walkers."""
         w = len(next(iter(resolved.values()))) if resolved else 0
         total = np.zeros(w, dtype=np.float64)
+        structured = self.structured_prior()
+        if structured is not None and w:
+            from . import _native
+            free = np.stack([resolved[name] for name, par in self.items() if not par.fixed], axis=1)
+            total += _native.prior_eval(structured, free)          # (-inf where a log-normal coordinate is <= 0)
         for name, par in self.items():
             col = resolved[name]
             bad = (col < par.min) | (col > par.max) | np.isnan(col)
