@@ -215,6 +215,24 @@ int mcd_pointwise_posterior(mcd_catalog* cat, int64_t n_samples, int32_t k, cons
  * kernels of every tile, summed over the shards). */
 int mcd_psis_loo(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double r_eff,
                  double* elpd_loo, double* pareto_k, double* lppd, double* n_eff);
+/* Per-star posterior predictive checks over S posterior samples (params: row-major [S][K], the kernel columns of
+ * mcd_loglike_batch).  With d = v_i - v_los,is and n = verr_i^2 + sigma_los,is^2 of star i under sample s:
+ *   z = d / sqrt(n)   t = erfc(|z| / sqrt 2)   pit = Phi(z) (the cluster component's CDF at v_i)
+ * out[f][i], f < MCD_PRED_FIELDS: mean and standard deviation (S-1; 0 when S == 1) over the samples of z, the means of t
+ * (MCD_PRED_TAIL_P) and pit, mean and standard deviation of the model's v_los (v_sys included) and of sigma_los.
+ * pit_mix[i] (may be NULL; MODEL_BGGAUSS / MODEL_PROFILE_BGGAUSS only, MCD_ERR_INVALID for any other model): the mean of
+ * m pit + (1 - m) Phi((v_i - v_back) / sqrt(verr_i^2 + sigma_back^2)), m = density_i / (density_i + f_back), the CDF of
+ * the whole mixture at v_i.  A star whose term is not finite (sigma_los = 0 with verr = 0) gets non-finite outputs; that
+ * is no error and touches no other star.  Un-binned catalogues only; `out` must not be NULL; the arrays hold this
+ * process' n_stars; synchronous; an MCD_ERR_INVALID call leaves the outputs untouched.  float32 catalogues: terms in
+ * float, everything else in float64.  Samples reach the device in passes of "posterior_pass" rows; deterministic: no
+ * atomics, partial states of sample slices merged in a fixed order.  With option "timing" on, mcd_last_kernel_ms gives the
+ * HIP-event time of the kernels as for mcd_pointwise_posterior. */
+enum { MCD_PRED_Z_MEAN, MCD_PRED_Z_STD, MCD_PRED_TAIL_P, MCD_PRED_PIT,
+       MCD_PRED_VLOS_MEAN, MCD_PRED_VLOS_STD, MCD_PRED_SIGMA_MEAN, MCD_PRED_SIGMA_STD, MCD_PRED_FIELDS };
+int mcd_posterior_predictive(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params,
+                             double* out      /* [MCD_PRED_FIELDS][n_stars] */,
+                             double* pit_mix  /* [n_stars], or NULL */);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

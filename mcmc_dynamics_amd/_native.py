@@ -55,6 +55,8 @@ SYMBOLS = {
                                                _c_double_p, _c_double_p, _c_double_p]),
     "mcd_psis_loo": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_double,
                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_posterior_predictive": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p,
+                                                _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -525,6 +527,33 @@ class Catalog(object):
         out = {k: np.empty(self.n_stars, dtype=np.float64) for k in names}
         rc = self.lib.mcd_psis_loo(self.handle, p.shape[0], self.k, _ptr(p), float(r_eff), *[_ptr(out[k]) for k in names])
         _check(self.lib, rc, "mcd_psis_loo")
+        return out
+
+    PREDICTIVE_FIELDS = ("z_mean", "z_std", "tail_p", "pit", "vlos_mean", "vlos_std", "sigma_mean", "sigma_std")
+
+    def posterior_predictive(self, table, mixture=False):
+        """Per-star posterior predictive checks over S posterior samples: ``table`` (S, K) in the kernel's column order ->
+        dict of (n_stars,) arrays ``z_mean`` / ``z_std`` (standardised residual against the cluster component), ``tail_p``
+        (mean two-sided tail probability), ``pit`` (mean cluster-component CDF at v_i), ``vlos_mean`` / ``vlos_std`` and
+        ``sigma_mean`` / ``sigma_std`` (the model's v_los and sigma_los at the star), and with ``mixture`` (the two models
+        with a Gaussian background only) ``pit_mix``, the CDF of the whole mixture (include/mcd.h: mcd_posterior_predictive)."""
+        self._alive()
+        if self.n_sets > 1:
+            raise ValueError("posterior_predictive is defined for un-binned catalogues only")
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (S, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        block = np.empty((len(self.PREDICTIVE_FIELDS), self.n_stars), dtype=np.float64)
+        mix = np.empty(self.n_stars, dtype=np.float64) if mixture else None
+        rc = self.lib.mcd_posterior_predictive(self.handle, p.shape[0], self.k, _ptr(p), _ptr(block),
+                                               _ptr(mix) if mixture else None)
+        _check(self.lib, rc, "mcd_posterior_predictive")
+        out = {k: block[f] for f, k in enumerate(self.PREDICTIVE_FIELDS)}
+        if mixture:
+            out["pit_mix"] = mix
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

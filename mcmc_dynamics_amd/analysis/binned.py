@@ -246,6 +246,13 @@ class BinnedConstantFit(ConstantFit):
         raise NotImplementedError("BinnedConstantFit: per-star posterior summaries (pointwise_posterior, waic) are defined "
                                   "for un-binned fits only; fit the bins' stars with ConstantFit to compare models")
 
+    def posterior_predictive(self, chain, n_burn, thin=1):
+        raise NotImplementedError("BinnedConstantFit: per-star posterior predictive checks (posterior_predictive, ppc) are "
+                                  "defined for un-binned fits only; fit the bins' stars with ConstantFit to check the model")
+
+    def ppc(self, chain, n_burn, thin=1, n_bins=20, outlier_p=None):
+        return self.posterior_predictive(chain, n_burn, thin)
+
     def loo(self, chain, n_burn, thin=1, r_eff=1.0):
         raise NotImplementedError("BinnedConstantFit: PSIS-LOO is defined for un-binned fits only; fit the bins' stars "
                                   "with ConstantFit to compare models")

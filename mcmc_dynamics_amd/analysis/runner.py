@@ -185,6 +185,38 @@ def elpd_compare(a, b, group=None):
     return {"elpd_diff": s_d, "se_diff": float(np.sqrt(n * max(var_i, 0.0))), "n_stars": int(n), "pointwise": d}
 
 
+# the central interval of the PIT whose complement ``ppc_summary`` reports: 5 % of the weight for a calibrated model
+PPC_TAIL = 0.025
+
+
+def ppc_summary(pit, weights=None, n_bins=20, group=None):
+    """Calibration of a fitted model from its stars' probability integral transforms (``Runner.posterior_predictive``:
+    ``pit_mix``, or ``pit`` weighted by the membership probability): ``hist`` = weighted counts in ``n_bins`` equal PIT
+    bins on [0, 1], ``n`` = the sum of the weights, ``chi2`` = sum_b (hist_b - n/B)^2 / (n/B) (for unit weights and a
+    calibrated model approximately chi^2 with B - 1 degrees of freedom), ``tail_fraction`` = the share of the weight with
+    a PIT outside [0.025, 0.975] (0.05 for a calibrated model), ``n_stars`` = the stars counted.  Stars whose PIT is not
+    finite are left out.  ``group``: the host group of a multi-rank job, whose ranks hold disjoint stars -- every entry
+    is additive over stars, so the totals are summed over it and every rank returns the same values."""
+    pit = np.asarray(pit, dtype=np.float64)
+    w = np.ones_like(pit) if weights is None else np.asarray(weights, dtype=np.float64)
+    if w.shape != pit.shape:
+        raise ValueError("weights must have the shape of pit")
+    n_bins = int(n_bins)
+    if n_bins < 1:
+        raise ValueError("n_bins must be >= 1")
+    ok = np.isfinite(pit) & np.isfinite(w)
+    pit, w = pit[ok], w[ok]
+    hist = np.histogram(pit, bins=n_bins, range=(0.0, 1.0), weights=w)[0]
+    tail = w[(pit < PPC_TAIL) | (pit > 1.0 - PPC_TAIL)].sum()
+    totals = np.concatenate([hist, [w.sum(), tail, float(pit.size)]])
+    if group is not None:
+        totals = np.asarray(group.allreduce(totals), dtype=np.float64)
+    hist, n, tail, n_stars = totals[:n_bins], float(totals[n_bins]), float(totals[n_bins + 1]), int(totals[n_bins + 2])
+    expect = n / n_bins
+    chi2 = float(np.sum((hist - expect) ** 2) / expect) if n > 0 else 0.0
+    return {"hist": hist, "n": n, "chi2": chi2, "tail_fraction": tail / n if n > 0 else 0.0, "n_stars": n_stars}
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -1006,6 +1038,51 @@ class Runner(object):
             raise ValueError("{0} has no background component: every star is a member".format(type(self).__name__))
         pp = self._pointwise_posterior(chain, n_burn, thin, True)
         return pp["pmem_mean"], pp["pmem_std"]
+
+    def _has_mixture_cdf(self):
+        """The two models whose background has a CDF (a Gaussian fitted with the cluster)."""
+        return self._catalog_spec()[0][0] in (_native.MODEL_CONST_BGGAUSS, _native.MODEL_PROFILE_BGGAUSS)
+
+    def posterior_predictive(self, chain, n_burn, thin=1):
+        """Per-star posterior predictive checks over the S post-burn-in samples of ``chain`` (W, steps, P), computed on the
+        device in one call (chain handling as ``pointwise_posterior``): posterior mean and standard deviation of the
+        standardised residual z = (v_i - v_los) / sqrt(verr_i^2 + sigma_los^2) (``z_mean``, ``z_std``), the posterior mean
+        of its two-sided tail probability (``tail_p``) and of the cluster component's CDF at v_i (``pit``), mean and
+        standard deviation of the model's v_los and sigma_los at the star (``vlos_*``, ``sigma_*``), and for
+        ConstantFitGB / ModelFitGB ``pit_mix``, the CDF of the whole cluster + background mixture; plus ``n_samples``.
+        Several ranks: this rank's stars."""
+        table, n_samples = self._posterior_table(chain, n_burn, thin)
+        out = self._ensure_catalog().posterior_predictive(table, mixture=self._has_mixture_cdf())
+        out["n_samples"] = n_samples
+        return out
+
+    def ppc(self, chain, n_burn, thin=1, n_bins=20, outlier_p=None):
+        """Posterior predictive check of the fitted model: the per-star arrays of ``posterior_predictive``, the entries of
+        ``ppc_summary`` (``hist``, ``n``, ``chi2``, ``tail_fraction``, ``n_stars``; summed over the ranks) and ``outliers``.
+        The summary is taken of ``pit_mix`` where it exists, else of ``pit`` weighted by the posterior mean of the
+        membership probability for the other background models (one ``pointwise_posterior`` call), else unweighted.
+        ``weight`` is that membership probability (1 without a background) and ``outliers`` are this rank's star indices
+        with ``weight`` > 0.5 and ``tail_p`` < ``outlier_p`` (default: 0.05 / n_stars over all ranks, Bonferroni):
+        likely members many sigma off the model -- binary candidates and bad measurements."""
+        out = self.posterior_predictive(chain, n_burn, thin)
+        n_local = out["pit"].size
+        if self._has_background():
+            weight = self._pointwise_posterior(chain, n_burn, thin, True)["pmem_mean"]
+        else:
+            weight = np.ones(n_local)
+        group = self._rank_group()
+        if "pit_mix" in out:
+            summary = ppc_summary(out["pit_mix"], None, n_bins, group)
+        else:
+            summary = ppc_summary(out["pit"], weight if self._has_background() else None, n_bins, group)
+        out.update(summary)
+        if outlier_p is None:
+            total = float(group.allreduce(np.array([float(n_local)]))[0]) if group is not None else float(n_local)
+            outlier_p = 0.05 / max(total, 1.0)
+        out["weight"] = weight
+        out["outlier_p"] = float(outlier_p)
+        out["outliers"] = np.flatnonzero((weight > 0.5) & (out["tail_p"] < outlier_p))
+        return out
 
     # ------------------------------------------------------------------ device catalogue
     # Sub-classes set `_model_id` and the ordered (name, canonical unit) columns of the kernel's parameter

@@ -1,8 +1,9 @@
 // mcd_api_summaries.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host
-// units): host drivers of the per-star posterior summaries (kernels: mcd_posterior.hip), of PSIS-LOO (mcd_psis.hip) and
-// of the kernel-density background (mcd_kde.hip).
+// units): host drivers of the per-star posterior summaries (kernels: mcd_posterior.hip), of PSIS-LOO (mcd_psis.hip),
+// of the kernel-density background (mcd_kde.hip), and of the posterior predictive checks (mcd_predictive.hip).
 #include "mcd_host.h"
 #include "mcd_posterior.h"
+#include "mcd_predictive.h"
 #include "mcd_psis.h"
 
 using namespace mcd::host;
@@ -47,17 +48,13 @@ void note_kernel_ms(mcd_catalog* cat, double kernel_ms) {
     }
 }
 
-int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double* const outs[4]) {
-    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: null catalogue or params");
-    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: n_samples must be >= 1");
-    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: parameter rows have the wrong number of columns");
-    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: defined for un-binned catalogues only");
-    const bool mem = outs[2] || outs[3];
-    if (mem && mcd::bg_kind(cat->model) == mcd::BG_NONE)
-        return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: membership outputs need a background model (pmem_* must be NULL)");
-    if (cat->n_stars == 0 || !(outs[0] || outs[1] || mem)) return MCD_OK;
+// What mcd_pointwise_posterior and mcd_posterior_predictive share: per shard, the scratch of the slice plan for `nf` state
+// fields and `n_out` output fields per star, the samples in passes of posterior_pass rows through `launch` (launch_posterior's
+// argument list after the shape and its flag), then `fetch(shard, slot, scratch, d_out, &kernel_ms)`.
+template <class Launch, class Fetch>
+int sliced_sample_passes(mcd_catalog* cat, int64_t S, int32_t k, const double* params, int nf, int n_out, Launch launch,
+                         Fetch fetch) {
     const size_t term_bytes = cat->precision == MCD_F64 ? 8 : 4;
-    const int nf = mcd::post_fields(mem);
     const int64_t pass_len = std::min<int64_t>(S, cat->posterior_pass);
     const int64_t n_passes = (S + pass_len - 1) / pass_len;
     double kernel_ms = 0.0;
@@ -78,7 +75,7 @@ int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* pa
         MCD_HIP(d.malloc(&d_inv, (size_t)max_len * sizeof(double)));
         MCD_HIP(d.malloc(&d_part, (size_t)max_slices * nf * sh.n * sizeof(double)));
         if (n_passes > 1) MCD_HIP(d.malloc(&d_state, (size_t)nf * sh.n * sizeof(double)));
-        MCD_HIP(d.malloc(&d_out, (size_t)4 * sh.n * sizeof(double)));
+        MCD_HIP(d.malloc(&d_out, (size_t)n_out * sh.n * sizeof(double)));
         std::vector<double> inv((size_t)max_len);
         for (int64_t j = 0; j < max_len; ++j) inv[j] = 1.0 / (double)(j + 1);
         MCD_HIP(hipMemcpy(d_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -90,14 +87,56 @@ int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* pa
             const int64_t n_slices = mcd::posterior_slices(sh.n, ns, &slice_len);
             // (every pass reuses the one pass buffer of derived rows)
             if (int rc = upload_samples(cat, slot, params, s0, ns, k, d_params, d_wpar, 0, p == 0 ? d.e0 : nullptr)) return rc;
-            MCD_HIP(mcd::launch_posterior(slot.stream, shape, mem, sh.records, sh.n, d_wpar, ns, d_inv, slice_len, n_slices,
-                                          d_part, d_state, s0, S, d_out));
+            MCD_HIP(launch(slot.stream, shape, sh.records, sh.n, d_wpar, ns, d_inv, slice_len, n_slices, d_part, d_state, s0, S,
+                           d_out));
             if (d.e1 && p == n_passes - 1) MCD_HIP(hipEventRecord(d.e1, slot.stream));
         }
-        if (int rc = fetch_outputs(sh, slot, d, d_out, outs, &kernel_ms)) return rc;
+        if (int rc = fetch(sh, slot, d, d_out, &kernel_ms)) return rc;
     }
     note_kernel_ms(cat, kernel_ms);
     return MCD_OK;
+}
+
+int pointwise_posterior(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double* const outs[4]) {
+    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: null catalogue or params");
+    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: n_samples must be >= 1");
+    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: parameter rows have the wrong number of columns");
+    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: defined for un-binned catalogues only");
+    const bool mem = outs[2] || outs[3];
+    if (mem && mcd::bg_kind(cat->model) == mcd::BG_NONE)
+        return fail(MCD_ERR_INVALID, "mcd_pointwise_posterior: membership outputs need a background model (pmem_* must be NULL)");
+    if (cat->n_stars == 0 || !(outs[0] || outs[1] || mem)) return MCD_OK;
+    return sliced_sample_passes(
+        cat, S, k, params, mcd::post_fields(mem), 4,
+        [&](hipStream_t s, const mcd::LaunchShape& shape, auto... rest) { return mcd::launch_posterior(s, shape, mem, rest...); },
+        [&](const Shard& sh, const DeviceSlot& slot, const DeviceScratch& d, const double* d_out, double* kernel_ms) {
+            return fetch_outputs(sh, slot, d, d_out, outs, kernel_ms);
+        });
+}
+
+// out [MCD_PRED_FIELDS][n_stars], pit_mix [n_stars] or null
+int posterior_predictive(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double* out, double* pit_mix) {
+    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: null catalogue or params");
+    if (!out) return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: out must not be NULL");
+    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: n_samples must be >= 1");
+    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: parameter rows have the wrong number of columns");
+    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: defined for un-binned catalogues only");
+    const bool mix = pit_mix != nullptr;
+    if (mix && mcd::bg_kind(cat->model) != mcd::BG_GAUSS)
+        return fail(MCD_ERR_INVALID, "mcd_posterior_predictive: pit_mix needs a Gaussian background model (pit_mix must be NULL)");
+    if (cat->n_stars == 0) return MCD_OK;
+    const int nf = mcd::pred_fields(mix);
+    return sliced_sample_passes(
+        cat, S, k, params, nf, nf,
+        [&](hipStream_t s, const mcd::LaunchShape& shape, auto... rest) { return mcd::launch_predictive(s, shape, mix, rest...); },
+        [&](const Shard& sh, const DeviceSlot& slot, const DeviceScratch& d, const double* d_out, double* kernel_ms) {
+            // the shard's stars at star_begin of every field, as fetch_outputs places them; it copies pit_mix and waits
+            for (int f = 0; f < MCD_PRED_FIELDS; ++f)
+                MCD_HIP(hipMemcpyAsync(out + (size_t)f * cat->n_stars + sh.star_begin, d_out + (size_t)f * sh.n,
+                                       (size_t)sh.n * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+            double* const rest[4] = {pit_mix, nullptr, nullptr, nullptr};
+            return fetch_outputs(sh, slot, d, mix ? d_out + (size_t)mcd::PO_PIT_MIX * sh.n : d_out, rest, kernel_ms);
+        });
 }
 
 // Per shard: the S derived sample rows once (uploaded in passes of posterior_pass rows), then tiles of stars whose
@@ -171,6 +210,13 @@ int mcd_psis_loo(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* p
     double* const outs[4] = {elpd_loo, pareto_k, lppd, n_eff};
     return psis_loo(cat, n_samples, k, params, r_eff, outs);
     } catch (...) { return on_exception("mcd_psis_loo"); }
+}
+
+int mcd_posterior_predictive(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double* out,
+                             double* pit_mix) {
+    try {
+    return posterior_predictive(cat, n_samples, k, params, out, pit_mix);
+    } catch (...) { return on_exception("mcd_posterior_predictive"); }
 }
 
 int mcd_kde_background(mcd_ctx* ctx, int64_t n_comp, const double* comp, int64_t n, const double* v,
