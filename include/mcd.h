@@ -398,6 +398,41 @@ int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_wal
                     double* eps_factor);
 int mcd_hmc_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);
 
+/* ---- convergence diagnostics of a stored chain ------------------------------------------- */
+
+/* Integrated autocorrelation time (the estimator of emcee's autocorr.integrated_time), split-R-hat (Gelman et al., BDA3)
+ * and the pooled moments of a chain in the samplers' layout chain[n_steps][n_groups][n_walkers][n_dim], float64: n_groups
+ * independent ensembles (the bins of a binned catalogue, or 1).  The reference has no such diagnostic: its users call
+ * emcee's sampler.get_autocorr_time().  Per (group g, parameter p), outputs [n_groups][n_dim]:
+ *   tau, window, found   with y the series of one walker minus its FIRST value and then minus its mean,
+ *                        a_k = sum_t y_t y_{t+k}, rho_k = the walkers' mean of a_k / a_0, tau_k = 2 sum_{j<=k} rho_j - 1:
+ *                        window = the smallest k <= max_lag with k >= c tau_k, found = 1, tau = tau_window; when there is
+ *                        none, found = 0, tau = tau_{max_lag}, window = max_lag (the chain is too short for max_lag)
+ *   rhat                 m = 2 n_walkers half-chains of n = n_steps / 2 steps: sqrt(((n-1)/n Wv + B/n) / Wv); NaN for
+ *                        n_steps < 4 or Wv = 0
+ *   mean, var            over the n_steps x n_walkers samples (var with ddof = 1)
+ *   rho                  NULL, or [n_groups][n_dim][max_lag + 1]
+ * A walker that never moves (a_0 = 0) makes rho, tau and rhat of its (g, p) NaN and found 0, as emcee's estimate is NaN.
+ * ctx == NULL: the loop of mcmc_dynamics_amd/csrc/mcd_diag.h on the host, no device needed.  Otherwise the kernels of
+ * csrc/mcd_diag.hip on the context's first device, waited for under the context's deadline: the chain goes up in tiles of
+ * whole groups within scratch_mb MiB of device memory (0: 1024).  One text, one order of every sum: host and device
+ * results are bit-identical, and independent of the tile plan.  No collective: every rank of a multi-rank job holds the
+ * whole chain and calls this locally.  MCD_ERR_INVALID (nothing written) for n_steps < 2, max_lag outside
+ * [1, n_steps - 1], c <= 0, a dimension < 1, a NULL output other than rho, or a scratch_mb that cannot hold one group. */
+typedef struct {
+    int64_t n_steps, n_groups, n_walkers;
+    int32_t n_dim;
+    int64_t max_lag;
+    double c;
+    int64_t scratch_mb;
+} mcd_diag_desc;
+
+int mcd_chain_diagnostics(mcd_ctx* ctx, const mcd_diag_desc* d, const double* chain, double* tau, int64_t* window,
+                          int32_t* found, double* rhat, double* mean, double* var, double* rho);
+/* Of the calling thread's last mcd_chain_diagnostics: groups per device tile, tiles, and the HIP-event time of its kernels
+ * in milliseconds (0 for ctx == NULL).  Any pointer may be NULL. */
+int mcd_chain_diagnostics_info(int64_t* tile_groups, int64_t* n_tiles, double* kernel_ms);
+
 /* ---- introspection for the measurement harness ------------------------------------------- */
 
 const char* mcd_last_error(void);

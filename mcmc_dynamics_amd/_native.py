@@ -84,6 +84,10 @@ SYMBOLS = {
     "mcd_hmc_block_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
                                            ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p,
                                            ctypes.c_void_p]),
+    "mcd_chain_diagnostics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_double_p, _c_double_p, _c_int64_p,
+                                             ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p, _c_double_p,
+                                             _c_double_p]),
+    "mcd_chain_diagnostics_info": (ctypes.c_int, [_c_int64_p, _c_int64_p, _c_double_p]),
     "mcd_last_error": (ctypes.c_char_p, []),
     "mcd_abi_version": (ctypes.c_int, []),
     "mcd_last_kernel_ms": (ctypes.c_double, [ctypes.c_void_p]),
@@ -163,6 +167,49 @@ def prior_eval(prior, x, want_grad=False):
     grad = np.empty(x.shape) if want_grad else None
     _check(lib, lib.mcd_prior_eval(ctypes.byref(d), x.shape[0], _ptr(x), _ptr(value), _ptr(grad)), "mcd_prior_eval")
     return (value, grad) if want_grad else value
+
+
+class DiagDesc(ctypes.Structure):
+    """Mirror of ``mcd_diag_desc``."""
+    _fields_ = [("n_steps", ctypes.c_int64), ("n_groups", ctypes.c_int64), ("n_walkers", ctypes.c_int64),
+                ("n_dim", ctypes.c_int32), ("max_lag", ctypes.c_int64), ("c", ctypes.c_double), ("scratch_mb", ctypes.c_int64)]
+
+
+def chain_diagnostics(chain, max_lag, c=5.0, context=None, scratch_mb=0, want_rho=False):
+    """``mcd_chain_diagnostics`` on ``chain`` (T, G, W, P) float64, steps first (include/mcd.h; csrc/mcd_diag.h): a dict of
+    ``tau``, ``window``, ``found``, ``rhat``, ``mean``, ``var`` of shape (G, P) [, ``rho`` (G, P, max_lag + 1)].
+    ``context=None``: the library's host loop, no device involved; a ``Context``: its first device, the chain going up in
+    tiles of whole groups within ``scratch_mb`` MiB (0: 1024) -- the same bits either way."""
+    lib = load_library()
+    chain = _f64(chain)
+    if chain.ndim != 4:
+        raise ValueError("chain_diagnostics: chain must have shape (steps, groups, walkers, parameters)")
+    T, G, W, P = chain.shape
+    d = DiagDesc(T, G, W, P, int(max_lag), float(c), int(scratch_mb))
+    out = {"tau": np.empty((G, P)), "window": np.empty((G, P), dtype=np.int64), "found": np.empty((G, P), dtype=np.int32),
+           "rhat": np.empty((G, P)), "mean": np.empty((G, P)), "var": np.empty((G, P))}
+    if want_rho:
+        out["rho"] = np.empty((G, P, max(int(max_lag), 0) + 1))
+    handle = None
+    if context is not None:
+        handle = getattr(context, "handle", None)
+        if not handle:
+            raise NativeError("context is closed")
+    rc = lib.mcd_chain_diagnostics(handle, ctypes.byref(d), _ptr(chain), _ptr(out["tau"]),
+                                   out["window"].ctypes.data_as(_c_int64_p),
+                                   out["found"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(out["rhat"]),
+                                   _ptr(out["mean"]), _ptr(out["var"]), _ptr(out.get("rho")))
+    _check(lib, rc, "mcd_chain_diagnostics")
+    return out
+
+
+def chain_diagnostics_info():
+    """Of this thread's last ``chain_diagnostics``: {'tile_groups', 'n_tiles', 'kernel_ms'} (include/mcd.h)."""
+    lib = load_library()
+    tg, nt, ms = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_double()
+    _check(lib, lib.mcd_chain_diagnostics_info(ctypes.byref(tg), ctypes.byref(nt), ctypes.byref(ms)),
+           "mcd_chain_diagnostics_info")
+    return {"tile_groups": tg.value, "n_tiles": nt.value, "kernel_ms": ms.value}
 
 
 class HmcDesc(ctypes.Structure):

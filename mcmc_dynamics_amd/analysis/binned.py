@@ -75,6 +75,15 @@ class BinnedSampler(object):
     def acceptance_fraction(self):
         return self._accepted / max(1, self.iteration)
 
+    def get_chain(self, discard=0):
+        """(steps, B, W, P): the steps-first layout of ``sampler.EnsembleSampler.get_chain`` with the bin axis after it."""
+        return self._chain[discard:self.iteration]
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """(B, P): the integrated autocorrelation time per bin and parameter in steps (``diagnostics.integrated_time``)."""
+        from ..diagnostics import sampler_autocorr_time
+        return sampler_autocorr_time(self, discard=discard, thin=thin, **kwargs)
+
     def reserve(self, total_steps):
         """Chain storage for ``total_steps`` steps in all (a run continued by further ``run_mcmc`` calls otherwise grows its
         storage geometrically and copies the rows it holds: 1.1 MB per step at 55 bins x 512 walkers)."""
@@ -260,6 +269,21 @@ class BinnedConstantFit(ConstantFit):
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")
+
+    def run_converged(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: run_converged drives one un-binned ensemble; run the bins with "
+                                  "__call__ and judge them with chain_diagnostics / sampler.get_autocorr_time()")
+
+    def chain_diagnostics(self, chain, n_burn, c=5.0, tol=50.0):
+        """``diagnostics.summary`` of a chain (B, W, steps, P) after ``n_burn`` steps: (B, P) arrays, plus ``names``."""
+        from .. import diagnostics
+        chain = np.asarray(chain, dtype=np.float64)
+        if chain.ndim != 4:
+            raise ValueError("chain must have shape (bins, walkers, steps, parameters)")
+        out = diagnostics.summary(np.transpose(chain[:, :, n_burn:, :], (2, 0, 1, 3)), c=c, tol=tol,
+                                  context=self._diagnostics_context())
+        out["names"] = list(self.fitted_parameters)
+        return out
 
     def compute_bestfit_values(self, chain, n_burn):
         """List of per-bin result tables (median / uperr / loerr), as the per-bin loop of

@@ -881,6 +881,67 @@ class Runner(object):
                 logger.info(output)
         return sampler
 
+    # ------------------------------------------------------------------ convergence (no counterpart in the reference)
+    def _diagnostics_context(self):
+        """Where the chain diagnostics run: this runner's device context."""
+        return self.context
+
+    def run_converged(self, n_walkers=100, max_steps=20000, check_every=500, tol=50.0, rtol=0.01, **call_kwargs):
+        """Run the MCMC until the integrated autocorrelation time says it is long enough (emcee's documented pattern):
+        increments of ``check_every`` steps, after each one ``tau`` from ``diagnostics.integrated_time(..., quiet=True)``;
+        stops when ``steps > tol max(tau)`` and ``max |tau - previous tau| / tau < rtol``, or at ``max_steps``.  Works with
+        whichever sampler ``SAMPLER`` selects (it needs ``run_mcmc`` and ``get_chain()``); ``pos`` and ``lnprob0`` as in
+        ``__call__``.  Returns ``(sampler, history)``, ``history`` a list of ``(steps, tau)`` per check."""
+        from .. import diagnostics
+        pos, lnprob0 = call_kwargs.pop("pos", None), call_kwargs.pop("lnprob0", None)
+        if call_kwargs:
+            raise TypeError("run_converged: unknown argument(s) {0}".format(sorted(call_kwargs)))
+        if pos is None:
+            pos = self.get_initials(n_walkers=n_walkers)
+        pos = np.asarray(pos, dtype=np.float64)
+        group, seed = self._rank_group(), None
+        if group is not None:
+            pos = group.bcast_array(pos, src=0)
+            seed = int(group.bcast_json(int(np.random.SeedSequence().entropy % (2 ** 32)), src=0))
+        if not np.all(np.isfinite(self.lnprior_batch(pos))):
+            raise ValueError("Invalid initial guesses for some walker(s).")
+        sampler = self._make_sampler(n_walkers, seed=seed)
+        history, previous, steps = [], None, 0
+        while steps < max_steps:
+            n = int(min(check_every, max_steps - steps))
+            try:
+                result = sampler.run_mcmc(pos, n, log_prob0=lnprob0, progress=False)
+            except BaseException as exc:
+                if group is not None:
+                    group.abort("{0}: {1}".format(type(exc).__name__, exc))
+                raise
+            pos, lnprob0 = tuple(result)[0], None
+            steps += n
+            if steps < 2:
+                continue
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")                     # (a chain that is still too short is the normal case here)
+                tau = np.array(diagnostics.integrated_time(sampler.get_chain(), tol=tol, quiet=True,
+                                                           context=self._diagnostics_context()))
+            history.append((steps, tau))
+            logger.info("convergence check at %d steps: tau = %s", steps, tau)
+            if np.all(np.isfinite(tau)) and steps > tol * np.max(tau) and previous is not None and \
+                    np.max(np.abs(tau - previous) / tau) < rtol:
+                break
+            previous = tau
+        return sampler, history
+
+    def chain_diagnostics(self, chain, n_burn, c=5.0, tol=50.0):
+        """``diagnostics.summary`` of a chain in the reference's layout (W, steps, P) after ``n_burn`` steps -- tau, window,
+        found, converged, ess, rhat, mean, std per fitted parameter -- plus ``names``."""
+        from .. import diagnostics
+        chain = np.asarray(chain, dtype=np.float64)
+        if chain.ndim != 3:
+            raise ValueError("chain must have shape (walkers, steps, parameters)")
+        out = diagnostics.summary(np.swapaxes(chain[:, n_burn:, :], 0, 1), c=c, tol=tol, context=self._diagnostics_context())
+        out["names"] = list(self.fitted_parameters)
+        return out
+
     # ------------------------------------------------------------------ checkpoints (runner.py:445-519)
     @staticmethod
     def save_chain(sampler, filename="samplerchain.pkl"):

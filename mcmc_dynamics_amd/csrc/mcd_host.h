@@ -9,6 +9,7 @@
 //   mcd_api_eval.hip       staging, enqueue, sync, fetch; the per-star outputs of one parameter row
 //   mcd_api_chain.hip      the stretch-move block and the HMC block, each resident on the device or host-driven
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
+//   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
 // What crosses units is in mcd::host (hidden: not among the library's exported symbols), the rest in each unit's

@@ -225,6 +225,12 @@ class EnsembleSampler(object):
         lp = self._lnprob[discard:self.iteration]
         return lp.reshape(-1) if flat else lp
 
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """The integrated autocorrelation time per parameter in steps, as emcee's method of this name (``c``, ``tol``,
+        ``quiet``; ``diagnostics.integrated_time`` has the rest): computed on the device beside the chain."""
+        from .diagnostics import sampler_autocorr_time
+        return sampler_autocorr_time(self, discard=discard, thin=thin, **kwargs)
+
     @property
     def random_state(self):
         return self._random.get_state()
@@ -387,6 +393,12 @@ class HMCSampler(object):
     def get_log_prob(self, discard=0, flat=False):
         lp = self._lnprob[discard:self.iteration]
         return lp.reshape(-1) if flat else lp
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """The integrated autocorrelation time per parameter in steps, as emcee's method of this name (``c``, ``tol``,
+        ``quiet``; ``diagnostics.integrated_time`` has the rest): computed on the device beside the chain."""
+        from .diagnostics import sampler_autocorr_time
+        return sampler_autocorr_time(self, discard=discard, thin=thin, **kwargs)
 
     def run_mcmc(self, initial_state, nsteps, **kwargs):
         """Advance the chains by ``nsteps``.  Returns ``(pos, log_prob, None)``."""

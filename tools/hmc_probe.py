@@ -14,8 +14,8 @@ Method.  MAP by optimize.maximize_batch on the device gradient from a ball aroun
 central differences of the gradient (what Runner.maximize / Runner.laplace do, on the kernel columns directly); when -H
 is not positive definite the metric falls back to diag(1 / |H_jj|) and the line says so.  HMC: warm-up blocks of 10 steps
 with eps *= exp(acceptance - 0.8), then the timed production blocks.  Stretch move: mcd_stretch_move_seeded, the walkers
-started in the same Laplace ball.  Integrated autocorrelation time: emcee's estimator, restated here -- the
-autocorrelation function of every walker's series by FFT, averaged over the walkers, tau(M) = 1 + 2 sum_{t=1..M} rho_t at
+started in the same Laplace ball.  Integrated autocorrelation time: emcee's estimator as the library has it
+(mcmc_dynamics_amd.diagnostics) -- every walker's normalised autocorrelation function, averaged over the walkers, tau(M) = 1 + 2 sum_{t=1..M} rho_t at
 the smallest window M with M >= c tau(M), c = 5 (Sokal).  For HMC the walkers are independent chains, for the stretch move
 one ensemble; both are treated alike.  ESS = walkers x steps / tau, per second of the sampler's wall time (warm-up and
 burn-in not counted on either side)."""
@@ -24,33 +24,27 @@ import json
 import os
 import sys
 import time
+import warnings
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mcmc_dynamics_amd import _native as native, synthetic            # noqa: E402
+from mcmc_dynamics_amd import _native as native, diagnostics, synthetic   # noqa: E402
 from mcmc_dynamics_amd.optimize import maximize_batch                  # noqa: E402
 
 CENTRE = (synthetic.CENTER_RA_DEG, synthetic.CENTER_DEC_DEG)
 INF = np.inf
 
 
-def autocorr_time(x, c=5.0):
-    """x (walkers, steps) -> integrated autocorrelation time in steps (emcee.autocorr.integrated_time's formula)."""
-    x = np.asarray(x, dtype=np.float64)
-    n = x.shape[1]
-    size = 1 << int(np.ceil(np.log2(2 * n)))
-    f = np.fft.rfft(x - x.mean(axis=1, keepdims=True), n=size, axis=1)
-    acf = np.fft.irfft(f * np.conjugate(f), n=size, axis=1)[:, :n]
-    acf = acf.mean(axis=0)
-    if acf[0] <= 0.0:
-        return float("nan")
-    rho = acf / acf[0]
-    taus = 2.0 * np.cumsum(rho) - 1.0
-    m = np.arange(n) < c * taus
-    window = int(np.argmin(m)) if not m.all() else n - 1
-    return float(taus[window])
+def autocorr_time(chain, ctx, c=5.0):
+    """chain (steps, walkers, parameters) -> integrated autocorrelation times in steps, per parameter: the library's
+    estimator (mcmc_dynamics_amd.diagnostics, on the device) over all lags, without its length test -- `tau_reliable` below
+    is this tool's."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return [float(v) for v in diagnostics.integrated_time(chain, c=c, tol=0, max_lag=chain.shape[0] - 1, quiet=True,
+                                                              context=ctx)]
 
 
 def workload(name, n_stars):
@@ -170,7 +164,7 @@ def main():
     res_s, _, _, _ = hmc(res_pos, eps, done + a.hmc_steps, a.host_steps, True, keep=False)
     info = cat.hmc_info()
     cat.set_option("device_chain", 1)
-    tau_h = [autocorr_time(chain_h[:, :, j].T) for j in range(p)]
+    tau_h = autocorr_time(chain_h, ctx)
 
     # ---- the resident stretch move on the same catalogue
     pos = pos0.copy()
@@ -183,7 +177,7 @@ def main():
     cat.stretch_move_seeded(plan, pos, lnp, a.seed, a.stretch_burn, a.stretch_steps, chain_s, None, acc)
     stretch_s = time.perf_counter() - t0
     sinfo = cat.stretch_info()
-    tau_s = [autocorr_time(chain_s[:, :, j].T) for j in range(p)]
+    tau_s = autocorr_time(chain_s, ctx)
 
     def ess(tau, steps, seconds):
         worst = float(np.nanmax(tau))
