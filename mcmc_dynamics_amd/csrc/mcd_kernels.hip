@@ -256,7 +256,10 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
 //
 // single0 >= 0: ONE parameter set whose slots are [0, single0) -- the range arrives as a kernel argument instead of two
 // dependent loads from `offs` in front of the first load of partial sums (one memory round trip less)
-template <int SUB, int U, bool ONE_ROUND>
+//
+// SEVERAL: the launch has several parameter sets of unequal length (instantiated apart, so that the kernels of launches
+// with one set stay as they are).
+template <int SUB, int U, bool ONE_ROUND, bool SEVERAL>
 __global__ __launch_bounds__(kPartialGroup * SUB) void reduce_group_kernel(const double* __restrict__ partials,
                                                                             const int64_t* __restrict__ offs,
                                                                             int64_t n_slots, int64_t n_walkers,
@@ -271,8 +274,21 @@ __global__ __launch_bounds__(kPartialGroup * SUB) void reduce_group_kernel(const
     const int64_t c0 = single0 >= 0 ? 0 : offs[pset], c1 = single0 >= 0 ? single0 : offs[pset + 1];
     const double add = pset_const ? pset_const[pset] : 0.0;          // walker-independent part (sum of lnL_bg), in flight early
     const double2* __restrict__ col = reinterpret_cast<const double2*>(partials + g * n_slots * kPartialGroup) + q;
-    double ax, ay;
-    reduce_sublane_sum<SUB, U, ONE_ROUND>(col, c0, c1, s, ax, ay);
+    // Several parameter sets: the launch's shape is the longest set's, but every set adds its slots in the order of the
+    // shape a launch of its own would take (the limits of launch_reduce) -- its first 2 x 8 or 2 x 32 sublanes (one wave,
+    // four waves) do the work and the other waves add +0.0.  A bin of a binned catalogue so keeps the bits of a stand-alone
+    // catalogue of its stars whatever the lengths of the other bins.  (The branches are uniform over the workgroup.)
+    double ax = 0.0, ay = 0.0;
+    const int64_t count = c1 - c0;
+    if (SEVERAL && SUB > 8 && count <= 2 * 8 * U) {
+        if (s < 2 * 8) reduce_sublane_sum<8, U, true>(col, c0, c1, s, ax, ay);
+    } else if (SEVERAL && SUB > 32 && count <= 2 * 32 * U) {
+        if (s < 2 * 32) reduce_sublane_sum<32, U, true>(col, c0, c1, s, ax, ay);
+    } else if (SEVERAL && !ONE_ROUND && count <= 2 * SUB * U) {
+        reduce_sublane_sum<SUB, U, true>(col, c0, c1, s, ax, ay);
+    } else {
+        reduce_sublane_sum<SUB, U, ONE_ROUND>(col, c0, c1, s, ax, ay);
+    }
     reduce_wave_combine(ax, ay);
     const int lane = threadIdx.x & (kWave - 1);
     if constexpr (kWaves > 1) {
@@ -440,19 +456,26 @@ hipError_t launch_reduce(hipStream_t s, const double* partials, const int64_t* o
     const int64_t n_groups = (n_walkers + kPartialGroup - 1) / kPartialGroup;
     const dim3 grid((unsigned)(n_psets * n_groups));
     const int64_t single0 = n_psets == 1 ? n_slots : -1;
-    // Shapes by the longest parameter set, each needing one round of loads up to its limit (2 SUB sublanes x U loads):
+    // Shapes by the longest parameter set, each needing one round of loads up to its limit (2 SUB sublanes x U loads); a
+    // shorter set of the same launch is added in the order of the shape of its own length (reduce_group_kernel):
     //   <= 256 slots: one wave per group, 16 loads per thread (radial bins with a few chunks each; the balanced plans of
     //   small catalogues; the SAME order as the step kernel's fused reduction, mcd_stretch.hip)
     //   <= 1024: 4 waves x 16;  <= 4096: 16 waves x 16 (C3: 3551 chunks);  beyond: 16 waves, several rounds
+#define MCD_LAUNCH_REDUCE_AS(SUB_, U_, ONE_, SEVERAL_)                                                                      \
+    hipLaunchKernelGGL((reduce_group_kernel<SUB_, U_, ONE_, SEVERAL_>), grid, dim3(kPartialGroup * SUB_), 0, s, partials,   \
+                       offs, n_slots, n_walkers, n_groups, pset_const, out, single0)
 #define MCD_LAUNCH_REDUCE(SUB_, U_, ONE_)                                                                                   \
-    hipLaunchKernelGGL((reduce_group_kernel<SUB_, U_, ONE_>), grid, dim3(kPartialGroup * SUB_), 0, s, partials, offs,       \
-                       n_slots, n_walkers, n_groups, pset_const, out, single0)
+    do {                                                                                                                    \
+        if (SUB_ > 8 && n_psets > 1) MCD_LAUNCH_REDUCE_AS(SUB_, U_, ONE_, (SUB_ > 8));                                      \
+        else MCD_LAUNCH_REDUCE_AS(SUB_, U_, ONE_, false);                                                                   \
+    } while (0)
     static_assert(kFusedReduceSlots == 2 * 8 * 16, "one round of the one-wave shape");
     if (max_slots_per_pset <= kFusedReduceSlots) MCD_LAUNCH_REDUCE(8, 16, true);
     else if (max_slots_per_pset <= 1024) MCD_LAUNCH_REDUCE(32, 16, true);
     else if (max_slots_per_pset <= 4096) MCD_LAUNCH_REDUCE(128, 16, true);
     else MCD_LAUNCH_REDUCE(128, 16, false);
 #undef MCD_LAUNCH_REDUCE
+#undef MCD_LAUNCH_REDUCE_AS
     return hipGetLastError();
 }
 

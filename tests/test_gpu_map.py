@@ -24,6 +24,9 @@ def _fit(kind):
     cat = synthetic.make_catalog(2000, config=2, background=bg)
     cols = ("ra", "dec", "v", "verr") + (("density",) if bg else ())
     fit = (ConstantFitGB if bg else ConstantFit)(DataReader({k: cat[k] for k in cols}), seed=SEED)
+    # the `initials` recipes draw from the parameter set's own generator, which a default set seeds from the system's
+    # entropy: without this line every process had other starts (11 .. 63 of 64 converged from run to run for ConstantFit)
+    fit.parameters.rng.bit_generator.state = np.random.default_rng(SEED).bit_generator.state
     centre = (synthetic.CENTER_RA_DEG, synthetic.CENTER_DEC_DEG)
     fit.parameters["ra_center"].set(value=centre[0], fixed=True)
     fit.parameters["dec_center"].set(value=centre[1], fixed=True)

@@ -8,6 +8,7 @@ which FD(h/2) keeps 1/4), the second is far above the 80-bit round-off of a diff
 import numpy as np
 import pytest
 
+import grad_bounds as gb
 import grad_helper as gh
 import variant_helper as vh
 
@@ -44,3 +45,22 @@ def test_float64_run_tracks_the_longdouble_run():
     g80, s80 = gh.grad(4, case["cat"], case["params"][0], None, L)
     assert g64.dtype == np.float64 and g80.dtype == L
     assert np.all(gh.col_err(g64, g80, s80) < 1e-9)
+
+
+@pytest.mark.parametrize("model,free", [(1, False), (4, True)])
+def test_prefix_reference_is_the_reference_of_the_sliced_catalogue(model, free):
+    """grad_bounds.prefix_reference serves every prefix catalogue from one evaluation of the term matrix: at two prefix
+    lengths (one of them no multiple of numpy's pairwise-summation blocks) it gives the gradient, S_k and err_np64 of
+    grad_bounds.reference on the sliced catalogue, exactly."""
+    case = vh.make_case(model, free, 4099)
+    lengths = (51, 2611)
+    for w in (0, 3):
+        got = gb.prefix_reference(case, w, lengths + (4099,))
+        assert sorted(got) == [51, 2611, 4099]
+        for n in lengths:
+            want = gb.reference(gb.sub_case(case, slice(0, n)), w)
+            assert got[n]["g"].dtype == L and got[n]["s"].dtype == L
+            for key in ("g", "s", "err64"):
+                assert np.array_equal(got[n][key], want[key]), (model, free, w, n, key)
+        whole = gb.reference(case, w)
+        assert np.array_equal(got[4099]["g"], whole["g"]) and np.array_equal(got[4099]["s"], whole["s"])
