@@ -398,6 +398,57 @@ int mcd_hmc_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_wal
                     double* eps_factor);
 int mcd_hmc_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);
 
+/* One block of parallel-tempering steps (Swendsen & Wang 1986; Geyer 1991): T ensembles ("rungs") of W walkers each sample
+ * prior(x) L(x)^beta_t on a ladder 1 = beta_0 > beta_1 > ... > beta_{T-1} >= 0.  Every rung advances by the stretch move of
+ * mcd_stretch_move_seeded (ensemble index = rung: the numbers are mcd_chain_numbers' for n_bins = T), adjacent rungs
+ * exchange walkers by a Metropolis swap, and the rungs' log-likelihood series give the marginal likelihood (the Python
+ * layer's evidence_summary).  The reference has one ensemble at one temperature (analysis/runner.py:403-419).  The algebra
+ * is mcmc_dynamics_amd/csrc/mcd_temper.h, one text for host and device:
+ *   half steps  h = 0, 1 in every rung at once: proposal q - (q - s) z from the other half of the walker's own rung; inside
+ *               the prior iff inside the inclusive box and every prior's support; accept iff
+ *               thr < beta_t (ll_new - ll_old) [+ (lp_new - lp_old) with mcd_temper_block_prior], in this order.  A proposal
+ *               outside the prior or with a non-finite ll_new is rejected at every rung, beta = 0 included; a NaN ll_new is
+ *               MCD_ERR_NONFINITE; fixed_ok == 0 rejects everything.
+ *   swap phase  after half step 1 of absolute step s: the pairs (t, t + 1) with t = s (mod 2), walker w of rung t with walker
+ *               w of rung t + 1; accept iff log(u) < (beta_t - beta_{t+1}) (ll_{t+1} - ll_t); the walkers then exchange
+ *               position, log-likelihood and log-prior.  One generator call per (step, t, w) with a key of its own:
+ *               mcd_temper_numbers returns log(u) as swap_thr [n_steps][T-1][W] (every pair, active or not).
+ *   pos [T][W][P], lnlike [T][W]   in: where the block starts and the log-likelihood there; out: where it ends
+ *   lnprior [T][W]       out: the log-prior at pos (0 inside the box without structured priors); the block computes the
+ *                        start positions' values itself, whatever the array holds on entry
+ *   chain [n_steps][n_chain_temps][W][P], lnlike_chain [n_steps][T][W]   the state after every step's swap phase; may be NULL
+ *   accepted [T][W], swap_proposed [T-1], swap_accepted [T-1]   incremented; each may be NULL.  accepted counts by slot
+ *                        (rung, walker index), not by the walker that travels through the ladder.
+ * pos, lnlike, lnprior and the counts are only ever written with final values.  Returns MCD_ERR_NONFINITE when a walker
+ * STARTS outside the prior or with a non-finite log-likelihood, MCD_ERR_INVALID (nothing touched) for a binned or a float32
+ * catalogue, an odd W, a ladder that does not start at 1 or is not strictly decreasing within [0, 1], n_chain_temps outside
+ * 1 .. T, n_dim > 12 or a descriptor whose k is not the catalogue's.
+ *
+ * Evaluations run the PLAIN kernels (option "fast_path" = 0) in both forms, whatever the option says, and leave it as it
+ * was: the hot rungs roam the whole prior box, where the fast families' range guard would refuse often.
+ * Where it runs.  One device per process without a communicator: RESIDENT -- propose / (walker prep, main kernel, reduction)
+ * / accept-and-propose / ... / swap-and-record are one chain of launches on the catalogue's stream, T W/2 parameter rows
+ * per launch, and the host waits once (csrc/mcd_temper.hip).  Everything else -- option "device_chain" = 0, several devices
+ * or ranks, option "timing", W > 8192, more than 512 MB of numbers and rows per block, or no memory for the arena -- runs
+ * HOST-DRIVEN: the same loop around mcd_loglike_batch.  Both give the same chain bit for bit; mcd_temper_info counts the
+ * blocks of either kind. */
+typedef struct {
+    mcd_stretch_desc map;       /* n_bins <= 1; n_walkers = W per rung (even, >= 2) */
+    int32_t n_temps;            /* T >= 1 */
+    const double* betas;        /* [T], betas[0] == 1, strictly decreasing, >= 0 */
+    int32_t n_chain_temps;      /* positions of rungs 0 .. n_chain_temps-1 are stored (1: the posterior only) */
+} mcd_temper_desc;
+
+int mcd_temper_block(mcd_catalog* cat, const mcd_temper_desc* desc, int64_t n_steps, double* pos, double* lnlike,
+                     double* lnprior, uint64_t seed, int64_t step0, double* chain, double* lnlike_chain, int64_t* accepted,
+                     int64_t* swap_proposed, int64_t* swap_accepted);
+int mcd_temper_block_prior(mcd_catalog* cat, const mcd_temper_desc* desc, int64_t n_steps, double* pos, double* lnlike,
+                           double* lnprior, uint64_t seed, int64_t step0, double* chain, double* lnlike_chain,
+                           int64_t* accepted, int64_t* swap_proposed, int64_t* swap_accepted,
+                           const mcd_prior_desc* prior);      /* mcd_prior_desc: above, with mcd_stretch_move_prior */
+int mcd_temper_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int32_t n_temps, int64_t n_walkers, double* swap_thr);
+int mcd_temper_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);
+
 /* ---- convergence diagnostics of a stored chain ------------------------------------------- */
 
 /* Integrated autocorrelation time (the estimator of emcee's autocorr.integrated_time), split-R-hat (Gelman et al., BDA3)

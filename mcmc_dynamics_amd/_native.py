@@ -84,6 +84,15 @@ SYMBOLS = {
     "mcd_hmc_block_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
                                            ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p,
                                            ctypes.c_void_p]),
+    "mcd_temper_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p, _c_double_p,
+                                        ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_int64_p,
+                                        _c_int64_p]),
+    "mcd_temper_block_prior": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
+                                              _c_double_p, ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p,
+                                              _c_int64_p, _c_int64_p, _c_int64_p, ctypes.c_void_p]),
+    "mcd_temper_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64,
+                                          _c_double_p]),
+    "mcd_temper_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p]),
     "mcd_chain_diagnostics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_double_p, _c_double_p, _c_int64_p,
                                              ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p, _c_double_p,
                                              _c_double_p]),
@@ -216,6 +225,11 @@ class HmcDesc(ctypes.Structure):
     """Mirror of ``mcd_hmc_desc``."""
     _fields_ = [("map", StretchDesc), ("chol", _c_double_p), ("step_size", ctypes.c_double), ("jitter", ctypes.c_double),
                 ("n_leap", ctypes.c_int32)]
+
+
+class TemperDesc(ctypes.Structure):
+    """Mirror of ``mcd_temper_desc``."""
+    _fields_ = [("map", StretchDesc), ("n_temps", ctypes.c_int32), ("betas", _c_double_p), ("n_chain_temps", ctypes.c_int32)]
 
 
 # Environment switches the library or this binding reads (INTEGRATION.md lists them).  None is needed in production: they
@@ -418,6 +432,17 @@ def hmc_numbers(seed, step0, n_steps, n_walkers, n_dim):
                              _ptr(thr), _ptr(r))
     _check(lib, rc, "mcd_hmc_numbers")
     return z, thr, r
+
+
+def temper_numbers(seed, step0, n_steps, n_temps, n_walkers):
+    """``mcd_temper_numbers``: the swap thresholds log(u) of steps ``step0 .. step0 + n_steps - 1`` of the tempered chain that
+    ``seed`` names (host code, no device involved), shape (steps, T - 1, W): pair t is rungs (t, t + 1); a step exchanges the
+    pairs of its own parity only.  The stretch-move numbers of the rungs are ``chain_numbers(..., n_bins=T, ...)``."""
+    lib = load_library()
+    thr = np.empty((int(n_steps), max(int(n_temps) - 1, 0), int(n_walkers)), dtype=np.float64)
+    rc = lib.mcd_temper_numbers(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), int(n_steps), int(n_temps), int(n_walkers), _ptr(thr))
+    _check(lib, rc, "mcd_temper_numbers")
+    return thr
 
 
 class Catalog(object):
@@ -743,6 +768,58 @@ class Catalog(object):
         _check(self.lib, self.lib.mcd_hmc_info(self.handle, ctypes.byref(a), ctypes.byref(b)), "mcd_hmc_info")
         return {"device_blocks": a.value, "host_blocks": b.value}
 
+    def temper_block(self, plan, betas, pos, lnlike, lnprior, seed, step0, n_steps, chain=None, lnlike_chain=None,
+                     accepted=None, swap_proposed=None, swap_accepted=None):
+        """``mcd_temper_block``: advance T ensembles of W walkers, one per inverse temperature of ``betas`` (T,), by
+        ``n_steps`` parallel-tempering steps (csrc/mcd_temper.h).  ``plan`` as for ``stretch_move`` (a ``prior`` entry selects
+        ``mcd_temper_block_prior``).  ``pos`` (T, W, P) and ``lnlike`` (T, W) are updated in place, ``lnprior`` (T, W) is
+        written; ``chain`` (steps, C, W, P) stores the positions of rungs 0 .. C - 1, ``lnlike_chain`` (steps, T, W) the
+        log-likelihood of every rung; ``accepted`` (T, W), ``swap_proposed`` and ``swap_accepted`` (T - 1,) int64 are
+        incremented.  Steps ``step0 .. step0 + n_steps - 1`` of the chain that ``seed`` names."""
+        if n_steps < 0 or step0 < 0 or pos.ndim != 3 or lnlike.shape != pos.shape[:2] or lnprior.shape != pos.shape[:2]:
+            raise ValueError("temper_block: inconsistent array shapes")
+        t, w, p = pos.shape
+        betas = _f64(betas)
+        if betas.shape != (t,):
+            raise ValueError("temper_block: betas must have one entry per rung")
+        if lnprior.dtype != np.float64 or not lnprior.flags.c_contiguous or not pos.flags.c_contiguous or \
+                not lnlike.flags.c_contiguous:
+            raise ValueError("temper_block needs C-contiguous arrays of the documented dtypes")
+        head, _tail, _keep = self._stretch_args("temper_block", plan, pos[0], lnlike[0], n_steps, None, None, None)
+        n_chain = 1
+        if chain is not None:
+            if chain.dtype != np.float64 or not chain.flags.c_contiguous or chain.ndim != 4 or \
+                    chain.shape[0] != n_steps or chain.shape[2:] != (w, p):
+                raise ValueError("temper_block: chain must be a C-contiguous float64 array of shape (steps, C, W, P)")
+            n_chain = chain.shape[1]
+        if lnlike_chain is not None and (lnlike_chain.dtype != np.float64 or not lnlike_chain.flags.c_contiguous or
+                                         lnlike_chain.shape != (n_steps, t, w)):
+            raise ValueError("temper_block: lnlike_chain must be a C-contiguous float64 array of shape (steps, T, W)")
+        for a, shape in ((accepted, (t, w)), (swap_proposed, (t - 1,)), (swap_accepted, (t - 1,))):
+            if a is not None and (a.dtype != np.int64 or a.shape != shape or not a.flags.c_contiguous):
+                raise ValueError("temper_block: accepted (T, W) and the swap counts (T - 1,) are C-contiguous int64 arrays")
+        d = TemperDesc()
+        d.map = head[1]._obj
+        d.n_temps, d.betas, d.n_chain_temps = t, _ptr(betas), n_chain
+
+        def ip(a):
+            return a.ctypes.data_as(_c_int64_p) if a is not None else None
+        args = (self.handle, ctypes.byref(d), int(n_steps), _ptr(pos), _ptr(lnlike), _ptr(lnprior),
+                int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), _ptr(chain), _ptr(lnlike_chain), ip(accepted), ip(swap_proposed),
+                ip(swap_accepted))
+        if self._prior_arg is not None:
+            rc = self.lib.mcd_temper_block_prior(*args, *self._prior_arg)
+        else:
+            rc = self.lib.mcd_temper_block(*args)
+        _check(self.lib, rc, "mcd_temper_block")
+        self._walkers = t * (w // 2)
+
+    def temper_info(self):
+        """Where the blocks of ``temper_block`` ran: {'device_blocks', 'host_blocks'} (``mcd_temper_info``)."""
+        a, b = ctypes.c_int64(), ctypes.c_int64()
+        _check(self.lib, self.lib.mcd_temper_info(self.handle, ctypes.byref(a), ctypes.byref(b)), "mcd_temper_info")
+        return {"device_blocks": a.value, "host_blocks": b.value}
+
     def stretch_info(self):
         """Where the blocks of ``stretch_move`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks', 'last_discard_status'}
         (``mcd_stretch_info``: resident on the device / host-driven / discarded by the device and re-run host-driven)."""
@@ -753,6 +830,12 @@ class Catalog(object):
 
     def set_option(self, key, value):
         _check(self.lib, self.lib.mcd_set_option(self.handle, key.encode(), int(value)), "mcd_set_option")
+        self.__dict__.setdefault("_options", {})[key] = int(value)
+
+    def get_option(self, key, default=None):
+        """The value ``set_option`` last gave option ``key`` through this object, else ``default`` (the library has no
+        query: a caller that changes an option for one evaluation restores what it found with this)."""
+        return self.__dict__.get("_options", {}).get(key, default)
 
     @property
     def last_kernel_ms(self):

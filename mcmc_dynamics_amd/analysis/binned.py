@@ -270,6 +270,10 @@ class BinnedConstantFit(ConstantFit):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")
 
+    def tempered(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: parallel tempering is defined for un-binned fits only (its rungs "
+                                  "take the place of the bins' lock-stepped ensembles)")
+
     def run_converged(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: run_converged drives one un-binned ensemble; run the bins with "
                                   "__call__ and judge them with chain_diagnostics / sampler.get_autocorr_time()")

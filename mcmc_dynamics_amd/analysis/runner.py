@@ -185,6 +185,108 @@ def elpd_compare(a, b, group=None):
     return {"elpd_diff": s_d, "se_diff": float(np.sqrt(n * max(var_i, 0.0))), "n_stars": int(n), "pointwise": d}
 
 
+# importance-sampling effective sample size of a stepping-stone pair below which ``evidence_summary`` warns
+EVIDENCE_PAIR_ESS_WARNING = 100.0
+EVIDENCE_BATCHES = 20              # batches of steps behind ``evidence_summary``'s ``se_batch``
+
+
+def _series_tau(series):
+    """Integrated autocorrelation time of a (W, steps) series in steps, >= 1 (``diagnostics.integrated_time`` on the
+    library's host loop; the estimate carried by its AutocorrError when the chain is short; the number of steps -- one
+    effective sample per walker -- when there is none)."""
+    from .. import diagnostics
+    chain = np.ascontiguousarray(np.swapaxes(series, 0, 1)[:, :, None])
+    n = chain.shape[0]
+    if n < 2 or np.all(chain == chain[0]):
+        return float(max(n, 1))
+    try:
+        tau = diagnostics.integrated_time(chain, context=None)
+    except diagnostics.AutocorrError as exc:
+        tau = exc.tau
+    tau = float(np.asarray(tau).reshape(-1)[0])
+    return min(max(tau, 1.0), float(n)) if np.isfinite(tau) else float(n)
+
+
+def evidence_summary(lnlike, betas, discard=0):
+    """Log marginal likelihood from a tempered run: ``lnlike`` (T, W, steps), the log-likelihood series of the rungs
+    (``TemperedSampler.lnlikelihood``), ``betas`` (T,) with ``betas[0] == 1`` and ``betas[-1] == 0`` (ValueError
+    otherwise), the first ``discard`` steps left out.
+
+    ``log_evidence``: the STEPPING-STONE estimator (Xie et al. 2011), sum over the pairs k of
+    ``pair_log_ratio[k]`` = log mean over rung k + 1's samples of exp((beta_k - beta_{k+1}) lnL), each by log-mean-exp.
+    It has no discretisation bias.  ``se``: per pair the delta-method variance Var(w) / (mean(w)^2 n_eff) over
+    n_eff = n / tau effective samples, tau the integrated autocorrelation time of that rung's lnL series
+    (``diagnostics.integrated_time``; its ``.tau`` when it raises for a short chain); the pair variances are summed
+    (``pair_se``).  The correlation BETWEEN rungs that the swaps introduce is neglected, which makes ``se`` optimistic;
+    ``se_batch`` is the cross-check that neglects nothing -- the standard error of the mean of the estimate on 20
+    consecutive batches of steps (it needs batches much longer than tau).  ``pair_ess``: the
+    importance-sampling effective sample size (sum w)^2 / sum w^2 of each pair; a value below 100 means the ladder is too
+    coarse there, and the function warns.
+
+    ``log_evidence_ti``: the thermodynamic integral, the trapezoid of the rungs' mean lnL over beta, with ``se_ti`` from
+    the same effective sample sizes -- a cross-check that is BIASED by the ladder's spacing (the trapezoid's error), which
+    ``se_ti`` does not contain.
+
+    The estimate is relative to the prior as the library evaluates it: int L pi~ / int pi~, where pi~ is the box times the
+    un-normalised truncated priors and the rung at beta = 0 samples pi~ / int pi~.  That IS the evidence under the
+    normalised prior, whatever the box volume or the truncation: nothing like log(hi - lo) is to be added."""
+    ll = np.asarray(lnlike, dtype=np.float64)
+    betas = np.asarray(betas, dtype=np.float64).reshape(-1)
+    if ll.ndim != 3 or ll.shape[0] != betas.size:
+        raise ValueError("lnlike must have shape (T, W, steps) with one rung per beta")
+    if betas.size < 2 or betas[0] != 1.0 or betas[-1] != 0.0 or np.any(np.diff(betas) >= 0.0):
+        raise ValueError("the evidence needs a ladder that decreases strictly from beta = 1 to beta = 0")
+    ll = ll[:, :, int(discard):]
+    T, W, steps = ll.shape
+    if steps < 2:
+        raise ValueError("no steps left after discard")
+    n = float(W * steps)
+    tau = np.array([_series_tau(ll[t]) for t in range(T)])
+    n_eff = n / tau
+    ratio, var, ess = np.empty(T - 1), np.empty(T - 1), np.empty(T - 1)
+    for k in range(T - 1):
+        a = (betas[k] - betas[k + 1]) * ll[k + 1].reshape(-1)
+        top = a.max()
+        w = np.exp(a - top)
+        mean = w.mean()
+        ratio[k] = top + np.log(mean)
+        var[k] = w.var(ddof=1) / (mean * mean * n_eff[k + 1])
+        ess[k] = w.sum() ** 2 / np.dot(w, w)
+    if np.any(ess < EVIDENCE_PAIR_ESS_WARNING):
+        bad = ", ".join("{0:g} -> {1:g} (ESS {2:.0f})".format(betas[k + 1], betas[k], ess[k])
+                        for k in np.flatnonzero(ess < EVIDENCE_PAIR_ESS_WARNING))
+        warnings.warn("evidence_summary: the ladder is too coarse between beta " + bad + ": the stepping-stone ratio of such "
+                      "a pair rests on a handful of samples; add rungs there")
+    # cross-check of `se` that neglects nothing: the estimate on EVIDENCE_BATCHES consecutive batches of steps (all rungs and
+    # walkers of a batch together, so the correlation between rungs and between walkers is in it), the standard error of
+    # their mean.  Needs batches much longer than tau; NaN when there are fewer than two steps per batch.
+    se_batch = float("nan")
+    if steps >= 2 * EVIDENCE_BATCHES:
+        edges = np.linspace(0, steps, EVIDENCE_BATCHES + 1).astype(int)
+        per_batch = np.zeros(EVIDENCE_BATCHES)
+        for k in range(T - 1):
+            a = (betas[k] - betas[k + 1]) * ll[k + 1]
+            top = a.max()
+            w = np.exp(a - top)
+            per_batch += [top + np.log(w[:, i0:i1].mean()) for i0, i1 in zip(edges[:-1], edges[1:])]
+        se_batch = float(per_batch.std(ddof=1) / np.sqrt(EVIDENCE_BATCHES))
+    means = ll.reshape(T, -1).mean(axis=1)
+    var_mean = ll.reshape(T, -1).var(axis=1, ddof=1) / n_eff
+    weight = np.zeros(T)
+    weight[:-1] += 0.5 * (betas[:-1] - betas[1:])
+    weight[1:] += 0.5 * (betas[:-1] - betas[1:])
+    return {"log_evidence": float(ratio.sum()), "se": float(np.sqrt(var.sum())), "se_batch": se_batch, "pair_log_ratio": ratio,
+            "pair_se": np.sqrt(var), "pair_ess": ess, "log_evidence_ti": float(np.dot(weight, means)),
+            "se_ti": float(np.sqrt(np.dot(weight * weight, var_mean))), "mean_lnlike": means, "tau": tau,
+            "betas": betas, "n_samples": int(n)}
+
+
+def bayes_factor(a, b):
+    """Log Bayes factor of two models from their ``evidence_summary`` results (``TemperedSampler.log_evidence``):
+    ``log_bf`` = a - b (positive: the data favour ``a``), ``se`` = hypot of the two standard errors (independent runs)."""
+    return {"log_bf": float(a["log_evidence"] - b["log_evidence"]), "se": float(np.hypot(a["se"], b["se"]))}
+
+
 # the central interval of the PIT whose complement ``ppc_summary`` reports: 5 % of the weight for a calibrated model
 PPC_TAIL = 0.025
 
@@ -654,6 +756,74 @@ class Runner(object):
             sampler.warmup_step_sizes.append(sampler.step_size)
             done += n
         sampler.reset()                                               # (the generator's step counter is not rewound)
+        sampler.reserve(n_steps)
+        sampler.run_mcmc(pos, n_steps)
+        return sampler
+
+    # ------------------------------------------------------------------ parallel tempering (new)
+    def _temper_block(self, betas, pos, lnlike, lnprior, seed, step0, n_steps, chain, lnlike_chain, accepted, swap_proposed,
+                      swap_accepted):
+        """One block of parallel-tempering steps inside the library (``_native.Catalog.temper_block``)."""
+        self._stretch_catalog(pos).temper_block(self._stretch_plan(), betas, pos, lnlike, lnprior, seed, step0, n_steps, chain,
+                                                lnlike_chain, accepted, swap_proposed, swap_accepted)
+
+    def _temper_lnlike(self, values):
+        """(n, P) -> (n,) log-likelihoods through the PLAIN kernels (option ``fast_path`` = 0 for this evaluation, then
+        back to what it was): what a tempered block evaluates with, so that the start of a run carries the same kernels'
+        values as every later row of ``lnlikelihood``."""
+        cat = self._stretch_catalog(values)
+        found = cat.get_option("fast_path", 1)
+        cat.set_option("fast_path", 0)
+        try:
+            return self.lnlike_batch(values)
+        finally:
+            cat.set_option("fast_path", found)
+
+    def improper_parameters(self):
+        """Names of the free parameters whose prior is improper: not two finite bounds and no normal / log-normal prior."""
+        plan = self._plan()
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        kind = np.zeros(plan.free_idx.size, dtype=np.int32) if plan.prior is None else np.asarray(plan.prior[0])
+        return [plan.names[int(i)] for j, i in enumerate(plan.free_idx)
+                if not (np.isfinite(lo[j]) and np.isfinite(hi[j])) and kind[j] == _native.PRIOR_FLAT]
+
+    def tempered(self, n_temps=16, n_walkers=64, n_steps=500, betas=None, beta_ratio=0.5, pos=None, seed=None, store_temps=1):
+        """Sample with parallel tempering (``sampler.TemperedSampler``; csrc/mcd_temper.h): ``n_temps`` ensembles of
+        ``n_walkers`` walkers on a ladder of inverse temperatures, ``n_steps`` steps.  Returns the sampler: its ``chain`` is
+        rung 0, the posterior; ``log_evidence(discard)`` the log marginal likelihood.  Burn-in is the caller's ``discard``.
+
+        ``betas``: the ladder, or by default ``sampler.default_ladder(n_temps, beta_ratio, proper)`` -- geometric with ratio
+        ``beta_ratio`` over ``n_temps - 1`` rungs and a final beta = 0 whenever the prior is proper (every free parameter
+        has two finite bounds or a normal / log-normal prior); with an improper prior there is no zero rung, and
+        ``log_evidence`` raises with the names of the unbounded parameters.  ``pos`` (W, P): the start of every rung,
+        default ``get_initials``; its log-likelihood is evaluated with the plain kernels in the block's launch shape
+        (``_temper_lnlike``).  ``store_temps``: positions are kept for that many rungs from 0.
+
+        ``expr`` / ``lnprior``-expression parameters and binned or non-float64 catalogues raise NotImplementedError, as for
+        ``hmc``."""
+        plan = self._plan()
+        ok, why_not = self.resident_ok()
+        if not ok:
+            raise NotImplementedError("Runner.tempered: " + why_not)
+        if self._precision != "f64":
+            raise NotImplementedError("Runner.tempered: tempered blocks need a float64 catalogue")
+        from ..sampler import TemperedSampler, default_ladder
+        improper = self.improper_parameters()
+        if betas is None:
+            betas = default_ladder(n_temps, beta_ratio, proper=not improper)
+        n_p = int(plan.free_idx.size)
+        pos = self.get_initials(n_walkers) if pos is None else pos
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.shape != (n_walkers, n_p):
+            raise ValueError("Array with starting values has invalid shape.")
+        lnprior_fn = None
+        if plan.prior is not None:
+            prior = plan.prior
+            lnprior_fn = lambda x: _native.prior_eval(prior, x)               # noqa: E731
+        sampler = TemperedSampler(n_walkers, n_p, betas, self._temper_block, self._temper_lnlike, lnprior_fn=lnprior_fn,
+                                  seed=seed, store_temps=store_temps, improper=improper)
+        logger.info("MCMC driver: parallel tempering, %d rungs of %d walkers, beta %g .. %g", sampler.ntemps, n_walkers,
+                    sampler.betas[0], sampler.betas[-1])
         sampler.reserve(n_steps)
         sampler.run_mcmc(pos, n_steps)
         return sampler

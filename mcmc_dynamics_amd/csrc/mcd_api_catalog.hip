@@ -466,6 +466,8 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
     if (cat->chain.h) (void)hipHostFree(cat->chain.h);
     if (cat->hmc.d) (void)hipFree(cat->hmc.d);
     if (cat->hmc.h) (void)hipHostFree(cat->hmc.h);
+    if (cat->temper.d) (void)hipFree(cat->temper.d);
+    if (cat->temper.h) (void)hipHostFree(cat->temper.h);
     delete cat;
     return MCD_OK;
 }

@@ -11,25 +11,11 @@
 
 using namespace mcd::host;
 
-namespace {
+MCD_HOST_BEGIN
 
-// ------------------------------------------------------------------------------------------------
-// mcd_stretch_move with the ensemble resident on the device (mcd_stretch.hip).  Runs the whole block as one chain of
-// launches and waits once.  *done = false when the block has to be run host-driven: the configuration is not covered, or
-// the device met something only the host loop handles (mcd::ChainStatus).  `pos`, `lnp` and `accepted` are then
-// untouched; the chain rows of a large block (cut into parts) may already hold rows of the discarded attempt, which the
-// host-driven re-run overwrites (and which stay if that re-run fails).
-// user <-> pinned copies of tens of MB (a binned block: 40 MB of random numbers in, 70 MB of chain rows out) on four
-// threads: one core moves ~10 GB/s, the copies would otherwise cost as much as the block's device time
-// The structured priors of a call: mcd_prior_desc checked and its derived constants (mcd_prior.h: prior_derive, libm, once
-// per call).  table.any() is false for a null descriptor and for one whose kinds are all flat: the call is then the
-// prior-free one, bit for bit.
-struct PriorHost {
-    std::vector<int32_t> kind;
-    std::vector<double> loc, scale, c0;
-    mcd::PriorTable table;
-};
-
+// The structured priors of a call (PriorHost: mcd_host.h): mcd_prior_desc checked and its derived constants (mcd_prior.h:
+// prior_derive, libm, once per call).  table.any() is false for a null descriptor and for one whose kinds are all flat: the
+// call is then the prior-free one, bit for bit.
 int prior_of(const mcd_prior_desc* p, int32_t n_dim, const char* who, PriorHost& out) {
     out.table = mcd::PriorTable();
     if (!p) return MCD_OK;
@@ -46,6 +32,8 @@ int prior_of(const mcd_prior_desc* p, int32_t n_dim, const char* who, PriorHost&
     return MCD_OK;
 }
 
+// user <-> pinned copies of tens of MB (a binned block: 40 MB of random numbers in, 70 MB of chain rows out) on four
+// threads: one core moves ~10 GB/s, the copies would otherwise cost as much as the block's device time
 void big_copy(void* dst, const void* src, size_t bytes) {
     constexpr size_t kSerial = (size_t)4 << 20;
     if (bytes < kSerial) { std::memcpy(dst, src, bytes); return; }
@@ -73,6 +61,16 @@ void big_copy(void* dst, const void* src, size_t bytes) {
     (void)started;
 }
 
+MCD_HOST_END
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------
+// mcd_stretch_move with the ensemble resident on the device (mcd_stretch.hip).  Runs the whole block as one chain of
+// launches and waits once.  *done = false when the block has to be run host-driven: the configuration is not covered, or
+// the device met something only the host loop handles (mcd::ChainStatus).  `pos`, `lnp` and `accepted` are then
+// untouched; the chain rows of a large block (cut into parts) may already hold rows of the discarded attempt, which the
+// host-driven re-run overwrites (and which stay if that re-run fails).
 // `seed` != nullptr: a seeded block (mcd_stretch_move_seeded) -- order / zz / thr / pick are null, a kernel generates the
 // numbers of absolute steps step0 .. step0 + n_steps - 1 on the device (mcd_rng.h, mcd_stretch.hip: chain_numbers_kernel)
 int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps, double* pos, double* lnp,

@@ -8,6 +8,7 @@
 //   mcd_api_catalog.hip    catalogues, work sets and chunk plans, the main kernel's launch shape, options, mcd_last_* queries
 //   mcd_api_eval.hip       staging, enqueue, sync, fetch; the per-star outputs of one parameter row
 //   mcd_api_chain.hip      the stretch-move block and the HMC block, each resident on the device or host-driven
+//   mcd_api_temper.hip     the parallel-tempering block in the same two forms
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
@@ -203,6 +204,13 @@ struct DeviceScratch {
     }
 };
 
+// The structured priors of a call, checked and derived by prior_of: `table` points into the vectors (or is empty)
+struct PriorHost {
+    std::vector<int32_t> kind;
+    std::vector<double> loc, scale, c0;
+    mcd::PriorTable table;
+};
+
 // ---- helpers that cross units (the comments are at the definitions) ----
 // mcd_api_ctx.hip
 int ctx_fail(mcd_ctx* ctx, const std::string& what);
@@ -216,6 +224,9 @@ const double* fast_pset_const(const mcd_catalog* cat, const Shard& sh, int level
 const void* main_records(const Shard& sh, const WorkSet& w);
 int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
 int64_t direct_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
+// mcd_api_chain.hip
+int prior_of(const mcd_prior_desc* p, int32_t n_dim, const char* who, PriorHost& out);
+void big_copy(void* dst, const void* src, size_t bytes);
 // mcd_api_eval.hip
 int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
 int sync_all(mcd_catalog* cat);
@@ -303,6 +314,9 @@ struct mcd_catalog {
     // Hamiltonian Monte Carlo blocks (mcd_hmc_block): trajectory state and chain rows of the resident block, its pinned mirror
     mcd::host::ChainArena hmc;
     int64_t hmc_device_blocks = 0, hmc_host_blocks = 0;
+    // parallel-tempering blocks (mcd_temper_block): state, numbers, scratch and rows of the resident block, its pinned mirror
+    mcd::host::ChainArena temper;
+    int64_t temper_device_blocks = 0, temper_host_blocks = 0;
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet

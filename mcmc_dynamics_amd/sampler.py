@@ -424,3 +424,161 @@ class HMCSampler(object):
             self.n_calls += 1 + n * self.n_leap
             done += n
         return pos, lnp, None
+
+
+def default_ladder(n_temps, beta_ratio=0.5, proper=True):
+    """The default ladder of inverse temperatures: geometric from 1 with ratio ``beta_ratio``, ending -- when the prior is
+    ``proper`` -- with a rung at beta = 0, which samples the prior and anchors the evidence: ``n_temps - 1`` geometric
+    rungs and the zero.  With an improper prior beta = 0 has no distribution: ``n_temps`` geometric rungs, no zero."""
+    n_temps = int(n_temps)
+    if n_temps < 1 or not (0.0 < beta_ratio < 1.0):
+        raise ValueError("n_temps >= 1 and 0 < beta_ratio < 1")
+    if proper and n_temps > 1:
+        return np.concatenate([float(beta_ratio) ** np.arange(n_temps - 1), [0.0]])
+    return float(beta_ratio) ** np.arange(n_temps)
+
+
+class TemperedSampler(object):
+    """Parallel tempering: ``len(betas)`` ensembles of ``nwalkers`` walkers, rung t sampling prior(x) L(x)^betas[t]
+    (``betas[0] == 1``, strictly decreasing, >= 0), each advanced by the stretch move, adjacent rungs exchanging walkers by
+    a Metropolis swap (csrc/mcd_temper.h; the reference has one ensemble at one temperature).  It crosses between separated
+    modes, which one ensemble cannot, and its rungs' log-likelihood series give the marginal likelihood
+    (``log_evidence``).  A sampler the user asks for by name (``Runner.tempered``); rung 0 is the posterior and carries the
+    attributes the other samplers expose.
+
+    ``block_fn(betas, pos, lnlike, lnprior, seed, step0, n_steps, chain, lnlike_chain, accepted, swap_proposed,
+    swap_accepted)`` advances ``pos`` (T, W, P) and ``lnlike`` (T, W) in place by a block of steps and writes ``lnprior``
+    (``Runner._temper_block``: ``mcd_temper_block``, resident on the device where it can be).  ``lnlike_fn((n, P)) ->
+    (n,)`` evaluates the start, in two calls of T W/2 rows (``Runner._temper_lnlike``: the plain kernels, as the block); ``lnprior_fn((n, P)) -> (n,)``, or None for a flat prior, is what ``lnprobability`` adds
+    to rung 0's log-likelihood.  ``store_temps``: the positions of rungs 0 .. store_temps - 1 are kept (the log-likelihood
+    of every rung always is).  ``improper``: names of the free parameters without a proper prior (``log_evidence`` then
+    raises).
+
+    The numbers of a step are a function of (seed, step counter, rung, walker); the step counter ``rng_step`` only ever
+    grows, as ``HMCSampler``'s."""
+
+    def __init__(self, nwalkers, ndim, betas, block_fn, lnlike_fn, lnprior_fn=None, seed=None, store_temps=1, improper=()):
+        betas = np.array(betas, dtype=np.float64).reshape(-1)
+        if betas.size < 1 or betas[0] != 1.0 or np.any(np.diff(betas) >= 0.0) or betas[-1] < 0.0 or not np.isfinite(betas).all():
+            raise ValueError("betas must start at 1 and decrease strictly to a value >= 0")
+        if int(nwalkers) < 2 or int(nwalkers) % 2:
+            raise ValueError("nwalkers must be even and >= 2")
+        if not 1 <= int(store_temps) <= betas.size:
+            raise ValueError("store_temps must lie in 1 .. len(betas)")
+        self.nwalkers, self.ndim, self.betas, self.ntemps = int(nwalkers), int(ndim), betas, int(betas.size)
+        self.block_fn, self.lnlike_fn, self.lnprior_fn = block_fn, lnlike_fn, lnprior_fn
+        self.store_temps, self.improper = int(store_temps), tuple(improper)
+        self.seed64 = int(seed) & 0xFFFFFFFFFFFFFFFF if seed is not None else \
+            (int(np.random.randint(0, 2 ** 32)) << 32) | int(np.random.randint(0, 2 ** 32))
+        self.block_steps = 64                    # steps per library call (NOT part of the stream's definition)
+        self.rng_step = 0                        # the generator's step counter: never rewound
+        self.reset()
+
+    def reset(self):
+        """Drop the chain and the counts.  The generator's step counter stays."""
+        self.iteration = 0
+        self._chain = np.empty((0, self.store_temps, self.nwalkers, self.ndim))
+        self._lnlike = np.empty((0, self.ntemps, self.nwalkers))
+        self._accepted = np.zeros((self.ntemps, self.nwalkers), dtype=np.int64)
+        self._swap_proposed = np.zeros(self.ntemps - 1, dtype=np.int64)
+        self._swap_accepted = np.zeros(self.ntemps - 1, dtype=np.int64)
+
+    def reserve(self, total_steps):
+        """Chain storage for ``total_steps`` steps in all; the rows already held are kept."""
+        total = int(total_steps)
+        if total > self._chain.shape[0]:
+            for name in ("_chain", "_lnlike"):
+                old = getattr(self, name)
+                new = np.empty((total,) + old.shape[1:])
+                new[:self.iteration] = old[:self.iteration]
+                setattr(self, name, new)
+
+    @property
+    def chain(self):
+        """Rung 0, the posterior: (nwalkers, nsteps, ndim), the layout the reference pickles (runner.py:471-472)."""
+        return np.swapaxes(self._chain[:self.iteration, 0], 0, 1)
+
+    @property
+    def flatchain(self):
+        return self._chain[:self.iteration, 0].reshape(-1, self.ndim)
+
+    @property
+    def lnlikelihood(self):
+        """(ntemps, nwalkers, nsteps): the log-likelihood of every rung's walkers after every step."""
+        return np.transpose(self._lnlike[:self.iteration], (1, 2, 0))
+
+    @property
+    def lnprobability(self):
+        """Rung 0: log-likelihood plus log-prior, (nwalkers, nsteps)."""
+        ll = np.swapaxes(self._lnlike[:self.iteration, 0], 0, 1)
+        if self.lnprior_fn is None:
+            return ll
+        lp = np.asarray(self.lnprior_fn(self._chain[:self.iteration, 0].reshape(-1, self.ndim)))
+        return ll + np.swapaxes(lp.reshape(self.iteration, self.nwalkers), 0, 1)
+
+    @property
+    def acceptance_fraction(self):
+        """(ntemps, nwalkers): accepted stretch-move proposals per step, by slot (rung, walker index)."""
+        return self._accepted / float(max(1, self.iteration))
+
+    @property
+    def swap_acceptance_fraction(self):
+        """(ntemps - 1,): accepted over proposed swaps of the pairs (t, t + 1)."""
+        return self._swap_accepted / np.maximum(1, self._swap_proposed).astype(np.float64)
+
+    def get_chain(self, temp=0, discard=0, flat=False):
+        """Steps first: (nsteps, nwalkers, ndim) of rung ``temp`` (< store_temps)."""
+        if not 0 <= int(temp) < self.store_temps:
+            raise ValueError("positions are stored for rungs 0 .. {0} (store_temps)".format(self.store_temps - 1))
+        c = self._chain[discard:self.iteration, int(temp)]
+        return c.reshape(-1, self.ndim) if flat else c
+
+    def get_log_prob(self, discard=0, flat=False):
+        lp = np.swapaxes(self.lnprobability, 0, 1)[discard:]
+        return lp.reshape(-1) if flat else lp
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """The integrated autocorrelation time per parameter of rung 0, in steps (``diagnostics.integrated_time``)."""
+        from .diagnostics import sampler_autocorr_time
+        return sampler_autocorr_time(self, discard=discard, thin=thin, **kwargs)
+
+    def log_evidence(self, discard=0):
+        """``analysis.runner.evidence_summary`` of this run's log-likelihood series after ``discard`` steps."""
+        if self.improper:
+            raise ValueError("log_evidence needs a proper prior: no finite bounds and no normal / log-normal prior on " +
+                             ", ".join(self.improper))
+        from .analysis.runner import evidence_summary
+        return evidence_summary(self.lnlikelihood, self.betas, discard=discard)
+
+    def run_mcmc(self, initial_state, nsteps, **kwargs):
+        """Advance every rung by ``nsteps``.  ``initial_state``: (W, P), the same start for every rung, or (T, W, P).
+        Returns ``(pos (T, W, P), lnlike (T, W), None)``."""
+        pos = np.array(initial_state, dtype=np.float64)
+        if pos.shape == (self.nwalkers, self.ndim):
+            pos = np.repeat(pos[None], self.ntemps, axis=0)
+        if pos.shape != (self.ntemps, self.nwalkers, self.ndim):
+            raise ValueError("incompatible input dimensions {0}".format(pos.shape))
+        if not np.isfinite(pos).all():
+            raise ValueError("At least one parameter value was infinite or NaN")
+        pos = np.ascontiguousarray(pos)
+        nsteps = int(nsteps)
+        if self.iteration + nsteps > self._chain.shape[0]:
+            self.reserve(max(self.iteration + nsteps, 2 * self._chain.shape[0]))
+        # the start's log-likelihood in the launch shape of a half step, T W/2 rows: with ``Runner._temper_lnlike`` behind
+        # ``lnlike_fn`` these are the values the block's own kernels would give (the order of a sum belongs to the row count)
+        flat = pos.reshape(-1, self.ndim)
+        rows = flat.shape[0] // 2
+        lnlike = np.ascontiguousarray(np.concatenate([np.asarray(self.lnlike_fn(flat[:rows]), dtype=np.float64),
+                                                      np.asarray(self.lnlike_fn(flat[rows:]), dtype=np.float64)])
+                                      .reshape(self.ntemps, self.nwalkers))
+        lnprior = np.zeros((self.ntemps, self.nwalkers))
+        done = 0
+        while done < nsteps:
+            n = min(max(1, int(self.block_steps)), nsteps - done)
+            it = self.iteration
+            self.block_fn(self.betas, pos, lnlike, lnprior, self.seed64, self.rng_step, n, self._chain[it:it + n],
+                          self._lnlike[it:it + n], self._accepted, self._swap_proposed, self._swap_accepted)
+            self.iteration += n
+            self.rng_step += n
+            done += n
+        return pos, lnlike, None
