@@ -542,6 +542,13 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      instruction per term fewer, results equal to rounding; refused per call where the range guard
  *                      cannot place every mixture value, scaled by up to 1.2016, inside the rescale interval.  0: never
  *                      (the results of a library without this option, bit for bit).  mcd_last_exp_split tells.
+ *   "root_quad"     1 (default): in a launch with the split exponent offset, a chunk in the direct form whose 32-star blocks
+ *                      (records 32 b .. 32 b + 31 of the verr-ordered array) are each narrower than 2^-17.5 (verr^2 + sigma^2)
+ *                      in half-width for every walker of the wave replaces the cubic by a quadratic per block, whose
+ *                      coefficients the record preparation leaves in the blocks' first two records: one float64
+ *                      instruction per term fewer, relative error of the root <= 4.9e-16, results equal to rounding.  0: never
+ *                      (the results of a library without this option, bit for bit).  mcd_last_root_quad tells,
+ *                      mcd_last_quad_chunks counts the chunks.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -590,6 +597,12 @@ int64_t mcd_last_direct_chunks(const mcd_catalog* cat);
 /* 1 when the direct chunks of the most recent main-kernel launch ran with the split exponent offset (option "exp_split"), 0
  * when not (option off, refused by the guard, another kernel family, the resident chain), -1 before the first launch. */
 int mcd_last_exp_split(const mcd_catalog* cat);
+/* 1 when the most recent main-kernel launch offered its direct chunks the quadratic form on 32-star bands (option
+ * "root_quad" on a launch with the split exponent offset), 0 when not, -1 before the first launch. */
+int mcd_last_root_quad(const mcd_catalog* cat);
+/* ... and the chunks in which every wave took it, counted as mcd_last_direct_chunks is and never more than that; 0 and -1
+ * as there. */
+int64_t mcd_last_quad_chunks(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

@@ -108,6 +108,8 @@ SYMBOLS = {
     "mcd_last_series_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_direct_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_exp_split": (ctypes.c_int, [ctypes.c_void_p]),
+    "mcd_last_root_quad": (ctypes.c_int, [ctypes.c_void_p]),
+    "mcd_last_quad_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
@@ -734,6 +736,18 @@ class Catalog(object):
         0 not; -1 before any launch."""
         return self.lib.mcd_last_exp_split(self.handle)
 
+    @property
+    def last_root_quad(self):
+        """1: the last main-kernel launch offered its direct chunks the quadratic series root on 32-star bands (option
+        ``root_quad`` on a launch with the split exponent offset); 0 not; -1 before any launch."""
+        return self.lib.mcd_last_root_quad(self.handle)
+
+    @property
+    def last_quad_chunks(self):
+        """... and the chunks in which every wave took it (counted on the host; never more than ``last_direct_chunks``);
+        0 none; -1 before any launch."""
+        return self.lib.mcd_last_quad_chunks(self.handle)
+
     def hmc_block(self, plan, chol, step_size, n_leap, pos, lnp, seed, step0, n_steps, chain=None, lnprob_chain=None,
                   accepted=None, energy_error=None, jitter=0.1):
         """``mcd_hmc_block``: advance W independent chains by ``n_steps`` Hamiltonian Monte Carlo steps of ``n_leap``
@@ -881,7 +895,7 @@ class Catalog(object):
                                                        ctypes.byref(ch), ctypes.byref(rb)), "mcd_last_launch_info")
         return {"workgroups": wg.value, "walker_tile": tile.value, "chunks": ch.value, "record_bytes": rb.value,
                 "series_chunks": self.last_series_chunks, "direct_chunks": self.last_direct_chunks,
-                "exp_split": self.last_exp_split}
+                "exp_split": self.last_exp_split, "root_quad": self.last_root_quad, "quad_chunks": self.last_quad_chunks}
 
     def close(self):
         if getattr(self, "handle", None):

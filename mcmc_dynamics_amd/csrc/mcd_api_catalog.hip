@@ -157,6 +157,7 @@ const Option kOptions[] = {
     {"verr_sorted", -1, 1, "verr_sorted: -1 (by record volume, default), 0 (catalogue order) or 1 (sorted by verr)", true, true, MCD_SET(c->verr_sorted = (int)v)},
     {"root_series", 0, 1, "root_series: 1 (series root on the narrow chunks of verr-sorted records, default) or 0 (never)", false, false, MCD_SET(c->root_series = (int)v)},
     {"exp_split", 0, 1, "exp_split: 1 (split exponent offset in the direct chunks where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->exp_split = (int)v)},
+    {"root_quad", 0, 1, "root_quad: 1 (quadratic series root on 32-star bands where a direct chunk admits it, default) or 0 (never)", false, false, MCD_SET(c->root_quad = (int)v)},
     {"root_direct", 0, 1, "root_direct: 1 (direct form of the series root where a chunk admits it, default) or 0 (delta form only)", false, false, MCD_SET(c->root_direct = (int)v)},
     {"prefetch", -1, 1, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)", false, false, MCD_SET(c->prefetch = (int)v)},
     {"spin_us", 0, kMax, "spin_us must be >= 0", false, false, MCD_SET(c->spin_us = v)},
@@ -189,6 +190,7 @@ LaunchShape main_launch_shape(mcd_catalog* cat, const Shard& sh, const WorkSet& 
     shape.rerun_flag = coll ? nullptr : out_buf + n_out;
     shape.root_series = w.sorted && cat->root_series != 0;
     shape.root_direct = shape.root_series && cat->root_direct != 0;
+    shape.root_quad = shape.root_direct && cat->root_quad != 0;          // (acts only with the split exponent offset)
     return shape;
 }
 
@@ -212,6 +214,15 @@ int64_t direct_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, 
     const mcd::ParamRanges pr = mcd::table_ranges(cat->model, cat->free_centre, cat->k, params, n_rows);
     if (!pr.finite) return 0;
     return (int64_t)(std::upper_bound(w.direct_need.begin(), w.direct_need.end(), pr.s2_min) - w.direct_need.begin());
+}
+
+// ... of which in the quadratic form on 32-star bands (option "root_quad"; the caller knows whether the launch holds the
+// third vote at all: mcd_internal.h: root_quad_launch)
+int64_t quad_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows) {
+    if (!w.sorted || !cat->root_series || !cat->root_direct || !cat->root_quad || level != 2 || w.quad_need.empty()) return 0;
+    const mcd::ParamRanges pr = mcd::table_ranges(cat->model, cat->free_centre, cat->k, params, n_rows);
+    if (!pr.finite) return 0;
+    return (int64_t)(std::upper_bound(w.quad_need.begin(), w.quad_need.end(), pr.s2_min) - w.quad_need.begin());
 }
 
 // the fast BGFIXED kernel leaves the walker-independent sum of lnL_bg to the reduction
@@ -261,7 +272,9 @@ int build_workset(mcd_catalog* cat, Shard& sh, int64_t n_walkers, WorkSet** out)
         w.series_need = mcd::series_thresholds(plan, sh.sorted_e2.data());
         w.direct_need = mcd::direct_thresholds(plan, sh.sorted_e2.data());
     }
-    const std::vector<double> split_const = sorted ? mcd::exp_split_chunk_consts(plan, sh.sorted_nbf.data()) : std::vector<double>();
+    const std::vector<double> split_const =
+        sorted ? mcd::exp_split_chunk_consts(plan, sh.sorted_nbf.data(), sh.sorted_e2.data(), sh.n) : std::vector<double>();
+    if (sorted) w.quad_need = mcd::quad_thresholds(plan, sh.sorted_e2.data(), split_const.data() + 1, 2);
     {
         // balanced plans with an even number of workgroups per CU run as half as many 8-wave workgroups that add their
         // chunks' sums up themselves: half (to an eighth of) the partial sums per walker (mcd_kernels.hip: loglike_kernel)
@@ -579,6 +592,8 @@ int64_t mcd_last_direct_chunks(const mcd_catalog* cat) { return cat ? cat->last_
 
 int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
 int mcd_last_exp_split(const mcd_catalog* cat) { return cat ? cat->last_exp_split : -1; }
+int mcd_last_root_quad(const mcd_catalog* cat) { return cat ? cat->last_root_quad : -1; }
+int64_t mcd_last_quad_chunks(const mcd_catalog* cat) { return cat ? cat->last_quad_chunks : -1; }
 
 int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_theta) {
     if (!cat) return -1;

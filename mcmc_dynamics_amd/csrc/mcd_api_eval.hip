@@ -117,6 +117,7 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
                                                       b ? narrow_rescale : 0);
         w->series_chunks = series_chunk_count(cat, *w, fast, params, n_rows);
         w->direct_chunks = direct_chunk_count(cat, *w, fast, params, n_rows);
+        w->quad_chunks = quad_chunk_count(cat, *w, fast, params, n_rows);
         w->staged = true;
     }
     cat->cur_walkers = n_walkers;
@@ -218,7 +219,9 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
             shape.split_const = w.d_split_const;
         }
         cat->last_exp_split = mcd::exp_split_launch(shape) ? 1 : 0;
-        if (&sh == &cat->shards.front()) cat->last_series_chunks = cat->last_direct_chunks = 0;
+        cat->last_root_quad = mcd::root_quad_launch(shape) ? 1 : 0;
+        if (&sh == &cat->shards.front()) cat->last_series_chunks = cat->last_direct_chunks = cat->last_quad_chunks = 0;
+        cat->last_quad_chunks += cat->last_root_quad && shape.fast == 2 ? w.quad_chunks : 0;
         cat->last_series_chunks += shape.root_series && shape.fast == 2 ? w.series_chunks : 0;
         cat->last_direct_chunks += shape.root_direct && shape.fast == 2 ? w.direct_chunks : 0;
         w.launch_tag = coll ? 0.0 : (double)(++cat->launch_seq);

@@ -257,6 +257,28 @@ inline std::vector<double> direct_thresholds(const ChunkPlan& plan, const double
     return need;
 }
 
+// Smallest sigma^2 with which such a chunk also takes the quadratic form on 32-star bands (mcd_math.h: RootQuad::quad_ok:
+// H <= 2^-17.5 (centre + sigma^2), H the largest half-width of a block the chunk touches), up to rounding
+inline double quad_threshold(double e_first, double e_last, double H) {
+    const double need = std::max(direct_threshold(e_first, e_last), H * 0x1.6a09e667f3bcdp+17 - (0.5 * e_first + 0.5 * e_last));
+    return need == need ? need : std::numeric_limits<double>::infinity();
+}
+
+// ... of every chunk of `plan` that is not flagged general; ascending.  chunk_width[c]: H of chunk c (mcd_exp_split.h:
+// quad_chunk_width, +inf where the chunk cannot take the form).  Chunk by chunk no smaller than direct_thresholds.
+inline std::vector<double> quad_thresholds(const ChunkPlan& plan, const double* sorted_e2, const double* chunk_width,
+                                           size_t width_stride = 1) {
+    std::vector<double> need;
+    need.reserve(plan.chunks.size());
+    for (size_t c = 0; c < plan.chunks.size(); ++c) {
+        const Chunk& ch = plan.chunks[c];
+        if (ch.count <= 0 || (!plan.general.empty() && plan.general[c])) continue;
+        need.push_back(quad_threshold(sorted_e2[ch.begin], sorted_e2[ch.begin + ch.count - 1], chunk_width[c * width_stride]));
+    }
+    std::sort(need.begin(), need.end());
+    return need;
+}
+
 // Walker-independent part of the fixed-background likelihoods: sum of lnL_bg over the shard's stars of each parameter
 // set (Neumaier-compensated).  Added once per output by the reduce kernel when a fast mixture kernel ran.
 inline std::vector<double> pset_background_sums(const double* lnlike_bg, const std::vector<int64_t>& bin_offsets,

@@ -105,8 +105,9 @@ struct WorkSet {
     mcd::Chunk* d_chunks = nullptr;
     int64_t* d_offsets = nullptr;      // [n_psets + 1] chunk offsets
     uint8_t* d_chunk_general = nullptr;   // [n_chunks] chunks excluded from the narrow-range variant; null when there are none
-    double* d_split_const = nullptr;      // [n_chunks] sorted: what a direct chunk run with the split exponent offset adds to
-                                          // its sum (mcd_exp_split.h: exp_split_chunk_consts)
+    double* d_split_const = nullptr;      // [n_chunks][2] sorted: what a direct chunk run with the split exponent offset adds
+                                          // to its sum, and the largest half-width of a 32-star block it touches
+                                          // (mcd_exp_split.h: exp_split_chunk_consts)
     double* d_params = nullptr;        // [n_psets][W][K]
     void* d_wpar = nullptr;            // [n_psets][W][KD]
     double* d_partials = nullptr;      // [roundup64(W) / 8][n_chunks][8]
@@ -148,6 +149,9 @@ struct WorkSet {
     std::vector<double> direct_need;   // sorted: ... and the smallest sigma^2 with which the chunk also passes the vote on the
                                        // direct form of the series (mcd_math.h: RootDirect)
     int64_t direct_chunks = 0;         // chunks of the staged batch every wave of which takes the direct form
+    std::vector<double> quad_need;     // sorted: ... and the smallest sigma^2 with which the chunk passes the third vote too
+                                       // (mcd_math.h: RootQuad; mcd_chunks.h: quad_thresholds)
+    int64_t quad_chunks = 0;           // chunks of the staged batch every wave of which takes the quadratic form
 };
 
 // device arena of the resident stretch-move chain and its pinned host mirror (same layout, see stretch_block_device)
@@ -224,6 +228,7 @@ const double* fast_pset_const(const mcd_catalog* cat, const Shard& sh, int level
 const void* main_records(const Shard& sh, const WorkSet& w);
 int64_t series_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
 int64_t direct_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
+int64_t quad_chunk_count(const mcd_catalog* cat, const WorkSet& w, int level, const double* params, int64_t n_rows);
 // mcd_api_chain.hip
 int prior_of(const mcd_prior_desc* p, int32_t n_dim, const char* who, PriorHost& out);
 void big_copy(void* dst, const void* src, size_t bytes);
@@ -282,6 +287,8 @@ struct mcd_catalog {
                                        // guard admits it (mcd_guard.h: exp_split_admitted), 0 never
     int root_direct = 1;               // option "root_direct": 1 the direct form of the series where a chunk admits it, 0 the
                                        // delta form on every series chunk
+    int root_quad = 1;                 // option "root_quad": 1 the quadratic form on 32-star bands where a direct chunk of a
+                                       // launch with the split exponent offset admits it (mcd_math.h: RootQuad), 0 never
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
                                        // small enough, 0 never, m > 0 forced with m workgroups per CU
     int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
@@ -322,6 +329,9 @@ struct mcd_catalog {
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
     int last_exp_split = -1;           // 1: the direct chunks of the last main-kernel launch ran with the split exponent offset,
                                        // 0 not (-1: no launch yet)
+    int last_root_quad = -1;           // 1: the last main-kernel launch held the third vote (option "root_quad" on a launch with
+                                       // the split exponent offset), 0 not (-1: no launch yet)
+    int64_t last_quad_chunks = -1;     // chunks of that launch in the quadratic form (host count), -1: no launch yet
     int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };
 

@@ -31,8 +31,10 @@ struct LaunchShape {
                                     // per-chunk series root (mcd_math.h: RootSeries); f64 only
     bool root_direct = false;       // ... and its direct form where a chunk admits it (mcd_math.h: RootDirect)
     const void* records_split = nullptr;    // ... with the split exponent offset (option "exp_split"): the direct chunks read
-    const double* split_const = nullptr;    // this array in place of the records and add split_const[chunk] (mcd_exp_split.h);
+    const double* split_const = nullptr;    // this array in place of the records and add split_const[2 chunk] (mcd_exp_split.h);
                                             // null: the direct form as it is
+    bool root_quad = false;         // ... and of those the chunks that admit it run the quadratic form on 32-star bands
+                                    // (option "root_quad"; mcd_math.h: RootQuad); acts only where exp_split_launch holds
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };
@@ -66,6 +68,9 @@ inline bool exp_split_launch(const LaunchShape& sh) {
     return sh.fast == 2 && sh.model == MODEL_BGFIXED && !sh.free_centre && sh.precision == 0 && sh.root_series &&
            sh.root_direct && sh.records_split != nullptr && sh.split_const != nullptr;
 }
+
+// ... and those that admit it in the quadratic form on 32-star bands (what mcd_last_root_quad reports)
+inline bool root_quad_launch(const LaunchShape& sh) { return sh.root_quad && exp_split_launch(sh); }
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& shape, const void* records, const Chunk* chunks,
                           int64_t n_chunks, const void* wpar, double* partials, int64_t n_walkers);

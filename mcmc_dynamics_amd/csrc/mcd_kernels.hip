@@ -113,9 +113,12 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // BOUNDED: the bounded sub-variant of the narrow-range BGFIXED loop (fixed centre, with prefetch; chunk_bgfixed_fast<.., BOUNDED>)
 // for the chunks that take the narrow-range form, rescaling after every `narrow_iters` 8-star iterations.
 // root_series: `recs` is sorted by verr and the level-2 BGFIXED fixed-centre loops may take the series root (RootSeries): 1
-// its delta form only, 2 the direct form where a chunk admits it (RootDirect).
+// its delta form only, 2 the direct form where a chunk admits it (RootDirect), 3 (launches with recs_split) the quadratic
+// form on 32-star bands where a direct chunk admits it (RootQuad; the block constants sit in recs_split, the chunk's widest
+// block in split_const).
 // recs_split (null: none): the split-offset records of a launch with option "exp_split" (mcd_exp_split.h), in the order and
-// stride of `recs`, read by the direct chunks in its place; split_const[chunk]: what such a chunk adds to its sum.
+// stride of `recs`, read by the direct chunks in its place; split_const[2 chunk]: what such a chunk adds to its sum,
+// split_const[2 chunk + 1]: the largest half-width of a 32-star block it touches (mcd_exp_split.h: exp_split_chunk_consts).
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
 __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
                                                                  const Chunk* __restrict__ chunks,
@@ -140,6 +143,10 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
     // the kernels with the narrow-range BGFIXED variant keep the exponent-biased table (mcd_math.h: exp_tab_scaled)
     constexpr bool kTabBiased = kUsesExpTab && FAST == 2 && MODEL == MODEL_BGFIXED;
     __shared__ double combine_lds[kCombine ? WAVES : 1][kCombine ? kWave : 1];
+    // the kernels that hold the quadratic series loop park what only its per-block fold reads (QuadArgs::park): 5 doubles
+    // per lane, 10 KiB per 256 threads
+    constexpr bool kQuad = kTabBiased && !FREE && FAST == 2;
+    __shared__ double quad_lds[kQuad ? 5 * kThreads : 1];
     if constexpr (kUsesExpTab) {
         static_assert(kExpTabSize % kThreads == 0, "whole table entries per thread");
         const double* __restrict__ src = exp_table_is_sqrt2_scaled(MODEL) ? kExpTabSqrt2Device : kExpTabDevice;
@@ -205,10 +212,21 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
             // general fast form; the flag is wave-uniform (one scalar byte load), so this is a scalar branch
             // (the narrow-range profile variant without background has no per-star conditions: no flags, one form)
             const bool general = bg_kind(MODEL) != BG_NONE && chunk_general != nullptr && chunk_general[chunk_id] != 0;
-            if (general) result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
-            else result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(
-                     chunk_recs, ch.count, w, denormal, exptab_lds, narrow_iters, root_series != 0, root_series > 1,
-                     recs_split ? (RecPtr<T>)(recs_split + ch.begin * ND) : (RecPtr<T>) nullptr, split_const + chunk_id);
+            if (general) {
+                result = chunk_loglike<MODEL, FREE, T, A, 1, PF, kTabBiased>(chunk_recs, ch.count, w, denormal, exptab_lds);
+            } else {
+                // (formed on this branch only: in front of the general / narrow test it made hipcc place the general form
+                // behind the five loop copies and keep sigma^2 in registers across all of them, 66 VGPRs)
+                QuadArgs quad;
+                if constexpr (kQuad) {
+                    quad = quad_args(ch.begin, n_records, root_series > 2);
+                    quad.park = (QuadParkPtr)quad_lds + wave * kWave;
+                    quad.stride = kThreads;
+                }
+                result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(
+                         chunk_recs, ch.count, w, denormal, exptab_lds, narrow_iters, root_series != 0, root_series > 1,
+                         recs_split ? (RecPtr<T>)(recs_split + ch.begin * ND) : (RecPtr<T>) nullptr, split_const + 2 * chunk_id, quad);
+            }
         } else {
             result = chunk_loglike<MODEL, FREE, T, A, FAST, PF>(chunk_recs, ch.count, w, denormal, exptab_lds);
         }
@@ -349,11 +367,12 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
     constexpr bool kCanBound = FAST == 2 && MODEL == MODEL_BGFIXED && !FREE && sizeof(T) == 8 && sizeof(A) == 8;
     const bool bounded = kCanBound && sh.prefetch && narrow_bounded_launch(sh);
     const int narrow_iters = bounded ? sh.narrow_rescale / 8 : 1;
+    const int root_level = sh.root_series ? (sh.root_direct ? (root_quad_launch(sh) ? 3 : 2) : 1) : 0;     // (loglike_kernel: root_series)
 #define MCD_LAUNCH_MAIN(PF_, WAVES_, BOUNDED_)                                                                               \
     hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
-                       sh.chunk_general, n_slots, narrow_iters, sh.root_series ? (sh.root_direct ? 2 : 1) : 0,                \
+                       sh.chunk_general, n_slots, narrow_iters, root_level,                                                   \
                        (const T*)(exp_split_launch(sh) ? sh.records_split : nullptr), sh.split_const)
     // bounded, else prefetch, else plain -- once, for a workgroup of decltype(waves)::value waves
     auto launch = [&](auto waves) {

@@ -723,22 +723,106 @@ MCD_HD double exp_poly_steps(double rv, double s1) {
 // coefficient is rounded as often as RootDirect's: G0s = fl(c G0) is off by eg = c G0 - G0s, which comes out exactly and
 // joins G0's own error in the one last FMA of c0 (eg / G0s to first order, with 1 / G0 = m0 G0 / 4 since G0^2 = 4 / m0)
 struct RootDirectSplit : RootDirect {
-    MCD_HD void setup_scaled(double eb, double s2, double scale) {
+    // c1, c2, c3 and what c0's one last FMA is made of: c0 = fma(G0s, A, G0s); returns q
+    MCD_HD double setup_parts(double eb, double s2, double scale, double& G0s, double& A) {
         RootCentre c;
         c.setup(eb, s2);
         const double q = c.q;
-        const double G0s = c.G0 * scale;
+        G0s = c.G0 * scale;
         const double eg = fma_(c.G0, scale, -G0s);
         const double rho = c.p * c.inv;
         const double P = rho * fma_(rho, fma_(rho, 0.3125, 0.375), 0.5);
-        c0 = fma_(G0s, (c.corr + P) + eg * ((0.25 / scale) * (c.m0 * c.G0)), G0s);
+        A = (c.corr + P) + eg * ((0.25 / scale) * (c.m0 * c.G0));
         const double gq = G0s * q;
         c1 = -gq * fma_(rho, fma_(rho, 0.9375, 0.75), 0.5);
         const double gq2 = gq * q;
         c2 = gq2 * fma_(rho, 0.9375, 0.375);
         c3 = -0.3125 * (gq2 * q);
+        return q;
+    }
+    MCD_HD void setup_scaled(double eb, double s2, double scale) {
+        double G0s, A;
+        setup_parts(eb, s2, scale, G0s, A);
+        c0 = fma_(G0s, A, G0s);
     }
 };
+
+// The cubic of RootDirectSplit economised to a quadratic on a 32-star band of the verr-sorted array (option "root_quad",
+// DESIGN 3.2).  Block b of a shard's sorted record array is records 32 b .. 32 b + 31 (the last block also takes a remainder
+// shorter than 32), whatever the chunk plan.  With e_lo, e_hi its first and last verr^2, m = (e_lo + e_hi) / 2 and
+// h = (e_hi - e_lo) / 2, on [m - h, m + h]
+//   (e - m)^3 = 3/4 h^2 (e - m) + R,  |R| <= h^3 / 4      (Chebyshev: 4 x^3 - 3 x = T3(x), x = (e - m) / h)
+// hence e^3 = a2 e^2 + a1 e + a0 + R with a2 = 3 m, a1 = 3/4 h^2 - 3 m^2, a0 = m^3 - 3/4 h^2 m: constants of the catalogue,
+// which the record preparation evaluates in long double and leaves in the unused slots of the block's first two split
+// records (mcd_exp_split.h: quad_block_consts).  The lanes fold them into their coefficients once per block,
+//   q2 = fma(c3, a2, c2)    q1 = fma(c3, a1, c1)    q0 = fma(G0s, fma(k3, a0, A), G0s)     (c3 = G0s k3, k3 = -5/16 q^3)
+// and the root is gs = fma(fma(q2, e, q1), e, q0): two FMAs per term instead of three, three FMAs and two more per 32 terms.
+// q0 is built the way c0 is -- A is the bracket of c0's one last FMA, which takes k3 a0 in -- so it carries c0's ONE rounding.
+// A chunk takes this form only where the direct vote has passed (and the launch runs the split offset) and, in every lane,
+//   H <= kMaxT (eb + s2),  kMaxT = 2^-17.5,  H the largest h of any block the chunk touches (a constant of the plan),
+// a third wave-wide vote with the eb of the coefficients (quad_ok).
+// Worst-case relative error against (2 (e + s2))^(-1/2), in units of u = 2^-53 relative to G, by the table above RootDirect
+// (x = q e <= 1/8 + 2^-13):
+//   last FMA                                                                                                       1.00
+//   q0: c0's ONE rounding and its bracket (1.64); k3 a0 <= 5/16 x^3 = 6.2e-4 joins the bracket, coefficient <= 12  1.65
+//   q1 e: |q1 e| <= |c1 e| + |c3 a1 e| <= (0.0762 + 3 x 6.2e-4) G = 0.0781 G; c1 9.2, the rounding of q1 1, the FMA that
+//       forms q1 + e q2 1: 0.0781 x 11.2                                                                           0.88
+//   q2 e^2: <= (0.0077 + 3 x 6.2e-4) G = 0.0096 G; c2 <= 14, the rounding of q2 1: 0.0096 x 15                       0.15
+//   c3 in q2, q1 (coefficient <= 12, on 3 x 6.2e-4 twice)                                                          0.05
+//   the a's, each rounded ONCE from long double: |c3 ai e^i| <= 3 x 6.2e-4 G (a2 e^2 and a1 e are three times e^3 each,
+//       a0 once), so their half ulps cost 7 x 6.2e-4 / 2                                                           0.01
+//   economisation |c3| h^3 / 4 = (5/64) (h q)^3 G, h q <= 2^-17.5                                                  0.111
+//   truncation of the cubic, 35/128 t^4                                                                            0.55
+// 4.40 u (1 + 2^-14) = 4.9e-16 = kErrorBound (the ceiling for this form: 5.9e-16).  Measured: tests/test_root_quad_cpu.py.
+struct RootQuadCentre : RootDirectSplit {
+    double G0s, A, k3;
+    // RootDirectSplit's c1 .. c3 (bit for bit) and, in place of c0, what q0 is built from
+    MCD_HD void setup_quad(double eb, double s2, double scale) {
+        const double q = setup_parts(eb, s2, scale, G0s, A);
+        k3 = -0.3125 * ((q * q) * q);
+    }
+};
+struct RootQuad {
+    static constexpr double kMaxT = 0x1.6a09e667f3bcdp-18;          // 2^-17.5
+    static constexpr double kErrorBound = 4.9e-16;
+    double q0, q1, q2;
+    // H <= 2^-17.5 (eb + s2), without a division (false for NaN; true for H = 0, a block of equal verr)
+    static MCD_HD bool quad_ok(double H, double eb, double s2) { return H <= kMaxT * (eb + s2); }
+    // a2, a1, a0: the block's constants from its first two split records (wave-uniform, SGPR pairs on the device)
+    MCD_HD void fold(const RootQuadCentre& c, double a2, double a1, double a0) {
+        q2 = fma_sgpr_factor(c.c3, a2, c.c2);
+        q1 = fma_sgpr_factor(c.c3, a1, c.c1);
+        q0 = fma_(c.G0s, fma_sgpr_factor(c.k3, a0, c.A), c.G0s);
+    }
+    MCD_HD double g_quad(double e) const { return fma_sgpr_factor(fma_sgpr_factor(q2, e, q1), e, q0); }
+};
+// What a chunk needs to run the quadratic form (the main kernel fills it from the chunk's first record index and the
+// length of the record array; default: never)
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef __attribute__((address_space(3))) double* QuadParkPtr;      // (LDS as such: ds_read / ds_write, a 32-bit address)
+#else
+typedef double* QuadParkPtr;
+#endif
+struct QuadArgs {
+    bool on = false;          // the third vote is held (option "root_quad", chunk start a multiple of 8, at least one block)
+    int back = 0;             // records from the first record of the chunk's first block to the chunk's first record
+    int to_boundary = 32;     // stars from the chunk's first record to the next multiple of 32
+    int folds = 0;            // of the block boundaries ahead, those that start a block (the last block has no end)
+    QuadParkPtr park = nullptr;   // device: 5 x `stride` doubles of LDS, one column per thread of the workgroup, for what
+    int stride = 0;               // only the fold reads; park points at the wave's 64 columns (wave-uniform)
+};
+// ... for the chunk that starts at record `begin` of an array of n_records.  Blocks of 32 records in absolute positions; the
+// last one also takes the remainder, so a chunk that starts beyond the last block's first 32 records still belongs to it.
+MCD_HD QuadArgs quad_args(int64_t begin, int64_t n_records, bool enabled) {
+    QuadArgs q;
+    const int64_t n_blocks = n_records >> 5, b = begin >> 5;
+    const int64_t b0 = b < n_blocks ? b : n_blocks - 1;
+    q.on = enabled && n_blocks > 0 && (begin & 7) == 0;
+    q.back = (int)(begin - 32 * b0);
+    q.to_boundary = 32 - (int)(begin & 31);
+    q.folds = b < n_blocks ? (int)(n_blocks - 1 - b) : 0;
+    return q;
+}
 
 // true when `ok` holds in every active lane of the wave (one s_cmp on the ballot: callers branch on the scalar unit);
 // host build: the caller has combined the lanes (tests/emul)
@@ -1334,7 +1418,7 @@ MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<d
 template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED>
 MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w, bool& denormal,
                                  const double* __restrict__ exptab, int rescale_iters, bool series, bool direct,
-                                 RecPtr<double> r_split, const double* __restrict__ split_const) {
+                                 RecPtr<double> r_split, const double* __restrict__ split_const, const QuadArgs& quad) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int XB = geometry_doubles(MODEL, FREE);
     constexpr bool HALVED = MODEL == MODEL_BGFIXED;
@@ -1351,7 +1435,10 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     auto one = [&](RecPtr<double> rr, auto SERIES, double sc) {
         double d, n;
         star_d_n<MODEL, double, FREE, true>(rr, w, d, n);
-        if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value) {
+        if constexpr (std::is_same<decltype(SERIES), const RootQuad*>::value) {
+            // the split loop with the block's quadratic in place of the chunk's cubic
+            acc.add_gs<TAB_BIASED, !BOUNDED>(d, SERIES->g_quad(rr[1]), rr[XB], rr[XB + 1], sc, exptab);
+        } else if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value) {
             // the split record [v, verr^2, cx, cy, M, omp', 0, 0]; sc: kExpSplitS1 here
             acc.add_gs<TAB_BIASED, !BOUNDED>(d, SERIES.g_direct(rr[1]), rr[XB], rr[XB + 1], sc, exptab);
         } else if constexpr (std::is_same<decltype(SERIES), RootDirect>::value) {
@@ -1366,7 +1453,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     const int n4 = count >> 2;
     static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
     auto four = [&](RecPtr<double> r4, auto SERIES) {
-        if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value) {
+        if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value || std::is_same<decltype(SERIES), const RootQuad*>::value) {
             // (the linear coefficient of the scaled polynomial in place of the rsq loops' variance scale)
 #pragma unroll
             for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, kExpSplitS1);
@@ -1375,7 +1462,42 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             for (int j = 0; j < 4; ++j) one(r4 + j * ND, SERIES, scale);
         }
     };
+    // The quadratic form (RootQuad): its coefficients change where the absolute record index reaches a multiple of 32 that
+    // starts a block.  A scalar countdown in stars, tested where an 8-star iteration, a 4-star group or a single star
+    // starts (chunk starts are multiples of 8, so a boundary never falls inside one); the fold is a block outside the loop
+    // body, as the bounded rescale is.  `fold_at`: set by the quadratic copy below.
+    RootQuad sq;
+    RootQuadCentre qc;
+    int to_boundary = quad.to_boundary, folds = quad.folds;
+    auto fold_at = [&](RecPtr<double> rb) {
+        RootQuadCentre c;
+        c.c3 = qc.c3;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (volatile: re-read here, five ds_read_b64 per 32 terms, instead of five register pairs across the loop; the
+        // thread's column is worked out here too, behind an empty volatile asm, so that no address stays in a register)
+        int column;                                                    // the lane
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(column));
+        const volatile __attribute__((address_space(3))) double* park = quad.park + column;
+        c.c1 = park[0];
+        c.c2 = park[quad.stride];
+        c.G0s = park[2 * quad.stride];
+        c.A = park[3 * quad.stride];
+        c.k3 = park[4 * quad.stride];
+#else
+        c.c1 = qc.c1; c.c2 = qc.c2; c.G0s = qc.G0s; c.A = qc.A; c.k3 = qc.k3;
+#endif
+        sq.fold(c, rb[XB + 2], rb[XB + 3], rb[ND + XB + 2]);
+    };
+    auto boundary = [&](RecPtr<double> rb, int step) {
+        if (to_boundary == 0) {
+            to_boundary = 32;
+            MCD_KEEP_BRANCH();
+            if (folds > 0) { --folds; fold_at(rb); }
+        }
+        to_boundary -= step;
+    };
     auto run = [&](auto SERIES) {
+        constexpr bool QUAD = std::is_same<decltype(SERIES), const RootQuad*>::value;
         if constexpr (BOUNDED) {
             // bounded sub-variant: every mixture value lies in [y_lo, y_hi] with R log2(y_hi) <= 1000 and
             // 1 + R (-log2 y_lo) <= 1000 (mcd_guard.h: bounded_rescale), so R = 8 rescale_iters raw factors fit between
@@ -1385,6 +1507,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             // while nothing overflows or goes subnormal: the same bits as the loop below.
             int until = rescale_iters;
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
+                if constexpr (QUAD) boundary(r, 8);
                 RecordPrefetch<8 * ND * 8, PF> pf;
                 pf.issue(r + 8 * ND);
                 four(r, SERIES);
@@ -1394,6 +1517,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             }
             acc.rescale_narrow();
             if (n4 & 1) {
+                if constexpr (QUAD) boundary(r, 4);
                 four(r, SERIES);
                 r += 4 * ND;
                 acc.rescale_narrow();
@@ -1405,6 +1529,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             // products and rescale points as the 4-star loop below.  (Without the prefetch hipcc hoists the second
             // group's record loads and takes 76 VGPRs, i.e. 6 waves per SIMD: that instantiation keeps 4-star groups.)
             for (int g = 0; g < (count >> 3); ++g, r += 8 * ND) {
+                if constexpr (QUAD) boundary(r, 8);
                 RecordPrefetch<8 * ND * 8, PF> pf;
                 pf.issue(r + 8 * ND);
                 four(r, SERIES);
@@ -1413,6 +1538,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
                 acc.rescale_narrow();
             }
             if (n4 & 1) {
+                if constexpr (QUAD) boundary(r, 4);
                 four(r, SERIES);
                 r += 4 * ND;
                 acc.rescale_narrow();
@@ -1420,6 +1546,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
         } else if constexpr (NARROW) {
             // eight raw factors per rescale: every second 4-star group (one scalar record-load batch each)
             for (int g = 0; g < n4; ++g, r += 4 * ND) {
+                if constexpr (QUAD) boundary(r, 4);
                 four(r, SERIES);
                 if (g & 1) { MCD_KEEP_BRANCH(); acc.rescale_narrow(); }    // wave-uniform: a scalar branch, not a select
             }
@@ -1434,7 +1561,8 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             }
         }
         for (int j = n4 * 4; j < count; ++j, r += ND) {
-            one(r, SERIES, std::is_same<decltype(SERIES), RootDirectSplit>::value ? kExpSplitS1 : kScale);
+            if constexpr (QUAD) boundary(r, 1);
+            one(r, SERIES, (std::is_same<decltype(SERIES), RootDirectSplit>::value || QUAD) ? kExpSplitS1 : kScale);
             acc.rescale();
         }
     };
@@ -1449,7 +1577,9 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     // `r_split` (a launch with the split exponent offset, option "exp_split"): the chunk's records in the split array, which
     // a direct chunk then reads INSTEAD of `r` -- the vote's two records included (the same verr^2 in both arrays), so that
     // such a chunk touches one array only
-    bool use_series = false, use_direct = false;
+    // A third vote (option "root_quad"), on the widest 32-star block the chunk touches against every lane's variance
+    // (RootQuad::quad_ok; split_const[1], a constant of the plan), sends a direct chunk of such a launch to the quadratic form.
+    bool use_series = false, use_direct = false, use_quad = false;
     const bool split = kCanSeries && r_split != nullptr;
     if constexpr (kCanSeries) {
         if (series && count > 0) {
@@ -1458,6 +1588,10 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
             const bool ok = vote.setup_chunk(rv[1], rv[(int64_t)(count - 1) * ND + 1], w.s2);
             use_series = wave_all(ok);
             if (use_series && direct) use_direct = wave_all(RootDirect::direct_ok(vote.eb, w.s2));
+            // (on 8 H, 8 eb and s2x = 8 s2, which the loops keep anyway: the verdict of quad_ok(H, eb, s2), since scaling by
+            // a power of two rounds nothing -- the range guard keeps all three far from the ends of the exponent range)
+            if (use_direct && split && quad.on)
+                use_quad = wave_all(RootQuad::quad_ok(kScale * split_const[1], kScale * vote.eb, s2x));
         }
     }
     if constexpr (kCanSeries) {
@@ -1468,7 +1602,28 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
         // vote's, bit for bit, BECAUSE s2x = 8 s2 and (1/8) s2x are exact: scaling by a power of two rounds nothing as
         // long as 8 s2 is finite (and the way back lands on s2, which is representable, subnormal or not); the range
         // guard admits no fast mixture kernel for a variance beyond 2^200 (mcd_guard.h: guard_verdict).
-        if (use_direct && split) {
+        if (use_quad) {
+            r = r_split;
+            const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
+            // (s2 itself, which the kernel keeps for its general form anyway -- the same bits as (1/8) s2x, see above -- so
+            // that s2x need not stay in registers across the split copy for this one)
+            qc.setup_quad(0.5 * e_first + 0.5 * e_last, vgpr_pinned((1.0 / kScale) * s2x), kExpSplitC);
+#if defined(__HIP_DEVICE_COMPILE__)
+            {
+                const QuadParkPtr park = quad.park + (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                park[0] = qc.c1;
+                park[quad.stride] = qc.c2;
+                park[2 * quad.stride] = qc.G0s;
+                park[3 * quad.stride] = qc.A;
+                park[4 * quad.stride] = qc.k3;
+            }
+#endif
+            fold_at(r - (int64_t)quad.back * ND);                   // the block the chunk starts in (or on)
+            run((const RootQuad*)&sq);
+            const double result = acc.finish() + *split_const;      // (the split loop's constant: the same kappa)
+            denormal = acc.denormal();
+            return result;
+        } else if (use_direct && split) {
             r = r_split;
             const double e_first = vgpr_pinned(r[1]), e_last = vgpr_pinned(r[(int64_t)(count - 1) * ND + 1]);
             RootDirectSplit sd;
@@ -1514,7 +1669,8 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
 template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
                             const double* __restrict__ exptab, int rescale_iters = 1, bool series = false, bool direct = false,
-                            RecPtr<T> r_split = nullptr, const double* __restrict__ split_const = nullptr) {
+                            RecPtr<T> r_split = nullptr, const double* __restrict__ split_const = nullptr,
+                            const QuadArgs& quad = QuadArgs()) {
     constexpr int BG = bg_kind(MODEL);
     denormal = false;
     if constexpr (!FAST) {
@@ -1527,7 +1683,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (FAST == 2 && MODEL == MODEL_PROFILE && !FREE) return chunk_profile_narrow<PF>(r, count, w);
         else return chunk_const_fast<MODEL, FREE, PF>(r, count, w);
     } else if constexpr (BG == BG_FIXED) {
-        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct, r_split, split_const);
+        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct, r_split, split_const, quad);
     } else if constexpr (BG == BG_FIXED_DENSITY) {
         // BG_FIXED_DENSITY, f64 fast forms
         constexpr int ND = record_doubles(MODEL, FREE);

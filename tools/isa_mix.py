@@ -15,9 +15,12 @@ keeps its row under "bgfixed_rsq"; the level-2 prefetching loop keeps its row un
 kernels also holds the two series forms of its loop (mcd_math.h: RootSeries about the chunk's centre, RootDirect in
 verr^2 itself; the chunks of a verr-sorted record array whose verr^2 band is narrow): rows "..., series" and "..., direct",
 and the direct loop once more with the split exponent offset (option "exp_split", BgFixedAcc::add_gs): rows "..., split".
-The bounded split loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded
-direct loop without the split keeps its row under "bgfixed_direct_bounded", the bounded delta series loop under
-"bgfixed_series_bounded".
+The split loop exists once more with the quadratic series root on 32-star bands (option "root_quad", mcd_math.h: RootQuad):
+rows "..., quad", 10 fused multiply-adds per term against the split rows' 11.  Its coefficients are folded once per 32
+stars in a block of its own (five ds_read_b64 and four FMAs), which the count adds once per 32 terms.  The bounded quad
+loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded split loop keeps
+its row under "bgfixed_split_bounded", the bounded direct loop without the split under "bgfixed_direct_bounded", the bounded
+delta series loop under "bgfixed_series_bounded".
 
 "slots" prices the mix with the issue costs measured on MI355X (tools/valu_rate_probe.hip): an f64 FMA/MUL/ADD wave-
 instruction = 1 slot (4 cycles on one SIMD), v_rsq/v_rcp_f64 = 2.9 slots, other VALU instructions (integer, v_ldexp,
@@ -76,7 +79,9 @@ BOUNDED = ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bou
 # feeds the first FMA of the cubic -- the direct form (RootDirect: the cubic in verr^2 itself) the first two only.  The
 # direct loop with the split exponent offset has two as well (v - v_sys and shifted - M): it is told from the direct loop
 # without the split by its fused multiply-adds (v_fma_f64 + v_fmac_f64) per term, 11 instead of 12.
-# Full tag, name, key, stars, trips, selector, prefetching, bounded
+# The quadratic loops (RootQuad) are the split loops with one FMA per term fewer: 10 against 11 (the fold block, wherever
+# the compiler puts it, is taken out before the selector sees the loop).
+# Full tag, name, key, stars, trips, selector, prefetching, bounded [, quad]
 SERIES = [
     ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, series", "bgfixed_series", 4, 2, _sel(rsq=0, frexp=0, add=12),
      False, False),
@@ -94,10 +99,17 @@ SERIES = [
      _sel(rsq=0, frexp=0, add=8, fma=44), False, False),
     ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, split", "bgfixed_split", 8, 1,
      _sel(rsq=0, frexp=1, add=16, fma=88), True, False),
-    # what C3's timed launches run on the chunks that qualify (98.2 % of the stars): the "bgfixed" key's prefetch fields
-    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, split", "bgfixed", 8, 4,
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, split", "bgfixed_split_bounded", 8, 4,
      _sel(rsq=0, frexp=0, add=16, fma=88), True, True),
+    ("ILi1ELb0EddLi2ELb0ELi4ELb0EE", "BGFIXED fixed, narrow, quad", "bgfixed_quad", 4, 2,
+     _sel(rsq=0, frexp=0, add=8, fma=40), False, False, True),
+    ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, quad", "bgfixed_quad", 8, 1,
+     _sel(rsq=0, frexp=1, add=16, fma=80), True, False, True),
+    # what C3's timed launches run on the chunks that qualify: the "bgfixed" key's prefetch fields
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, quad", "bgfixed", 8, 4,
+     _sel(rsq=0, frexp=0, add=16, fma=80), True, True, True),
 ]
+QUAD_BLOCK = 32      # stars per fold of the quadratic loops
 
 
 def _ops(lines):
@@ -114,6 +126,25 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+def fold_block(k, lo, hi):
+    """(first, end) lines of the fold block of a quadratic loop between lines lo and hi, or None: the five ds_read_b64 in a
+    row that re-read the parked coefficients, from the branch (or label) in front of them to the label or branch behind."""
+    for i in range(lo, min(hi, len(k) - 5)):
+        if all(k[i + j].startswith("\tds_read_b64") for j in range(5)):
+            a = next(j for j in range(i, 0, -1) if re.match(r"\s*s_c?branch|^\.LBB", k[j]))
+            e = next(j for j in range(i, len(k)) if re.match(r"\s*s_c?branch|^\.LBB", k[j]))
+            return a + 1, e
+    return None
+
+
+def body_lines(k, sp):
+    """the lines of loop `sp` without a fold block inside it"""
+    blk = fold_block(k, sp[0], sp[1])
+    if blk and blk[1] <= sp[1] + 1:
+        return k[sp[0]:blk[0]] + k[blk[1]:sp[1] + 1]
+    return k[sp[0]:sp[1] + 1]
+
+
 def rescale_block(k, labels, best, bounded, trips):
     """(first, end) lines of the rescale block of a narrow-range loop `best` (label line, closing branch line), or None.
     The 4-star loops: behind the loop's closing conditional branch, jumping back with an unconditional s_branch.  The
@@ -127,7 +158,8 @@ def rescale_block(k, labels, best, bounded, trips):
             for j in range(a0 + 1, min(a0 + 24, len(k))):
                 mb = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j])
                 if mb:
-                    if mb.group(1) in labels and best[0] <= labels[mb.group(1)] <= best[1]:
+                    if mb.group(1) in labels and best[0] <= labels[mb.group(1)] <= best[1] and \
+                            not any(l.startswith("\tds_read_b64") for l in k[a0:j]):      # (not the quadratic loops' fold block)
                         return a0 + 1, j
                     break
         return None
@@ -160,8 +192,9 @@ def analyse(out="/tmp/isa_mix"):
                  (row[6] if len(row) > 6 else row[3:6]) + (True,) for row in KERNELS]
     variants = [v + (False,) for v in variants]
     variants.append(BOUNDED + (True, True))
-    variants += SERIES
-    for tag, name, key, per, trips, selector, with_prefetch, bounded in variants:
+    variants += [v + (False,) * (9 - len(v)) for v in SERIES]
+    variants = [v + (False,) * (9 - len(v)) for v in variants]
+    for tag, name, key, per, trips, selector, with_prefetch, bounded, quad in variants:
         starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag)]
         if not starts:
             continue
@@ -180,11 +213,11 @@ def analyse(out="/tmp/isa_mix"):
         if selector is not None:
             # (the longest loop the selector accepts that does real work: the series loops share their kernels with short
             # copy and tail loops without a v_rsq_f64 either)
-            hits = [sp for sp in ranked if selector(Counter(_ops(k[sp[0]:sp[1]]))) and sp[1] - sp[0] >= 8 * per]
+            hits = [sp for sp in ranked if selector(Counter(_ops(body_lines(k, sp)[:-1]))) and sp[1] - sp[0] >= 8 * per]
             best = hits[0] if hits else None
         if best is None:
             best = ranked[0]
-        body = Counter(_ops(k[best[0]:best[1] + 1]))
+        body = Counter(_ops(body_lines(k, best) if quad else k[best[0]:best[1] + 1]))
         extra = Counter()
         blk = rescale_block(k, labels, best, bounded, trips)
         if blk:
@@ -195,6 +228,16 @@ def analyse(out="/tmp/isa_mix"):
             total[op] += v * trips
         for op, v in extra.items():
             total[op] += v
+        if quad:
+            # per 32 terms: the loop (and its rescale block) as often as it takes, the fold block once
+            fold = fold_block(k, best[0], best[1] + 120)
+            if fold is None:
+                continue
+            for op in total:
+                total[op] *= QUAD_BLOCK // terms
+            terms = QUAD_BLOCK
+            for op, v in Counter(_ops(k[fold[0]:fold[1]])).items():
+                total[op] += v
 
         def is_f64(o):
             return "f64" in o
