@@ -233,6 +233,31 @@ enum { MCD_PRED_Z_MEAN, MCD_PRED_Z_STD, MCD_PRED_TAIL_P, MCD_PRED_PIT,
 int mcd_posterior_predictive(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params,
                              double* out      /* [MCD_PRED_FIELDS][n_stars] */,
                              double* pit_mix  /* [n_stars], or NULL */);
+/* Leave-one-out expectations per star under the PSIS weights of mcd_psis_loo (same params, r_eff, tail rules and
+ * smoothing): with lw_is the smoothed, truncated log weights and w~_is = exp(lw_is) / sum_s exp(lw_is),
+ *   E_loo,i[x] = sum_s w~_is x_is,
+ * accumulated as sum_s e_s x_s / sum_s e_s with e_s = exp(lw_s - max lw) in sample order per lane, then over the wave.
+ * loo_pred[f][i], f < MCD_LOOX_FIELDS: the expectations of pit, z, v_los and sigma_los of mcd_posterior_predictive's
+ * (star, sample) term -- loo_pred[MCD_LOOX_PIT] is the leave-one-out probability integral transform (LOO-PIT);
+ * loo_pit_mix[i] that of the mixture CDF (Gaussian-background models only, MCD_ERR_INVALID otherwise).
+ * loo_func[q][i] = sum_s w~_is func[s][q] for n_func <= MCD_LOO_MAX_FUNC star-independent functions of the sample
+ * (func row-major [S][n_func]): with func = the parameters, the case-deletion posterior means E[theta | y_-i].
+ * pareto_k / n_eff: bit for bit those of mcd_psis_loo.  Every output pointer may be NULL; all NULL is MCD_OK without
+ * work.  n_func outside [0, MCD_LOO_MAX_FUNC], or func / loo_func NULL with n_func > 0, is MCD_ERR_INVALID; an invalid
+ * call leaves the outputs untouched.  M < 5, a failed fit and a constant tail keep the raw truncated weights; S = 1
+ * gives w~ = 1.  A star with non-finite terms gets non-finite outputs and touches no other star.  Un-binned catalogues
+ * only; this process' n_stars; synchronous; float32 catalogues: terms in float, everything else in float64.  Device
+ * scratch ([star][rows][S] tiles with rows = 1 + the rows asked for, the sample table and func) stays within option
+ * "loo_scratch_mb" and is released on every exit path; options "posterior_pass" and "timing" as for mcd_psis_loo.
+ * Deterministic: no floating-point atomics; a star's bits depend on its own rows only. */
+enum { MCD_LOOX_PIT, MCD_LOOX_Z, MCD_LOOX_VLOS, MCD_LOOX_SIGMA, MCD_LOOX_FIELDS };
+#define MCD_LOO_MAX_FUNC 16
+int mcd_psis_loo_expect(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double r_eff,
+                        int32_t n_func, const double* func  /* [S][n_func] row-major, or NULL when n_func == 0 */,
+                        double* loo_func     /* [n_func][n_stars], or NULL */,
+                        double* loo_pred     /* [MCD_LOOX_FIELDS][n_stars], or NULL */,
+                        double* loo_pit_mix  /* [n_stars] or NULL; Gaussian-background models only */,
+                        double* pareto_k, double* n_eff  /* [n_stars] or NULL each */);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

@@ -57,6 +57,9 @@ SYMBOLS = {
                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "mcd_posterior_predictive": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_double_p,
                                                 _c_double_p]),
+    "mcd_psis_loo_expect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_double,
+                                           ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                           _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -628,6 +631,50 @@ class Catalog(object):
         out = {k: block[f] for f, k in enumerate(self.PREDICTIVE_FIELDS)}
         if mixture:
             out["pit_mix"] = mix
+        return out
+
+    LOO_EXPECT_FIELDS = ("pit", "z", "vlos", "sigma")
+    LOO_MAX_FUNC = 16
+
+    def psis_loo_expect(self, table, r_eff=1.0, func=None, predictive=True, mixture=False):
+        """Leave-one-out expectations per star under the PSIS weights of ``psis_loo`` (include/mcd.h: mcd_psis_loo_expect):
+        ``table`` (S, K) in the kernel's column order -> dict of (n_stars,) arrays ``pareto_k`` and ``n_eff`` (bit for bit
+        those of ``psis_loo``); with ``predictive`` the expectations ``pit`` (the LOO-PIT), ``z``, ``vlos`` and ``sigma`` of
+        the (star, sample) term of ``posterior_predictive``; with ``mixture`` (the two models with a Gaussian background
+        only) ``pit_mix``; and with ``func`` (S, Q), Q <= 16 star-independent functions of the sample, ``func`` (n_stars, Q):
+        the expectation of every column with each star left out."""
+        self._alive()
+        if self.n_sets > 1:
+            raise ValueError("psis_loo_expect is defined for un-binned catalogues only")
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (S, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        n_func, f, loo_func = 0, None, None
+        if func is not None:
+            f = _f64(func)
+            if f.ndim == 1:
+                f = f[:, None]
+            if f.ndim != 2 or f.shape[0] != p.shape[0]:
+                raise ValueError("func must have shape ({0}, Q)".format(p.shape[0]))
+            f = np.ascontiguousarray(f)
+            n_func = f.shape[1]
+            loo_func = np.empty((n_func, self.n_stars), dtype=np.float64)
+        pred = np.empty((len(self.LOO_EXPECT_FIELDS), self.n_stars), dtype=np.float64) if predictive else None
+        mix = np.empty(self.n_stars, dtype=np.float64) if mixture else None
+        out = {k: np.empty(self.n_stars, dtype=np.float64) for k in ("pareto_k", "n_eff")}
+        rc = self.lib.mcd_psis_loo_expect(self.handle, p.shape[0], self.k, _ptr(p), float(r_eff), n_func,
+                                          _ptr(f) if n_func else None, _ptr(loo_func) if n_func else None, _ptr(pred) if predictive else None,
+                                          _ptr(mix) if mixture else None, _ptr(out["pareto_k"]), _ptr(out["n_eff"]))
+        _check(self.lib, rc, "mcd_psis_loo_expect")
+        if predictive:
+            out.update({k: pred[i] for i, k in enumerate(self.LOO_EXPECT_FIELDS)})
+        if mixture:
+            out["pit_mix"] = mix
+        if func is not None:
+            out["func"] = np.ascontiguousarray(loo_func.T)
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

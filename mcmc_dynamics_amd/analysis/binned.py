@@ -266,6 +266,12 @@ class BinnedConstantFit(ConstantFit):
         raise NotImplementedError("BinnedConstantFit: PSIS-LOO is defined for un-binned fits only; fit the bins' stars "
                                   "with ConstantFit to compare models")
 
+    def loo_pit(self, chain, n_burn, thin=1, r_eff=1.0, n_bins=20):
+        return self.loo(chain, n_burn, thin, r_eff)
+
+    def loo_influence(self, chain, n_burn, thin=1, r_eff=1.0, functions=None):
+        return self.loo(chain, n_burn, thin, r_eff)
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

@@ -1,5 +1,5 @@
 // mcd_api_summaries.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host
-// units): host drivers of the per-star posterior summaries (kernels: mcd_posterior.hip), of PSIS-LOO (mcd_psis.hip),
+// units): host drivers of the per-star posterior summaries (kernels: mcd_posterior.hip), of PSIS-LOO (mcd_psis.hip) and the expectations under its weights (mcd_loo_expect.hip),
 // of the kernel-density background (mcd_kde.hip), and of the posterior predictive checks (mcd_predictive.hip).
 #include "mcd_host.h"
 #include "mcd_posterior.h"
@@ -192,6 +192,86 @@ int psis_loo(mcd_catalog* cat, int64_t S, int32_t k, const double* params, doubl
     return MCD_OK;
 }
 
+// mcd_psis_loo's plan with `rows` rows per star in the tile and the function table in the fixed part of the budget.
+int psis_loo_expect(mcd_catalog* cat, int64_t S, int32_t k, const double* params, double r_eff, int32_t n_func,
+                    const double* func, double* loo_func, double* loo_pred, double* loo_pit_mix, double* pareto_k,
+                    double* n_eff) {
+    if (!cat || !params) return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: null catalogue or params");
+    if (S < 1) return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: n_samples must be >= 1");
+    if (S > INT32_MAX) return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: n_samples must be < 2^31");
+    if (!(r_eff > 0.0) || !std::isfinite(r_eff))
+        return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: r_eff must be > 0 and finite");
+    if (k != cat->k) return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: parameter rows have the wrong number of columns");
+    if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: defined for un-binned catalogues only");
+    if (n_func < 0 || n_func > MCD_LOO_MAX_FUNC)
+        return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: n_func must be in [0, " + std::to_string(MCD_LOO_MAX_FUNC) + "]");
+    if (n_func > 0 && (!func || !loo_func))
+        return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: func and loo_func must not be NULL when n_func > 0");
+    if (loo_pit_mix && mcd::bg_kind(cat->model) != mcd::BG_GAUSS)
+        return fail(MCD_ERR_INVALID,
+                    "mcd_psis_loo_expect: loo_pit_mix needs a Gaussian background model (loo_pit_mix must be NULL)");
+    const int64_t M = mcd::psis_tail_len(S, r_eff);
+    if (M > mcd::kPsisMaxTail)
+        return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: the Pareto tail of " + std::to_string(M) + " samples exceeds " +
+                                         std::to_string(mcd::kPsisMaxTail) + " (S / r_eff too large)");
+    if (cat->n_stars == 0 || !(n_func > 0 || loo_pred || loo_pit_mix || pareto_k || n_eff)) return MCD_OK;
+    const int mode = loo_pit_mix ? mcd::LOOX_PRED_MIX : loo_pred ? mcd::LOOX_PRED : mcd::LOOX_NONE;
+    const int rows = mcd::loox_rows(mode), n_out = mcd::LXF_ROWS + rows - 1 + n_func;
+    const size_t term_bytes = cat->precision == MCD_F64 ? 8 : 4;
+    const size_t rec_bytes = term_bytes * (size_t)mcd::record_doubles(cat->model, cat->free_centre);
+    const int64_t pass_len = std::min<int64_t>(S, cat->posterior_pass);
+    const size_t func_bytes = (size_t)S * n_func * sizeof(double);
+    const int64_t fixed = (int64_t)((size_t)pass_len * k * sizeof(double) + (size_t)S * mcd::KD * term_bytes + func_bytes);
+    const int64_t budget = cat->loo_scratch_mb * (int64_t)1048576;
+    double kernel_ms = 0.0;
+    for (Shard& sh : cat->shards) {
+        if (sh.n == 0) continue;
+        const int64_t tile = mcd::psis_tile_stars_rows(sh.n, S, rows, fixed, budget);
+        if (tile < 1)
+            return fail(MCD_ERR_INVALID, "mcd_psis_loo_expect: option loo_scratch_mb = " + std::to_string(cat->loo_scratch_mb) +
+                                             " cannot hold the sample table and one star's " + std::to_string(rows) +
+                                             " rows of " + std::to_string(S) + " terms");
+        const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+        MCD_HIP(hipSetDevice(slot.device));
+        DeviceScratch d;                                    // (one shard's)
+        double *d_params = nullptr, *d_terms = nullptr, *d_out = nullptr, *d_func = nullptr;
+        void* d_wpar = nullptr;
+        MCD_HIP(d.malloc(&d_params, (size_t)pass_len * k * sizeof(double)));
+        MCD_HIP(d.malloc(&d_wpar, (size_t)S * mcd::KD * term_bytes));
+        MCD_HIP(d.malloc(&d_terms, (size_t)tile * rows * S * sizeof(double)));
+        MCD_HIP(d.malloc(&d_out, (size_t)n_out * sh.n * sizeof(double)));
+        if (n_func > 0) {
+            MCD_HIP(d.malloc(&d_func, func_bytes));
+            MCD_HIP(hipMemcpyAsync(d_func, func, func_bytes, hipMemcpyHostToDevice, slot.stream));
+        }
+        if (cat->timing) MCD_HIP(d.create_events());
+        for (int64_t s0 = 0; s0 < S; s0 += pass_len) {      // (the passes fill the whole [S][KD] table)
+            const int64_t ns = std::min(pass_len, S - s0);
+            if (int rc = upload_samples(cat, slot, params, s0, ns, k, d_params, d_wpar, s0, s0 == 0 ? d.e0 : nullptr)) return rc;
+        }
+        const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+        for (int64_t t0 = 0; t0 < sh.n; t0 += tile) {
+            const int64_t nt = std::min(tile, sh.n - t0);
+            MCD_HIP(mcd::launch_loo_expect(slot.stream, shape, mode, (const char*)sh.records + (size_t)t0 * rec_bytes, nt, d_wpar,
+                                           S, M, r_eff, d_func, n_func, d_terms, d_out + t0, sh.n));
+        }
+        if (d.e1) MCD_HIP(hipEventRecord(d.e1, slot.stream));
+        // the shard's stars at star_begin of every field; fetch_outputs copies k^ and n_eff and waits
+        auto field = [&](double* dst, int f) {
+            return hipMemcpyAsync(dst + sh.star_begin, d_out + (size_t)f * sh.n, (size_t)sh.n * sizeof(double),
+                                  hipMemcpyDeviceToHost, slot.stream);
+        };
+        if (loo_pred)
+            for (int f = 0; f < MCD_LOOX_FIELDS; ++f) MCD_HIP(field(loo_pred + (size_t)f * cat->n_stars, mcd::LXF_ROWS + f));
+        if (loo_pit_mix) MCD_HIP(field(loo_pit_mix, mcd::LXF_ROWS + mcd::LR_MIX - 1));
+        for (int q = 0; q < n_func; ++q) MCD_HIP(field(loo_func + (size_t)q * cat->n_stars, mcd::LXF_ROWS + rows - 1 + q));
+        double* const rest[4] = {pareto_k, n_eff, nullptr, nullptr};
+        if (int rc = fetch_outputs(sh, slot, d, d_out, rest, &kernel_ms)) return rc;
+    }
+    note_kernel_ms(cat, kernel_ms);
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -210,6 +290,14 @@ int mcd_psis_loo(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* p
     double* const outs[4] = {elpd_loo, pareto_k, lppd, n_eff};
     return psis_loo(cat, n_samples, k, params, r_eff, outs);
     } catch (...) { return on_exception("mcd_psis_loo"); }
+}
+
+int mcd_psis_loo_expect(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double r_eff,
+                        int32_t n_func, const double* func, double* loo_func, double* loo_pred, double* loo_pit_mix,
+                        double* pareto_k, double* n_eff) {
+    try {
+    return psis_loo_expect(cat, n_samples, k, params, r_eff, n_func, func, loo_func, loo_pred, loo_pit_mix, pareto_k, n_eff);
+    } catch (...) { return on_exception("mcd_psis_loo_expect"); }
 }
 
 int mcd_posterior_predictive(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params, double* out,

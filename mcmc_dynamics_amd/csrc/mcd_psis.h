@@ -112,12 +112,43 @@ MCD_HD int64_t psis_tile_stars(int64_t n, int64_t S, int64_t fixed_bytes, int64_
     return t < n ? t : n;
 }
 
+// ---- leave-one-out expectations under the same weights (mcd_psis_loo_expect) ---------------
+// Rows of one star in the term tile [star][rows][S]: lnL first, then what the call asked for.
+enum LooxRow : int { LR_LNL = 0, LR_PIT = 1, LR_Z = 2, LR_VLOS = 3, LR_SIG = 4, LR_MIX = 5 };
+// What the term kernel writes next to lnL: nothing, the four predictive rows, or those and pit_mix.
+enum LooxMode : int { LOOX_NONE = 0, LOOX_PRED = 1, LOOX_PRED_MIX = 2 };
+MCD_HD constexpr int loox_rows(int mode) { return mode == LOOX_NONE ? 1 : mode == LOOX_PRED ? 5 : 6; }
+// Most star-independent functions of the sample per call (include/mcd.h: MCD_LOO_MAX_FUNC).
+constexpr int kLooMaxFunc = 16;
+// Fields of the device's out[][n]: k^, n_eff, then the rows after lnL in LooxRow order, then the functions.
+enum LooxField : int { LXF_K = 0, LXF_NEFF = 1, LXF_ROWS = 2 };
+
+// Un-normalised weight of a sample whose (smoothed or raw) log weight is v <= 0, with the shift mw of the star: the
+// e_s of a1 = sum_s e_s in psis_tail_kernel.
+MCD_HD double loox_weight(double v, double mw) { return exp_(v - mw); }
+// E_loo[x] = sum_s e_s x_s / sum_s e_s
+MCD_HD double loox_ratio(double num, double den) { return num / den; }
+
+// psis_tile_stars for tiles of `rows` rows of S terms per star.
+MCD_HD int64_t psis_tile_stars_rows(int64_t n, int64_t S, int64_t rows, int64_t fixed_bytes, int64_t budget) {
+    const int64_t row = S * 8 * rows;
+    if (budget - fixed_bytes < row) return 0;
+    int64_t t = (budget - fixed_bytes) / row;
+    if (t >= 64) t -= t % 64;
+    return t < n ? t : n;
+}
+
 #if defined(__HIPCC__)
 // mcd_psis.hip: PSIS-LOO of the n stars of one tile (records: the tile's first record; wpar: the S derived sample rows,
 // [S][KD] in term precision).  terms: [n][S] float64 scratch; out: out[f * out_stride + i] for the four PsisFields.
 struct LaunchShape;
 hipError_t launch_psis(hipStream_t s, const LaunchShape& shape, const void* records, int64_t n, const void* wpar,
                        int64_t S, int64_t M, double r_eff, double* terms, double* out, int64_t out_stride);
+// mcd_loo_expect.hip: the leave-one-out expectations of the n stars of one tile.  mode: LooxMode; terms: [n][rows][S]
+// float64 scratch; func: [S][n_func] on the device (null when n_func == 0); out: out[f * out_stride + i], LooxField.
+hipError_t launch_loo_expect(hipStream_t s, const LaunchShape& shape, int mode, const void* records, int64_t n,
+                             const void* wpar, int64_t S, int64_t M, double r_eff, const double* func, int n_func,
+                             double* terms, double* out, int64_t out_stride);
 #endif
 
 }  // namespace mcd
