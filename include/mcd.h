@@ -258,6 +258,30 @@ int mcd_psis_loo_expect(mcd_catalog* cat, int64_t n_samples, int32_t k, const do
                         double* loo_pred     /* [MCD_LOOX_FIELDS][n_stars], or NULL */,
                         double* loo_pit_mix  /* [n_stars] or NULL; Gaussian-background models only */,
                         double* pareto_k, double* n_eff  /* [n_stars] or NULL each */);
+/* Exact leave-out refits: E ensembles that each leave out their own set of stars share ONE evaluation of the catalogue.
+ * Hold-out sets: set_offsets[n_sets + 1], non-decreasing, set_offsets[0] = 0, set_offsets[n_sets] <= n_stars; set e is the
+ * stars [set_offsets[e], set_offsets[e + 1]) in catalogue order (the caller orders the stars so), the stars from
+ * set_offsets[n_sets] on belong to no set, a set may be empty.  With l_i(theta) the star's plain term (what
+ * mcd_loglike_per_star returns) and rows theta[e][w] (params: row-major [E][W][K], the kernel columns of mcd_loglike_batch):
+ *   train[e][w] = sum of l_i over the stars outside set e      test[e][w] = sum of l_i over set e (+0.0 for an empty set)
+ * train + test equals mcd_loglike_batch with option "fast_path" = 0 to rounding.  Every row meets every star once; the
+ * chunk sums are added per star range in a fixed order and `train` is the sum of the other ranges' sums in ascending
+ * order -- no difference of two sums is formed.  `test` may be NULL.  Synchronous and deterministic: bit-identical from run
+ * to run, independent of earlier calls.  The plan of (set_offsets, E W) and its buffers stay with the catalogue.
+ * MCD_ERR_INVALID, with a message and nothing written: a binned or a float32 catalogue; several devices or a
+ * communicator; invalid offsets; n_sets < 1; E W > 65536; a foreign k; range sums ((n_sets + 1) x roundup64(E W) x 8
+ * bytes) beyond 256 MiB.  Waits under the context's deadline; honours option "timing" (mcd_last_kernel_ms: the main kernel). */
+int mcd_holdout_loglike(mcd_catalog* cat, int32_t n_sets, const int64_t* set_offsets, int64_t n_walkers, int32_t k,
+                        const double* params /* [E][W][K] */, double* train /* [E][W] */,
+                        double* test /* [E][W], may be NULL */);
+/* ... and the closing step: for star i of set e and that set's S sample rows (params: row-major [E][S][K]),
+ *   lppd[i] = log( (1/S) sum_s exp(l_i(theta[e][s])) )      lnl_var[i] = sample variance (S-1) of l_i (0 when S == 1)
+ * with the accumulators and merge rules of mcd_pointwise_posterior on the set's star range: one set that covers the
+ * catalogue gives that call's bits.  Outputs hold set_offsets[n_sets] stars; either may be NULL.  Refusals as above
+ * (without the row cap); samples go up in passes of "posterior_pass" rows; synchronous, deterministic, honours "timing". */
+int mcd_holdout_pointwise(mcd_catalog* cat, int32_t n_sets, const int64_t* set_offsets, int64_t n_samples, int32_t k,
+                          const double* params /* [E][S][K] */, double* lppd /* [set_offsets[E]] */,
+                          double* lnl_var /* may be NULL */);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

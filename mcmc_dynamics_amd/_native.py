@@ -60,6 +60,10 @@ SYMBOLS = {
     "mcd_psis_loo_expect": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_double,
                                            ctypes.c_int32, _c_double_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                            _c_double_p]),
+    "mcd_holdout_loglike": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_int64_p, ctypes.c_int64, ctypes.c_int32, _c_double_p,
+                                           _c_double_p, _c_double_p]),
+    "mcd_holdout_pointwise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_int64_p, ctypes.c_int64, ctypes.c_int32,
+                                             _c_double_p, _c_double_p, _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -675,6 +679,42 @@ class Catalog(object):
             out["pit_mix"] = mix
         if func is not None:
             out["func"] = np.ascontiguousarray(loo_func.T)
+        return out
+
+    def _holdout_args(self, set_offsets, table):
+        offs = np.ascontiguousarray(set_offsets, dtype=np.int64).reshape(-1)
+        if offs.size < 2:
+            raise ValueError("set_offsets must hold n_sets + 1 >= 2 offsets")
+        p = _f64(table)
+        if p.ndim != 3 or p.shape[0] != offs.size - 1 or p.shape[2] != self.k:
+            raise ValueError("table must have shape ({0}, rows, {1})".format(offs.size - 1, self.k))
+        return offs, np.ascontiguousarray(p)
+
+    def holdout_loglike(self, set_offsets, table, want_test=True):
+        """Hold-out evaluation (include/mcd.h: mcd_holdout_loglike): ``set_offsets`` (E + 1,) star offsets of the sets, which
+        are consecutive prefixes of the catalogue, ``table`` (E, W, K) kernel rows -> (train (E, W), test (E, W)): the sum of
+        the per-star terms outside / inside row e's set.  ``want_test=False`` passes a null pointer and returns (train, None).
+        Un-binned float64 catalogues on one device; synchronous and bit-identical from run to run."""
+        self._alive()
+        offs, p = self._holdout_args(set_offsets, table)
+        train = np.empty(p.shape[:2], dtype=np.float64)
+        test = np.empty(p.shape[:2], dtype=np.float64) if want_test else None
+        rc = self.lib.mcd_holdout_loglike(self.handle, offs.size - 1, offs.ctypes.data_as(_c_int64_p), p.shape[1], p.shape[2],
+                                          _ptr(p), _ptr(train), _ptr(test))
+        _check(self.lib, rc, "mcd_holdout_loglike")
+        return train, test
+
+    def holdout_pointwise(self, set_offsets, table):
+        """Hold-out pointwise summaries (include/mcd.h: mcd_holdout_pointwise): ``table`` (E, S, K), the S sample rows of
+        every set's own refit -> dict of (set_offsets[E],) arrays ``lppd`` and ``lnl_var`` for the held-out stars, each
+        under its own set's samples."""
+        self._alive()
+        offs, p = self._holdout_args(set_offsets, table)
+        n = int(offs[-1]) if 0 <= int(offs[-1]) <= self.n_stars else 0
+        out = {k: np.empty(n, dtype=np.float64) for k in ("lppd", "lnl_var")}
+        rc = self.lib.mcd_holdout_pointwise(self.handle, offs.size - 1, offs.ctypes.data_as(_c_int64_p), p.shape[1], p.shape[2],
+                                            _ptr(p), _ptr(out["lppd"]), _ptr(out["lnl_var"]))
+        _check(self.lib, rc, "mcd_holdout_pointwise")
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

@@ -272,6 +272,16 @@ class BinnedConstantFit(ConstantFit):
     def loo_influence(self, chain, n_burn, thin=1, r_eff=1.0, functions=None):
         return self.loo(chain, n_burn, thin, r_eff)
 
+    def holdout_fit(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: hold-out refits (holdout_fit, reloo, kfold) are defined for un-binned "
+                                  "fits only; fit the bins' stars with ConstantFit to cross-validate")
+
+    def reloo(self, *args, **kwargs):
+        return self.holdout_fit()
+
+    def kfold(self, *args, **kwargs):
+        return self.holdout_fit()
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

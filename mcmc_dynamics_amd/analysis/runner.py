@@ -168,6 +168,34 @@ def loo_summary(elpd_loo, lppd, pareto_k, n_samples, group=None):
             "k_threshold": float(thr), "n_bad_k": int(n_bad), "pareto_k": k, "pointwise": elpd}
 
 
+def _elpd_totals(elpd, group=None):
+    """(sum, se, N) of per-star elpd values by the arithmetic of ``loo_summary``: se = sqrt(N Var_i(elpd_i))."""
+    elpd = np.asarray(elpd, dtype=np.float64)
+    totals = np.array([elpd.sum(), np.dot(elpd, elpd), float(elpd.size)])
+    if group is not None:
+        totals = np.asarray(group.allreduce(totals), dtype=np.float64)
+    s_elpd, s_elpd2, n = (float(t) for t in totals)
+    var_i = (s_elpd2 - s_elpd * s_elpd / n) / (n - 1.0) if n > 1 else 0.0
+    return s_elpd, float(np.sqrt(n * max(var_i, 0.0))), int(n)
+
+
+def kfold_summary(pointwise, folds=None):
+    """K-fold cross-validation totals from the per-star predictive densities of ``Runner.kfold`` (each star under the
+    refit that left its fold out; Vehtari, Gelman & Gabry 2017, section 2.4): ``elpd_kfold`` = sum_i elpd_i, ``se`` =
+    sqrt(N Var_i(elpd_i)) as in ``loo_summary``, ``pointwise``, ``n_stars``, ``n_folds`` and ``folds`` (the fold id per
+    star, or None).  A higher ``elpd_kfold`` is the better model for the same stars; ``elpd_compare`` takes the result."""
+    elpd = np.asarray(pointwise, dtype=np.float64)
+    if elpd.ndim != 1 or not np.all(np.isfinite(elpd)):
+        raise ValueError("pointwise must hold one finite value per star (every star in exactly one fold)")
+    if folds is not None:
+        folds = np.asarray(folds, dtype=np.int64)
+        if folds.shape != elpd.shape:
+            raise ValueError("folds must hold one fold id per star")
+    s_elpd, se, n = _elpd_totals(elpd)
+    return {"elpd_kfold": s_elpd, "se": se, "pointwise": elpd, "n_stars": n,
+            "n_folds": int(np.unique(folds).size) if folds is not None else None, "folds": folds}
+
+
 def elpd_compare(a, b, group=None):
     """Difference of two models' expected log predictive densities on the same stars: ``a``, ``b`` are ``waic()`` or
     ``loo()`` results.  elpd_diff = sum_i (a_i - b_i) (positive: ``a`` predicts better), se_diff = sqrt(N Var_i(a_i - b_i)),
@@ -1260,6 +1288,197 @@ class Runner(object):
         if out["n_bad_k"]:
             logger.warning("PSIS-LOO: %d of %d stars have a Pareto k above %.2f; their leave-one-out estimates are "
                            "unreliable (see pareto_k)", out["n_bad_k"], out["n_stars"], out["k_threshold"])
+        return out
+
+    # ------------------------------------------------------------------ exact leave-out refits (new)
+    def _holdout_check(self, what):
+        """Hold-out refits run on one un-binned float64 catalogue of one device in one process."""
+        ctx = self._context
+        if ctx is not None and getattr(ctx, "n_ranks", 1) > 1:
+            raise NotImplementedError("Runner.{0}: hold-out refits run in one process on one device; this runner sits on a "
+                                      "context of {1} ranks".format(what, ctx.n_ranks))
+        if ctx is not None and int(getattr(ctx, "n_devices", 1)) > 1:
+            raise NotImplementedError("Runner.{0}: hold-out refits run on one device; this runner's context has "
+                                      "{1}".format(what, int(ctx.n_devices)))
+        if self._precision != "f64":
+            raise NotImplementedError("Runner.{0}: hold-out refits need a float64 catalogue".format(what))
+
+    def _holdout_sibling(self, data):
+        """A runner of this class on ``data``: a deep copy of the parameters, the same background object, context and
+        precision (NumPy's global generator, which every Runner seeds, is left as found)."""
+        state = np.random.get_state()
+        try:
+            kwargs = {"parameters": self.parameters.copy(), "context": self._context, "precision": self._precision}
+            if self.background is not None:
+                kwargs["background"] = self.background
+            return type(self)(data, **kwargs)
+        finally:
+            np.random.set_state(state)
+
+    @staticmethod
+    def _holdout_layout(sets, n_data):
+        """(sets as index arrays, permutation with the held-out stars first, set by set, offsets (E + 1,))."""
+        sets = [np.asarray(s, dtype=np.intp).reshape(-1) for s in sets]
+        if not sets:
+            raise ValueError("sets must hold at least one index array")
+        held = np.concatenate(sets) if sets else np.zeros(0, dtype=np.intp)
+        if held.size and (held.min() < 0 or held.max() >= n_data):
+            raise ValueError("star indices must lie in [0, {0})".format(n_data))
+        if np.unique(held).size != held.size:
+            raise ValueError("the hold-out sets must be disjoint")
+        rest = np.setdiff1d(np.arange(n_data, dtype=np.intp), held, assume_unique=True)
+        offsets = np.concatenate([[0], np.cumsum([s.size for s in sets])]).astype(np.int64)
+        return sets, np.concatenate([held, rest]), offsets
+
+    def holdout_fit(self, sets, n_walkers=64, n_steps=600, n_burn=200, pos=None, seed=None, thin=1):
+        """Refit the model once per hold-out set, all refits in lock step, and evaluate every held-out star under the
+        refit that left it out (Vehtari, Gelman & Gabry 2017, sections 2.3 and 2.4).  ``sets``: a list of E disjoint
+        arrays of star indices.  E ensembles of ``n_walkers`` walkers take ``n_steps`` stretch-move steps
+        (``BinnedSampler``, ``rng="device"``: the chain is a function of ``seed``); ensemble e samples the posterior of
+        all stars but set e -- one device launch evaluates all E W proposals against the whole catalogue and keeps each
+        set's sum apart (``_native.Catalog.holdout_loglike``).  ``pos``: start positions (E, W, P), default E W rows of
+        ``get_initials``.  The post-burn-in samples (every ``thin``-th step after ``n_burn``) of ensemble e then give
+        the predictive density of set e's stars (``_native.Catalog.holdout_pointwise``).
+
+        Returns ``elpd`` and ``lnl_var`` (n_data,) in this runner's star order (NaN for stars in no set), ``sets``,
+        ``sampler`` (``chain``: (E, W, steps, P)), ``tau`` (E,) the largest integrated autocorrelation time of each
+        refit and ``converged`` (E,) whether its post-burn-in chain holds 50 of them (``diagnostics.summary``; logged
+        where not), and ``n_samples`` per set."""
+        self._holdout_check("holdout_fit")
+        from .binned import BinnedSampler
+        from .. import diagnostics
+        if int(thin) < 1:
+            raise ValueError("thin must be >= 1")
+        if not 0 <= int(n_burn) < int(n_steps):
+            raise ValueError("n_burn must lie in [0, n_steps)")
+        sets, perm, offsets = self._holdout_layout(sets, self.n_data)
+        n_sets, n_p = len(sets), self.n_fitted_parameters
+        sib = self._holdout_sibling(self.data.take(perm))
+        try:
+            if pos is None:
+                pos = self.get_initials(n_sets * n_walkers).reshape(n_sets, n_walkers, n_p)
+            pos = np.ascontiguousarray(pos, dtype=np.float64)
+            if pos.shape != (n_sets, n_walkers, n_p):
+                raise ValueError("Array with starting values has invalid shape: expected {0}".format((n_sets, n_walkers, n_p)))
+            pars = sib.parameters
+            if not np.all(np.isfinite(pars.lnprior_batch(pars.resolve_batch(pos.reshape(-1, n_p))))):
+                raise ValueError("Invalid initial guesses: start positions outside the prior")
+            cat = sib._ensure_catalog()
+
+            def log_prob(values):
+                # box and structured priors as in lnprob_batch; rows outside the prior take a donor row for the launch
+                lead = values.shape[:-1]
+                resolved = pars.resolve_batch(values.reshape(-1, n_p))
+                lp = pars.lnprior_batch(resolved)
+                ok = np.isfinite(lp)
+                out = np.full(lp.shape, -np.inf)
+                if ok.any():
+                    if not ok.all():
+                        donor = int(np.flatnonzero(ok)[0])
+                        resolved = OrderedDict((k, np.where(ok, col, col[donor])) for k, col in resolved.items())
+                    table = sib._kernel_table(resolved)
+                    train, _ = cat.holdout_loglike(offsets, table.reshape(lead + (table.shape[1],)), want_test=False)
+                    out[ok] = train.reshape(-1)[ok] + lp[ok]
+                return out.reshape(lead)
+
+            sampler = BinnedSampler(n_sets, n_walkers, n_p, log_prob, seed=seed, rng="device")
+            logger.info("hold-out refits: %d sets of %d .. %d stars, %d walkers each, %d steps", n_sets,
+                        min(s.size for s in sets), max(s.size for s in sets), n_walkers, n_steps)
+            sampler.reserve(n_steps)
+            sampler.run_mcmc(pos, n_steps)
+            chain = sampler.chain                                           # (E, W, steps, P)
+            kept = chain[:, :, int(n_burn)::int(thin), :]
+            n_samples = kept.shape[1] * kept.shape[2]
+            resolved = pars.resolve_batch(kept.reshape(-1, n_p))
+            table = sib._kernel_table(resolved).reshape(n_sets, n_samples, -1)
+            pw = cat.holdout_pointwise(offsets, table)
+        finally:
+            sib.close()
+        elpd, var = np.full(self.n_data, np.nan), np.full(self.n_data, np.nan)
+        held = perm[:int(offsets[-1])]
+        elpd[held], var[held] = pw["lppd"], pw["lnl_var"]
+        diag = diagnostics.summary(np.transpose(chain[:, :, int(n_burn):, :], (2, 0, 1, 3)), context=self._diagnostics_context())
+        with np.errstate(invalid="ignore"):
+            tau = np.max(np.atleast_2d(diag["tau"]), axis=1)
+        converged = np.all(np.atleast_2d(diag["converged"]), axis=1)
+        for e in np.flatnonzero(~converged):
+            logger.warning("hold-out refit %d: %d post-burn-in steps are fewer than 50 autocorrelation times (tau = %.1f); "
+                           "its stars' estimates carry more Monte-Carlo error than the sample count suggests", int(e),
+                           n_steps - int(n_burn), float(tau[e]))
+        return {"elpd": elpd, "lnl_var": var, "sets": sets, "sampler": sampler, "tau": tau, "converged": converged,
+                "n_samples": int(n_samples)}
+
+    def reloo(self, loo_result, chain, n_burn, stars=None, max_refits=16, **fit):
+        """Exact leave-one-out values for the stars PSIS cannot handle: refit without each of them (``holdout_fit`` with
+        singleton sets) and put the exact elpd_i in place of the PSIS estimate.  ``loo_result``: what ``loo`` returned for
+        ``chain`` / ``n_burn``.  ``stars``: the stars to refit; default those with ``pareto_k`` above ``k_threshold``,
+        largest k^ first, at most ``max_refits`` (a logged line says how many were left out).  The refits start from
+        draws of the post-burn-in rows of ``chain`` -- the full posterior is an excellent start for a leave-one-out
+        posterior; ``fit``: further arguments of ``holdout_fit`` (``n_burn`` here is the burn-in of ``chain``: the refits' own
+        is ``refit_burn``, default ``holdout_fit``'s).
+
+        Returns a copy of ``loo_result`` with ``pointwise`` replaced for the refitted stars, ``elpd_loo``, ``p_loo``,
+        ``looic`` and ``se`` recomputed (the arithmetic of ``loo_summary``), ``refit`` (their indices), ``n_bad_k``
+        counting only the stars that still rely on PSIS, ``refit_converged`` / ``refit_tau`` of the refits and ``fit``
+        (what ``holdout_fit`` returned).
+        ``elpd_compare`` takes the result."""
+        self._holdout_check("reloo")
+        k = np.asarray(loo_result["pareto_k"], dtype=np.float64)
+        thr = float(loo_result["k_threshold"])
+        if stars is None:
+            bad = np.flatnonzero(k > thr)
+            bad = bad[np.argsort(-k[bad], kind="stable")]
+            stars = bad[:int(max_refits)]
+            logger.info("reloo: %d of %d stars have a Pareto k above %.2f; refitting %d, %d left to PSIS", bad.size, k.size,
+                        thr, stars.size, bad.size - stars.size)
+        stars = np.asarray(stars, dtype=np.intp).reshape(-1)
+        out = dict(loo_result)
+        pointwise = np.array(loo_result["pointwise"], dtype=np.float64)
+        out["pareto_k"] = k.copy()
+        out["refit"] = stars.copy()
+        if stars.size:
+            fit = dict(fit)
+            refit_burn = fit.pop("refit_burn", None)
+            if refit_burn is not None:
+                fit["n_burn"] = refit_burn
+            n_walkers = int(fit.get("n_walkers", 64))
+            if fit.get("pos") is None:
+                chain = np.asarray(chain, dtype=np.float64)
+                flat = chain[:, int(n_burn):, :].reshape(-1, chain.shape[2])
+                need = stars.size * n_walkers
+                if flat.shape[0] == 0:
+                    raise ValueError("no samples left after n_burn = {0}".format(n_burn))
+                rng = np.random.RandomState(fit.get("seed"))
+                rows = rng.choice(flat.shape[0], size=need, replace=flat.shape[0] < need)
+                fit["pos"] = flat[rows].reshape(stars.size, n_walkers, chain.shape[2])
+            res = self.holdout_fit([[int(i)] for i in stars], **fit)
+            pointwise[stars] = res["elpd"][stars]
+            out["refit_converged"], out["refit_tau"], out["fit"] = res["converged"], res["tau"], res
+        s_elpd, se, _ = _elpd_totals(pointwise)
+        still = np.ones(k.size, dtype=bool)
+        still[stars] = False
+        out.update({"pointwise": pointwise, "elpd_loo": s_elpd, "p_loo": float(loo_result["lppd"]) - s_elpd,
+                    "looic": -2.0 * s_elpd, "se": se, "n_bad_k": int(np.count_nonzero((k > thr) & still))})
+        return out
+
+    def kfold(self, n_folds=10, seed=None, **fit):
+        """K-fold cross-validation: a random partition of the stars into ``n_folds`` sets drawn from ``seed``, one refit
+        per fold in lock step (``holdout_fit``; ``fit``: its further arguments, ``seed`` by default this one), every star
+        evaluated under the refit that left its fold out.  Returns ``kfold_summary`` -- ``elpd_kfold``, ``se``,
+        ``pointwise``, ``n_stars``, ``n_folds``, ``folds`` -- plus ``converged`` and ``tau`` per fold, ``n_samples`` and ``fit`` (what
+        ``holdout_fit`` returned).
+        The remedy when many Pareto k^ are bad; ``elpd_compare`` takes the result."""
+        self._holdout_check("kfold")
+        n, n_folds = self.n_data, int(n_folds)
+        if not 2 <= n_folds <= n:
+            raise ValueError("n_folds must lie in [2, n_data]")
+        folds = np.empty(n, dtype=np.int64)
+        folds[np.random.RandomState(seed).permutation(n)] = np.arange(n) % n_folds
+        fit = dict(fit)
+        fit.setdefault("seed", seed)
+        res = self.holdout_fit([np.flatnonzero(folds == f) for f in range(n_folds)], **fit)
+        out = kfold_summary(res["elpd"], folds)
+        out.update({"converged": res["converged"], "tau": res["tau"], "n_samples": res["n_samples"], "fit": res})
         return out
 
     def _warn_bad_k(self, what, n_bad, n_stars, threshold):

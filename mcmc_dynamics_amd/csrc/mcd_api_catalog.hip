@@ -474,6 +474,7 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
         if (sh.ev_end) (void)hipEventDestroy(sh.ev_end);
         for (auto& pr : sh.ring) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     }
+    release_holdout(cat);
     for (hipEvent_t e : cat->chain_events) (void)hipEventDestroy(e);
     if (cat->chain.d) (void)hipFree(cat->chain.d);
     if (cat->chain.h) (void)hipHostFree(cat->chain.h);
@@ -545,6 +546,7 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
                 for (auto& kv : sh.work) free_workset(kv.second);
                 sh.work.clear();
             }
+            release_holdout(cat);
             cat->cur_walkers = 0;
         }
         return MCD_OK;

@@ -10,6 +10,7 @@
 //   mcd_api_chain.hip      the stretch-move block and the HMC block, each resident on the device or host-driven
 //   mcd_api_temper.hip     the parallel-tempering block in the same two forms
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
+//   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -184,6 +185,24 @@ struct Shard {
     size_t ring_used = 0;
 };
 
+// mcd_holdout_loglike: the range plan of one (set_offsets, E W) and its buffers (mcd_api_holdout.hip), kept by the catalogue
+struct HoldoutWork {
+    int64_t n_rows = 0;                // E W
+    int64_t n_ranges = 0;              // the sets [, the remainder] (mcd_holdout.h: holdout_ranges)
+    int64_t n_chunks = 0;
+    int64_t max_chunks_per_range = 0;
+    mcd::Chunk* d_chunks = nullptr;
+    int64_t* d_offsets = nullptr;      // [n_ranges + 1] chunk offsets
+    double* d_params = nullptr;        // [E W][K]
+    void* d_wpar = nullptr;            // [E W][KD]
+    double* d_partials = nullptr;      // [roundup64(E W) / 8][n_chunks][8]
+    double* d_sums = nullptr;          // [n_ranges][E W]
+    double* d_out = nullptr;           // [2][E W] train, test
+    double* h_params = nullptr;        // pinned
+    double* h_out = nullptr;           // pinned
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // option "timing": around the main kernel
+};
+
 // Device scratch of one call: hipMalloc'ed blocks and an optional pair of timing events, released on every exit path.
 struct DeviceScratch {
     std::vector<void*> blocks;
@@ -235,6 +254,8 @@ void big_copy(void* dst, const void* src, size_t bytes);
 // mcd_api_eval.hip
 int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
 int sync_all(mcd_catalog* cat);
+// mcd_api_holdout.hip
+void release_holdout(mcd_catalog* cat);
 
 MCD_HOST_END
 
@@ -324,6 +345,8 @@ struct mcd_catalog {
     // parallel-tempering blocks (mcd_temper_block): state, numbers, scratch and rows of the resident block, its pinned mirror
     mcd::host::ChainArena temper;
     int64_t temper_device_blocks = 0, temper_host_blocks = 0;
+    // exact leave-out refits (mcd_holdout_loglike): plans and buffers per (set_offsets, E W), released with the catalogue
+    std::map<std::pair<std::vector<int64_t>, int64_t>, mcd::host::HoldoutWork> holdout;
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet

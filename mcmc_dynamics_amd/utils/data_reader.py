@@ -151,6 +151,14 @@ class DataReader(object):
             return None
         return self.__class__(self.data[bins == i])
 
+    def take(self, indices):
+        """DataReader of the rows ``indices``, in that order (a permutation reorders the stars; units are kept)."""
+        idx = np.asarray(indices, dtype=np.intp).reshape(-1)
+        n = self.sample_size
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise IndexError("row indices must lie in [0, {0})".format(n))
+        return self.__class__(self.data[idx])
+
     def sorted_by_bin(self):
         """(DataReader sorted by bin, offsets[B + 1]): the layout the binned kernel launch expects."""
         bins = np.asarray(self.data["bin"], dtype=np.int64)

@@ -1,0 +1,66 @@
+#!/usr/bin/env python3
+"""Register and scratch use of the kernels of csrc/mcd_holdout.hip, from hipcc's resource-usage remarks for gfx950 (the
+sibling of tools/loo_expect_resources.py).
+
+    python tools/holdout_resources.py              # one line per instantiation
+    python tools/holdout_resources.py --json OUT   # also writes the rows as JSON
+
+DESIGN.md section 3.16 quotes the table; tests/test_holdout_cpu.py asserts that no instantiation uses scratch or spills.
+"""
+import json
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
+MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
+          6: "PROFILE_BGFIXED"}
+_MAIN = re.compile(r"holdout_kernelILi(\d)ELb(\d)EE")
+_FIELD = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\w+) \[-Rpass")
+KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize": "scratch_bytes_per_lane",
+        "Occupancy": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size": "lds_bytes"}
+
+
+def analyse():
+    """Rows (dicts) per kernel instantiation of the unit."""
+    out = tempfile.mkdtemp(prefix="holdout_resources_")
+    res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
+                          "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, "mcd_holdout.hip"),
+                          "-o", os.path.join(out, "mcd_holdout.o")], check=True, capture_output=True, text=True)
+    rows, row = [], None
+    for line in res.stderr.split("\n"):
+        if "remark: Function Name:" in line:
+            name = line.split("Function Name:")[1].split()[0]
+            m = _MAIN.search(name)
+            if m:
+                row = {"kernel": "holdout", "model": MODELS[int(m.group(1))], "free_centre": m.group(2) == "1"}
+            else:
+                row = {"kernel": "combine" if "holdout_combine_kernel" in name else name}
+            row["symbol"] = name
+            rows.append(row)
+            continue
+        f = _FIELD.search(line)
+        if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
+            row[KEYS[f.group(1).strip()]] = int(f.group(2))
+    return rows
+
+
+def main():
+    rows = analyse()
+    print("{0:8s} {1:16s} {2:6s} {3:>6s} {4:>6s} {5:>8s} {6:>10s}".format("kernel", "model", "centre", "VGPRs", "SGPRs",
+                                                                        "scratch", "waves/SIMD"))
+    for r in rows:
+        print("{0:8s} {1:16s} {2:6s} {3:6d} {4:6d} {5:8d} {6:10d}".format(
+            r["kernel"][:8], r.get("model", "-"), "free" if r.get("free_centre") else "fixed", r["vgprs"], r["sgprs"],
+            r["scratch_bytes_per_lane"], r["occupancy"]))
+    if len(sys.argv) == 3 and sys.argv[1] == "--json":
+        with open(sys.argv[2], "w") as fh:
+            json.dump({"generated_by": "tools/holdout_resources.py", "rows": rows}, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    sys.exit(main())
