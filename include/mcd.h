@@ -498,6 +498,43 @@ int mcd_temper_block_prior(mcd_catalog* cat, const mcd_temper_desc* desc, int64_
 int mcd_temper_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int32_t n_temps, int64_t n_walkers, double* swap_thr);
 int mcd_temper_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks);
 
+/* Moment matching for PSIS-LOO (Paananen, Piironen, Buerkner & Vehtari 2021; loo_moment_match.default of the R package loo):
+ * the cheaper remedy, before a refit, for the stars whose Pareto k^ is too large.  The S posterior draws (row-major [S][P],
+ * the free parameters in their own units, resolved into kernel rows by `map` as in mcd_stretch_move) are moved towards each
+ * star's leave-one-out posterior by affine maps theta -> A theta + b that match the importance-weighted mean, then the
+ * variances, then (cov, S > 10 P) the covariance; a trial is kept when it lowers k^.  The algebra, the order of the trials
+ * and the meaning of `iterations` / `accepted` are mcmc_dynamics_amd/csrc/mcd_mmatch.h.  With l_i the star's plain term and
+ * L_-i the sum of all others (mcd_holdout_loglike's test and train for the singleton set {i}), the log weights are
+ *   baseline  -l_i(theta_s)                                        lp0_s = L_-i + l_i + lnprior, by these plain terms
+ *   trial     L_-i(theta') + lnprior(theta') - lp0_s               -inf for a row outside the prior (box, support, fixed_ok)
+ *   split     (split, and at least one trial kept) the first floor(S/2) rows transformed, the rest as drawn:
+ *             L_-i + lnprior - logaddexp(lp, lp(T^-1 .) - log|det A|) -- the estimate no longer depends on the draws that
+ *             chose the map
+ * each smoothed with the tail rules of mcd_psis_loo.  Per star of `stars` (ascending, distinct): elpd = log sum w~ exp(l_i)
+ * over the final rows, pareto_k and n_eff = r_eff / sum w~^2 of the final weights, k_before (the baseline's k^; elpd and
+ * pareto_k equal mcd_psis_loo's to rounding when max_iters = 0), k_loop (k^ when the loop ended), iterations, accepted
+ * [n_match][3] per level, and the total map A [n_match][P][P], b [n_match][P] (identity and 0 when nothing was kept).
+ * Stars run in lock-stepped groups of floor(65536 / S); rows, weights, moments and kernel tables stay on the device, one
+ * hold-out evaluation per trial and group, and only per-star scalars come back between two of them.  Synchronous and
+ * deterministic: bit-identical from run to run, independent of earlier calls.  Any output pointer may be NULL.
+ * MCD_ERR_INVALID, with a message and nothing written: a binned or a float32 catalogue; several devices or a communicator;
+ * n_dim outside 1 .. 12; n_samples > 65536 or with a PSIS tail shorter than 5; star indices unsorted, repeated or outside
+ * the catalogue; r_eff <= 0; max_iters < 0; a bad prior descriptor.  MCD_ERR_NONFINITE (nothing written): a draw outside
+ * the prior.  Device scratch is released on every exit path; waits under the context's deadline; honours option "timing"
+ * (mcd_last_kernel_ms: the hold-out main kernels of all rounds). */
+typedef struct {
+    mcd_stretch_desc map;     /* column map, box, fixed_ok; n_walkers ignored, n_bins 0 or 1 */
+    int32_t max_iters;        /* >= 0; 0: baseline only */
+    int32_t cov, split;       /* 0 / 1 */
+    double k_threshold, r_eff;
+} mcd_mmatch_desc;
+int mcd_moment_match(mcd_catalog* cat, const mcd_mmatch_desc* d, const mcd_prior_desc* prior /* may be NULL */,
+                     int64_t n_samples, const double* draws /* [S][P] */, int64_t n_match,
+                     const int64_t* stars /* ascending, distinct */,
+                     double* elpd, double* pareto_k, double* n_eff, double* k_before, double* k_loop, /* [n_match] */
+                     int32_t* iterations, int32_t* accepted /* [n_match][3] */, double* A /* [n_match][P][P] */,
+                     double* b /* [n_match][P] */);
+
 /* ---- convergence diagnostics of a stored chain ------------------------------------------- */
 
 /* Integrated autocorrelation time (the estimator of emcee's autocorr.integrated_time), split-R-hat (Gelman et al., BDA3)

@@ -64,6 +64,10 @@ SYMBOLS = {
                                            _c_double_p, _c_double_p]),
     "mcd_holdout_pointwise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_int64_p, ctypes.c_int64, ctypes.c_int32,
                                              _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_moment_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
+                                        ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                        _c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                        _c_double_p, _c_double_p]),
     "mcd_kde_background": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_int64, _c_double_p,
                                           _c_double_p, ctypes.c_double, _c_double_p, _c_double_p]),
     "mcd_stretch_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
@@ -234,6 +238,12 @@ class HmcDesc(ctypes.Structure):
     """Mirror of ``mcd_hmc_desc``."""
     _fields_ = [("map", StretchDesc), ("chol", _c_double_p), ("step_size", ctypes.c_double), ("jitter", ctypes.c_double),
                 ("n_leap", ctypes.c_int32)]
+
+
+class MmatchDesc(ctypes.Structure):
+    """Mirror of ``mcd_mmatch_desc``."""
+    _fields_ = [("map", StretchDesc), ("max_iters", ctypes.c_int32), ("cov", ctypes.c_int32), ("split", ctypes.c_int32),
+                ("k_threshold", ctypes.c_double), ("r_eff", ctypes.c_double)]
 
 
 class TemperDesc(ctypes.Structure):
@@ -715,6 +725,45 @@ class Catalog(object):
         rc = self.lib.mcd_holdout_pointwise(self.handle, offs.size - 1, offs.ctypes.data_as(_c_int64_p), p.shape[1], p.shape[2],
                                             _ptr(p), _ptr(out["lppd"]), _ptr(out["lnl_var"]))
         _check(self.lib, rc, "mcd_holdout_pointwise")
+        return out
+
+    def moment_match(self, plan, draws, stars, k_threshold, max_iters=30, cov=True, split=True, r_eff=1.0, out=None):
+        """Moment matching for PSIS-LOO (include/mcd.h: mcd_moment_match; csrc/mcd_mmatch.h): ``plan`` as for
+        ``stretch_move`` (column map, box, ``fixed_ok``, optional ``prior``), ``draws`` (S, P) posterior draws of the free
+        parameters, ``stars`` ascending distinct star indices -> dict of per-star arrays ``elpd``, ``pareto_k``, ``n_eff``,
+        ``k_before``, ``k_loop`` (n,), ``iterations`` (n,), ``accepted`` (n, 3) int32, and the total affine maps ``A``
+        (n, P, P), ``b`` (n, P).  ``max_iters=0`` is the baseline: plain PSIS by the hold-out terms.  ``out``: such a dict
+        of C-contiguous arrays to write into (a refused call leaves them as they were)."""
+        self._alive()
+        x = np.ascontiguousarray(_f64(draws))
+        if x.ndim != 2:
+            raise ValueError("moment_match: draws must have shape (S, P)")
+        S, P = x.shape
+        idx = np.ascontiguousarray(stars, dtype=np.int64).reshape(-1)
+        head, _tail, _keep = self._stretch_args("moment_match", plan, x[:2], np.zeros(min(S, 2)), 0, None, None, None)
+        d = MmatchDesc()
+        d.map = head[1]._obj
+        d.map.n_bins = 1
+        d.max_iters, d.cov, d.split = int(max_iters), int(bool(cov)), int(bool(split))
+        d.k_threshold, d.r_eff = float(k_threshold), float(r_eff)
+        n = idx.size
+        if out is None:
+            out = {k: np.empty(n) for k in ("elpd", "pareto_k", "n_eff", "k_before", "k_loop")}
+            out["iterations"] = np.empty(n, dtype=np.int32)
+            out["accepted"] = np.empty((n, 3), dtype=np.int32)
+            out["A"], out["b"] = np.empty((n, P, P)), np.empty((n, P))
+        shapes = {"iterations": (n,), "accepted": (n, 3), "A": (n, P, P), "b": (n, P)}
+        for key, a in out.items():
+            want = np.int32 if key in ("iterations", "accepted") else np.float64
+            if a.dtype != want or not a.flags.c_contiguous or a.shape != shapes.get(key, (n,)):
+                raise ValueError("moment_match: out['{0}'] has the wrong dtype, layout or shape".format(key))
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        prior = self._prior_arg[0] if self._prior_arg is not None else None
+        rc = self.lib.mcd_moment_match(self.handle, ctypes.byref(d), prior, S, _ptr(x), n, idx.ctypes.data_as(_c_int64_p),
+                                       _ptr(out["elpd"]), _ptr(out["pareto_k"]), _ptr(out["n_eff"]), _ptr(out["k_before"]),
+                                       _ptr(out["k_loop"]), out["iterations"].ctypes.data_as(i32),
+                                       out["accepted"].ctypes.data_as(i32), _ptr(out["A"]), _ptr(out["b"]))
+        _check(self.lib, rc, "mcd_moment_match")
         return out
 
     def _stretch_args(self, name, plan, pos, lnp, n_steps, chain, lnprob_chain, accepted):

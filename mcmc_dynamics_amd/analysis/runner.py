@@ -1461,6 +1461,63 @@ class Runner(object):
                     "looic": -2.0 * s_elpd, "se": se, "n_bad_k": int(np.count_nonzero((k > thr) & still))})
         return out
 
+    def loo_moment_match(self, loo_result, chain, n_burn, thin=1, stars=None, max_stars=256, max_iters=30, k_threshold=None,
+                         cov=True, split=True, r_eff=1.0):
+        """Moment matching (Paananen et al. 2021; ``loo_moment_match`` of the R package loo) for the stars PSIS cannot
+        handle: the cheaper remedy to try before ``reloo``.  The post-burn-in draws of ``chain`` (every ``thin``-th step)
+        are moved towards each star's leave-one-out posterior by affine maps that match the importance-weighted mean,
+        variances and (``cov``) covariance, on the device (``_native.Catalog.moment_match``; csrc/mcd_mmatch.h), with the
+        ``split`` step that removes the bias of choosing the map with the draws that carry the estimate.
+        ``loo_result``: what ``loo`` returned for the same ``chain`` / ``n_burn`` / ``thin``.  ``stars``: the stars to
+        match; default those with ``pareto_k`` above ``k_threshold`` (default ``loo_result["k_threshold"]``), largest k^
+        first, at most ``max_stars``.
+
+        Returns a copy of ``loo_result`` with ``pointwise``, ``pareto_k`` and ``n_eff`` replaced for the matched stars,
+        ``elpd_loo``, ``p_loo``, ``looic`` and ``se`` recomputed (the arithmetic of ``reloo``), ``n_bad_k`` recounted, and
+        ``matched`` (their indices, ascending), ``k_before``, ``k_loop``, ``iterations``, ``accepted`` (n, 3) and
+        ``transform`` (``A`` (n, P, P), ``b`` (n, P)) per matched star.  ``reloo`` on the result refits only what is still
+        above the threshold; ``elpd_compare`` takes it."""
+        self._holdout_check("loo_moment_match")
+        self._grad_plan()                      # refuses expr constraints and lnprior expressions
+        k = np.asarray(loo_result["pareto_k"], dtype=np.float64)
+        thr = float(loo_result["k_threshold"]) if k_threshold is None else float(k_threshold)
+        if stars is None:
+            bad = np.flatnonzero(k > thr)
+            bad = bad[np.argsort(-k[bad], kind="stable")]
+            stars = bad[:int(max_stars)]
+            logger.info("loo_moment_match: %d of %d stars have a Pareto k above %.2f; matching %d", bad.size, k.size, thr,
+                        stars.size)
+        stars = np.unique(np.asarray(stars, dtype=np.int64).reshape(-1))
+        if stars.size and (stars[0] < 0 or stars[-1] >= k.size):
+            raise ValueError("star indices must lie in [0, {0})".format(k.size))
+        out = dict(loo_result)
+        pointwise = np.array(loo_result["pointwise"], dtype=np.float64)
+        pareto_k, n_eff = k.copy(), np.array(loo_result["n_eff"], dtype=np.float64)
+        n_p = self.n_fitted_parameters
+        res = {"k_before": np.zeros(0), "k_loop": np.zeros(0), "iterations": np.zeros(0, dtype=np.int32),
+               "accepted": np.zeros((0, 3), dtype=np.int32), "A": np.zeros((0, n_p, n_p)), "b": np.zeros((0, n_p))}
+        if stars.size:
+            chain = np.asarray(chain, dtype=np.float64)
+            if chain.ndim != 3 or chain.shape[2] != n_p:
+                raise ValueError("chain must have shape (n_walkers, n_steps, {0})".format(n_p))
+            if int(thin) < 1:
+                raise ValueError("thin must be >= 1")
+            draws = np.ascontiguousarray(chain[:, n_burn::int(thin), :].reshape(-1, n_p))
+            if draws.shape[0] != int(loo_result["n_samples"]):
+                raise ValueError("chain, n_burn and thin give {0} draws, loo_result was made from {1}".format(
+                    draws.shape[0], int(loo_result["n_samples"])))
+            res = self._stretch_catalog(draws).moment_match(self._stretch_plan(), draws, stars, thr, max_iters=max_iters,
+                                                            cov=cov, split=split, r_eff=r_eff)
+            pointwise[stars], pareto_k[stars], n_eff[stars] = res["elpd"], res["pareto_k"], res["n_eff"]
+        s_elpd, se, _ = _elpd_totals(pointwise)
+        out.update({"pointwise": pointwise, "pareto_k": pareto_k, "n_eff": n_eff, "elpd_loo": s_elpd,
+                    "p_loo": float(loo_result["lppd"]) - s_elpd, "looic": -2.0 * s_elpd, "se": se,
+                    "n_bad_k": int(np.count_nonzero(pareto_k > float(loo_result["k_threshold"]))), "matched": stars,
+                    "k_before": res["k_before"], "k_loop": res["k_loop"], "iterations": res["iterations"],
+                    "accepted": res["accepted"], "transform": {"A": res["A"], "b": res["b"]}})
+        self._warn_bad_k("loo_moment_match", out["n_bad_k"], k.size, float(loo_result["k_threshold"]))
+        return out
+
     def kfold(self, n_folds=10, seed=None, **fit):
         """K-fold cross-validation: a random partition of the stars into ``n_folds`` sets drawn from ``seed``, one refit
         per fold in lock step (``holdout_fit``; ``fit``: its further arguments, ``seed`` by default this one), every star

@@ -136,6 +136,39 @@ int holdout_loglike(mcd_catalog* cat, int32_t n_sets, const int64_t* set_offsets
     return MCD_OK;
 }
 
+}  // namespace
+
+MCD_HOST_BEGIN
+
+// For callers whose parameter table is made ON the device (mcd_api_mmatch.hip): the plan over any ranges with offsets
+// 0 .. n_stars and its buffers, from the same cache ...
+int holdout_device_plan(mcd_catalog* cat, const std::vector<int64_t>& ranges, int64_t n_rows, HoldoutWork** out) {
+    return holdout_work(cat, cat->shards[0], ranges, (int32_t)ranges.size() - 1, n_rows, out);
+}
+
+// ... and one evaluation of the table the caller left in w.d_params: the launch sequence of mcd_holdout_loglike on the
+// catalogue's stream, without a copy and without a wait.  Row e n_walkers + i belongs to the set whose range is
+// d_set_range[e] (device memory); train and test stay in w.d_out ([2][n_rows]).  The device is current.
+int holdout_device_eval(mcd_catalog* cat, HoldoutWork& w, int64_t n_walkers, const int64_t* d_set_range) {
+    Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    MCD_HIP(mcd::launch_prepare_walkers(slot.stream, w.d_params, w.n_rows, cat->k, cat->model, cat->free_centre,
+                                        cat->precision, w.d_wpar));
+    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e0, slot.stream));
+    MCD_HIP(mcd::launch_holdout(slot.stream, shape, sh.records, w.d_chunks, w.n_chunks, w.d_wpar, w.d_partials, w.n_rows));
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e1, slot.stream));
+    MCD_HIP(mcd::launch_holdout_reduce(slot.stream, w.d_partials, w.n_chunks, w.d_offsets, w.n_ranges, w.max_chunks_per_range,
+                                       w.n_rows, n_walkers, w.d_sums, w.d_out, d_set_range));
+    cat->last_chunks = w.n_chunks;
+    cat->last_grid = mcd::main_grid(w.n_chunks, w.n_rows);
+    return MCD_OK;
+}
+
+MCD_HOST_END
+
+namespace {
+
 // Per set: its S sample rows in passes of posterior_pass rows through the slice and merge kernels of
 // mcd_pointwise_posterior on the set's records (the slice plan of a catalogue of the set's size: one set that covers the
 // catalogue gives mcd_pointwise_posterior's bits).  The scratch is sized for the largest set and shared by all.

@@ -71,14 +71,14 @@ MCD_HD T chunk_holdout(RecPtr<T> r, int count, const WalkerConsts<T>& w) {
 }
 
 #if defined(__HIPCC__)
-// mcd_holdout.hip.  partials: [roundup64(rows) / 8][n_chunks][8]; range_sums: [n_ranges][rows]; out: [2][rows] = train, test
+// mcd_holdout.hip.  set_range (device, [rows / n_walkers], or null: set e is range e): each set's range.  partials: [roundup64(rows) / 8][n_chunks][8]; range_sums: [n_ranges][rows]; out: [2][rows] = train, test
 struct LaunchShape;
 struct Chunk;
 hipError_t launch_holdout(hipStream_t s, const LaunchShape& shape, const void* records, const Chunk* chunks, int64_t n_chunks,
                           const void* wpar, double* partials, int64_t n_rows);
 hipError_t launch_holdout_reduce(hipStream_t s, const double* partials, int64_t n_chunks, const int64_t* range_slot_offsets,
                                  int64_t n_ranges, int64_t max_chunks_per_range, int64_t n_rows, int64_t n_walkers,
-                                 double* range_sums, double* out);
+                                 double* range_sums, double* out, const int64_t* set_range = nullptr);
 #endif
 
 }  // namespace mcd

@@ -40,14 +40,17 @@ __global__ __launch_bounds__(kBlock) void holdout_kernel(const double* __restric
     partials[partial_index(w_raw, n_chunks, chunk_id)] = acc;
 }
 
-// One thread per row: mcd_holdout.h: holdout_combine on the range sums.  out: [2][n_rows] = train, test
+// One thread per row: mcd_holdout.h: holdout_combine on the range sums.  out: [2][n_rows] = train, test.  set_range
+// (null: set e is range e): the range of every set, for sets that are not the first ranges of the plan
 __global__ __launch_bounds__(kBlock) void holdout_combine_kernel(const double* __restrict__ range_sums, int64_t n_ranges,
                                                                   int64_t n_rows, int64_t n_walkers,
+                                                                  const int64_t* __restrict__ set_range,
                                                                   double* __restrict__ out) {
     const int64_t row = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (row >= n_rows) return;
     double train, test;
-    holdout_combine(range_sums, n_ranges, n_rows, row, row / n_walkers, train, test);
+    const int64_t e = row / n_walkers;
+    holdout_combine(range_sums, n_ranges, n_rows, row, set_range ? set_range[e] : e, train, test);
     out[row] = train;
     out[n_rows + row] = test;
 }
@@ -78,13 +81,13 @@ hipError_t launch_holdout(hipStream_t s, const LaunchShape& sh, const void* reco
 // comes out as +0.0: reduce_group_kernel loads no slot), then the combine kernel.
 hipError_t launch_holdout_reduce(hipStream_t s, const double* partials, int64_t n_chunks, const int64_t* range_slot_offsets,
                                  int64_t n_ranges, int64_t max_chunks_per_range, int64_t n_rows, int64_t n_walkers,
-                                 double* range_sums, double* out) {
+                                 double* range_sums, double* out, const int64_t* set_range) {
     if (n_rows <= 0 || n_ranges <= 0 || n_walkers <= 0) return hipErrorInvalidValue;
     const hipError_t e = launch_reduce(s, partials, range_slot_offsets, n_ranges, n_chunks,
                                        n_ranges == 1 ? n_chunks : max_chunks_per_range, n_rows, nullptr, range_sums);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(holdout_combine_kernel, dim3((unsigned)((n_rows + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
-                       range_sums, n_ranges, n_rows, n_walkers, out);
+                       range_sums, n_ranges, n_rows, n_walkers, set_range, out);
     return hipGetLastError();
 }
 

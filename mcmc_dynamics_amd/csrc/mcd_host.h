@@ -11,6 +11,7 @@
 //   mcd_api_temper.hip     the parallel-tempering block in the same two forms
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
 //   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
+//   mcd_api_mmatch.hip     mcd_moment_match: the decision loop of moment matching around the hold-out evaluation
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -256,6 +257,8 @@ int fast_level(const mcd_catalog* cat, const double* params, int64_t n_rows);
 int sync_all(mcd_catalog* cat);
 // mcd_api_holdout.hip
 void release_holdout(mcd_catalog* cat);
+int holdout_device_plan(mcd_catalog* cat, const std::vector<int64_t>& ranges, int64_t n_rows, HoldoutWork** out);
+int holdout_device_eval(mcd_catalog* cat, HoldoutWork& w, int64_t n_walkers, const int64_t* d_set_range);
 
 MCD_HOST_END
 

@@ -6,7 +6,7 @@
 //                      (section 3.7): lane = star with its record in VGPRs, the samples wave-uniform with their derived
 //                      constants read through the scalar cache.  A wave evaluates 16 samples of its 64 stars into LDS and
 //                      writes them transposed, so that every star's row is written 128 contiguous bytes at a time.
-//   psis_tail_kernel   one wave per star: the largest log ratio, a radix select of the cutoff over an order-preserving
+//   psis_tail_kernel   one wave per star (mcd_psis_row.h, shared with moment matching): the largest log ratio, a radix select of the cutoff over an order-preserving
 //                      64-bit key (8-bit digits, LDS histograms with integer atomics, ties by sample index), the M tail
 //                      values gathered and ranked in LDS, the GPD fit with lanes = grid points, the smoothing, and the
 //                      log-sum-exps over the row.  Every sum has a fixed order (per lane in sample order, then a butterfly
@@ -18,24 +18,12 @@
 #include "mcd_dispatch.h"
 #include "mcd_posterior.h"
 #include "mcd_psis.h"
+#include "mcd_psis_row.h"
 
 namespace mcd {
 namespace {
 
 constexpr int kChunk = 16;                 // samples per LDS transpose of the term kernel
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);        // a + b == b + a: every lane ends with the same bits
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o >= 1; o >>= 1) v = max_(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
-__device__ __forceinline__ int prefix_count(uint64_t mask) {             // set bits of mask below this lane
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
 
 // terms: [n][S]; one wave per (64-star group, sample slice)
 template <int MODEL, bool FREE, class T>
@@ -75,233 +63,19 @@ __global__ __launch_bounds__(kWave) void psis_term_kernel(const T* __restrict__ 
     }
 }
 
-// One wave per star of the tile.  Dynamic LDS: hist[256] u32 | key[M] u64 | idx[M] i32 | skey[M] u64 | sidx[M] i32 |
-// theta[kPsisMaxGrid] | lj[kPsisMaxGrid]
+// One wave per star of the tile (mcd_psis_row.h: psis_row with the ratios -lnL; dynamic LDS: psis_tail_lds_bytes)
 __global__ __launch_bounds__(kWave) void psis_tail_kernel(const double* __restrict__ terms, int64_t S, int64_t M,
                                                           double r_eff, double* __restrict__ out, int64_t out_stride) {
     extern __shared__ uint64_t lds64[];
-    uint32_t* hist = (uint32_t*)lds64;                                        // 256 x 4 B = 128 x 8 B
-    uint64_t* tkey = lds64 + 128;
-    uint64_t* skey = tkey + M;
-    double* theta = (double*)(skey + M);
-    double* lj = theta + kPsisMaxGrid;
-    int32_t* tidx = (int32_t*)(lj + kPsisMaxGrid);
-    int32_t* sidx = tidx + M;
-    double* x = (double*)tkey;                                                // x_t reuses the unsorted keys
-
-    const int lane = lane_id();
     const int64_t star = blockIdx.x;
     const double* __restrict__ row = terms + star * S;
-
-    // the largest log ratio (max r = -min lnL) and the largest lnL
-    double rmax = -INFINITY, lmax = -INFINITY;
-    for (int64_t s = lane; s < S; s += kWave) {
-        const double l = row[s];
-        rmax = max_(rmax, -l);
-        lmax = max_(lmax, l);
-    }
-    rmax = wave_max(rmax);
-    lmax = wave_max(lmax);
-
-    // cutoff = the (M+1)-th largest (lw, index): the key by radix select, then the index among equal keys
-    bool tail = M >= 5;
-    uint64_t key_c = 0;
-    int64_t idx_c = -1;
-    if (tail) {
-        uint64_t prefix = 0, mask = 0;
-        int64_t kth = M + 1;                                                  // rank from the top among the candidates
-        for (int shift = 56; shift >= 0; shift -= 8) {
-            for (int b = lane; b < 256; b += kWave) hist[b] = 0u;
-            __syncthreads();
-            for (int64_t s = lane; s < S; s += kWave) {
-                const uint64_t k = psis_key(-row[s] - rmax);
-                if ((k & mask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-            }
-            __syncthreads();
-            uint32_t c[4];
-            uint32_t mine = 0;
-            for (int b = 0; b < 4; ++b) {
-                c[b] = hist[4 * lane + b];
-                mine += c[b];
-            }
-            // counts in the bins above this lane's four (lanes above hold higher bins)
-            uint32_t inc = mine;                                              // inclusive suffix sum over lanes
-            for (int o = 1; o < kWave; o <<= 1) {
-                const uint32_t v = __shfl_down(inc, o);
-                if (lane + o < kWave) inc += v;
-            }
-            uint32_t above = inc - mine;
-            int found = -1;
-            uint32_t above_b = 0;
-            for (int b = 3; b >= 0; --b) {
-                if (found < 0 && (int64_t)above < kth && (int64_t)(above + c[b]) >= kth) {
-                    found = 4 * lane + b;
-                    above_b = above;
-                }
-                above += c[b];
-            }
-            const uint64_t who = __ballot(found >= 0);
-            const int src = __ffsll((unsigned long long)who) - 1;
-            const int bucket = __shfl(found, src);
-            const uint32_t gt = __shfl(above_b, src);
-            const uint32_t cnt = hist[bucket];
-            kth -= gt;
-            prefix |= (uint64_t)bucket << shift;
-            mask |= (uint64_t)255u << shift;
-            __syncthreads();
-            if (cnt == 1u) break;                                             // the cutoff is the only candidate left
-        }
-        // the kth candidate counted from the highest sample index
-        int64_t seen = 0;
-        for (int64_t top = S; top > 0; top -= kWave) {
-            const int64_t s = top - 1 - lane;
-            uint64_t k = 0;
-            bool match = false;
-            if (s >= 0) {
-                k = psis_key(-row[s] - rmax);
-                match = (k & mask) == prefix;
-            }
-            const uint64_t bm = __ballot(match);
-            const int64_t pc = __popcll(bm);
-            if (seen + pc >= kth) {
-                const bool hit = match && (seen + prefix_count(bm) + 1 == kth);
-                const int src = __ffsll((unsigned long long)__ballot(hit)) - 1;
-                key_c = ((uint64_t)__shfl((int)(uint32_t)(k >> 32), src) << 32) | (uint32_t)__shfl((int)(uint32_t)k, src);
-                idx_c = __shfl((int)s, src);
-                break;
-            }
-            seen += pc;
-        }
-        // gather the tail, (key, index) > (key_c, idx_c), in sample order
-        int64_t base = 0;
-        for (int64_t s0 = 0; s0 < S; s0 += kWave) {
-            const int64_t s = s0 + lane;
-            bool in = false;
-            uint64_t k = 0;
-            if (s < S) {
-                k = psis_key(-row[s] - rmax);
-                in = k > key_c || (k == key_c && s > idx_c);
-            }
-            const uint64_t bm = __ballot(in);
-            if (in) {
-                const int64_t pos = base + prefix_count(bm);
-                tkey[pos] = k;
-                tidx[pos] = (int32_t)s;
-            }
-            base += __popcll(bm);
-        }
-        __syncthreads();
-        // rank sort of the M tail entries by (key, index)
-        for (int64_t t = lane; t < M; t += kWave) {
-            const uint64_t k = tkey[t];
-            const int32_t id = tidx[t];
-            int64_t rank = 0;
-            for (int64_t u = 0; u < M; ++u) {
-                const uint64_t ku = tkey[u];
-                rank += (ku < k || (ku == k && tidx[u] < id)) ? 1 : 0;
-            }
-            skey[rank] = k;
-            sidx[rank] = id;
-        }
-        __syncthreads();
-    }
-
-    const double cutoff = tail ? psis_unkey(key_c) : 0.0;
-    const double ec = exp_(cutoff);
-    double khat = INFINITY;
-    double sigma = 0.0;
-    bool smooth = false;
-    if (tail) {
-        const double lo = psis_unkey(skey[0]), hi = psis_unkey(skey[M - 1]);
-        if (hi - lo < kPsisConstTail) {
-            khat = -INFINITY;
-        } else {
-            for (int64_t t = lane; t < M; t += kWave) x[t] = exp_(psis_unkey(skey[t])) - ec;
-            __syncthreads();
-            const int m = gpd_grid_m(M);
-            const double x_last = x[M - 1], x_star = x[gpd_xstar_index(M)];
-            bool bad = false;
-            double lmx = -INFINITY;
-            for (int j = lane; j < m; j += kWave) {
-                const double th = gpd_theta(j + 1, m, x_last, x_star);
-                const double l = gpd_profile(th, gpd_mean_log1p(th, x, M), M);
-                theta[j] = th;
-                lj[j] = l;
-                bad = bad || l != l;
-                lmx = max_(lmx, l);
-            }
-            __syncthreads();
-            bad = __ballot(bad) != 0;
-            lmx = wave_max(lmx);
-            double se = 0.0;
-            for (int j = lane; j < m; j += kWave) se += exp_(lj[j] - lmx);
-            const double lse = lmx + log_(wave_sum(se));
-            double th = 0.0;
-            for (int j = lane; j < m; j += kWave) th += theta[j] * exp_(lj[j] - lse);
-            const double theta_hat = bad ? NAN : wave_sum(th);
-            double kk = 0.0;
-            for (int64_t t = lane; t < M; t += kWave) kk += log1p_(-theta_hat * x[t]);
-            const double k = wave_sum(kk) / (double)M;
-            sigma = -k / theta_hat;
-            khat = gpd_adjust(k, M);
-            smooth = khat < INFINITY && khat > -INFINITY;
-        }
-    }
-    // smoothed (or kept) tail log weights, truncated at 0, into x[]
-    double tmax = -INFINITY, tmax2 = -INFINITY;
-    if (tail) {
-        __syncthreads();
-        for (int64_t t = lane; t < M; t += kWave) {
-            double v = psis_unkey(skey[t]);
-            if (smooth) v = psis_smoothed(t, M, khat, sigma, ec);
-            v = v < 0.0 ? v : 0.0;
-            x[t] = v;
-            tmax = max_(tmax, v);
-            tmax2 = max_(tmax2, v + row[sidx[t]]);
-        }
-        __syncthreads();
-        tmax = wave_max(tmax);
-        tmax2 = wave_max(tmax2);
-    }
-    // shifts: lw's largest value, and for lw + lnL the body's common value -rmax or the tail's largest
-    const double mw = tail ? max_(tmax, cutoff) : 0.0;                       // the body's largest lw: cutoff, or 0
-    const double m2 = max_(-rmax, tmax2);
-    double a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-    for (int64_t s = lane; s < S; s += kWave) {
-        const double l = row[s];
-        const double lw = -l - rmax;
-        a4 += exp_(l - lmax);
-        bool in = false;
-        if (tail) {
-            const uint64_t k = psis_key(lw);
-            in = k > key_c || (k == key_c && s > idx_c);
-        }
-        if (!in) {
-            const double v = lw < 0.0 ? lw : 0.0;
-            const double e = exp_(v - mw);
-            a1 += e;
-            a2 += e * e;
-            a3 += exp_(v + l - m2);
-        }
-    }
-    if (tail) {
-        for (int64_t t = lane; t < M; t += kWave) {
-            const double v = x[t];
-            const double e = exp_(v - mw);
-            a1 += e;
-            a2 += e * e;
-            a3 += exp_(v + row[sidx[t]] - m2);
-        }
-    }
-    a1 = wave_sum(a1);
-    a2 = wave_sum(a2);
-    a3 = wave_sum(a3);
-    a4 = wave_sum(a4);
-    if (lane == 0) {
-        out[PSF_ELPD * out_stride + star] = (m2 + log_(a3)) - (mw + log_(a1));
-        out[PSF_K * out_stride + star] = khat;
-        out[PSF_LPPD * out_stride + star] = lmax + (log_(a4) - log_((double)S));
-        out[PSF_NEFF * out_stride + star] = r_eff * (a1 * a1) / a2;
+    const PsisRow r = psis_row<true>([&](int64_t s) { return -row[s]; }, [&](int64_t s) { return row[s]; }, S, M, lds64,
+                                     nullptr);
+    if (lane_id() == 0) {
+        out[PSF_ELPD * out_stride + star] = (r.m2 + log_(r.a3)) - (r.mw + log_(r.a1));
+        out[PSF_K * out_stride + star] = r.khat;
+        out[PSF_LPPD * out_stride + star] = r.lmax + (log_(r.a4) - log_((double)S));
+        out[PSF_NEFF * out_stride + star] = r_eff * (r.a1 * r.a1) / r.a2;
     }
 }
 
@@ -318,8 +92,6 @@ hipError_t term_launch(hipStream_t s, int precision, const void* records, int64_
         return hipGetLastError();
     });
 }
-
-size_t psis_tail_lds_bytes(int64_t M) { return 256 * 4 + (size_t)M * (8 + 8 + 4 + 4) + 2 * kPsisMaxGrid * 8; }
 
 }  // namespace
 
