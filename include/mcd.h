@@ -282,6 +282,35 @@ int mcd_holdout_loglike(mcd_catalog* cat, int32_t n_sets, const int64_t* set_off
 int mcd_holdout_pointwise(mcd_catalog* cat, int32_t n_sets, const int64_t* set_offsets, int64_t n_samples, int32_t k,
                           const double* params /* [E][S][K] */, double* lppd /* [set_offsets[E]] */,
                           double* lnl_var /* may be NULL */);
+/* Replicated-data predictive checks per range of stars (Gelman, Meng & Stern 1996).  For sample row s (params: row-major
+ * [S][K], the kernel columns of mcd_loglike_batch) and star i (index in catalogue order), with d, n as for
+ * mcd_posterior_predictive:  z_obs = d / sqrt(n), and a replicate drawn from the model at that row:
+ *   g = the standard normal, u = the uniform of (seed, s, i) (mcd_replicate_numbers gives both)
+ *   z_rep = g                                   when the model has no background, or u < m, the model's membership prior
+ *         = ((mu_b - v_i) + d + sqrt(verr_i^2 + sigma_b^2) g) / sqrt(n)      otherwise (a background star)
+ * with m = pmember_i or density_i / (density_i + f_back) and (mu_b, sigma_b) = the row's (v_back, sigma_back) for the
+ * Gaussian-background models, (bg_mean, bg_sigma) for the fixed-background ones (ignored otherwise; NaN: none).
+ * Ranges: order[range_offsets[n_ranges]] holds the stars of range 0, then of range 1, ...: range r is
+ * order[range_offsets[r] .. range_offsets[r + 1]); stars in no range are absent; a range may be empty (all +0.0).
+ * out[s][r][f][0 / 1], f < MCD_REP_FIELDS, for z = z_obs / z_rep over the stars of range r: sum z, z^2, z^3, z^4,
+ * sum z sin(theta), sum z cos(theta) (theta: the position angle the model's v_los uses), max |z|, the count of |z| > 3.
+ * A replicate is a function of (seed, s + option "replicate_row0", i) alone: ranges, chunking and passes never change
+ * it.  A non-finite term makes that row's fields of that range non-finite and touches nothing else.  Synchronous and
+ * deterministic: a range's chunk sums are combined in a fixed order, bit-identical from run to run and independent of
+ * earlier calls.  Rows beyond 65536 run in passes.  MCD_ERR_INVALID, with a message and nothing written: a binned or a
+ * float32 catalogue; several devices or a communicator; offsets that do not start at 0 or decrease; an index in `order`
+ * out of range or repeated; a fixed-background model without finite bg_mean and bg_sigma >= 0; n_samples < 1; a foreign
+ * k; more ranges than the 256 MiB of partial sums allow.  Waits under the context's deadline; honours option "timing"
+ * (mcd_last_kernel_ms: the main kernel, summed over the passes) and option "chunk_len" (a forced nominal chunk length). */
+enum { MCD_REP_S1, MCD_REP_S2, MCD_REP_S3, MCD_REP_S4, MCD_REP_SIN, MCD_REP_COS, MCD_REP_MAX, MCD_REP_TAIL3, MCD_REP_FIELDS };
+int mcd_replicate_check(mcd_catalog* cat, int64_t n_samples, int32_t k, const double* params /* [S][K] */,
+                        uint64_t seed, int32_t n_ranges, const int64_t* range_offsets /* [R+1] */,
+                        const int64_t* order /* [range_offsets[R]] */, double bg_mean, double bg_sigma /* NaN: none */,
+                        double* out /* [S][R][MCD_REP_FIELDS][2]: observed, replicated */);
+/* The generator's numbers for sample rows sample0 .. and stars star0 ..: g, u row-major [S][N]; either may be NULL.
+ * Host only, as mcd_chain_numbers. */
+int mcd_replicate_numbers(uint64_t seed, int64_t sample0, int64_t n_samples, int64_t star0, int64_t n_stars,
+                          double* g /* [S][N] */, double* u /* [S][N] */);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute
@@ -655,6 +684,8 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *   "defer_guard"   1 (default): resident blocks of ONE ensemble judge the range guard of all their launches after the
  *                      last step instead of between two main kernels (same verdicts, same discards); 0: in the step kernel
  *   "f32_domain"    1 (default): float32 catalogues refuse parameter tables outside the float32 accuracy domain (below)
+ *   "replicate_row0"  index that the generator of mcd_replicate_check gives the first row of its table (default 0): a
+ *                      table split over several calls reproduces the one-call result bit for bit
  * Returns MCD_ERR_INVALID for an unknown key. */
 int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value);
 /* With "timing" = 2: waits for the device, returns the summed HIP-event duration (ms) of all main-kernel

@@ -64,6 +64,10 @@ SYMBOLS = {
                                            _c_double_p, _c_double_p]),
     "mcd_holdout_pointwise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, _c_int64_p, ctypes.c_int64, ctypes.c_int32,
                                              _c_double_p, _c_double_p, _c_double_p]),
+    "mcd_replicate_check": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_uint64,
+                                           ctypes.c_int32, _c_int64_p, _c_int64_p, ctypes.c_double, ctypes.c_double, _c_double_p]),
+    "mcd_replicate_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             _c_double_p, _c_double_p]),
     "mcd_moment_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
                                         ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                         _c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
@@ -453,6 +457,18 @@ def hmc_numbers(seed, step0, n_steps, n_walkers, n_dim):
     return z, thr, r
 
 
+def replicate_numbers(seed, sample0, n_samples, star0, n_stars):
+    """``mcd_replicate_numbers``: the numbers of ``replicate_check`` for sample rows ``sample0 ..`` and stars ``star0 ..``
+    (host code, no device involved): standard normals g and membership uniforms u, both (n_samples, n_stars)."""
+    lib = load_library()
+    g = np.empty((int(n_samples), int(n_stars)), dtype=np.float64)
+    u = np.empty_like(g)
+    rc = lib.mcd_replicate_numbers(int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), int(n_samples), int(star0), int(n_stars),
+                                   _ptr(g), _ptr(u))
+    _check(lib, rc, "mcd_replicate_numbers")
+    return g, u
+
+
 def temper_numbers(seed, step0, n_steps, n_temps, n_walkers):
     """``mcd_temper_numbers``: the swap thresholds log(u) of steps ``step0 .. step0 + n_steps - 1`` of the tempered chain that
     ``seed`` names (host code, no device involved), shape (steps, T - 1, W): pair t is rungs (t, t + 1); a step exchanges the
@@ -725,6 +741,37 @@ class Catalog(object):
         rc = self.lib.mcd_holdout_pointwise(self.handle, offs.size - 1, offs.ctypes.data_as(_c_int64_p), p.shape[1], p.shape[2],
                                             _ptr(p), _ptr(out["lppd"]), _ptr(out["lnl_var"]))
         _check(self.lib, rc, "mcd_holdout_pointwise")
+        return out
+
+    REPLICATE_FIELDS = ("s1", "s2", "s3", "s4", "sin", "cos", "max", "tail3")
+
+    def replicate_check(self, table, seed, range_offsets, order, bg_mean=float("nan"), bg_sigma=float("nan"), row0=0):
+        """Replicated-data predictive checks per range of stars (include/mcd.h: mcd_replicate_check): ``table`` (S, K)
+        kernel rows, ``order`` the star indices of range 0, then of range 1, ..., ``range_offsets`` (R + 1,) the ranges'
+        offsets into it -> (S, R, 8, 2) float64: the fields ``REPLICATE_FIELDS`` of the observed ([..., 0]) and of the
+        replicated ([..., 1]) standardised residuals.  ``bg_mean`` / ``bg_sigma``: the background's Gaussian for the
+        fixed-background models.  ``row0``: the generator's index of the first row (option ``replicate_row0``), for
+        tables that are split over several calls.  Un-binned float64 catalogues on one device; synchronous and
+        bit-identical from run to run."""
+        self._alive()
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (S, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        offs = np.ascontiguousarray(range_offsets, dtype=np.int64).reshape(-1)
+        if offs.size < 2:
+            raise ValueError("range_offsets must hold n_ranges + 1 >= 2 offsets")
+        order = np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
+        if order.size != int(offs[-1]):
+            raise ValueError("order must hold range_offsets[-1] = {0} indices".format(int(offs[-1])))
+        out = np.empty((p.shape[0], offs.size - 1, len(self.REPLICATE_FIELDS), 2), dtype=np.float64)
+        self.set_option("replicate_row0", int(row0))
+        rc = self.lib.mcd_replicate_check(self.handle, p.shape[0], self.k, _ptr(p), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          offs.size - 1, offs.ctypes.data_as(_c_int64_p), order.ctypes.data_as(_c_int64_p),
+                                          float(bg_mean), float(bg_sigma), _ptr(out))
+        _check(self.lib, rc, "mcd_replicate_check")
         return out
 
     def moment_match(self, plan, draws, stars, k_threshold, max_iters=30, cov=True, split=True, r_eff=1.0, out=None):

@@ -262,6 +262,10 @@ class BinnedConstantFit(ConstantFit):
     def ppc(self, chain, n_burn, thin=1, n_bins=20, outlier_p=None):
         return self.posterior_predictive(chain, n_burn, thin)
 
+    def replicate_check(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: replicated-data checks (replicate_check) are defined for un-binned fits "
+                                  "only; fit the bins' stars with ConstantFit and pass the bins as groups")
+
     def loo(self, chain, n_burn, thin=1, r_eff=1.0):
         raise NotImplementedError("BinnedConstantFit: PSIS-LOO is defined for un-binned fits only; fit the bins' stars "
                                   "with ConstantFit to compare models")

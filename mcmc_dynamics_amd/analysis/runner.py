@@ -20,6 +20,7 @@ import numpy as np
 from .. import _native, units
 from ..background import Gaussian, SingleStars
 from ..parameter import Parameters
+from ..utils.coordinates import calc_xy_offset
 from ..utils.data_reader import DataReader
 from ..utils.results import ResultsTable
 
@@ -345,6 +346,54 @@ def ppc_summary(pit, weights=None, n_bins=20, group=None):
     expect = n / n_bins
     chi2 = float(np.sum((hist - expect) ** 2) / expect) if n > 0 else 0.0
     return {"hist": hist, "n": n, "chi2": chi2, "tail_fraction": tail / n if n > 0 else 0.0, "n_stars": n_stars}
+
+
+REPLICATE_NAMES = ("mean", "var_ratio", "skew", "kurt_excess", "rot_amp", "max_abs_z", "n_tail3")
+
+
+def _replicate_discrepancies(f, n):
+    """The discrepancies REPLICATE_NAMES (last axis) from the eight additive fields ``f`` (..., 8) of ``n`` stars (shape
+    broadcastable against f[..., 0]); n == 0 gives NaN."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n = np.where(np.asarray(n, dtype=np.float64) > 0, n, np.nan)
+        m1, r2, r3, r4 = f[..., 0] / n, f[..., 1] / n, f[..., 2] / n, f[..., 3] / n
+        c2 = r2 - m1 * m1
+        c3 = r3 - 3.0 * m1 * r2 + 2.0 * m1 ** 3
+        c4 = r4 - 4.0 * m1 * r3 + 6.0 * m1 * m1 * r2 - 3.0 * m1 ** 4
+        rot = 2.0 * np.hypot(f[..., 4], f[..., 5]) / n
+        return np.stack([m1, r2, c3 / c2 ** 1.5, c4 / (c2 * c2) - 3.0, rot, f[..., 6] + 0.0 * n, f[..., 7] + 0.0 * n], axis=-1)
+
+
+def replicate_summary(out, counts):
+    """Posterior predictive p-values with realized discrepancies (Gelman, Meng & Stern 1996) from the fields of
+    ``Catalog.replicate_check``: ``out`` (S, R, 8, 2) and ``counts`` (R,), the stars per range.  Rows: "all" (the ranges
+    combined in ascending order: sums and counts added, the maximum taken), then one per range.  For the observed and
+    the replicated residuals alike the discrepancies ``names`` are derived per sample: ``mean`` = S1/n, ``var_ratio`` =
+    S2/n, ``skew`` and ``kurt_excess`` from the raw moments, ``rot_amp`` = 2 hypot(SIN, COS)/n, ``max_abs_z``,
+    ``n_tail3``.  Returns ``names``, ``n_stars`` (R + 1,), ``obs`` / ``rep`` (S, R + 1, 7), ``p_value`` (R + 1, 7) =
+    mean_s[T_rep >= T_obs], ``extreme`` = min(p, 1 - p), ``bands`` (R + 1, 7, 2, 3): the 16 / 50 / 84 % quantiles over the
+    samples of observed ([..., 0, :]) and replicated.  A row without stars is NaN throughout.  Every field is additive
+    over stars, so the fields of disjoint star sets may be added before the summary."""
+    out = np.asarray(out, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.float64).reshape(-1)
+    if out.ndim != 4 or out.shape[2:] != (8, 2) or out.shape[1] != counts.size:
+        raise ValueError("out must have shape (S, R, 8, 2) and counts (R,)")
+    total = np.zeros((out.shape[0], 8, 2))
+    for r in range(out.shape[1]):
+        total[:, :6] += out[:, r, :6]
+        total[:, 7] += out[:, r, 7]
+        total[:, 6] = np.maximum(total[:, 6], out[:, r, 6])                         # (keeps a NaN)
+    fields = np.concatenate([total[:, None], out], axis=1)                          # (S, R + 1, 8, 2)
+    n = np.concatenate([[counts.sum()], counts])
+    obs = _replicate_discrepancies(fields[..., 0], n[None, :])
+    rep = _replicate_discrepancies(fields[..., 1], n[None, :])
+    p = np.mean(rep >= obs, axis=0)
+    p[n == 0] = np.nan
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        bands = np.stack([np.nanpercentile(x, [16, 50, 84], axis=0) for x in (obs, rep)], axis=0)     # (2, 3, R + 1, 7)
+    return {"names": REPLICATE_NAMES, "n_stars": n.astype(np.int64), "obs": obs, "rep": rep, "p_value": p,
+            "extreme": np.minimum(p, 1.0 - p), "bands": np.transpose(bands, (2, 3, 0, 1))}
 
 
 class Runner(object):
@@ -1672,6 +1721,89 @@ class Runner(object):
         out["weight"] = weight
         out["outlier_p"] = float(outlier_p)
         out["outliers"] = np.flatnonzero((weight > 0.5) & (out["tail_p"] < outlier_p))
+        return out
+
+    # ------------------------------------------------------------------ replicated-data checks per group of stars (new)
+    def _replicate_background(self):
+        """(mean, sigma) in km/s of the fixed background a replicate is drawn from; NaN for the other models."""
+        model = self._catalog_spec()[0][0]
+        if model not in (_native.MODEL_CONST_BGFIXED, _native.MODEL_PROFILE_BGFIXED, _native.MODEL_PROFILE_BGDENS):
+            return float("nan"), float("nan")
+        if not isinstance(self.background, Gaussian):
+            raise NotImplementedError("Runner.replicate_check: a {0} background cannot be sampled from its log-likelihood "
+                                      "column alone; replicated data need a background.Gaussian"
+                                      .format(type(self.background).__name__))
+        return self.background.mean, self.background.sigma
+
+    def _replicate_groups(self, annuli, groups):
+        """(range_offsets, order, (label key, label value)) of the groups of a replicate_check."""
+        n = self.n_data
+        if groups is not None:
+            groups = np.asarray(groups)
+            if groups.shape != (n,) or not np.issubdtype(groups.dtype, np.integer):
+                raise ValueError("groups must be an int array with one entry per star")
+            if groups.size and groups.min() < -1:
+                raise ValueError("groups: -1 leaves a star out; other negative labels are not allowed")
+            n_groups = int(groups.max()) + 1 if groups.size and groups.max() >= 0 else 1
+            label = ("groups", np.arange(n_groups))
+        else:
+            pr, pd = self.parameters["ra_center"], self.parameters["dec_center"]
+            dx, dy = calc_xy_offset(self.ra, self.dec, units.to_unit(pr.value, "deg", pr.unit),
+                                    units.to_unit(pd.value, "deg", pd.unit))
+            r = np.hypot(dx, dy)
+            if np.ndim(annuli) == 0:
+                n_groups = int(annuli)
+                if n_groups < 1:
+                    raise ValueError("annuli must be >= 1")
+                rank = np.empty(n, dtype=np.int64)
+                rank[np.argsort(r, kind="stable")] = np.arange(n)
+                groups = rank * n_groups // max(n, 1)
+                by_r = np.sort(r)
+                cuts = [by_r[min(n - 1, -(-n * g // n_groups))] for g in range(1, n_groups)] if n else []
+                edges = np.array([by_r[0] if n else 0.0] + cuts + [by_r[-1] if n else 0.0])
+            else:
+                edges = np.asarray(annuli, dtype=np.float64).reshape(-1)
+                if edges.size < 2 or np.any(np.diff(edges) <= 0):
+                    raise ValueError("annuli: the edges must increase")
+                n_groups = edges.size - 1
+                groups = np.searchsorted(edges, r, side="right") - 1
+                groups[(r < edges[0]) | (r >= edges[-1])] = -1
+            label = ("edges", edges)
+        order = np.argsort(groups, kind="stable").astype(np.int64)
+        order = order[groups[order] >= 0]
+        counts = np.bincount(groups[order], minlength=n_groups)
+        return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), order, label
+
+    def replicate_check(self, chain, n_burn, thin=1, annuli=8, groups=None, seed=None):
+        """Posterior predictive check with replicated data, per group of stars (Gelman, Meng & Stern 1996): for every
+        post-burn-in sample of ``chain`` (handled as by ``posterior_predictive``) the device draws a replicated catalogue
+        from the model at that sample and accumulates, per group, eight additive fields of the standardised residuals
+        of the observed and of the replicated velocities (``Catalog.replicate_check``); ``replicate_summary`` turns them
+        into discrepancies and p-values P(T_rep >= T_obs) for all grouped stars and for every group.
+        ``groups``: an int array per star, -1 leaves the star out.  Otherwise ``annuli``: an int for that many annuli of
+        equal star count in projected radius about the parameters' current centre value, or a list of edges in arcmin.
+        Fixed-background classes draw background replicates from their ``background.Gaussian``.  Returns the entries of
+        ``replicate_summary`` plus ``edges`` (arcmin) or ``groups`` (the labels), ``seed`` and ``n_samples``.
+        NotImplementedError: a SingleStars background, several ranks or devices, float32 catalogues."""
+        ctx = self._context
+        if ctx is not None and getattr(ctx, "n_ranks", 1) > 1:
+            raise NotImplementedError("Runner.replicate_check runs in one process on one device; this runner sits on a "
+                                      "context of {0} ranks".format(ctx.n_ranks))
+        if ctx is not None and int(getattr(ctx, "n_devices", 1)) > 1:
+            raise NotImplementedError("Runner.replicate_check runs on one device; this runner's context has "
+                                      "{0}".format(int(ctx.n_devices)))
+        if self._precision != "f64":
+            raise NotImplementedError("Runner.replicate_check needs a float64 catalogue")
+        bg_mean, bg_sigma = self._replicate_background()
+        offsets, order, label = self._replicate_groups(annuli, groups)
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        table, n_samples = self._posterior_table(chain, n_burn, thin)
+        fields = self._ensure_catalog().replicate_check(table, seed, offsets, order, bg_mean, bg_sigma)
+        out = replicate_summary(fields, np.diff(offsets))
+        out[label[0]] = label[1]
+        out["seed"] = int(seed)
+        out["n_samples"] = n_samples
         return out
 
     # ------------------------------------------------------------------ device catalogue

@@ -152,6 +152,7 @@ const Option kOptions[] = {
     {"f32_domain", kMin, kMax, nullptr, false, false, MCD_SET(c->f32_domain = v != 0)},
     {"loo_scratch_mb", 1, kMax, "loo_scratch_mb must be >= 1", false, false, MCD_SET(c->loo_scratch_mb = v)},
     {"posterior_pass", 1, kMax, "posterior_pass must be >= 1", false, false, MCD_SET(c->posterior_pass = v)},
+    {"replicate_row0", 0, kMax, "replicate_row0 must be >= 0", false, false, MCD_SET(c->replicate_row0 = v)},
     {"two_lanes", kMin, kMax, nullptr, true, false, MCD_SET(c->two_lanes = v != 0)},
     {"narrow_bounded", 0, 1, "narrow_bounded: 1 (where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->narrow_bounded = (int)v)},
     {"verr_sorted", -1, 1, "verr_sorted: -1 (by record volume, default), 0 (catalogue order) or 1 (sorted by verr)", true, true, MCD_SET(c->verr_sorted = (int)v)},

@@ -12,6 +12,7 @@
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
 //   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
 //   mcd_api_mmatch.hip     mcd_moment_match: the decision loop of moment matching around the hold-out evaluation
+//   mcd_api_replicate.hip  mcd_replicate_check, mcd_replicate_numbers: replicated-data predictive checks per range of stars
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -320,6 +321,7 @@ struct mcd_catalog {
                                        // with MCD_ERR_INVALID, 0 they are evaluated anyway (mcd_last_f32_domain tells)
     mcd::F32Domain last_f32;           // verdict on the last staged parameter table (float32 catalogues)
     int64_t posterior_pass = 65536;    // option "posterior_pass": samples per device pass of mcd_pointwise_posterior
+    int64_t replicate_row0 = 0;        // option "replicate_row0": generator row index of the first sample row of mcd_replicate_check
     int64_t loo_scratch_mb = 2048;    // option "loo_scratch_mb": device scratch of mcd_psis_loo (sample table + term tile)
     int combine = 1;                   // option "combine": balanced plans may use 8- / 16-wave workgroups that combine their
                                        // chunks' sums: 0 never, 1 the largest the plan allows, 8 / 16 at most that many waves

@@ -52,6 +52,32 @@ MCD_HD double star_sigma2(RecPtr<T> r, const WalkerConsts<T>& w) {
     }
 }
 
+// (cos theta, sin theta) of one star's position angle for one sample, the angle the model's own v_los uses: the record's
+// fields 3 and 2 for the constant models with a fixed centre, else (x, y) / r with the offsets as star_d_n forms them.
+// r == 0: (0, 0) for the profile models (their v_los has no angle there), numpy's arctan2(+0, -+0) for the constant ones
+// (free_centre_residual: sin = 0, cos = -+1).
+template <int MODEL, bool FREE, class T>
+MCD_HD void star_unit(RecPtr<T> r, const WalkerConsts<T>& w, double& c, double& s) {
+    if constexpr (!is_profile(MODEL) && !FREE) {
+        c = (double)r[3];
+        s = (double)r[2];
+    } else {
+        T x, y;
+        if (FREE) {
+            free_centre_xy(r[2], r[3], r[4], w.sac, w.cac, w.sdc, w.cdc, x, y);
+            if constexpr (is_profile(MODEL)) { x = T(kArcsecPerRad) * x; y = T(kArcsecPerRad) * y; }
+        } else {
+            x = r[2];
+            y = r[3];
+        }
+        const T r2 = (is_profile(MODEL) && !FREE) ? r[4] : fma_(x, x, y * y);
+        const double inv = 1.0 / sqrt_((double)r2);
+        const bool on = !(r2 > T(0));
+        c = on ? (is_profile(MODEL) ? 0.0 : (std::signbit(x) ? -1.0 : 1.0)) : (double)x * inv;
+        s = on ? 0.0 : (double)y * inv;
+    }
+}
+
 // Normal tail and CDF of a standardised residual from ONE erfc: t = P(|Z| > |z|), cdf = P(Z < z).
 MCD_HD void normal_tail_cdf(double z, double& t, double& cdf) {
     t = erfc_(fabs_(z) * kInvSqrt2);
