@@ -106,6 +106,9 @@ extern "C" int emul_psis(int64_t n, int64_t S, const double* lnl, double r_eff, 
 // the GPD fit alone: x ascending, length M -> k^, sigma
 extern "C" double emul_gpd_fit(const double* x, int64_t M, double* sigma) { return gpd_fit(x, M, *sigma); }
 
+// the order-preserving key the select works on
+extern "C" uint64_t emul_psis_key(double v) { return psis_key(v); }
+
 extern "C" int64_t emul_psis_tail_len(int64_t S, double r_eff) { return psis_tail_len(S, r_eff); }
 
 extern "C" int64_t emul_psis_tile_stars(int64_t n, int64_t S, int64_t fixed, int64_t budget) {

@@ -31,6 +31,8 @@ def lib():
         L.emul_psis_tail_len.restype = ctypes.c_int64
         L.emul_psis_tile_stars.argtypes = [ctypes.c_int64] * 4
         L.emul_psis_tile_stars.restype = ctypes.c_int64
+        L.emul_psis_key.argtypes = [ctypes.c_double]
+        L.emul_psis_key.restype = ctypes.c_uint64
         _lib = L
     return _lib
 

@@ -15,7 +15,7 @@ import posterior_helper as ph
 import predictive_helper as pr
 import psis_helper as psh
 from conftest import ROOT
-from test_gpu_psis import _lnl_matrix
+from test_gpu_psis import CAP_R_EFF, CAP_S, _lnl_matrix, cap_case
 
 pytestmark = pytest.mark.gpu
 MODELS = [0, 1, 2, 3, 4, 5, 6]
@@ -164,6 +164,68 @@ def test_heavy_tails_and_ties(ctx, cat2k):
     _, lnl = _check_device(gpu, cat, table, 0, ph.CENTRE, got, "heavy")
     lh.check_expect({"func": got["func"], "pareto_k": got["pareto_k"]}, lnl, None, func, what="heavy")
     assert np.count_nonzero(got["pareto_k"] > 0.7) >= 5
+    gpu.close()
+
+
+def near_tie_table(cat, S, seed):
+    """Runs of repeated rows (rejected moves) interleaved with rows whose v_sys differs from the run's by 1 to 32 ulps (one
+    ulp of v_sys moves lnL by well under one of its own, so fewer would only make more exact ties): every star's lnL row has
+    exact ties, and most have entries a few ulps apart, at the cutoff as anywhere else."""
+    rng = np.random.default_rng(seed)
+    base = ph.samples(cat, 2, False, S, seed=seed)
+    table = np.ascontiguousarray(base[np.repeat(np.arange(S), rng.integers(1, 6, size=S))[:S]])
+    col = ph.abi_names(2, False).index("v_sys")
+    odd = np.arange(S) % 2 == 1
+    table[odd, col] += rng.integers(1, 33, size=int(odd.sum())) * rng.choice([-1.0, 1.0], size=int(odd.sum())) * \
+        np.spacing(table[odd, col])
+    return table
+
+
+@pytest.mark.parametrize("S", [63, 65, 400])
+def test_ties_and_near_ties_reach_the_second_copy_of_the_selection(ctx, cat2k, S):
+    """loox_tail_kernel carries its own copy of psis_row's select, scan, gather and rank sort: on rows with ties and
+    near-ties its k^ and n_eff are mcd_psis_loo's bit for bit, and the expectation of the sample index under its weights --
+    which sees who is in the tail and at which rank -- follows the rule."""
+    cat = pr.head(cat2k, 65)
+    table = near_tie_table(cat2k, S, seed=31 + S)
+    gpu = pr.device_catalog(ctx, cat, 2, ph.CENTRE)
+    index = np.arange(S, dtype=np.float64)[:, None]
+    got = gpu.psis_loo_expect(table, func=index, predictive=False)
+    ref = gpu.psis_loo(table)
+    assert np.array_equal(got["pareto_k"], ref["pareto_k"]) and np.array_equal(got["n_eff"], ref["n_eff"])
+    lnl = _lnl_matrix(gpu, cat, table, 2, ph.CENTRE)
+    gaps = [np.diff(np.sort(row)) / np.spacing(np.abs(row).max()) for row in lnl]
+    ties = np.array([np.count_nonzero(g == 0.0) for g in gaps])
+    near = np.array([np.count_nonzero((g > 0.0) & (g <= 8.0)) for g in gaps])
+    print("S", S, "neighbours per star that are equal:", ties.min(), "..", ties.max(), "; 1 to 8 ulps apart:", near.min(),
+          "..", near.max(), "in", int(np.count_nonzero(near)), "stars")
+    assert np.all(ties >= S // 8) and np.count_nonzero(near) >= 8
+    lh.check_expect({"func": got["func"], "pareto_k": got["pareto_k"]}, lnl, None, index, what="near ties S={0}".format(S))
+    gpu.close()
+
+
+def test_the_largest_tail_is_accepted_and_the_next_refused(ctx, cat2k):
+    """S = 12 800 with r_eff = 0.0175: M = kPsisMaxTail = 2 560, the largest dynamic LDS of loox_tail_kernel."""
+    cat, table, lnl = cap_case(ctx, cat2k)
+    gpu = pr.device_catalog(ctx, cat, 2, ph.CENTRE)
+    func = np.ascontiguousarray((table - table.mean(axis=0)) / table.std(axis=0))
+    got = gpu.psis_loo_expect(table, r_eff=CAP_R_EFF, func=func, predictive=False)
+    ref = gpu.psis_loo(table, r_eff=CAP_R_EFF)
+    assert np.array_equal(got["pareto_k"], ref["pareto_k"]) and np.array_equal(got["n_eff"], ref["n_eff"])
+    want = lh.check_expect({"func": got["func"], "pareto_k": got["pareto_k"]}, lnl, None, func, r_eff=CAP_R_EFF, what="cap")
+    k_tol = np.maximum(1e-10, 10.0 * psh.k_noise(lnl, CAP_R_EFF))
+    fin = np.isfinite(want["pareto_k"])
+    assert np.all(np.abs(got["pareto_k"][fin] - want["pareto_k"][fin]) <= k_tol[fin])
+    assert np.all(np.abs(got["n_eff"] - want["n_eff"]) <= 1e-9 * want["n_eff"])
+    more = np.ascontiguousarray(ph.samples(cat2k, 2, False, 12805, seed=23))
+    dp = ctypes.POINTER(ctypes.c_double)
+    outs = [np.full(70, -7.0), np.full(70, -7.0), np.full(4 * 70, -7.0)]
+    pk, ne, lp = (o.ctypes.data_as(dp) for o in outs)
+    rc = gpu.lib.mcd_psis_loo_expect(gpu.handle, 12805, more.shape[1], more.ctypes.data_as(dp), CAP_R_EFF, 0, None, None, lp,
+                                     None, pk, ne)
+    assert rc == -1 and b"S / r_eff too large" in gpu.lib.mcd_last_error()
+    for o in outs:
+        assert np.all(o == -7.0)
     gpu.close()
 
 

@@ -115,6 +115,79 @@ def test_float32_catalogue(ctx, cat2k, model, precision):
     g64.close()
 
 
+# ---- short chains, ragged groups and the largest tail (the selection itself: tests/test_gpu_psis_rows.py) -----------------
+SHORT_S = [1, 20, 21, 24, 63, 65]          # M = 1, 4 (no tail), 5, 5, 13, 13; all but 20 and 24 leave a ragged 16-sample block
+STAR_COUNTS = [1, 63, 65, 130]             # a ragged last 64-star group of psis_term_kernel, alone and after full ones
+CAP_S, CAP_R_EFF = 12800, 0.0175           # M = min(2 560, ceil(3 sqrt(S / r_eff)) = 2 566): kPsisMaxTail, 64 000 B of LDS
+_cap = {}
+
+
+def _head(cat, n):
+    return {k: (v[:n].copy() if isinstance(v, np.ndarray) else v) for k, v in cat.items()}
+
+
+def cap_case(ctx, cat2k):
+    """70 stars of model 2 with CAP_S samples: (catalogue, table, lnL (70, CAP_S)); computed once, read-only (shared with
+    tests/test_gpu_loo_expect.py)."""
+    if not _cap:
+        cat = _head(cat2k, 70)
+        table = ph.samples(cat2k, 2, False, CAP_S, seed=23)
+        gpu = _catalog(ctx, cat, 2, ph.CENTRE)
+        lnl = _lnl_matrix(gpu, cat, table, 2, ph.CENTRE)
+        gpu.close()
+        table.setflags(write=False)
+        lnl.setflags(write=False)
+        _cap["case"] = (cat, table, lnl)
+    return _cap["case"]
+
+
+@pytest.fixture(scope="module")
+def short_table(cat2k):
+    return ph.samples(cat2k, 2, False, max(SHORT_S), seed=21)
+
+
+@pytest.mark.parametrize("n", STAR_COUNTS)
+@pytest.mark.parametrize("S", SHORT_S)
+def test_short_chains_and_ragged_groups(ctx, cat2k, short_table, S, n):
+    cat = _head(cat2k, n)
+    table = np.ascontiguousarray(short_table[:S])
+    gpu = _catalog(ctx, cat, 2, ph.CENTRE)
+    got = gpu.psis_loo(table)
+    lnl = _lnl_matrix(gpu, cat, table, 2, ph.CENTRE)
+    assert lnl.shape == (n, S)
+    psh.assert_matches(got, psh.numpy_psis(lnl), k_tol=_k_tol(lnl))
+    pp = gpu.pointwise_posterior(table)
+    assert np.all(np.abs(got["lppd"] - pp["lppd"]) <= 1e-13 * np.maximum(np.abs(pp["lppd"]), 1.0))
+    if psh.tail_len(S) < 5:
+        assert np.all(got["pareto_k"] == np.inf)
+    else:
+        assert np.all(got["pareto_k"] < np.inf)
+    if S == 1:
+        assert np.all(got["n_eff"] == 1.0) and np.array_equal(got["elpd_loo"], got["lppd"])
+    gpu.close()
+
+
+def test_the_largest_tail_is_accepted_and_the_next_refused(ctx, cat2k):
+    import ctypes
+    cat, table, lnl = cap_case(ctx, cat2k)
+    assert psh.tail_len(CAP_S, CAP_R_EFF) == 2560
+    gpu = _catalog(ctx, cat, 2, ph.CENTRE)
+    got = gpu.psis_loo(table, r_eff=CAP_R_EFF)
+    want = psh.numpy_psis(lnl, CAP_R_EFF)
+    psh.assert_matches(got, want, k_tol=np.maximum(1e-10, 10.0 * psh.k_noise(lnl, CAP_R_EFF)))
+    # S = 12 805: ceil(0.2 S) = 2 561
+    more = np.ascontiguousarray(ph.samples(cat2k, 2, False, 12805, seed=23))
+    assert psh.tail_len(12805, CAP_R_EFF) > 2560
+    dp = ctypes.POINTER(ctypes.c_double)
+    outs = [np.full(70, -7.0) for _ in range(4)]
+    rc = gpu.lib.mcd_psis_loo(gpu.handle, 12805, more.shape[1], more.ctypes.data_as(dp), CAP_R_EFF,
+                              *[o.ctypes.data_as(dp) for o in outs])
+    assert rc == -1 and b"S / r_eff too large" in gpu.lib.mcd_last_error()
+    for o in outs:
+        assert np.all(o == -7.0)
+    gpu.close()
+
+
 def test_refusals(ctx, cat2k):
     import ctypes
     from mcmc_dynamics_amd import _native
