@@ -63,10 +63,17 @@ typedef enum {
                                      (analysis/model.py:391-456)                                    */
     MCD_MODEL_PROFILE_BGDENS = 5, /* ModelFitConstantBackground: fixed per-star background lnL, density prior
                                      with per-walker f_back (analysis/model.py:565-623)             */
-    MCD_MODEL_PROFILE_BGFIXED = 6 /* ModelFit(background=Gaussian / SingleStars): the profiles of MCD_MODEL_PROFILE
+    MCD_MODEL_PROFILE_BGFIXED = 6,/* ModelFit(background=Gaussian / SingleStars): the profiles of MCD_MODEL_PROFILE
                                      with the fixed per-star background lnL and pmember mixture that
                                      Runner._calculate_lnlike applies to every subclass
                                      (analysis/model.py:182-222 -> analysis/runner.py:272-286)      */
+    MCD_MODEL_DOUBLE = 7,         /* DoubleModelFit: TWO Lynden-Bell components (r^2 in both denominators, so that
+                                     zero second amplitudes give MCD_MODEL_PROFILE) on one Plummer dispersion profile;
+                                     the second peak radius is r_peak_ratio * r_peak.  Columns: v_sys, sigma_max, a,
+                                     v_maxx, v_maxy, r_peak, v_maxx_c, v_maxy_c, r_peak_ratio [, ra_center, dec_center].
+                                     MCD_F64 only (mcd_catalog_create refuses the float32 precisions)            */
+    MCD_MODEL_DOUBLE_BGGAUSS = 8  /* DoubleModelFitGB: + per-walker Gaussian background and density prior, as
+                                     MCD_MODEL_PROFILE_BGGAUSS: [, v_back, sigma_back, f_back] behind the centre */
 } mcd_model;
 
 typedef enum {
@@ -153,6 +160,8 @@ int mcd_catalog_destroy(mcd_catalog* cat);
  *   *_BGGAUSS: ... + v_back, sigma_back, f_back
  *   PROFILE, PROFILE_BGFIXED: v_sys, sigma_max, a, v_maxx, v_maxy, r_peak [, ra_center, dec_center] (a, r_peak in arcsec)
  *   PROFILE_BGGAUSS: ... + v_back, sigma_back, f_back        PROFILE_BGDENS: ... + f_back
+ *   DOUBLE: v_sys, sigma_max, a, v_maxx, v_maxy, r_peak, v_maxx_c, v_maxy_c, r_peak_ratio [, ra_center, dec_center]
+ *   DOUBLE_BGGAUSS: ... + v_back, sigma_back, f_back          (K = 9, 11, 12 or 14; r_peak_ratio is dimensionless)
  * (order of config/constant.json:6-11, constant_with_background.json:6-14, model_with_background.json:6-16;
  * config/model.json interleaves the centre between v_maxx and v_maxy -- the host maps columns by name). */
 int mcd_catalog_param_count(const mcd_catalog* cat);

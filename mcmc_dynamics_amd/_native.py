@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("MCD_LIB_PATH") or os.path.join(_HERE, "libmcd_hip.so"
 
 MODEL_CONST, MODEL_CONST_BGFIXED, MODEL_CONST_BGGAUSS = 0, 1, 2
 MODEL_PROFILE, MODEL_PROFILE_BGGAUSS, MODEL_PROFILE_BGDENS, MODEL_PROFILE_BGFIXED = 3, 4, 5, 6
+MODEL_DOUBLE, MODEL_DOUBLE_BGGAUSS = 7, 8        # two Lynden-Bell components (analysis/double_model.py); float64 only
 CENTRE_FIXED, CENTRE_FREE = 0, 1
 F64, F32, F32_ACC64 = 0, 1, 2
 PRECISIONS = {"f64": F64, "f32": F32, "f32acc64": F32_ACC64}

@@ -764,6 +764,15 @@ class Runner(object):
         self._stretch_catalog(pos).hmc_block(self._stretch_plan(), chol, step_size, n_leap, pos, lnp, seed, step0, n_steps,
                                              chain, lnprob_chain, accepted, energy_error, jitter=jitter)
 
+    # the resident HMC and tempering blocks hold a walker's coordinates in registers (csrc/mcd_hmc.h: kHmcMaxDim,
+    # csrc/mcd_temper.h: kTemperMaxDim)
+    RESIDENT_MAX_DIM = 12
+
+    def _check_resident_dim(self, what, n_p):
+        if n_p > self.RESIDENT_MAX_DIM:
+            raise NotImplementedError("Runner.{0}: {1} free parameters, the resident blocks take at most {2} (fix some, e.g. "
+                                      "the centre; the stretch move has no such limit)".format(what, n_p, self.RESIDENT_MAX_DIM))
+
     def hmc(self, n_walkers=64, n_steps=500, pos=None, covariance=None, step_size=None, n_leap=8, n_warmup=None, seed=None,
             jitter=0.1, warmup_block=10):
         """Sample the posterior with Hamiltonian Monte Carlo on the device gradient (``sampler.HMCSampler``; csrc/mcd_hmc.h):
@@ -787,6 +796,7 @@ class Runner(object):
         ``expr`` / ``lnprior``-expression parameters and binned or non-float64 catalogues raise NotImplementedError: the
         gradient's own limits."""
         plan = self._grad_plan()
+        self._check_resident_dim("hmc", int(plan.free_idx.size))
         ok, why_not = self.resident_ok()
         if not ok:
             raise NotImplementedError("Runner.hmc: " + why_not)
@@ -879,6 +889,7 @@ class Runner(object):
         ``expr`` / ``lnprior``-expression parameters and binned or non-float64 catalogues raise NotImplementedError, as for
         ``hmc``."""
         plan = self._plan()
+        self._check_resident_dim("tempered", int(plan.free_idx.size))
         ok, why_not = self.resident_ok()
         if not ok:
             raise NotImplementedError("Runner.tempered: " + why_not)
@@ -1275,7 +1286,7 @@ class Runner(object):
     # ------------------------------------------------------------------ per-star posterior summaries (new)
     def _has_background(self):
         model = self._catalog_spec()[0][0]
-        return model not in (_native.MODEL_CONST, _native.MODEL_PROFILE)
+        return model not in (_native.MODEL_CONST, _native.MODEL_PROFILE, _native.MODEL_DOUBLE)
 
     def _pointwise_posterior(self, chain, n_burn, thin, membership):
         """mcd_pointwise_posterior over the post-burn-in samples of ``chain`` (W, steps, P), every ``thin``-th step, in the
@@ -1680,7 +1691,8 @@ class Runner(object):
 
     def _has_mixture_cdf(self):
         """The two models whose background has a CDF (a Gaussian fitted with the cluster)."""
-        return self._catalog_spec()[0][0] in (_native.MODEL_CONST_BGGAUSS, _native.MODEL_PROFILE_BGGAUSS)
+        return self._catalog_spec()[0][0] in (_native.MODEL_CONST_BGGAUSS, _native.MODEL_PROFILE_BGGAUSS,
+                                             _native.MODEL_DOUBLE_BGGAUSS)
 
     def posterior_predictive(self, chain, n_burn, thin=1):
         """Per-star posterior predictive checks over the S post-burn-in samples of ``chain`` (W, steps, P), computed on the

@@ -8,7 +8,7 @@ using namespace mcd::host;
 namespace {
 
 int param_count(int model, bool free_centre) {
-    int k = (mcd::is_profile(model) ? 6 : 4) + (free_centre ? 2 : 0);
+    int k = mcd::cluster_columns(model) + (free_centre ? 2 : 0);
     const int bg = mcd::bg_kind(model);
     if (bg == mcd::BG_GAUSS) k += 3;
     if (bg == mcd::BG_FIXED_DENSITY) k += 1;
@@ -50,7 +50,8 @@ void free_workset(WorkSet& w) {
 // guided tail wins.
 // "work" = stars x (walker tiles / 4) x (instructions per term / those of CONST): the thresholds are in CONST stars.
 double model_cost(int model, bool free_centre) {
-    static const double kCost[mcd::kNumModels] = {8.5, 24.0, 45.0, 25.0, 60.0, 40.0, 42.0};   // fast f64 loops, DESIGN 3.3
+    // fast f64 loops, DESIGN 3.3 (the double models: their profile counterparts plus the second component)
+    static const double kCost[mcd::kNumAllModels] = {8.5, 24.0, 45.0, 25.0, 60.0, 40.0, 42.0, 33.0, 68.0};
     return (kCost[model] + (free_centre ? 7.0 : 0.0)) / 8.5;
 }
 int balance_auto_m(const mcd_catalog* cat, int64_t n, int64_t n_walkers) {
@@ -368,10 +369,13 @@ int mcd_catalog_create(mcd_ctx* ctx, const mcd_catalog_desc* d, mcd_catalog** ou
 static int catalog_create_impl(mcd_ctx* ctx, const mcd_catalog_desc* d, std::unique_ptr<mcd_catalog>& cat) {
     if (int urc = ctx_usable(ctx)) return urc;
     if (d->n_stars < 0) return fail(MCD_ERR_INVALID, "negative n_stars");
-    if (d->model < 0 || d->model >= mcd::kNumModels) return fail(MCD_ERR_INVALID, "unknown model");
+    if (d->model < 0 || d->model >= mcd::kNumAllModels) return fail(MCD_ERR_INVALID, "unknown model");
     const int bgk = mcd::bg_kind(d->model);
     if (d->centre != MCD_CENTRE_FIXED && d->centre != MCD_CENTRE_FREE) return fail(MCD_ERR_INVALID, "unknown centre mode");
     if (d->precision < MCD_F64 || d->precision > MCD_F32_ACC64) return fail(MCD_ERR_INVALID, "unknown precision");
+    if (mcd::is_double(d->model) && d->precision != MCD_F64)
+        return fail(MCD_ERR_INVALID, "the double Lynden-Bell models (MCD_MODEL_DOUBLE, MCD_MODEL_DOUBLE_BGGAUSS) are float64 only: "
+                                     "float32 and f32acc64 catalogues are out of scope for them");
     if (d->n_stars > 0 && (!d->ra || !d->dec || !d->v || !d->verr)) return fail(MCD_ERR_INVALID, "missing ra/dec/v/verr column");
     if (bgk == mcd::BG_FIXED && d->n_stars > 0 && (!d->lnlike_bg || !d->pmember))
         return fail(MCD_ERR_INVALID, "background model needs lnlike_bg and pmember columns");

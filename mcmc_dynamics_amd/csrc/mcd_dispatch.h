@@ -8,7 +8,8 @@
 
 namespace mcd {
 
-// THE list of models: a new one is added here (and to mcd_math.h: Model, kNumModels) and reaches every launcher
+// The list of the models of the reference's running classes (mcd_math.h: Model, kNumModels); the double Lynden-Bell models
+// follow in MCD_DOUBLE_MODEL_LIST below, and a launcher reaches both lists through dispatch_any_model
 #define MCD_MODEL_LIST(X)                                                                                           \
     X(MODEL_CONST) X(MODEL_BGFIXED) X(MODEL_BGGAUSS) X(MODEL_PROFILE) X(MODEL_PROFILE_BGGAUSS) X(MODEL_PROFILE_BGDENS) \
     X(MODEL_PROFILE_BGFIXED)
@@ -29,6 +30,25 @@ R dispatch_model(int model, bool free_centre, F&& f, R fallback) {
     return fallback;
 }
 #undef MCD_MODEL_LIST
+
+// The launchers' dispatcher: the models of dispatch_model and, behind them, the double Lynden-Bell models (models
+// kNumModels .. kNumAllModels - 1; mcd_math.h: is_double).  Every launcher of the library calls this one; dispatch_model
+// keeps the list of the reference's running classes, which the host builds of the older test harnesses are written for.
+#define MCD_DOUBLE_MODEL_LIST(X) X(MODEL_DOUBLE) X(MODEL_DOUBLE_BGGAUSS)
+template <class F, class R>
+R dispatch_any_model(int model, bool free_centre, F&& f, R fallback) {
+#define MCD_MODEL_COUNT(M) +1
+    static_assert(kNumModels MCD_DOUBLE_MODEL_LIST(MCD_MODEL_COUNT) == kNumAllModels, "MCD_DOUBLE_MODEL_LIST names every further model");
+#undef MCD_MODEL_COUNT
+#define MCD_MODEL_CASE(M)                                                                   \
+    case M:                                                                                 \
+        return free_centre ? f(std::integral_constant<int, M>{}, std::true_type{})          \
+                           : f(std::integral_constant<int, M>{}, std::false_type{});
+    switch (model) { MCD_DOUBLE_MODEL_LIST(MCD_MODEL_CASE) }
+#undef MCD_MODEL_CASE
+    return dispatch_model(model, free_centre, static_cast<F&&>(f), fallback);
+}
+#undef MCD_DOUBLE_MODEL_LIST
 
 // f(T{}) with the type of the terms: double for precision 0 (MCD_F64), float for the float32 catalogues
 template <class F>

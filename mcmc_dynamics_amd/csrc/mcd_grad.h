@@ -13,6 +13,11 @@
 //                  dd/dv_maxx = -2 r_p dy / (r_p^2 + r^2), dd/dv_maxy = 2 r_p dx / (r_p^2 + r^2),
 //                  dd/dr_p = -2 cross (r^2 - r_p^2) / (r_p^2 + r^2)^2,
 //                  dn/dsigma_max = 2 sigma_max a / sqrt(a^2 + r^2),  dn/da = sigma_max^2 r^2 / (a^2 + r^2)^(3/2)
+//   DOUBLE         d = v - v_sys - sum_k 2 rho_k cross_k / D_k,  rho_1 = r_p, rho_2 = ratio r_p, D_k = rho_k^2 + r^2,
+//                  cross_k = v_maxx_k dy - v_maxy_k dx;  with f_k = 2 rho_k / D_k, g_k = -2 cross_k (r^2 - rho_k^2) / D_k^2:
+//                  dd/dv_maxx_k = -f_k dy, dd/dv_maxy_k = f_k dx, dd/dr_p = g_1 + ratio g_2, dd/dratio = r_p g_2,
+//                  dd/d(dx) = sum_k f_k (v_maxy_k + 2 cross_k dx / D_k), dd/d(dy) = sum_k f_k (-v_maxx_k + 2 cross_k dy / D_k);
+//                  n and its partials are PROFILE's.  The value d itself is formed as the value path forms it (star_d_n).
 //   free centre    chain rule through free_centre_xy (mcd_math.h): with t = B cos(ra_c) + A sin(ra_c),
 //                  dx/dra_c = t, dy/dra_c = sin(dec_c) x, dx/ddec_c = 0, dy/ddec_c = -(sd sin(dec_c) + cos(dec_c) t)
 //                  CONST:   sin(theta) = y/r, cos(theta) = x/r, so with u = cross / r (cross = v_maxx y - v_maxy x)
@@ -37,17 +42,19 @@
 namespace mcd {
 
 constexpr double kDegToRad = 0.017453292519943295769;
-constexpr int kGradMaxColumns = 11;       // PROFILE_BGGAUSS with a free centre
+constexpr int kGradMaxColumns = 14;       // DOUBLE_BGGAUSS with a free centre
 
 // kernel columns of a model (the C-ABI's parameter order, mcd_prep.h)
 MCD_HD constexpr int grad_columns(int model, bool free_centre) {
-    return (is_profile(model) ? 6 : 4) + (free_centre ? 2 : 0) +
+    return cluster_columns(model) + (free_centre ? 2 : 0) +
            (bg_kind(model) == BG_GAUSS ? 3 : bg_kind(model) == BG_FIXED_DENSITY ? 1 : 0);
 }
 template <int MODEL, bool FREE> struct GradCols {
     static constexpr bool kProf = is_profile(MODEL);
     static constexpr int kVsys = 0, kSigma = 1, kA = 2, kVx = kProf ? 3 : 2, kVy = kProf ? 4 : 3, kRp = 5;
-    static constexpr int kRa = kProf ? 6 : 4, kDec = kRa + 1;
+    static constexpr bool kDouble = is_double(MODEL);
+    static constexpr int kVxc = 6, kVyc = 7, kRatio = 8;     // (double models)
+    static constexpr int kRa = cluster_columns(MODEL), kDec = kRa + 1;
     static constexpr int kBg = kRa + (FREE ? 2 : 0);          // v_back, sigma_back, f_back | f_back
     static constexpr int kFb = bg_kind(MODEL) == BG_GAUSS ? kBg + 2 : kBg;
     static constexpr int K = grad_columns(MODEL, FREE);
@@ -55,7 +62,7 @@ template <int MODEL, bool FREE> struct GradCols {
 
 // what the derivatives need of the parameter row itself (WalkerConsts holds squares and products only)
 template <class T> struct GradRaw {
-    T sigma, a, rp, sb;
+    T sigma, a, rp, sb, ratio;
     template <int MODEL, bool FREE>
     MCD_HD void load(const double* __restrict__ p) {
         using C = GradCols<MODEL, FREE>;
@@ -63,6 +70,7 @@ template <class T> struct GradRaw {
         a = C::kProf ? (T)p[C::kA] : T(0);
         rp = C::kProf ? (T)p[C::kRp] : T(0);
         sb = bg_kind(MODEL) == BG_GAUSS ? (T)p[C::kBg + 1] : T(0);
+        ratio = C::kDouble ? (T)p[C::kRatio] : T(0);
     }
 };
 
@@ -75,6 +83,7 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
     // ---- cluster part: d, n and their partials
     T d, n;
     T d_vx, d_vy, d_rp = T(0), n_sigma, n_a = T(0);
+    T d_vxc = T(0), d_vyc = T(0), d_ratio = T(0);                  // (double models)
     T d_ra = T(0), d_dec = T(0), n_ra = T(0), n_dec = T(0);
     // free centre, in units of r0: dx/dra_c = t, dy/dra_c = y_ra, dx/ddec_c = 0, dy/ddec_c = y_dec
     T x = T(0), y = T(0), t = T(0), y_ra = T(0), y_dec = T(0);
@@ -115,17 +124,37 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
         const T inv = T(1) / (w.rp2 + r2);
         const T cross = fma_(w.vx, dy, -(w.vy * dx));
         const T f = w.rp_2 * inv;                                  // 2 r_p / (r_p^2 + r^2)
-        d = fma_(-f, cross, r[0] - w.vsys);
+        T f2 = T(0), inv2 = T(0), cross2 = T(0);                   // (double models: the second component's)
+        if constexpr (C::kDouble) {
+            const T m1 = w.rp2 + r2, m2 = w.rc2 + r2;
+            inv2 = T(1) / m2;
+            cross2 = fma_(w.vxc, dy, -(w.vyc * dx));
+            f2 = w.rc_2 * inv2;
+            const T num = fma_(w.rp_2 * cross, m2, (w.rc_2 * cross2) * m1);      // star_d_n's plain form
+            d = fma_(-num, T(1) / (m1 * m2), r[0] - w.vsys);
+            const T g1 = T(-2) * cross * (r2 - w.rp2) * inv * inv, g2 = T(-2) * cross2 * (r2 - w.rc2) * inv2 * inv2;
+            d_rp = fma_(q.ratio, g2, g1);
+            d_ratio = q.rp * g2;
+            d_vxc = -(f2 * dy);
+            d_vyc = f2 * dx;
+        } else {
+            d = fma_(-f, cross, r[0] - w.vsys);
+            d_rp = T(-2) * cross * (r2 - w.rp2) * inv * inv;
+        }
         n = fma_(w.s2a, tt, r[1]);
         d_vx = -(f * dy);
         d_vy = f * dx;
-        d_rp = T(-2) * cross * (r2 - w.rp2) * inv * inv;
         n_sigma = T(2) * q.sigma * q.a * tt;
         const T tt3 = tt * tt * tt;
         n_a = w.s2 * r2 * tt3;
         if constexpr (FREE) {
             const T ci = T(2) * cross * inv;
-            const T d_dx = f * fma_(ci, dx, w.vy), d_dy = f * fma_(ci, dy, -w.vx);
+            T d_dx = f * fma_(ci, dx, w.vy), d_dy = f * fma_(ci, dy, -w.vx);
+            if constexpr (C::kDouble) {
+                const T ci2 = T(2) * cross2 * inv2;
+                d_dx = fma_(f2, fma_(ci2, dx, w.vyc), d_dx);
+                d_dy = fma_(f2, fma_(ci2, dy, -w.vxc), d_dy);
+            }
             const T n_r = -(w.s2a * tt3);                          // dn/d(dx) = n_r dx, dn/d(dy) = n_r dy
             const T dx_ra = T(kArcsecPerRad) * t, dy_ra = T(kArcsecPerRad) * y_ra, dy_dec = T(kArcsecPerRad) * y_dec;
             d_ra = fma_(d_dx, dx_ra, d_dy * dy_ra);
@@ -175,6 +204,11 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
     if constexpr (C::kProf) {
         g[C::kA] += c_n * n_a;
         g[C::kRp] += c_d * d_rp;
+    }
+    if constexpr (C::kDouble) {
+        g[C::kVxc] += c_d * d_vxc;
+        g[C::kVyc] += c_d * d_vyc;
+        g[C::kRatio] += c_d * d_ratio;
     }
     if constexpr (FREE) {
         if constexpr (C::kProf) {

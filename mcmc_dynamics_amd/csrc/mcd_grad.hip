@@ -4,7 +4,7 @@
 // Work decomposition: the value kernel's (mcd_kernels.hip: loglike_kernel; mcd_launch.h has the shared mapping and the
 // partial-sum address).  lane = walker; a wave evaluates 64 walkers against one
 // chunk of the catalogue's chunk table; the record pointer is wave-uniform, so records arrive by scalar loads and are SGPR
-// operands of the f64 vector ops.  Each lane keeps 1 + K float64 sums (at most 12) in registers over its chunk and
+// operands of the f64 vector ops.  Each lane keeps 1 + K float64 sums (at most 15) in registers over its chunk and
 // stores them as partials[field][walker / 8][chunk][walker % 8] -- per field the layout of the value kernel's partial
 // sums, so the value path's fixed-order reduction (launch_reduce) adds them up unchanged, with field f of walker w as its
 // "walker" f x roundup64(W) + w.  No float atomics: results are bitwise repeatable.
@@ -31,7 +31,7 @@ __global__ __launch_bounds__(kBlock) void loglike_grad_kernel(const double* __re
                                                                int n_wtiles, int64_t n_walkers, int64_t n_chunks) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int K = grad_columns(MODEL, FREE);
-    static_assert(K <= kGradMaxColumns, "at most 12 sums per lane");
+    static_assert(K <= kGradMaxColumns, "at most 15 sums per lane");
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = threadIdx.x & (kWave - 1);
     int64_t chunk_id;
@@ -76,7 +76,7 @@ hipError_t launch_loglike_grad(hipStream_t s, const LaunchShape& sh, const void*
                                int64_t n_chunks, const double* params, const void* wpar, double* partials,
                                int64_t n_walkers) {
     if (sh.precision != 0) return hipErrorInvalidValue;
-    return dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_grad_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, params, wpar, partials,
                                                                            n_walkers);
     }, hipErrorInvalidValue);

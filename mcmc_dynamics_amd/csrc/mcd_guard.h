@@ -169,6 +169,15 @@ struct ParamRanges {
         double a = fabs(p[0]) + fabs(p[ix]) + fabs(p[iy]);
         bool ok = true;
         if (prof) ok = ok && finite_value(p[2]) && finite_value(p[5]);
+        // double models: the second component's amplitude joins the residual bound (each Lynden-Bell factor is <= 1) and
+        // its peak radius rho_2 = r_peak_ratio r_peak the lengths
+        const bool dbl = is_double(model);
+        double rc = 0.0;
+        if (dbl) {
+            a += fabs(p[6]) + fabs(p[7]);
+            rc = p[8] * p[5];
+            ok = ok && finite_value(rc);
+        }
         double sb2 = 0.0, f = 0.0;
         if (bg == BG_GAUSS) {
             sb2 = p[k - 2] * p[k - 2];
@@ -180,7 +189,7 @@ struct ParamRanges {
             ok = ok && finite_value(f);
         }
         if (free_centre) {
-            const int ic = prof ? 6 : 4;
+            const int ic = cluster_columns(model);
             ok = ok && finite_value(p[ic]) && finite_value(p[ic + 1]);
         }
         ok = ok && finite_value(s2) && finite_value(a);
@@ -189,6 +198,7 @@ struct ParamRanges {
             len_min = lesser(len_min, lesser(p[2], p[5]));
             len_max = greater(len_max, greater(p[2], p[5]));
         }
+        if (dbl) { len_min = lesser(len_min, rc); len_max = greater(len_max, rc); }
         if (bg == BG_GAUSS) { sb2_min = lesser(sb2_min, sb2); sb2_max = greater(sb2_max, sb2); }
         if (bg == BG_GAUSS || bg == BG_FIXED_DENSITY) { f_min = lesser(f_min, f); f_max = greater(f_max, f); }
         s2_min = lesser(s2_min, s2);
@@ -282,6 +292,7 @@ MCD_HD int level_verdict(const StatsScalars& st, int model, bool f32, int64_t n_
     GuardRanges g;
     if (!guard_verdict(st, model, f32, n_rows, pr, &g)) return 0;
     if (f32) return 1;
+    if (is_double(model)) return 1;          // no narrow-range variant: the shared reciprocal is what the level-2 tree would replace
     // MODEL_PROFILE with a fixed centre (ProfileNarrowAcc, mcd_math.h): m = r_peak^2 + r^2 <= 2^34 arcsec^2 (a 36 degree
     // field), lengths >= 2^-10 arcsec, variances within 2^-30 .. 2^30, residuals below 2^30: the 8-star tree on
     // ((dv m - K c)^2, m^2 n) stays within 2^+-820
@@ -392,7 +403,7 @@ inline F32Domain f32_domain(const CatalogStats& st, int model, bool free_centre,
     ParamRanges pr;
     double rot = 0.0, a_min = kInfinity, off_max = 0.0;
     const bool prof = is_profile(model);
-    const int ix = prof ? 3 : 2, ic = prof ? 6 : 4;
+    const int ix = prof ? 3 : 2, ic = cluster_columns(model);
     for (int64_t i = 0; i < n_rows; ++i) {
         const double* p = params + i * k;
         pr.add_row(p, k, model, free_centre);

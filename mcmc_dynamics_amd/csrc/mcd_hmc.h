@@ -38,7 +38,7 @@
 
 namespace mcd {
 
-constexpr int kHmcMaxDim = 12;                 // P <= 12 free parameters (K <= 11 kernel columns today)
+constexpr int kHmcMaxDim = 12;                 // P <= 12 free parameters (K <= 14 kernel columns today: some stay fixed)
 constexpr uint64_t kHmcKey1 = 0x6d63645f686d63ull;          // "mcd_hmc": never the stretch move's stream (kChainKey1)
 // Marsaglia's polar method accepts a pair with probability pi / 4.  Each generator call holds two pairs; after
 // kHmcNormalCalls calls (32 pairs) the draw gives up and returns 0.0: probability (1 - pi/4)^32 = 4.1e-22 per normal,

@@ -161,7 +161,8 @@ hipError_t launch_stretch_judge(hipStream_t s, const StretchDevice& d, int64_t n
 bool chain_numbers_on_device(int64_t n_walkers);
 hipError_t launch_chain_numbers(hipStream_t s, uint64_t seed, int64_t step0, int64_t i0, int64_t i1, int64_t n_bins,
                                 int64_t n_walkers, int n_dim, int32_t* order, double* zz, double* thr, int32_t* pick);
-// several ensembles need the step kernel that keeps an ensemble in LDS (<= 512 walkers, <= 12 columns, <= 32 KiB of positions)
+// several ensembles need the step kernel that keeps an ensemble in LDS (<= 512 walkers, <= 12 columns, <= 32 KiB of positions;
+// the double models with more columns take the general step kernel: one ensemble)
 bool stretch_step_handles(const StretchDevice& d);
 // ... and only that kernel can add up the main kernel's partial sums itself (StretchDevice::fused)
 bool stretch_step_fuses(const StretchDevice& d);

@@ -369,7 +369,7 @@ hipError_t launch_loo_expect(hipStream_t s, const LaunchShape& sh, int mode, con
                              double* terms, double* out, int64_t out_stride) {
     if (n <= 0 || S <= 0) return hipSuccess;
     if (M > kPsisMaxTail || n_func < 0 || n_func > kLooMaxFunc) return hipErrorInvalidValue;
-    const hipError_t e = dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         // pit_mix exists for the two models whose background has a CDF only

@@ -57,7 +57,8 @@ enum WalkerSlot : int {
     W_SAC = 4, W_CAC = 5, W_SDC = 6, W_CDC = 7,     // sin/cos(ra_center), sin/cos(dec_center)
     W_VB = 8, W_SB2 = 9, W_FB = 10,                 // v_back, sigma_back^2, f_back
     W_A2 = 11, W_S2A = 12, W_RP2 = 13, W_2RP = 14,  // profile models: a^2, sigma_max^2 a, r_peak^2, 2 r_peak (arcsec)
-    KD = 16
+    W_VXC = 15, W_VYC = 16, W_RC2 = 17, W_2RC = 18, // double models: v_maxx_c, v_maxy_c, rho_2^2, 2 rho_2 (rho_2 = ratio r_peak)
+    KD = 20                                         // (a row stays a whole number of 32-byte segments; slot 19 is padding)
 };
 
 // Likelihood variants.  Cluster part: CONST (analysis/constant.py) or PROFILE (analysis/model.py:93-180);
@@ -66,14 +67,22 @@ enum WalkerSlot : int {
 enum Model : int {
     MODEL_CONST = 0, MODEL_BGFIXED = 1, MODEL_BGGAUSS = 2,
     MODEL_PROFILE = 3, MODEL_PROFILE_BGGAUSS = 4, MODEL_PROFILE_BGDENS = 5,
-    MODEL_PROFILE_BGFIXED = 6          // ModelFit(background=...): profile cluster part + the pmember mixture of runner.py:272-286
+    MODEL_PROFILE_BGFIXED = 6,         // ModelFit(background=...): profile cluster part + the pmember mixture of runner.py:272-286
+    // DoubleModelFit / DoubleModelFitGB: two Lynden-Bell components on one Plummer dispersion profile (star_d_n), without
+    // background / with the per-walker Gaussian background and density prior of MODEL_PROFILE_BGGAUSS.  float64 only, no
+    // narrow-range (level 2) variant.
+    MODEL_DOUBLE = 7, MODEL_DOUBLE_BGGAUSS = 8
 };
-constexpr int kNumModels = 7;
+constexpr int kNumModels = 7;           // the models of the reference's running classes: what dispatch_model lists
+constexpr int kNumAllModels = 9;        // ... and the double Lynden-Bell models: what dispatch_any_model lists (mcd_dispatch.h)
 enum Background : int { BG_NONE = 0, BG_FIXED = 1, BG_GAUSS = 2, BG_FIXED_DENSITY = 3 };
 
 MCD_HD constexpr bool is_profile(int model) { return model >= MODEL_PROFILE; }
+MCD_HD constexpr bool is_double(int model) { return model == MODEL_DOUBLE || model == MODEL_DOUBLE_BGGAUSS; }
+// kernel columns of the cluster part in front of the centre columns (mcd_prep.h has the order)
+MCD_HD constexpr int cluster_columns(int model) { return is_double(model) ? 9 : is_profile(model) ? 6 : 4; }
 MCD_HD constexpr int bg_kind(int model) {
-    return (model == MODEL_CONST || model == MODEL_PROFILE) ? BG_NONE
+    return (model == MODEL_CONST || model == MODEL_PROFILE || model == MODEL_DOUBLE) ? BG_NONE
            : (model == MODEL_BGFIXED || model == MODEL_PROFILE_BGFIXED) ? BG_FIXED
            : (model == MODEL_PROFILE_BGDENS) ? BG_FIXED_DENSITY : BG_GAUSS;
 }
@@ -1130,12 +1139,14 @@ struct RecordPrefetch {
 // read below is a scalar load and the record values are SGPR operands of the vector ops.
 template <class T> struct WalkerConsts {
     T vsys, s2, vx, vy, sac, cac, sdc, cdc, vb, sb2, fb, a2, s2a, rp2, rp_2;
+    T vxc, vyc, rc2, rc_2;                            // double models only: dead loads for every other MODEL
     template <class P>
     MCD_HD void load(const P* __restrict__ p) {
         vsys = p[W_VSYS]; s2 = p[W_S2]; vx = p[W_VX]; vy = p[W_VY];
         sac = p[W_SAC]; cac = p[W_CAC]; sdc = p[W_SDC]; cdc = p[W_CDC];
         vb = p[W_VB]; sb2 = p[W_SB2]; fb = p[W_FB];
         a2 = p[W_A2]; s2a = p[W_S2A]; rp2 = p[W_RP2]; rp_2 = p[W_2RP];
+        vxc = p[W_VXC]; vyc = p[W_VYC]; rc2 = p[W_RC2]; rc_2 = p[W_2RC];
     }
 };
 
@@ -1143,6 +1154,13 @@ template <class T> struct WalkerConsts {
 //   CONST   (constant.py:52-111): v_los = v_sys + v_maxx sin(theta) - v_maxy cos(theta), sigma_los = sigma_max
 //   PROFILE (model.py:93-180):    v_los = v_sys + 2 r_peak (v_maxx dy - v_maxy dx) / (r_peak^2 + r^2)
 //                                 sigma_los^2 = sigma_max^2 a / sqrt(a^2 + r^2)           (all lengths in arcsec)
+//   DOUBLE:  a second Lynden-Bell component with its own amplitudes and the peak radius rho_2 = r_peak_ratio r_peak on the
+//            same dispersion profile.  With m_k = rho_k^2 + r^2, K_k = 2 rho_k, cross_k = v_maxx_k dy - v_maxy_k dx the two
+//            quotients share ONE reciprocal:
+//                d = (v - v_sys) - (K_1 cross_1 m_2 + K_2 cross_2 m_1) rcp(m_1 m_2),
+//            i.e. two crosses, the product m_1 m_2 and four multiply-adds more than PROFILE and no second reciprocal
+//            sequence.  The guard's general domain (lengths within 2^-100 .. 2^100, mcd_guard.h) keeps m_1 m_2 within
+//            2^+-402.  With both second amplitudes 0 the value is PROFILE's up to the rounding of the shared reciprocal.
 // NEWTON1 (narrow-range variants of the profile mixtures, f64): the Plummer root from ONE Newton step in its
 // three-instruction form (rsqrt2_newton: low by <= 4.1e-15 relative, see there), two instructions fewer than rsqrt_nr.
 template <int MODEL, class T, bool FREE, bool FASTMATH = false, bool NEWTON1 = false>
@@ -1161,6 +1179,24 @@ MCD_HD void star_d_n(RecPtr<T> r, const WalkerConsts<T>& w, T& d, T& n) {
             r2 = fma_(dx, dx, dy * dy);
         } else { dx = r[2]; dy = r[3]; r2 = r[4]; }
         T t, inv;
+        if constexpr (is_double(MODEL)) {
+            // (NEWTON1 changes nothing here: the double models have no narrow-range variant, level_verdict never returns 2
+            // for them and no launcher instantiates one)
+            const T m1 = w.rp2 + r2, m2 = w.rc2 + r2, mm = m1 * m2;
+            if constexpr (FASTMATH && sizeof(T) == 8) {
+                t = (T)rsqrt_nr((double)(w.a2 + r2));
+                inv = (T)rcp_nr((double)mm);
+            } else {
+                t = T(1) / sqrt_(w.a2 + r2);
+                inv = T(1) / mm;
+            }
+            const T cross1 = fma_(w.vx, dy, -(w.vy * dx));
+            const T cross2 = fma_(w.vxc, dy, -(w.vyc * dx));
+            const T num = fma_(w.rp_2 * cross1, m2, (w.rc_2 * cross2) * m1);
+            d = fma_(-num, inv, r[0] - w.vsys);
+            n = fma_(w.s2a, t, r[1]);
+            return;
+        }
         if constexpr (FASTMATH && NEWTON1 && sizeof(T) == 8) {
             // rsqrt2_newton returns 2 (a^2 + r^2)^-1/2: the factor goes into sigma_max^2 a / 2 (loop-invariant)
             const T cross = fma_(w.vx, dy, -(w.vy * dx));

@@ -139,7 +139,7 @@ hipError_t launch_posterior(hipStream_t s, const LaunchShape& sh, bool mem, cons
                             const void* wpar, int64_t n_samples, const double* inv, int64_t slice_len, int64_t n_slices,
                             double* part, double* state, int64_t n_prev, int64_t n_total, double* out) {
     if (n <= 0 || n_samples <= 0) return hipSuccess;
-    const hipError_t e = dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         // the membership fields exist for the models with a background only

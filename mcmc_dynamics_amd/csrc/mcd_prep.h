@@ -12,6 +12,7 @@ constexpr double kDeg2Rad = 0.017453292519943295769;
 
 // CONST:   v_sys, sigma_max, v_maxx, v_maxy [, ra_c, dec_c] [, v_back, sigma_back, f_back]
 // PROFILE: v_sys, sigma_max, a, v_maxx, v_maxy, r_peak [, ra_c, dec_c] [, v_back, sigma_back, f_back | f_back]
+// DOUBLE:  v_sys, sigma_max, a, v_maxx, v_maxy, r_peak, v_maxx_c, v_maxy_c, r_peak_ratio [, ra_c, dec_c] [, v_back, sigma_back, f_back]
 template <class T>
 __device__ __forceinline__ void walker_constants(const double* __restrict__ p, int model, bool free_centre, T* __restrict__ w) {
     const bool prof = is_profile(model);
@@ -22,8 +23,12 @@ __device__ __forceinline__ void walker_constants(const double* __restrict__ p, i
     w[W_VX] = (T)(prof ? p[3] : p[2]);
     w[W_VY] = (T)(prof ? p[4] : p[3]);
     w[W_A2] = (T)(a * a); w[W_S2A] = (T)(sigma * sigma * a); w[W_RP2] = (T)(rp * rp); w[W_2RP] = (T)(2.0 * rp);
-    w[15] = (T)0;
-    int j = prof ? 6 : 4;
+    // second component of the double models: rho_2 = r_peak_ratio r_peak; zeros for every other model
+    const bool dbl = is_double(model);
+    const double rc = dbl ? p[8] * rp : 0.0;
+    w[W_VXC] = (T)(dbl ? p[6] : 0.0); w[W_VYC] = (T)(dbl ? p[7] : 0.0); w[W_RC2] = (T)(rc * rc); w[W_2RC] = (T)(2.0 * rc);
+    w[19] = (T)0;
+    int j = cluster_columns(model);
     double sac = 0, cac = 1, sdc = 0, cdc = 1;
     if (free_centre) {
         sincos(p[j] * kDeg2Rad, &sac, &cac);

@@ -99,7 +99,7 @@ hipError_t launch_psis(hipStream_t s, const LaunchShape& sh, const void* records
                        int64_t M, double r_eff, double* terms, double* out, int64_t out_stride) {
     if (n <= 0 || S <= 0) return hipSuccess;
     if (M > kPsisMaxTail) return hipErrorInvalidValue;
-    const hipError_t e = dispatch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return term_launch<decltype(M)::value, decltype(FREE)::value>(s, sh.precision, records, n, wpar, S, terms);
     }, hipErrorInvalidValue);
     if (e != hipSuccess) return e;

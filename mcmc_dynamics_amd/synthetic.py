@@ -179,3 +179,32 @@ def example_polar_to_catalog(r_arcmin, theta_rad, v, verr, ra_center_deg=180.0):
     y = np.asarray(r_arcmin) * np.sin(theta_rad)
     ra, dec = offsets_to_radec(x, y, ra_center_deg, 0.0)
     return {"ra": ra, "dec": dec, "v": np.asarray(v, dtype=np.float64), "verr": np.asarray(verr, dtype=np.float64)}
+
+
+def make_double_catalog(n_stars, seed=20260419, r_max_arcsec=300.0, sigma_max=10.0, a=60.0, v_max=6.0, r_peak=90.0,
+                        v_max_c=8.0, r_peak_ratio=0.15, verr_scale=0.05):
+    """A cluster with a decoupled core: an outer Lynden-Bell rotation component (amplitude ``v_max`` at ``r_peak`` arcsec)
+    and a second, inner, COUNTER-rotating one (amplitude ``v_max_c`` at ``r_peak_ratio * r_peak``, axis turned by pi) on
+    one Plummer dispersion profile (``sigma_max``, ``a``) -- the model of ``analysis.DoubleModelFit``.  Same geometry
+    recipe as ``make_catalog``; ``truth`` holds every parameter of the double model (and of ``ModelFit``)."""
+    rng = np.random.default_rng(seed)
+    n = int(n_stars)
+    theta_0 = 2.0 * np.pi * rng.random()
+    r_max = r_max_arcsec / 60.0
+    sep = _truncated_halfnormal(rng, r_max / 2.0, r_max, n)
+    theta = rng.uniform(-np.pi, np.pi, size=n)
+    dx, dy = 60.0 * sep * np.cos(theta), 60.0 * sep * np.sin(theta)                 # arcsec
+    ra, dec = offsets_to_radec(dx / 60.0, dy / 60.0, CENTER_RA_DEG, CENTER_DEC_DEG)
+    r2 = dx * dx + dy * dy
+    vx, vy = v_max * np.cos(theta_0), v_max * np.sin(theta_0)
+    vxc, vyc = -v_max_c * np.cos(theta_0), -v_max_c * np.sin(theta_0)
+    rho_2 = r_peak_ratio * r_peak
+    v_los = TRUTH["v_sys"] + 2.0 * r_peak * (vx * dy - vy * dx) / (r_peak ** 2 + r2) \
+        + 2.0 * rho_2 * (vxc * dy - vyc * dx) / (rho_2 ** 2 + r2)
+    sigma = sigma_max / (1.0 + r2 / a ** 2) ** 0.25
+    verr = verr_scale * sigma_max * rng.lognormal(0.0, 0.5, size=n)
+    v = v_los + rng.normal(size=n) * sigma + rng.normal(size=n) * verr
+    truth = {"v_sys": TRUTH["v_sys"], "sigma_max": float(sigma_max), "a": float(a), "v_maxx": float(vx), "v_maxy": float(vy),
+             "r_peak": float(r_peak), "v_maxx_c": float(vxc), "v_maxy_c": float(vyc), "r_peak_ratio": float(r_peak_ratio),
+             "theta_0": float(theta_0), "ra_center": CENTER_RA_DEG, "dec_center": CENTER_DEC_DEG}
+    return {"ra": ra, "dec": dec, "v": v, "verr": verr, "truth": truth}

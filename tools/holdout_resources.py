@@ -17,14 +17,17 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+# analyse() reports the seven models of the reference's running classes unless told otherwise (the tests that quote
+# its table count them); the double Lynden-Bell models: analyse(models=DOUBLE_MODELS), tests/test_double_resources_cpu.py
+BASE_MODELS, DOUBLE_MODELS, ALL_MODELS = tuple(range(7)), (7, 8), tuple(range(9))
 _MAIN = re.compile(r"holdout_kernelILi(\d)ELb(\d)EE")
 _FIELD = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\w+) \[-Rpass")
 KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize": "scratch_bytes_per_lane",
         "Occupancy": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size": "lds_bytes"}
 
 
-def analyse():
+def analyse(models=None):
     """Rows (dicts) per kernel instantiation of the unit."""
     out = tempfile.mkdtemp(prefix="holdout_resources_")
     res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
@@ -36,7 +39,7 @@ def analyse():
             name = line.split("Function Name:")[1].split()[0]
             m = _MAIN.search(name)
             if m:
-                row = {"kernel": "holdout", "model": MODELS[int(m.group(1))], "free_centre": m.group(2) == "1"}
+                row = {"kernel": "holdout", "model": MODELS[int(m.group(1))], "model_id": int(m.group(1)), "free_centre": m.group(2) == "1"}
             else:
                 row = {"kernel": "combine" if "holdout_combine_kernel" in name else name}
             row["symbol"] = name
@@ -45,11 +48,11 @@ def analyse():
         f = _FIELD.search(line)
         if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
             row[KEYS[f.group(1).strip()]] = int(f.group(2))
-    return rows
+    return [r for r in rows if "model_id" not in r or r["model_id"] in (BASE_MODELS if models is None else models)]
 
 
 def main():
-    rows = analyse()
+    rows = analyse(models=ALL_MODELS)
     print("{0:8s} {1:16s} {2:6s} {3:>6s} {4:>6s} {5:>8s} {6:>10s}".format("kernel", "model", "centre", "VGPRs", "SGPRs",
                                                                         "scratch", "waves/SIMD"))
     for r in rows:

@@ -64,6 +64,10 @@ KERNELS = [
     ("ILi3ELb0EddLi2E", "PROFILE fixed, narrow", "profile", 8, 1, _sel(rsq=8, rcp=1)),
     ("ILi4ELb0EddLi1E", "PROFILE_BGGAUSS fixed", "profile_bggauss", 4, 1, _sel(frexp=4)),
     ("ILi5ELb0EddLi1E", "PROFILE_BGDENS fixed", "profile_bgdens", 4, 1, _sel(frexp=4)),
+    # the double Lynden-Bell models (one fast form, no narrow-range variant): PROFILE's / PROFILE_BGGAUSS's loops with the
+    # second component on the shared reciprocal
+    ("ILi7ELb0EddLi1E", "DOUBLE fixed centre", "double", 8, 1, None),
+    ("ILi8ELb0EddLi1E", "DOUBLE_BGGAUSS fixed", "double_bggauss", 4, 1, _sel(frexp=4)),
     ("ILi0ELb0EffLi1E", "CONST fixed, f32", "const_f32", 16, 1, None),
     ("ILi0ELb0EfdLi1E", "CONST fixed, f32 terms f64 sums", "const_f32acc64", 16, 1, None),
     ("ILi1ELb0EffLi1E", "BGFIXED fixed, f32", "bgfixed_f32", 4, 1, None),
@@ -278,11 +282,22 @@ def main():
         print("{0:34s} {1:9.2f} {2:8.2f} {3:8.2f} {4:10.2f} {5:14.1f}".format(r["name"], r["valu_per_term"], r["f64_per_term"],
                                                                            r["other_per_term"], r["slots_per_term"], pred))
     if len(sys.argv) == 3 and sys.argv[1] == "--json":
+        merged = merge_variants(rows)
+        # what the second Lynden-Bell component adds to PROFILE's loop per term (tests/test_double_isa_cpu.py holds the margin)
+        double_note = {
+            "valu_per_term_over_profile": merged["double"]["valu_per_term"] - merged["profile_general"]["valu_per_term"],
+            "valu_per_term_over_profile_bggauss": merged["double_bggauss"]["valu_per_term"] - merged["profile_bggauss"]["valu_per_term"],
+            "trans_f64_per_term_over_profile": merged["double"]["trans_f64_per_term"] - merged["profile_general"]["trans_f64_per_term"],
+            "margin": 7.0,
+            "listing": "per term: 1 v_add_f64 (m_2 = rho_2^2 + r^2), 4 v_mul_f64 (v_maxy_c dx, m_1 m_2, K_2 cross_2, its "
+                       "product with m_1; K_1 cross_1 takes the place of PROFILE's K_1 inv), 2 v_fma_f64 (the second cross, "
+                       "the numerator); no second v_rcp_f64 sequence",
+        } if "double" in merged and "double_bggauss" in merged else None
         with open(sys.argv[2], "w") as f:
-            json.dump({"source_sha16": source_hash(), "generated_by": "tools/isa_mix.py",
+            json.dump({"source_sha16": source_hash(), "generated_by": "tools/isa_mix.py", "double_models": double_note,
                        "note": "VALU wave-instructions per star-walker term in the hot loop nest of mcd::loglike_kernel "
                                "(gfx950 ISA from hipcc -save-temps); prologue, final log and tails not included",
-                       "kernels": merge_variants(rows)}, f, indent=1, sort_keys=True)
+                       "kernels": merged}, f, indent=1, sort_keys=True)
             f.write("\n")
 
 

@@ -31,7 +31,7 @@ CASES = [
     ("CONST_BGGAUSS", 2, False, 10000, 16384),
 ]
 MIX_MODELS = (2, 4)
-KD = 16                                                # derived values per sample row (csrc/mcd_math.h)
+KD = 20                                                # derived values per sample row (csrc/mcd_math.h)
 
 
 def timed(gpu, call, calls):

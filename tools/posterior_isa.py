@@ -22,7 +22,10 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+# analyse() reports the seven models of the reference's running classes unless told otherwise (the tests that quote
+# its table count them); the double Lynden-Bell models: analyse(models=DOUBLE_MODELS), tests/test_double_resources_cpu.py
+BASE_MODELS, DOUBLE_MODELS, ALL_MODELS = tuple(range(7)), (7, 8), tuple(range(9))
 # _ZN3mcd12_GLOBAL__N_122posterior_slice_kernelILi<model>ELb<free>ELb<mem>E<d|f>EEvPKT2_...
 _NAME = re.compile(r"^(_ZN3mcd12_GLOBAL__N_122posterior_slice_kernelILi(\d)ELb(\d)ELb(\d)E([df])E\w*):")
 
@@ -38,7 +41,7 @@ def compile_isa(out):
     return os.path.join(out, "mcd_posterior-hip-amdgcn-amd-amdhsa-gfx950.s")
 
 
-def analyse(out=None):
+def analyse(out=None, models=None):
     """Rows (dicts) per slice-kernel instantiation; `out`: directory for the compiler's temporaries (default: a fresh
     temporary directory)."""
     if out is None:
@@ -63,17 +66,17 @@ def analyse(out=None):
         # one trip = one term: the compiler does not unroll a loop of a few hundred instructions with a run-time trip count
         valu = sum(v for o, v in body.items() if o.startswith("v_"))
         f64 = sum(v for o, v in body.items() if o.startswith("v_") and "f64" in o and not o.startswith(("v_ldexp", "v_frexp")))
-        rows.append({"kernel": m.group(1), "model": MODELS[int(m.group(2))], "free_centre": m.group(3) == "1",
+        rows.append({"kernel": m.group(1), "model": MODELS[int(m.group(2))], "model_id": int(m.group(2)), "free_centre": m.group(3) == "1",
                      "membership": m.group(4) == "1", "precision": "f64" if m.group(5) == "d" else "f32",
                      "loop_lines": hi - lo, "valu_per_term": valu, "f64_per_term": f64,
                      "s_load_in_loop": sum(v for o, v in body.items() if o.startswith("s_load")),
                      "vector_loads_in_loop": sum(v for o, v in body.items() if o.startswith(("global_load", "flat_load", "buffer_load"))),
                      "scratch_in_loop": sum(v for o, v in body.items() if o.startswith("scratch_"))})
-    return rows
+    return [r for r in rows if "model_id" not in r or r["model_id"] in (BASE_MODELS if models is None else models)]
 
 
 def main():
-    rows = analyse()
+    rows = analyse(models=ALL_MODELS)
     print("{0:16s} {1:5s} {2:4s} {3:4s} {4:>10s} {5:>8s} {6:>7s} {7:>7s}".format("model", "free", "mem", "prec", "VALU/term",
                                                                                "f64", "s_load", "vload"))
     for r in sorted(rows, key=lambda r: (r["precision"], r["model"], r["free_centre"], r["membership"])):

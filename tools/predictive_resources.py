@@ -19,7 +19,10 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+# analyse() reports the seven models of the reference's running classes unless told otherwise (the tests that quote
+# its table count them); the double Lynden-Bell models: analyse(models=DOUBLE_MODELS), tests/test_double_resources_cpu.py
+BASE_MODELS, DOUBLE_MODELS, ALL_MODELS = tuple(range(7)), (7, 8), tuple(range(9))
 _SLICE = re.compile(r"predictive_slice_kernelILi(\d)ELb(\d)ELb(\d)E([df])E")
 _MERGE = re.compile(r"predictive_merge_kernelILb(\d)EE")
 _FIELD = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\w+) \[-Rpass")
@@ -36,7 +39,7 @@ def remarks(out=None):
     return res.stderr
 
 
-def analyse(out=None):
+def analyse(out=None, models=None):
     """Rows (dicts) per kernel instantiation of the unit."""
     rows, row = [], None
     for line in remarks(out).split("\n"):
@@ -44,7 +47,7 @@ def analyse(out=None):
             name = line.split("Function Name:")[1].split()[0]
             s, m = _SLICE.search(name), _MERGE.search(name)
             if s:
-                row = {"kernel": "slice", "model": MODELS[int(s.group(1))], "free_centre": s.group(2) == "1",
+                row = {"kernel": "slice", "model": MODELS[int(s.group(1))], "model_id": int(s.group(1)), "free_centre": s.group(2) == "1",
                        "mix": s.group(3) == "1", "precision": "f64" if s.group(4) == "d" else "f32"}
             elif m:
                 row = {"kernel": "merge", "mix": m.group(1) == "1"}
@@ -56,7 +59,7 @@ def analyse(out=None):
         f = _FIELD.search(line)
         if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
             row[KEYS[f.group(1).strip()]] = int(f.group(2))
-    return rows
+    return [r for r in rows if "model_id" not in r or r["model_id"] in (BASE_MODELS if models is None else models)]
 
 
 def families(rows):
@@ -80,7 +83,7 @@ def families(rows):
 
 
 def main():
-    rows = analyse()
+    rows = analyse(models=ALL_MODELS)
     for r in rows:
         print(r)
     print("{0:22s} {1:4s} {2:>3s} {3:>6s} {4:>6s} {5:>8s} {6:>10s}".format("family", "prec", "n", "VGPRs", "SGPRs", "scratch",
