@@ -321,6 +321,45 @@ int mcd_replicate_check(mcd_catalog* cat, int64_t n_samples, int32_t k, const do
 int mcd_replicate_numbers(uint64_t seed, int64_t sample0, int64_t n_samples, int64_t star0, int64_t n_stars,
                           double* g /* [S][N] */, double* u /* [S][N] */);
 
+/* Weighted log-likelihood and gradient: every parameter row sees the catalogue under its own star weights (the
+ * nonparametric and the weighted-likelihood bootstrap: Rubin 1981; Newton & Raftery 1994; Lyddon, Holmes & Walker 2019).
+ * With l_i(theta) the star's plain term (what mcd_loglike_per_star returns), rows theta[r] (params: row-major [R][K], the
+ * kernel columns of mcd_loglike_batch) and b = row_replicate[r], the replicate of row r:
+ *   out[r] = sum_i w(b, i) l_i(theta[r])        grad[r][k] = sum_i w(b, i) dl_i/dtheta_k(theta[r])
+ * the terms and partial derivatives of mcd_loglike_grad_batch, added per chunk in star order and over the chunks in a
+ * fixed order.  Several rows may share a replicate.  The weights, by `scheme`:
+ *   MCD_WEIGHT_EXPONENTIAL  w = -log(u), Exp(1);  MCD_WEIGHT_POISSON  w = the Poisson(1) count whose cumulative
+ *     probabilities bracket u: both generated on the device from (seed, replicate, star) alone, star = the index in
+ *     catalogue order; u = ((x >> 11) + 0.5) 2^-53 of the generator word x (mcd_bootstrap_weights gives the same
+ *     numbers on the host, bit for bit).  Replicate ids are any non-negative int64: neither ordered nor dense.
+ *   MCD_WEIGHT_EXPLICIT     w = weights[b][i] (row-major [n_replicates][n_stars], finite and >= 0); row_replicate
+ *     indexes its rows.  Every call checks the array and fingerprints its contents; the transposed copy on the device is
+ *     kept with the catalogue while (n_replicates, fingerprint) stand -- keyed by contents, never by address.
+ * Weights are NOT normalised: their sum over the stars is about n_stars, not n_stars (the Newton-Raftery form).
+ * A star of weight 0 is selected out, not multiplied: it adds exactly +0.0 to every field of that row, even where its
+ * term is not finite.  Either output may be NULL; both NULL is MCD_OK without work.  Synchronous and deterministic:
+ * bit-identical from run to run, independent of earlier calls, and a generated weight does not depend on the chunk plan.
+ * MCD_ERR_INVALID, with a message and nothing written: a binned or a float32 catalogue; several devices or a communicator;
+ * a foreign k; n_rows < 1 or > 65536; an unknown scheme; row_replicate NULL or negative; for MCD_WEIGHT_EXPLICIT an index
+ * outside [0, n_replicates), weights NULL, a negative or non-finite weight, n_replicates x n_stars x 8 bytes beyond
+ * 256 MiB.  The work buffers of a row count stay with the catalogue.  Waits under the context's deadline; honours
+ * option "timing" (mcd_last_kernel_ms: the main kernel) and option "chunk_len". */
+enum { MCD_WEIGHT_EXPONENTIAL = 0, MCD_WEIGHT_POISSON = 1, MCD_WEIGHT_EXPLICIT = 2 };
+typedef struct {
+    int32_t scheme;                /* MCD_WEIGHT_* */
+    uint64_t seed;                 /* generated schemes */
+    int64_t n_replicates;          /* MCD_WEIGHT_EXPLICIT: rows of `weights`; ignored otherwise */
+    const int64_t* row_replicate;  /* [n_rows] */
+    const double* weights;         /* MCD_WEIGHT_EXPLICIT: [n_replicates][n_stars]; NULL otherwise */
+} mcd_weight_desc;
+int mcd_weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
+                              const mcd_weight_desc* w, double* out /* [R], may be NULL */,
+                              double* grad /* [R][K], may be NULL */);
+/* The generated weights of replicates rep0 .. and stars star0 .., row-major [n_reps][n_stars], for a generated scheme.
+ * Host only, as mcd_replicate_numbers. */
+int mcd_bootstrap_weights(int32_t scheme, uint64_t seed, int64_t rep0, int64_t n_reps, int64_t star0, int64_t n_stars,
+                          double* w /* [n_reps][n_stars] */);
+
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute
  * whose output is the `lnlike_bg` column of a MCD_MODEL_CONST_BGFIXED / _PROFILE_BGDENS catalogue (runner.py:96-106).

@@ -69,6 +69,10 @@ SYMBOLS = {
                                            ctypes.c_int32, _c_int64_p, _c_int64_p, ctypes.c_double, ctypes.c_double, _c_double_p]),
     "mcd_replicate_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              _c_double_p, _c_double_p]),
+    "mcd_weighted_loglike_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_void_p,
+                                                 _c_double_p, _c_double_p]),
+    "mcd_bootstrap_weights": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                             ctypes.c_int64, _c_double_p]),
     "mcd_moment_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
                                         ctypes.c_int64, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p,
                                         _c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
@@ -166,6 +170,24 @@ class PriorDesc(ctypes.Structure):
 
 
 PRIOR_FLAT, PRIOR_NORMAL, PRIOR_LOGNORMAL = 0, 1, 2
+
+
+class WeightDesc(ctypes.Structure):
+    """Mirror of ``mcd_weight_desc``."""
+    _fields_ = [("scheme", ctypes.c_int32), ("seed", ctypes.c_uint64), ("n_replicates", ctypes.c_int64),
+                ("row_replicate", _c_int64_p), ("weights", _c_double_p)]
+
+
+WEIGHT_EXPONENTIAL, WEIGHT_POISSON, WEIGHT_EXPLICIT = 0, 1, 2
+WEIGHT_SCHEMES = {"exponential": WEIGHT_EXPONENTIAL, "poisson": WEIGHT_POISSON, "explicit": WEIGHT_EXPLICIT}
+
+
+def _weight_scheme(scheme):
+    if isinstance(scheme, str):
+        if scheme not in WEIGHT_SCHEMES:
+            raise ValueError("scheme must be one of {0}".format(sorted(WEIGHT_SCHEMES)))
+        return WEIGHT_SCHEMES[scheme]
+    return int(scheme)
 
 
 def _prior_desc(prior):
@@ -470,6 +492,18 @@ def replicate_numbers(seed, sample0, n_samples, star0, n_stars):
     return g, u
 
 
+def bootstrap_weights(scheme, seed, rep0, n_reps, star0, n_stars):
+    """``mcd_bootstrap_weights``: the star weights that ``Catalog.weighted_loglike_grad`` generates on the device for
+    replicates ``rep0 ..`` and stars ``star0 ..`` (host code, no device involved, the same bits), (n_reps, n_stars).
+    ``scheme``: "exponential" (Exp(1), the weighted-likelihood bootstrap) or "poisson" (Poisson(1) counts)."""
+    lib = load_library()
+    w = np.empty((int(n_reps), int(n_stars)), dtype=np.float64)
+    rc = lib.mcd_bootstrap_weights(_weight_scheme(scheme), int(seed) & 0xFFFFFFFFFFFFFFFF, int(rep0), int(n_reps), int(star0),
+                                   int(n_stars), _ptr(w))
+    _check(lib, rc, "mcd_bootstrap_weights")
+    return w
+
+
 def temper_numbers(seed, step0, n_steps, n_temps, n_walkers):
     """``mcd_temper_numbers``: the swap thresholds log(u) of steps ``step0 .. step0 + n_steps - 1`` of the tempered chain that
     ``seed`` names (host code, no device involved), shape (steps, T - 1, W): pair t is rungs (t, t + 1); a step exchanges the
@@ -743,6 +777,42 @@ class Catalog(object):
                                             _ptr(p), _ptr(out["lppd"]), _ptr(out["lnl_var"]))
         _check(self.lib, rc, "mcd_holdout_pointwise")
         return out
+
+    def weighted_loglike_grad(self, table, row_replicate, scheme="exponential", seed=0, weights=None, want_value=True,
+                              want_grad=True):
+        """Value and gradient under per-row star weights (include/mcd.h: mcd_weighted_loglike_grad): ``table`` (R, K) kernel
+        rows, ``row_replicate`` (R,) int64 the replicate of every row -> ((R,), (R, K)): sum_i w(b, i) l_i and its gradient
+        with respect to the K kernel columns.  ``scheme``: "exponential" or "poisson" (weights generated on the device from
+        (seed, replicate, star); ``bootstrap_weights`` gives the same numbers), or "explicit" with ``weights``
+        (n_replicates, n_stars), finite and >= 0, which ``row_replicate`` indexes.  Weights are not normalised; a star of
+        weight 0 adds exactly +0.0 whatever its term.  ``want_value`` / ``want_grad`` = False pass a null pointer and return
+        None in its place.  Un-binned float64 catalogues on one device; synchronous and bit-identical from run to run."""
+        self._alive()
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (R, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        rep = np.ascontiguousarray(row_replicate, dtype=np.int64).reshape(-1)
+        if rep.size != p.shape[0]:
+            raise ValueError("row_replicate must hold one replicate per row of the table")
+        d = WeightDesc()
+        d.scheme = _weight_scheme(scheme)
+        d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        d.row_replicate = rep.ctypes.data_as(_c_int64_p)
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(_f64(weights))
+            if w.ndim != 2 or w.shape[1] != self.n_stars:
+                raise ValueError("weights must have shape (n_replicates, {0})".format(self.n_stars))
+            d.n_replicates = w.shape[0]
+        d.weights = _ptr(w)
+        out = np.empty(p.shape[0], dtype=np.float64) if want_value else None
+        grad = np.empty(p.shape, dtype=np.float64) if want_grad else None
+        rc = self.lib.mcd_weighted_loglike_grad(self.handle, p.shape[0], self.k, _ptr(p), ctypes.byref(d), _ptr(out), _ptr(grad))
+        _check(self.lib, rc, "mcd_weighted_loglike_grad")
+        return out, grad
 
     REPLICATE_FIELDS = ("s1", "s2", "s3", "s4", "sin", "cos", "max", "tail3")
 

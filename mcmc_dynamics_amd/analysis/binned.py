@@ -286,6 +286,14 @@ class BinnedConstantFit(ConstantFit):
     def kfold(self, *args, **kwargs):
         return self.holdout_fit()
 
+    def bootstrap(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: the weighted-likelihood bootstrap (bootstrap, "
+                                  "lnprob_weighted_grad_batch) is defined for un-binned fits only; fit the bins' stars "
+                                  "with ConstantFit")
+
+    def lnprob_weighted_grad_batch(self, *args, **kwargs):
+        return self.bootstrap()
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

@@ -396,6 +396,42 @@ def replicate_summary(out, counts):
             "extreme": np.minimum(p, 1.0 - p), "bands": np.transpose(bands, (2, 3, 0, 1))}
 
 
+BOOTSTRAP_PERCENTILES = (2.5, 16.0, 50.0, 84.0, 97.5)
+
+
+def bootstrap_summary(x, x_hat, converged, names, laplace_covariance=None):
+    """Moments of the bootstrap replicates ``x`` (B, P) of ``Runner.bootstrap`` around the estimate ``x_hat`` (P,), over the
+    CONVERGED replicates only: ``mean``, ``covariance`` (sample, B - 1; the sandwich covariance of the estimate when the
+    model is misspecified), ``std``, ``bias`` = mean - x_hat, ``percentiles`` ({2.5, 16, 50, 84, 97.5} -> (P,)),
+    ``n_converged``, ``n_replicates``, ``names``.  With ``laplace_covariance`` (``Runner.laplace(x_hat)["covariance"]``)
+    also ``std_ratio`` = std / sqrt(diag laplace_covariance): about 1 when the model describes the scatter of the data,
+    above 1 where the model-based width is too narrow.  Warns when fewer than 90 % of the replicates converged."""
+    x = np.atleast_2d(np.asarray(x, dtype=np.float64))
+    x_hat = np.asarray(x_hat, dtype=np.float64).reshape(-1)
+    converged = np.asarray(converged, dtype=bool).reshape(-1)
+    if x.shape != (converged.size, x_hat.size):
+        raise ValueError("bootstrap_summary: x must have shape (len(converged), len(x_hat))")
+    n_b, n_p = x.shape
+    n_ok = int(np.count_nonzero(converged))
+    if n_ok < 0.9 * n_b:
+        warnings.warn("bootstrap_summary: only {0} of {1} replicates converged; the moments are those of the converged "
+                      "ones (raise max_iter, or look at the replicates in x)".format(n_ok, n_b))
+    good = x[converged]
+    nan = np.full(n_p, np.nan)
+    mean = good.mean(axis=0) if n_ok else nan
+    cov = np.atleast_2d(np.cov(good, rowvar=False, ddof=1)) if n_ok > 1 else np.full((n_p, n_p), np.nan)
+    std = np.sqrt(np.diag(cov))
+    pct = {q: (np.percentile(good, q, axis=0) if n_ok else nan.copy()) for q in BOOTSTRAP_PERCENTILES}
+    out = {"mean": mean, "covariance": cov, "std": std, "bias": mean - x_hat, "percentiles": pct, "n_converged": n_ok,
+           "n_replicates": int(n_b), "names": list(names)}
+    if laplace_covariance is not None:
+        lap = np.atleast_2d(np.asarray(laplace_covariance, dtype=np.float64))
+        if lap.shape != (n_p, n_p):
+            raise ValueError("bootstrap_summary: laplace_covariance must have shape (P, P)")
+        out["std_ratio"] = std / np.sqrt(np.diag(lap))
+    return out
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -636,6 +672,10 @@ class Runner(object):
         their own units), one launch of the device's value-and-gradient kernel.  The chain rule of the batch plan is
         applied on the host: a kernel column fed by free parameter j contributes its unit factor times the column's
         partial derivative, columns fed by fixed parameters are dropped.  Rows outside the prior get (-inf, zero row)."""
+        return self._lnlike_grad_rows(values, lambda cat, table: cat.loglike_grad(table))
+
+    def _lnlike_grad_rows(self, values, evaluate):
+        """``lnlike_grad_batch`` around ``evaluate(catalogue, kernel table) -> (values, kernel-column gradients)``."""
         values = np.atleast_2d(np.asarray(values, dtype=np.float64))
         plan = self._grad_plan()
         if values.shape[1] != plan.free_idx.size:
@@ -655,7 +695,7 @@ class Runner(object):
             cat = self._ensure_catalog()
         if cat.n_sets != 1:
             raise NotImplementedError("gradients are defined for un-binned analyses")
-        ll, g_cols = cat.loglike_grad(plan.table(full))
+        ll, g_cols = evaluate(cat, plan.table(full))
         if plan.kernel_fac is not None:
             g_cols = g_cols * plan.kernel_fac
         free_pos = {int(i): j for j, i in enumerate(plan.free_idx)}
@@ -675,6 +715,10 @@ class Runner(object):
         plan = self._grad_plan()
         if plan.prior is None:
             return self.lnlike_grad_batch(values)
+        return self._lnprob_grad_rows(values, plan, self.lnlike_grad_batch)
+
+    def _lnprob_grad_rows(self, values, plan, lnlike_grad):
+        """The structured priors of ``plan`` around ``lnlike_grad(rows) -> (values, gradients)``."""
         if values.shape[1] != plan.free_idx.size:
             raise ValueError("expected {0} free parameters per row, got {1}".format(plan.free_idx.size, values.shape[1]))
         lp, g_lp = _native.prior_eval(plan.prior, values, want_grad=True)
@@ -685,7 +729,7 @@ class Runner(object):
         if not inside.all():                       # such a row takes a valid row's place in the launch and is masked
             rows = values.copy()
             rows[~inside] = values[int(np.flatnonzero(inside)[0])]
-        out, grad = self.lnlike_grad_batch(rows)
+        out, grad = lnlike_grad(rows)
         ok = inside & np.isfinite(out)
         out = np.where(ok, out + np.where(inside, lp, 0.0), -np.inf)
         grad = np.where(ok[:, None], grad + np.where(inside[:, None], g_lp, 0.0), 0.0)
@@ -754,6 +798,71 @@ class Runner(object):
         chol = np.linalg.cholesky(np.asarray(covariance, dtype=np.float64))
         draws = x + np.random.standard_normal((int(n_walkers), x.size)) @ chol.T      # (NumPy's global generator, as get_initials)
         return np.clip(draws, plan.lo[plan.free_idx], plan.hi[plan.free_idx])
+
+    # ------------------------------------------------------------------ weighted-likelihood bootstrap (new)
+    def lnprob_weighted_grad_batch(self, values, row_replicate, scheme="exponential", seed=0, weights=None):
+        """``lnprob_grad_batch`` with the stars of row r weighted by its replicate ``row_replicate[r]``: (W, P) free-parameter
+        vectors -> ((W,) values, (W, P) gradients) of  sum_i w(b, i) lnL_i + ln prior,  one launch of the device's weighted
+        value-and-gradient kernel (``_native.Catalog.weighted_loglike_grad``: the weights of "exponential" and "poisson"
+        are generated on the device from (seed, replicate, star); "explicit" reads ``weights`` (n_replicates, N)).  The
+        chain rule, the prior handling and the donor rows are ``lnprob_grad_batch``'s; structured priors enter UNWEIGHTED
+        (the weighted-likelihood bootstrap of Newton & Raftery 1994).  The refusals of gradients apply, and the call runs on
+        one device in one process."""
+        self._holdout_check("lnprob_weighted_grad_batch")
+        values = np.atleast_2d(np.asarray(values, dtype=np.float64))
+        rep = np.ascontiguousarray(row_replicate, dtype=np.int64).reshape(-1)
+        if rep.size != values.shape[0]:
+            raise ValueError("row_replicate must hold one replicate per row of values")
+        plan = self._grad_plan()
+
+        def lnlike_grad(rows):
+            return self._lnlike_grad_rows(rows, lambda cat, table: cat.weighted_loglike_grad(
+                table, rep, scheme=scheme, seed=seed, weights=weights))
+        if plan.prior is None:
+            return lnlike_grad(values)
+        return self._lnprob_grad_rows(values, plan, lnlike_grad)
+
+    def bootstrap(self, n_replicates=256, scheme="exponential", seed=None, x_hat=None, max_iter=200, gtol=1e-8):
+        """Weighted-likelihood bootstrap of the maximum (Rubin 1981; Newton & Raftery 1994; Lyddon, Holmes & Walker 2019):
+        ``n_replicates`` refits of the catalogue under random star weights -- ``scheme`` "exponential": Exp(1) weights, the
+        smooth Bayesian bootstrap; "poisson": Poisson(1) counts, the nonparametric bootstrap -- as ONE lock-stepped
+        ``optimize.maximize_batch`` run: replicate b = row b starts at ``x_hat`` (default: ``maximize()["x"]``) and climbs
+        ``lnprob_weighted_grad_batch`` with replicate id b.  The weights are a function of (seed, b, star) alone
+        (``_native.bootstrap_weights`` replays them); the same seed gives the same result bit for bit.
+
+        Returns ``bootstrap_summary`` of the replicates (with ``std_ratio`` against ``laplace(x_hat)`` where that exists)
+        plus ``x`` (B, P), ``converged`` (B,), ``n_iter`` (B,), ``x_hat``, ``seed`` and ``scheme``.  The spread of the
+        replicates is the sampling (sandwich) covariance of the estimate whether or not the model describes the data;
+        ``covariance`` is accepted wherever ``laplace()["covariance"]`` is: ``get_initials_laplace`` and
+        ``hmc(covariance=...)``."""
+        from ..optimize import maximize_batch
+        self._holdout_check("bootstrap")
+        plan = self._grad_plan()
+        n_b = int(n_replicates)
+        if n_b < 1:
+            raise ValueError("bootstrap: n_replicates must be >= 1")
+        if scheme not in ("exponential", "poisson"):
+            raise ValueError("bootstrap: scheme must be 'exponential' or 'poisson'")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        x_hat = self.maximize(max_iter=max_iter, gtol=gtol)["x"] if x_hat is None else \
+            np.asarray(x_hat, dtype=np.float64).reshape(-1)
+        if x_hat.size != plan.free_idx.size:
+            raise ValueError("bootstrap: x_hat must hold the {0} free parameters".format(plan.free_idx.size))
+        rep = np.arange(n_b, dtype=np.int64)
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+
+        def value_and_grad(x):
+            return self.lnprob_weighted_grad_batch(x, rep, scheme=scheme, seed=seed)
+        res = maximize_batch(value_and_grad, np.tile(x_hat, (n_b, 1)), lo, hi, max_iter=max_iter, gtol=gtol)
+        try:
+            laplace = self.laplace(x_hat)["covariance"]
+        except ValueError:
+            laplace = None
+        out = bootstrap_summary(res["x"], x_hat, res["converged"], [plan.names[int(i)] for i in plan.free_idx], laplace)
+        out.update({"x": res["x"], "converged": res["converged"], "n_iter": res["n_iter"], "x_hat": x_hat, "seed": int(seed),
+                    "scheme": scheme})
+        return out
 
     # ------------------------------------------------------------------ Hamiltonian Monte Carlo (new)
     HMC_TARGET_ACCEPT = 0.8

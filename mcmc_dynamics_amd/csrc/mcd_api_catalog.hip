@@ -480,6 +480,7 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
         for (auto& pr : sh.ring) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
     }
     release_holdout(cat);
+    release_weighted(cat);
     for (hipEvent_t e : cat->chain_events) (void)hipEventDestroy(e);
     if (cat->chain.d) (void)hipFree(cat->chain.d);
     if (cat->chain.h) (void)hipHostFree(cat->chain.h);
@@ -552,6 +553,7 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
                 sh.work.clear();
             }
             release_holdout(cat);
+            release_weighted(cat);
             cat->cur_walkers = 0;
         }
         return MCD_OK;

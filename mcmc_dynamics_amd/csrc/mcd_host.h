@@ -13,6 +13,7 @@
 //   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
 //   mcd_api_mmatch.hip     mcd_moment_match: the decision loop of moment matching around the hold-out evaluation
 //   mcd_api_replicate.hip  mcd_replicate_check, mcd_replicate_numbers: replicated-data predictive checks per range of stars
+//   mcd_api_weighted.hip   mcd_weighted_loglike_grad, mcd_bootstrap_weights: value and gradient under per-row star weights
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -205,6 +206,24 @@ struct HoldoutWork {
     hipEvent_t e0 = nullptr, e1 = nullptr;   // option "timing": around the main kernel
 };
 
+// mcd_weighted_loglike_grad: the chunk table over `records` for one row count and its buffers (mcd_api_weighted.hip), kept
+// by the catalogue
+struct WeightedWork {
+    int64_t n_rows = 0;
+    int64_t n_chunks = 0;
+    mcd::Chunk* d_chunks = nullptr;
+    int64_t* d_offsets = nullptr;      // [2] chunk offsets of the one range
+    double* d_params = nullptr;        // [R][K]
+    void* d_wpar = nullptr;            // [R][KD]
+    int64_t* d_replicate = nullptr;    // [R]
+    double* d_partials = nullptr;      // [1 + K][roundup64(R) / 8][n_chunks][8]
+    double* d_out = nullptr;           // [1 + K][roundup64(R)]
+    double* h_params = nullptr;        // pinned
+    int64_t* h_replicate = nullptr;    // pinned
+    double* h_out = nullptr;           // pinned
+    hipEvent_t e0 = nullptr, e1 = nullptr;   // option "timing": around the main kernel
+};
+
 // Device scratch of one call: hipMalloc'ed blocks and an optional pair of timing events, released on every exit path.
 struct DeviceScratch {
     std::vector<void*> blocks;
@@ -260,6 +279,8 @@ int sync_all(mcd_catalog* cat);
 void release_holdout(mcd_catalog* cat);
 int holdout_device_plan(mcd_catalog* cat, const std::vector<int64_t>& ranges, int64_t n_rows, HoldoutWork** out);
 int holdout_device_eval(mcd_catalog* cat, HoldoutWork& w, int64_t n_walkers, const int64_t* d_set_range);
+// mcd_api_weighted.hip
+void release_weighted(mcd_catalog* cat);
 
 MCD_HOST_END
 
@@ -352,6 +373,14 @@ struct mcd_catalog {
     int64_t temper_device_blocks = 0, temper_host_blocks = 0;
     // exact leave-out refits (mcd_holdout_loglike): plans and buffers per (set_offsets, E W), released with the catalogue
     std::map<std::pair<std::vector<int64_t>, int64_t>, mcd::host::HoldoutWork> holdout;
+    // weighted evaluations (mcd_weighted_loglike_grad): plan and buffers per row count, and the transposed explicit weights
+    // of the last call ([n_stars][n_replicates], grown as needed) with the fingerprint of their contents (-1 replicates:
+    // none), released with the catalogue
+    std::map<int64_t, mcd::host::WeightedWork> weighted;
+    double* d_weights = nullptr;
+    size_t d_weights_bytes = 0;
+    int64_t weights_replicates = -1;
+    uint64_t weights_print[2] = {0, 0};
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
