@@ -118,6 +118,39 @@ def loglike(cat, params, model, centre, fast, chunk_len=248):
     return out
 
 
+SRC_F32 = os.path.join(ROOT, "tests", "emul", "f32_emul.cpp")
+OUT_F32 = os.path.join(ROOT, "tests", "emul", "libf32_emul.so")
+_lib_f32 = None
+
+
+def lib_f32():
+    """Host build of the float32 instantiations of chunk_loglike (tests/emul/f32_emul.cpp), a library of its own."""
+    global _lib_f32
+    if _lib_f32 is None:
+        deps = [SRC_F32] + [os.path.join(INC, h) for h in ("mcd_math.h", "mcd_exp_table.h", "mcd_chunks.h", "mcd_dispatch.h")]
+        if not os.path.exists(OUT_F32) or any(os.path.getmtime(d) > os.path.getmtime(OUT_F32) for d in deps):
+            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", INC, SRC_F32,
+                            "-o", OUT_F32], check=True)
+        _lib_f32 = ctypes.CDLL(OUT_F32)
+        _lib_f32.emul_loglike_f32.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_void_p]
+    return _lib_f32
+
+
+def loglike_f32(cat, params, model, centre, fast, acc64, chunk_len=96):
+    """The float32 kernels' arithmetic on the host: records and walker constants rounded to float, chunk by chunk;
+    ``fast`` 0 the plain float32 kernels, 1 the float32 fast formulations; ``acc64`` the accumulator of "f32acc64"
+    (double) or of "f32" (float)."""
+    rec = pack_records(cat, model, centre)
+    wp = pack_walkers(params, model, centre is None)
+    out = np.empty(wp.shape[0])
+    rc = lib_f32().emul_loglike_f32(model, int(centre is None), int(fast), int(acc64), rec.shape[0], rec.ctypes.data,
+                                    wp.ctypes.data, wp.shape[0], int(chunk_len), out.ctypes.data)
+    assert rc == 0
+    return out
+
+
 def per_star(cat, params_row, model, centre, mode):
     rec = pack_records(cat, model, centre)
     wp = pack_walkers(np.asarray(params_row)[None, :], model, centre is None)
