@@ -786,6 +786,16 @@ int mcd_last_fast_level(const mcd_catalog* cat);
  * MCD_ERR_INVALID with the reason (option "f32_domain" = 0: evaluate regardless).  mcd_last_f32_domain reports the verdict
  * on the last staged table (1 inside, 0 outside; always 1 for MCD_F64 catalogues) and the two condition numbers. */
 int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_theta);
+/* The same verdict accumulated over EVERY table the catalogue has staged since mcd_catalog_create -- a block of
+ * mcd_stretch_move / mcd_stretch_move_seeded stages two tables per step and mcd_last_f32_domain reports only the last:
+ *   calls               tables staged outside the domain (evaluated with option "f32_domain" = 0, refused with 1);
+ *   worst_kappa_v,
+ *   worst_kappa_theta   the largest condition numbers of any staged table, inside the domain or not;
+ *   reason              the reason of the most recent table outside ("" when calls == 0): a static string, never freed.
+ * Host-side counters; any of the four pointers may be null.  All zero for an MCD_F64 catalogue.  MCD_ERR_INVALID for a
+ * null catalogue.  (An added entry point: MCD_ABI_VERSION stays at 1.) */
+int mcd_f32_outside(const mcd_catalog* cat, int64_t* calls, double* worst_kappa_v, double* worst_kappa_theta,
+                    const char** reason);
 /* Launch geometry of the main kernel for the last call: workgroups, walker tile (walkers that
  * reuse one star record load), chunks per parameter set, bytes per star record. */
 int mcd_last_launch_info(const mcd_catalog* cat, int64_t* n_workgroups, int32_t* walker_tile,

@@ -132,6 +132,7 @@ SYMBOLS = {
     "mcd_last_quad_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
+    "mcd_f32_outside": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_char_p)]),
     "mcd_set_option": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int64]),
     "mcd_last_launch_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, ctypes.POINTER(ctypes.c_int32), _c_int64_p,
                                             ctypes.POINTER(ctypes.c_int32)]),
@@ -1141,6 +1142,17 @@ class Catalog(object):
         kv, kt = ctypes.c_double(), ctypes.c_double()
         self.lib.mcd_last_f32_domain(self.handle, ctypes.byref(kv), ctypes.byref(kt))
         return kv.value, kt.value
+
+    def f32_outside(self):
+        """The float32 domain verdict over every table staged since the catalogue was created (``mcd_f32_outside``; a
+        library block stages two per step): {'calls': tables outside the domain, 'worst_kappa_v', 'worst_kappa_theta': the
+        largest condition numbers of any staged table, 'reason': of the last table outside, '' without one}."""
+        self._alive()
+        calls, kv, kt, why = ctypes.c_int64(), ctypes.c_double(), ctypes.c_double(), ctypes.c_char_p()
+        _check(self.lib, self.lib.mcd_f32_outside(self.handle, ctypes.byref(calls), ctypes.byref(kv), ctypes.byref(kt),
+                                                  ctypes.byref(why)), "mcd_f32_outside")
+        return {"calls": calls.value, "worst_kappa_v": kv.value, "worst_kappa_theta": kt.value,
+                "reason": (why.value or b"").decode()}
 
     def launch_info(self):
         wg, ch = ctypes.c_int64(), ctypes.c_int64()

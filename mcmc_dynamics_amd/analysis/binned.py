@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from ..sampler import _reserve, _run_blocks, _setup
+from ..sampler import _clear, _host_seed, _reserve, _run_blocks, _setup
 from .constant import ConstantFit
 
 logger = logging.getLogger(__name__)
@@ -45,7 +45,7 @@ class BinnedSampler(object):
         self.log_prob_fn = log_prob_fn
         self.block_steps = 64                     # steps whose random numbers are drawn together (defines the stream)
         self.device_block_steps = 256             # rng="device": steps per library call (NOT part of the stream's definition)
-        self._random = np.random.RandomState(seed)
+        self._random = np.random.RandomState(_host_seed(self, seed))
         # the steps of a block are drawn by N_STREAMS generators seeded from the master (see _draw)
         self._streams = [np.random.RandomState(int(s)) for s in self._random.randint(0, 2 ** 31 - 1, size=self.N_STREAMS)]
         self._pool = None
@@ -61,6 +61,11 @@ class BinnedSampler(object):
             self.close()
         except Exception:
             pass
+
+    def reset(self):
+        """Drop the chain, the log-probabilities, the acceptance counts and ``n_calls``, as ``sampler.EnsembleSampler.reset``:
+        the random stream carries on where it stands (``rng_step`` and the NumPy generators are left alone)."""
+        _clear(self)
 
     @property
     def chain(self):
@@ -178,8 +183,11 @@ class BinnedConstantFit(ConstantFit):
     def _launch(self, w, flat):
         cat = self._ensure_catalog()
         table = self._kernel_table(flat)
-        return cat.loglike(table.reshape(self.n_bins, w, -1)) if self.n_bins > 1 else \
+        ll = cat.loglike(table.reshape(self.n_bins, w, -1)) if self.n_bins > 1 else \
             cat.loglike(table.reshape(w, -1))[None, :]
+        if self._precision != "f64":
+            self._note_f32(cat)
+        return ll
 
     def lnlike_batch(self, values):
         w, flat = self._resolve(values)
@@ -202,6 +210,8 @@ class BinnedConstantFit(ConstantFit):
                 table = plan.table(full)
                 ll = (cat.loglike(table.reshape(self.n_bins, w, -1)) if self.n_bins > 1 else
                       cat.loglike(table.reshape(w, -1))[None, :]).reshape(-1)
+                if self._precision != "f64":
+                    self._note_f32(cat)
                 out[ok] = ll[ok] if lp is None else ll[ok] + lp[ok]
             return out.reshape(self.n_bins, w)
         w, flat = self._resolve(values)
@@ -237,7 +247,9 @@ class BinnedConstantFit(ConstantFit):
         group = self._rank_group()
         if group is not None:
             pos = group.bcast_array(pos, src=0)
-            seed = int(group.bcast_json(int(seed) if seed is not None else int(np.random.SeedSequence().entropy % (2 ** 63)), src=0))
+            # (a seed the sampler takes in the mode it runs in: 64 bits for the device generator, 32 for NumPy's)
+            bits = 64 if (rng or self.RNG) == "device" else 32
+            seed = int(group.bcast_json(int(seed) if seed is not None else int(np.random.SeedSequence().entropy % (2 ** bits)), src=0))
         lp = self.parameters.lnprior_batch(self.parameters.resolve_batch(pos.reshape(-1, pos.shape[-1])))
         if not np.all(np.isfinite(lp)):
             raise ValueError("Invalid initial guesses for {0} walker(s).".format(int(np.sum(~np.isfinite(lp)))))

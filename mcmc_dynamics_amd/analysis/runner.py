@@ -455,7 +455,12 @@ class Runner(object):
         context : _native.Context, optional
             GPU context (devices / rank).  Default: one process-wide context on device 0.
         precision : {'f64', 'f32', 'f32acc64'}
-            Arithmetic of the kernels; 'f64' is the parity mode.
+            Arithmetic of the kernels; 'f64' is the parity mode.  The float32 kernels keep their stated tolerances
+            only inside the float32 accuracy domain (include/mcd.h); a walker can leave it in the middle of a chain, so
+            the catalogues this class creates for 'f32' / 'f32acc64' evaluate such tables regardless (option
+            ``f32_domain`` = 0; ``_native.Catalog``'s own default refuses them) and count them.  The first time a
+            catalogue's count is non-zero one ``UserWarning`` gives the library's reason and the condition numbers;
+            ``f32_outside()`` returns the counters.
         """
         assert not kwargs, "Unknown keyword arguments provided: {0}".format(kwargs)      # runner.py:56
 
@@ -612,6 +617,8 @@ class Runner(object):
             if cat is None or plan.catalog_key != self._catalog_key:
                 cat = self._ensure_catalog()
             ll = cat.loglike(plan.table_direct(values))
+            if self._precision != "f64":
+                self._note_f32(cat)
             if lp is not None:
                 ll = ll + lp
             if n_ok == ok.size:
@@ -633,6 +640,8 @@ class Runner(object):
             if cat is None or plan.catalog_key != self._catalog_key:
                 cat = self._ensure_catalog()
             ll = cat.loglike(plan.table(full))
+            if self._precision != "f64":
+                self._note_f32(cat)
             if lp is not None:
                 ll = ll + lp
             if n_ok == ok.size:
@@ -951,7 +960,9 @@ class Runner(object):
             sampler.step_size *= float(np.exp(rate - self.HMC_TARGET_ACCEPT))
             sampler.warmup_step_sizes.append(sampler.step_size)
             done += n
-        sampler.reset()                                               # (the generator's step counter is not rewound)
+        # (reset() leaves the generator's step counter ``rng_step`` alone -- as every sampler of mcmc_dynamics_amd.sampler and
+        # analysis.binned does: the run below never replays the warm-up's numbers)
+        sampler.reset()
         sampler.reserve(n_steps)
         sampler.run_mcmc(pos, n_steps)
         return sampler
@@ -1169,13 +1180,17 @@ class Runner(object):
 
     def _stretch_block_seeded(self, pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted):
         """One block of steps with the random numbers generated inside the library (``_native.Catalog.stretch_move_seeded``)."""
-        self._stretch_catalog(pos).stretch_move_seeded(self._stretch_plan(), pos, lnp, seed, step0, n_steps, chain,
-                                                       lnprob_chain, accepted)
+        cat = self._stretch_catalog(pos)
+        cat.stretch_move_seeded(self._stretch_plan(), pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted)
+        if self._precision != "f64":
+            self._note_f32(cat)
 
     def _stretch_block(self, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted):
         """One block of stretch-move steps inside the library (``_native.Catalog.stretch_move``)."""
-        self._stretch_catalog(pos).stretch_move(self._stretch_plan(), pos, lnp, order, zz, thr, pick, chain, lnprob_chain,
-                                                accepted)
+        cat = self._stretch_catalog(pos)
+        cat.stretch_move(self._stretch_plan(), pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted)
+        if self._precision != "f64":
+            self._note_f32(cat)
 
     def __call__(self, n_walkers=100, n_steps=500, n_burn=100, n_threads=1, n_out=None, pos=None, lnprob0=None,
                  plot=False, prefix="sampler", true_values=None, **kwargs):
@@ -1973,7 +1988,33 @@ class Runner(object):
             self._catalog = _native.Catalog(self.context, self.ra, self.dec, self.v, self.verr,
                                             precision=self._precision, **self._catalog_kwargs(), **spec)
             self._catalog_key = key
+            if self._precision != "f64":
+                # a chain must not end because one proposal leaves the float32 accuracy domain: evaluate regardless, and
+                # tell (``_note_f32``)
+                self._catalog.set_option("f32_domain", 0)
         return self._catalog
+
+    def _note_f32(self, cat):
+        """float32 catalogues: one ``UserWarning`` per catalogue, the first time it has staged a table outside the float32
+        accuracy domain (in a direct evaluation or anywhere inside a library block)."""
+        if getattr(self, "_f32_warned", None) is cat:
+            return
+        out = cat.f32_outside()
+        if out["calls"]:
+            self._f32_warned = cat
+            warnings.warn("{0} (precision={1!r}): {2} evaluation(s) outside the float32 accuracy domain, where the stated "
+                          "float32 tolerances do not hold: {3} (largest kappa_v = {4:.4g}, kappa_theta = {5:.4g} so far; "
+                          "f32_outside() has the counters, precision='f64' evaluates exactly)".format(
+                              type(self).__name__, self._precision, out["calls"], out["reason"], out["worst_kappa_v"],
+                              out["worst_kappa_theta"]), UserWarning, stacklevel=3)
+
+    def f32_outside(self):
+        """Evaluations of this fit's current catalogue outside the float32 accuracy domain since it was created:
+        ``{'calls', 'worst_kappa_v', 'worst_kappa_theta', 'reason'}`` (``_native.Catalog.f32_outside``).  Zeros for
+        precision 'f64' and before the first evaluation."""
+        if self._precision == "f64" or self._catalog is None:
+            return {"calls": 0, "worst_kappa_v": 0.0, "worst_kappa_theta": 0.0, "reason": ""}
+        return self._catalog.f32_outside()
 
     def _kernel_table(self, resolved):
         """(W, K) float64 table in the column order and canonical units the C-ABI expects."""
@@ -1985,7 +2026,10 @@ class Runner(object):
 
     def _lnlike_batch(self, resolved):
         cat = self._ensure_catalog()
-        return cat.loglike(self._kernel_table(resolved))
+        ll = cat.loglike(self._kernel_table(resolved))
+        if self._precision != "f64":
+            self._note_f32(cat)
+        return ll
 
     def _per_star(self, values, what):
         """Per-star device outputs for ONE parameter vector: 'membership' or 'lnlike'."""

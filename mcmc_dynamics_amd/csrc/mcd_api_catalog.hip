@@ -612,6 +612,16 @@ int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_t
     return cat->last_f32.inside ? 1 : 0;
 }
 
+int mcd_f32_outside(const mcd_catalog* cat, int64_t* calls, double* worst_kappa_v, double* worst_kappa_theta,
+                    const char** reason) {
+    if (!cat) return fail(MCD_ERR_INVALID, "null catalogue");
+    if (calls) *calls = cat->f32_outside_calls;
+    if (worst_kappa_v) *worst_kappa_v = cat->f32_worst_kappa_v;
+    if (worst_kappa_theta) *worst_kappa_theta = cat->f32_worst_kappa_theta;
+    if (reason) *reason = cat->f32_outside_reason;
+    return MCD_OK;
+}
+
 int mcd_last_fast_level(const mcd_catalog* cat) {
     if (!cat || cat->cur_walkers <= 0 || cat->shards.empty()) return -1;
     const auto it = cat->shards.front().work.find(cat->cur_walkers);

@@ -75,6 +75,12 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
     if (cat->precision != MCD_F64) {
         // float32 catalogues: is this table inside the domain in which float32 keeps the stated tolerances?
         cat->last_f32 = mcd::f32_domain(cat->stats, cat->model, cat->free_centre, cat->k, params, n_rows);
+        if (cat->last_f32.kappa_v > cat->f32_worst_kappa_v) cat->f32_worst_kappa_v = cat->last_f32.kappa_v;
+        if (cat->last_f32.kappa_theta > cat->f32_worst_kappa_theta) cat->f32_worst_kappa_theta = cat->last_f32.kappa_theta;
+        if (!cat->last_f32.inside) {
+            ++cat->f32_outside_calls;
+            cat->f32_outside_reason = cat->last_f32.reason;
+        }
         if (!cat->last_f32.inside && cat->f32_domain)
             return fail(MCD_ERR_INVALID, std::string("outside the float32 accuracy domain (use an MCD_F64 catalogue, or option "
                                                      "f32_domain = 0 to evaluate regardless): ") + cat->last_f32.reason);

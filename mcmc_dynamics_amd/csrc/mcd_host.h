@@ -341,6 +341,10 @@ struct mcd_catalog {
     int f32_domain = 1;                // option "f32_domain": 1 calls outside the float32 accuracy domain (mcd_guard.h) are refused
                                        // with MCD_ERR_INVALID, 0 they are evaluated anyway (mcd_last_f32_domain tells)
     mcd::F32Domain last_f32;           // verdict on the last staged parameter table (float32 catalogues)
+    // ... and over every table staged since creation (mcd_f32_outside): a library block stages many per call
+    int64_t f32_outside_calls = 0;     // tables staged outside the domain (evaluated or refused)
+    double f32_worst_kappa_v = 0.0, f32_worst_kappa_theta = 0.0;      // largest condition numbers of any staged table
+    const char* f32_outside_reason = "";                              // reason of the last table outside
     int64_t posterior_pass = 65536;    // option "posterior_pass": samples per device pass of mcd_pointwise_posterior
     int64_t replicate_row0 = 0;        // option "replicate_row0": generator row index of the first sample row of mcd_replicate_check
     int64_t loo_scratch_mb = 2048;    // option "loo_scratch_mb": device scratch of mcd_psis_loo (sample table + term tile)

@@ -49,7 +49,12 @@ def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn):
     generator of csrc/mcd_rng.h (Philox4x64-10) instead of NumPy's Mersenne twister -- a function of (seed, step, half
     step, ensemble, walker) alone, generated on the device (csrc/mcd_stretch.hip: chain_numbers_kernel) by
     ``seeded_block_fn`` (``Runner._stretch_block_seeded``), or taken from ``_native.chain_numbers`` by the NumPy loop when
-    there is none: the same chain either way, and however it is cut into blocks."""
+    there is none: the same chain either way, and however it is cut into blocks.
+
+    ``rng_step`` is that generator's step counter: it advances with ``iteration`` and ``reset()`` leaves it alone, so the
+    steps after a ``reset()`` take the numbers that follow the ones already used (as ``HMCSampler`` and
+    ``TemperedSampler``).  ``seed`` may be any Python integer there: it wraps to 64 bits (-1 is 2^64 - 1), as
+    ``_native.Catalog.stretch_move_seeded`` takes it."""
     if rng not in ("host", "device"):
         raise ValueError("rng must be 'host' or 'device'")
     if rng == "device" and float(a) != 2.0:
@@ -67,11 +72,22 @@ def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn):
         raise ValueError("The number of walkers must be even.")
     s._lead, s.nwalkers, s.ndim, s.a = tuple(lead), int(nwalkers), int(ndim), float(a)
     s.rng, s.block_fn, s.seeded_block_fn = rng, block_fn, seeded_block_fn
+    s.rng_step = 0                                           # the device generator's step counter: never rewound
     _clear(s)
 
 
+def _host_seed(s, seed):
+    """What seeds the sampler's NumPy generator.  ``rng="host"``: the caller's seed as it is (one NumPy refuses raises
+    NumPy's ValueError, as with emcee).  ``rng="device"``: that generator draws nothing for the move; it gets the 64-bit
+    seed folded to the 32 bits NumPy takes (a seed below 2^32 is its own fold)."""
+    if seed is None or s.rng != "device":
+        return seed
+    return (s.seed64 ^ (s.seed64 >> 32)) & 0xFFFFFFFF
+
+
 def _clear(s):
-    """No steps, no storage, no accepted moves, no posterior calls."""
+    """No steps, no storage, no accepted moves, no posterior calls.  The random stream is not rewound: neither the NumPy
+    generators (``rng="host"``) nor ``rng_step`` (``rng="device"``)."""
     s.iteration = 0
     s._chain = np.empty((0,) + s._lead + (s.nwalkers, s.ndim))
     s._lnprob = np.empty((0,) + s._lead + (s.nwalkers,))
@@ -109,7 +125,7 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
         from . import _native
 
         def draw(n):                                          # noqa: F811 -- the same numbers the device generates
-            return _native.chain_numbers(s.seed64, s.iteration, n, lnp.size // s.nwalkers, s.nwalkers, s.ndim,
+            return _native.chain_numbers(s.seed64, s.rng_step, n, lnp.size // s.nwalkers, s.nwalkers, s.ndim,
                                          squeeze=not s._lead)
     library = s.seeded_block_fn if device else s.block_fn
     lookahead = None
@@ -123,7 +139,7 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
             it = s.iteration
             rows = (s._chain[it:it + n], s._lnprob[it:it + n]) if store else (None, None)
             if device and library is not None:
-                numbers = (s.seed64, it, n)
+                numbers = (s.seed64, s.rng_step, n)
             else:
                 numbers = pending.result() if pending is not None else draw(n)
                 pending = None
@@ -136,6 +152,7 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
                 library(pos, lnp, *numbers, *rows, accepted)
                 s._accepted += accepted
                 s.iteration += n
+                s.rng_step += n
                 s.n_calls += 2 * n
             done += n
     finally:
@@ -173,6 +190,7 @@ def _half_steps(s, pos, lnp, numbers, evaluate, store):
             s._chain[s.iteration] = pos
             s._lnprob[s.iteration] = lnp
         s.iteration += 1
+        s.rng_step += 1
 
 
 class EnsembleSampler(object):
@@ -194,9 +212,12 @@ class EnsembleSampler(object):
         # is kept short -- the device starts after 0.8 ms of draws instead of 3 ms (1e5 stars x 256 walkers: 3 of 39 us per
         # step over a 1024-step run).  Also part of the definition of the random stream.
         self.first_block_steps = 64
-        self._random = np.random.RandomState(seed)
+        self._random = np.random.RandomState(_host_seed(self, seed))
 
     def reset(self):
+        """Drop the chain, the log-probabilities, the acceptance counts and ``n_calls``; ``iteration`` is 0 again.  The
+        random stream carries on where it stands, in both modes (``_clear``): a production run after a burn-in never
+        replays the numbers that produced its own starting point."""
         _clear(self)
 
     # ------------------------------------------------------------------ emcee-compatible views

@@ -31,7 +31,9 @@ int main(int argc, char** argv) {
         (any_fn)mcd_ctx_comm_info, (any_fn)mcd_stretch_move, (any_fn)mcd_stretch_info, (any_fn)mcd_last_prefetch,
         /* round 3 (additions: the ABI version stays) */
         (any_fn)mcd_ctx_set_option, (any_fn)mcd_ctx_abort, (any_fn)mcd_ctx_failed, (any_fn)mcd_last_f32_domain,
-        (any_fn)mcd_stretch_move_seeded, (any_fn)mcd_chain_numbers};
+        (any_fn)mcd_stretch_move_seeded, (any_fn)mcd_chain_numbers,
+        /* float32 domain counters of a catalogue (an addition: the ABI version stays) */
+        (any_fn)mcd_f32_outside};
     size_t i;
     double out[3] = {0.0, 0.0, 0.0};
     for (i = 0; i < sizeof table / sizeof table[0]; ++i) CHECK(table[i] != NULL);
@@ -44,6 +46,7 @@ int main(int argc, char** argv) {
     CHECK(mcd_kde_background(NULL, 1, out, 1, out, out, 0.0, out, NULL) != MCD_OK);
     CHECK(mcd_last_fast_level(NULL) == -1);
     CHECK(mcd_last_prefetch(NULL) == -1);
+    CHECK(mcd_f32_outside(NULL, NULL, NULL, NULL, NULL) != MCD_OK);
     CHECK(mcd_ctx_comm_info(NULL, NULL, NULL, NULL) != MCD_OK);
     CHECK(mcd_stretch_move(NULL, NULL, 1, out, out, NULL, out, out, NULL, NULL, NULL, NULL) != MCD_OK);
     CHECK(mcd_stretch_info(NULL, NULL, NULL, NULL, NULL) != MCD_OK);
@@ -81,6 +84,14 @@ int main(int argc, char** argv) {
             }
         for (w = 0; w < 2; ++w) CHECK(fabs(got[w] - want[w]) < 1e-13);
         CHECK(mcd_loglike_batch(cat, 2, 5, &rows[0][0], got) != MCD_OK);      /* wrong column count */
+        {
+            /* a float64 catalogue never counts a table outside the float32 domain */
+            int64_t calls = -1;
+            double kv = -1.0, kt = -1.0;
+            const char* why = NULL;
+            CHECK(mcd_f32_outside(cat, &calls, &kv, &kt, &why) == MCD_OK);
+            CHECK(calls == 0 && kv == 0.0 && kt == 0.0 && why != NULL && strlen(why) == 0);
+        }
         {
             /* one stretch-move step of two walkers driven from C: identity column map, no bounds; with z = 1 the proposal
              * is the walker itself, so the log-probability is unchanged and (thr = -1 < 0) the "move" is accepted */

@@ -3,7 +3,8 @@ device, with tests/fake_rccl standing in for librccl.so (RCCL refuses two ranks 
 real streams; only the collective itself is host-staged.
 
     fake_rccl_worker.py single N         one process, N "devices" (all device 0): mcd_ctx_create(n_dev = N)
-    fake_rccl_worker.py rank             one process per rank (RANK / WORLD_SIZE from the launcher): mcd_ctx_create_rank
+    fake_rccl_worker.py rank             one process per rank (RANK / WORLD_SIZE from the launcher): mcd_ctx_create_rank;
+                                         then a ConstantFit chain and a 3-bin BinnedConstantFit chain on the rank context
     fake_rccl_worker.py deadline KIND    two ranks, one of which never completes a collective (KIND: hang -- the stand-in's
                                          all-reduce sits; raise -- rank 1 raises inside a block of Runner.__call__; die --
                                          rank 1's process dies): rank 0 must get the error within the collective deadline
@@ -190,6 +191,24 @@ def rank_mode():
     assert np.max(np.abs(lp - np.asarray(sampler.lnprobability)[:, -1]) / np.abs(lp)) < 1e-13
     fit.close()
     full.close()
+    # BinnedConstantFit.__call__ on the rank context, every bin's stars dealt out over the ranks, no seed given: rank 0's
+    # start and ONE seed that the sampler takes (64 bits for the device generator) reach every rank -- identical chains, and
+    # log-probabilities a single context gives for the whole bins
+    import stream_helper
+    binned = stream_helper.make_fit(binned=True, context=ctx, rows=slice(rank, None, world))
+    assert binned.n_bins == 3
+    bpos = np.stack([stream_helper.walkers(seed=40 + b) for b in range(3)])
+    bs = binned(n_walkers=stream_helper.W, n_steps=6, pos=bpos if rank == 0 else bpos + 1.0)
+    bchain = bs.get_chain()
+    assert bchain.shape == (6, 3, stream_helper.W, 4) and bs.rng == "device" and bs.seeded_block_fn is not None
+    assert group.same_everywhere(bchain) and group.same_everywhere(np.array([float(bs.seed64 >> 32), float(bs.seed64 & 0xFFFFFFFF)]))
+    assert np.all(np.isfinite(bs.lnprobability)) and np.unique(bchain.reshape(6, -1), axis=0).shape[0] == 6
+    whole = stream_helper.make_fit(binned=True, context=one)
+    blp = whole.lnprob_batch(bchain[-1])
+    assert np.max(np.abs(blp - bs.lnprobability[:, :, -1]) / np.abs(blp)) < 1e-13
+    bs.close()
+    binned.close()
+    whole.close()
     group.barrier()
     if rank == 0:
         print("FAKE_RCCL_RANKS_OK world={0} worst={1:.2e}".format(world, worst))

@@ -2,7 +2,8 @@
 (``python -m torch.distributed.run``), NO torch in the worker -- the host side of a multi-GPU run as bench.py and
 ``distributed.rank_context`` do it: HostGroup rendezvous, unique-id hand-off, sharded sums, max-over-ranks timing, and a
 ``Runner.__call__`` on a rank context (stub device: the oracle evaluates this rank's star shard and the host group plays
-the all-reduce) whose chains must come out identical on every rank."""
+the all-reduce) whose chains must come out identical on every rank -- and a ``BinnedConstantFit.__call__`` on the same
+context, with and without a seed, whose one broadcast seed its sampler must accept."""
 import os
 import sys
 
@@ -131,6 +132,39 @@ def main():
     # the chain is the one a single process gets from the same start and seed on the full catalogue
     ref_lp = oracle.batched_constant_lnlike(full, chain[:, -1, :], *centre)
     assert np.max(np.abs(ref_lp - np.asarray(sampler.lnprobability)[:, -1]) / np.abs(ref_lp)) < 1e-12
+    # BinnedConstantFit on the rank context: ONE seed for every rank, and one its sampler takes in the mode it runs in (a
+    # full 64-bit name for the device generator, NumPy's 32 bits for rng="host"), whether the caller gives a seed or not.
+    # The posterior is overridden outside the package: the NumPy loop drives it and no catalogue is built.
+    from mcmc_dynamics_amd.analysis import BinnedConstantFit
+    reader = DataReader({k: full[k] for k in ("ra", "dec", "v", "verr")})
+    reader.make_radial_bins(centre[0], centre[1], nstars=1000, dlogr=0.05)
+
+    class Tilted(BinnedConstantFit):
+        def lnprob_batch(self, values):
+            values = np.asarray(values, dtype=np.float64)
+            return -0.5 * np.sum((values - np.array([1.0, 10.0, -2.0, 2.0])) ** 2, axis=-1)
+
+    binned = Tilted(reader, context=StubContext(rank, world, group), seed=2000 + rank)       # different global seeds again
+    binned.parameters["ra_center"].set(value=centre[0], fixed=True)
+    binned.parameters["dec_center"].set(value=centre[1], fixed=True)
+    for n, scale in (("v_sys", 1.0), ("sigma_max", None), ("v_maxx", 2.0), ("v_maxy", 2.0)):
+        binned.parameters[n].set(initials="10.0 * rng.lognormal(sigma=0.05, size=n)" if scale is None else
+                                 "rng.normal(scale={0}, size=n)".format(scale))
+    assert binned.n_bins >= 2 and not binned.resident_ok()[0]
+    binned_chains = {}
+    for label, kwargs in (("no seed", {}), ("wide seed", {"seed": 2 ** 40}), ("no seed, host numbers", {"rng": "host"})):
+        bs = binned(n_walkers=8, n_steps=6, **kwargs)
+        bchain = np.asarray(bs.chain)
+        assert bchain.shape == (binned.n_bins, 8, 6, 4) and np.all(np.isfinite(bchain)), label
+        assert group.same_everywhere(bchain) and group.same_everywhere(np.asarray(bs.lnprobability)), label
+        assert bs.rng == ("host" if "rng" in kwargs else "device") and bs.seeded_block_fn is None and bs.block_fn is None
+        if label == "wide seed":
+            assert bs.seed64 == 2 ** 40
+        binned_chains[label] = bchain
+        bs.close()
+    assert binned._catalog is None
+    assert not np.array_equal(binned_chains["no seed"][:, :, -1], binned_chains["wide seed"][:, :, -1])
+
     # a rank that proposes something else is caught by the checksum, not summed silently
     bad = chain[:, -1, :] + (1e-9 if rank == world - 1 else 0.0)
     fit._n_rank_batches = 0
