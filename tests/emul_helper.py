@@ -127,7 +127,8 @@ def lib_f32():
     """Host build of the float32 instantiations of chunk_loglike (tests/emul/f32_emul.cpp), a library of its own."""
     global _lib_f32
     if _lib_f32 is None:
-        deps = [SRC_F32] + [os.path.join(INC, h) for h in ("mcd_math.h", "mcd_exp_table.h", "mcd_chunks.h", "mcd_dispatch.h")]
+        deps = [SRC_F32] + [os.path.join(INC, h) for h in ("mcd_math.h", "mcd_exp_table.h", "mcd_chunks.h", "mcd_dispatch.h",
+                                                               "mcd_posterior.h")]
         if not os.path.exists(OUT_F32) or any(os.path.getmtime(d) > os.path.getmtime(OUT_F32) for d in deps):
             subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I", INC, SRC_F32,
                             "-o", OUT_F32], check=True)
@@ -135,6 +136,10 @@ def lib_f32():
         _lib_f32.emul_loglike_f32.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_void_p]
+        _lib_f32.emul_per_star_f32.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        _lib_f32.emul_posterior_f32.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]
     return _lib_f32
 
 
@@ -147,6 +152,30 @@ def loglike_f32(cat, params, model, centre, fast, acc64, chunk_len=96):
     out = np.empty(wp.shape[0])
     rc = lib_f32().emul_loglike_f32(model, int(centre is None), int(fast), int(acc64), rec.shape[0], rec.ctypes.data,
                                     wp.ctypes.data, wp.shape[0], int(chunk_len), out.ctypes.data)
+    assert rc == 0
+    return out
+
+
+def per_star_f32(cat, table, model, centre):
+    """per_star_kernel<..., float> on the host for every row of ``table`` (S, K): (lnL, membership), each (S, n); records and
+    walker constants rounded to float.  The models without a background give the Gaussian term and p = 1."""
+    rec = pack_records(cat, model, centre)
+    wp = pack_walkers(table, model, centre is None)
+    out_l, out_p = np.empty((wp.shape[0], rec.shape[0])), np.empty((wp.shape[0], rec.shape[0]))
+    rc = lib_f32().emul_per_star_f32(model, int(centre is None), rec.shape[0], rec.ctypes.data, wp.ctypes.data, wp.shape[0],
+                                     out_l.ctypes.data, out_p.ctypes.data)
+    assert rc == 0
+    return out_l, out_p
+
+
+def posterior_f32(cat, table, model, centre, mem):
+    """posterior_term<..., float> folded through PostAcc with the library's slice plan: (4, n) = lppd, lnl_var, pmem_mean,
+    pmem_std (the last two meaningful with ``mem`` only)."""
+    rec = pack_records(cat, model, centre)
+    wp = pack_walkers(table, model, centre is None)
+    out = np.zeros((4, rec.shape[0]))
+    rc = lib_f32().emul_posterior_f32(model, int(centre is None), int(mem), rec.shape[0], rec.ctypes.data, wp.ctypes.data,
+                                      wp.shape[0], out.ctypes.data)
     assert rc == 0
     return out
 
