@@ -355,6 +355,17 @@ typedef struct {
 int mcd_weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
                               const mcd_weight_desc* w, double* out /* [R], may be NULL */,
                               double* grad /* [R][K], may be NULL */);
+/* The weighted log-likelihood alone: out[r] = sum_i w(row_replicate[r], i) l_i(theta[r]), for callers that read no
+ * gradient (a stretch-move chain under bootstrap weights: the bagged posterior).  mcd_weighted_loglike_grad with
+ * grad = NULL computes the same sums through the gradient kernel, 1 + K of them per row; this call runs a kernel that
+ * carries one.  The term is mcd_loglike_per_star's, the weights and their selection rule are those above (same
+ * descriptor, same generator, same explicit table: one table is kept per catalogue, whichever of the two calls uploaded
+ * it).  The two calls agree to rounding; equal bits are not promised (the gradient kernel's value comes out of its own term).
+ * Refusals as above, under this call's name, with nothing written; out = NULL is MCD_OK without work.  Synchronous and
+ * deterministic, independent of earlier calls; the work buffers of a row count stay with the catalogue, in a cache apart
+ * from the gradient call's.  Waits under the context's deadline; honours options "timing" and "chunk_len". */
+int mcd_weighted_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
+                         const mcd_weight_desc* w, double* out /* [R], may be NULL */);
 /* The generated weights of replicates rep0 .. and stars star0 .., row-major [n_reps][n_stars], for a generated scheme.
  * Host only, as mcd_replicate_numbers. */
 int mcd_bootstrap_weights(int32_t scheme, uint64_t seed, int64_t rep0, int64_t n_reps, int64_t star0, int64_t n_stars,

@@ -71,6 +71,8 @@ SYMBOLS = {
                                              _c_double_p, _c_double_p]),
     "mcd_weighted_loglike_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_void_p,
                                                  _c_double_p, _c_double_p]),
+    "mcd_weighted_loglike": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_void_p,
+                                            _c_double_p]),
     "mcd_bootstrap_weights": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, _c_double_p]),
     "mcd_moment_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
@@ -788,6 +790,15 @@ class Catalog(object):
         (n_replicates, n_stars), finite and >= 0, which ``row_replicate`` indexes.  Weights are not normalised; a star of
         weight 0 adds exactly +0.0 whatever its term.  ``want_value`` / ``want_grad`` = False pass a null pointer and return
         None in its place.  Un-binned float64 catalogues on one device; synchronous and bit-identical from run to run."""
+        p, d, keep = self._weight_desc(table, row_replicate, scheme, seed, weights)
+        out = np.empty(p.shape[0], dtype=np.float64) if want_value else None
+        grad = np.empty(p.shape, dtype=np.float64) if want_grad else None
+        rc = self.lib.mcd_weighted_loglike_grad(self.handle, p.shape[0], self.k, _ptr(p), ctypes.byref(d), _ptr(out), _ptr(grad))
+        _check(self.lib, rc, "mcd_weighted_loglike_grad")
+        return out, grad
+
+    def _weight_desc(self, table, row_replicate, scheme, seed, weights):
+        """The checked table, the mcd_weight_desc of a weighted call and the arrays it points into (to be kept alive)."""
         self._alive()
         p = _f64(table)
         if p.ndim == 1:
@@ -809,11 +820,19 @@ class Catalog(object):
                 raise ValueError("weights must have shape (n_replicates, {0})".format(self.n_stars))
             d.n_replicates = w.shape[0]
         d.weights = _ptr(w)
-        out = np.empty(p.shape[0], dtype=np.float64) if want_value else None
-        grad = np.empty(p.shape, dtype=np.float64) if want_grad else None
-        rc = self.lib.mcd_weighted_loglike_grad(self.handle, p.shape[0], self.k, _ptr(p), ctypes.byref(d), _ptr(out), _ptr(grad))
-        _check(self.lib, rc, "mcd_weighted_loglike_grad")
-        return out, grad
+        return p, d, (rep, w)
+
+    def weighted_loglike(self, table, row_replicate, scheme="exponential", seed=0, weights=None):
+        """The value alone under per-row star weights (include/mcd.h: mcd_weighted_loglike): the arguments of
+        ``weighted_loglike_grad`` -> (R,) sum_i w(b, i) l_i, from a kernel that carries one sum per row and no partial
+        derivative: what a chain under bootstrap weights (``Runner.bagged``) evaluates twice per step.  Agrees with
+        ``weighted_loglike_grad``'s value to rounding.  Un-binned float64 catalogues on one device; synchronous and
+        bit-identical from run to run."""
+        p, d, keep = self._weight_desc(table, row_replicate, scheme, seed, weights)
+        out = np.empty(p.shape[0], dtype=np.float64)
+        rc = self.lib.mcd_weighted_loglike(self.handle, p.shape[0], self.k, _ptr(p), ctypes.byref(d), _ptr(out))
+        _check(self.lib, rc, "mcd_weighted_loglike")
+        return out
 
     REPLICATE_FIELDS = ("s1", "s2", "s3", "s4", "sin", "cos", "max", "tail3")
 

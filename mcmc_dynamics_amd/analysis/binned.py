@@ -306,6 +306,13 @@ class BinnedConstantFit(ConstantFit):
     def lnprob_weighted_grad_batch(self, *args, **kwargs):
         return self.bootstrap()
 
+    def bagged(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: the bagged posterior (bagged, lnprob_weighted_batch) is defined "
+                                  "for un-binned fits only; fit the bins' stars with ConstantFit")
+
+    def lnprob_weighted_batch(self, *args, **kwargs):
+        return self.bagged()
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

@@ -432,6 +432,70 @@ def bootstrap_summary(x, x_hat, converged, names, laplace_covariance=None):
     return out
 
 
+def bagged_summary(chain, n_burn, names, thin=1):
+    """The bagged posterior of ``Runner.bagged`` from its chains ``chain`` (B, W, steps, P): bag b sampled the posterior of
+    the catalogue under the bootstrap weights of replicate b.  Over the kept draws (every ``thin``-th step after
+    ``n_burn``; T_kept per walker):
+
+    * pooled over all bags -- the bagged posterior itself: ``mean``, ``covariance`` (sample, all B W T_kept draws), ``std``,
+      ``percentiles`` ({2.5, 16, 50, 84, 97.5} -> (P,));
+    * per bag: ``bag_mean`` (B, P), ``bag_var`` (B, P), ``tau`` (B,) the largest integrated autocorrelation time in kept
+      steps and ``converged`` (B,) whether the bag keeps 50 of them (``diagnostics.summary`` on the host), and
+      ``mean_mcse`` (B, P) = sqrt(bag_var tau / (W T_kept)), the Monte-Carlo standard error of ``bag_mean``;
+    * ``within`` (P, P): the mean over the bags of the within-bag covariance; ``between`` (P, P): the sample covariance of
+      the bag means; ``mismatch_ratio`` (P,) = diag(between) / diag(within); ``n_bags``, ``n_samples`` (per bag), ``names``.
+
+    What the ratio means.  By the law of total covariance the pooled covariance is within + between (up to the (B - 1) / B
+    of the sample formulas).  A bag's posterior is, to first order, a Gaussian around the weighted maximum theta_b with the
+    covariance H^-1 of the curvature; weights of mean 1 leave the expected curvature as it is, so ``within`` estimates
+    the covariance the standard posterior reports.  The bag means scatter as the weighted maxima do: with weights of
+    variance 1 (and ``bag_fraction`` = 1) that is the sandwich H^-1 J H^-1 of the bootstrap, J the covariance of the
+    per-star score -- the sampling covariance of the posterior mean whether or not the model describes the data.  Where it
+    does, J = H: ``between`` and ``within`` agree, the ratio is about 1 and the bagged covariance is about twice the
+    standard posterior's.  A ratio well above 1 says the data scatter more than the model allows (understated errors, a
+    background that misses non-members): the symptom ``bootstrap()``'s ``std_ratio`` shows for the point estimate, here
+    carried into the intervals.  ``mean_mcse`` tells how much of ``between`` is Monte-Carlo noise of the bag means: its
+    mean square adds to diag(between).
+
+    Warns when fewer than 90 % of the bags converged."""
+    from .. import diagnostics
+    chain = np.asarray(chain, dtype=np.float64)
+    if chain.ndim != 4:
+        raise ValueError("bagged_summary: chain must have shape (B, W, steps, P)")
+    if int(thin) < 1:
+        raise ValueError("bagged_summary: thin must be >= 1")
+    if not 0 <= int(n_burn) < chain.shape[2]:
+        raise ValueError("bagged_summary: n_burn must lie in [0, steps)")
+    kept = chain[:, :, int(n_burn)::int(thin), :]
+    n_b, n_w, n_t, n_p = kept.shape
+    if len(names) != n_p:
+        raise ValueError("bagged_summary: names must hold one name per parameter")
+    draws = kept.reshape(n_b, n_w * n_t, n_p)
+    pooled = draws.reshape(-1, n_p)
+    cov = np.atleast_2d(np.cov(pooled, rowvar=False, ddof=1))
+    bag_mean = draws.mean(axis=1)
+    bag_cov = np.stack([np.atleast_2d(np.cov(d, rowvar=False, ddof=1)) for d in draws])
+    bag_var = np.stack([np.diag(c) for c in bag_cov])
+    within = bag_cov.mean(axis=0)
+    between = np.atleast_2d(np.cov(bag_mean, rowvar=False, ddof=1)) if n_b > 1 else np.full((n_p, n_p), np.nan)
+    diag = diagnostics.summary(np.ascontiguousarray(np.transpose(kept, (2, 0, 1, 3))), context=None)
+    with np.errstate(invalid="ignore"):
+        tau = np.max(np.atleast_2d(diag["tau"]), axis=1)
+    converged = np.all(np.atleast_2d(diag["converged"]), axis=1)
+    n_ok = int(np.count_nonzero(converged))
+    if n_ok < 0.9 * n_b:
+        warnings.warn("bagged_summary: only {0} of {1} bags keep 50 autocorrelation times of steps; the bag means carry more "
+                      "Monte-Carlo error than the sample count suggests (see mean_mcse; run longer)".format(n_ok, n_b))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ratio = np.diag(between) / np.diag(within)
+    return {"mean": pooled.mean(axis=0), "covariance": cov, "std": np.sqrt(np.diag(cov)),
+            "percentiles": {q: np.percentile(pooled, q, axis=0) for q in BOOTSTRAP_PERCENTILES},
+            "bag_mean": bag_mean, "bag_var": bag_var, "within": within, "between": between, "mismatch_ratio": ratio,
+            "tau": tau, "converged": converged, "n_converged": n_ok,
+            "mean_mcse": np.sqrt(bag_var * tau[:, None] / float(n_w * n_t)), "n_bags": int(n_b), "n_samples": int(n_w * n_t),
+            "names": list(names)}
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -871,6 +935,91 @@ class Runner(object):
         out = bootstrap_summary(res["x"], x_hat, res["converged"], [plan.names[int(i)] for i in plan.free_idx], laplace)
         out.update({"x": res["x"], "converged": res["converged"], "n_iter": res["n_iter"], "x_hat": x_hat, "seed": int(seed),
                     "scheme": scheme})
+        return out
+
+    # ------------------------------------------------------------------ bagged posterior (new)
+    def lnprob_weighted_batch(self, values, row_replicate, scheme="exponential", seed=0, weights=None, weight_scale=1.0):
+        """``lnprob_batch`` with the stars of every row weighted by the row's replicate: ``values`` (..., P) free-parameter
+        vectors and ``row_replicate``, one replicate id per row in C order, -> (...) values of
+        weight_scale sum_i w(b, i) lnL_i + ln prior,  one launch of the device's weighted VALUE kernel
+        (``_native.Catalog.weighted_loglike``; no gradient is computed: what a stretch move reads).  Weights as in
+        ``lnprob_weighted_grad_batch``.  Box and structured priors as in ``lnprob_batch``: rows outside the prior are
+        -inf and take a donor row for the launch; structured priors enter unweighted and unscaled.  Runs on one device
+        in one process, on un-binned float64 catalogues."""
+        self._holdout_check("lnprob_weighted_batch")
+        values = np.asarray(values, dtype=np.float64)
+        n_p = self.n_fitted_parameters
+        if values.ndim < 1 or values.shape[-1] != n_p:
+            raise ValueError("values must have shape (..., {0})".format(n_p))
+        lead = values.shape[:-1]
+        rep = np.ascontiguousarray(row_replicate, dtype=np.int64).reshape(-1)
+        rows = values.reshape(-1, n_p)
+        if rep.size != rows.shape[0]:
+            raise ValueError("row_replicate must hold one replicate per row of values")
+        pars = self.parameters
+        resolved = pars.resolve_batch(rows)
+        lp = pars.lnprior_batch(resolved)
+        ok = np.isfinite(lp)
+        out = np.full(lp.shape, -np.inf)
+        if ok.any():
+            if not ok.all():
+                donor = int(np.flatnonzero(ok)[0])
+                resolved = OrderedDict((k, np.where(ok, col, col[donor])) for k, col in resolved.items())
+            lnl = self._ensure_catalog().weighted_loglike(self._kernel_table(resolved), rep, scheme=scheme, seed=seed,
+                                                          weights=weights)
+            out[ok] = float(weight_scale) * lnl[ok] + lp[ok]
+        return out.reshape(lead)
+
+    def bagged(self, n_bags=64, n_walkers=64, n_steps=600, n_burn=200, scheme="exponential", seed=None, pos=None,
+               bag_fraction=1.0, thin=1):
+        """The bagged posterior ("BayesBag": Huggins & Miller 2019, 2023): ``n_bags`` posteriors of the same model, bag b on
+        the catalogue under the bootstrap weights of replicate b (``scheme`` "exponential": Exp(1), "poisson": Poisson(1)
+        counts; the weights of ``bootstrap`` -- a function of (seed, b, star), ``_native.bootstrap_weights`` replays them),
+        sampled in lock step and pooled.  B ensembles of ``n_walkers`` walkers take ``n_steps`` stretch-move steps
+        (``BinnedSampler``, ``rng="device"``: the chains are a function of ``seed``); one launch of the weighted value
+        kernel (``lnprob_weighted_batch``) evaluates all B W / 2 proposals of a half step, row (b, w) under replicate b.
+        ``bag_fraction`` scales every bag's log-likelihood: the M / N of a bag of M stars drawn from N; 1.0 is the standard
+        choice.  ``pos``: start positions (B, W, P), default B W rows of ``get_initials``.
+
+        Returns ``bagged_summary`` of the chains -- the pooled moments are the bagged posterior, ``within`` / ``between`` /
+        ``mismatch_ratio`` compare the model's own width with the sampling scatter (see there) -- plus ``sampler``
+        (``chain``: (B, W, steps, P)), ``seed``, ``scheme`` and ``bag_fraction``.  Unlike every interval taken from one
+        chain, the bagged intervals keep their coverage when the model understates the scatter of the data."""
+        self._holdout_check("bagged")
+        from .binned import BinnedSampler
+        n_b, n_w, n_p = int(n_bags), int(n_walkers), self.n_fitted_parameters
+        if n_b < 1:
+            raise ValueError("bagged: n_bags must be >= 1")
+        if scheme not in ("exponential", "poisson"):
+            raise ValueError("bagged: scheme must be 'exponential' or 'poisson'")
+        if int(thin) < 1:
+            raise ValueError("bagged: thin must be >= 1")
+        if not 0 <= int(n_burn) < int(n_steps):
+            raise ValueError("bagged: n_burn must lie in [0, n_steps)")
+        if not (np.isfinite(bag_fraction) and bag_fraction > 0.0):
+            raise ValueError("bagged: bag_fraction must be positive")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        if pos is None:
+            pos = self.get_initials(n_b * n_w).reshape(n_b, n_w, n_p)
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.shape != (n_b, n_w, n_p):
+            raise ValueError("Array with starting values has invalid shape: expected {0}".format((n_b, n_w, n_p)))
+        pars = self.parameters
+        if not np.all(np.isfinite(pars.lnprior_batch(pars.resolve_batch(pos.reshape(-1, n_p))))):
+            raise ValueError("Invalid initial guesses: start positions outside the prior")
+
+        def log_prob(values):
+            # (B, rows, P): bag b's rows under replicate b
+            rep = np.repeat(np.arange(n_b, dtype=np.int64), values.shape[1])
+            return self.lnprob_weighted_batch(values, rep, scheme=scheme, seed=seed, weight_scale=bag_fraction)
+
+        sampler = BinnedSampler(n_b, n_w, n_p, log_prob, seed=seed, rng="device")
+        logger.info("bagged posterior: %d bags (%s weights), %d walkers each, %d steps", n_b, scheme, n_w, n_steps)
+        sampler.reserve(int(n_steps))
+        sampler.run_mcmc(pos, int(n_steps))
+        out = bagged_summary(sampler.chain, n_burn, self.fitted_parameters, thin=thin)
+        out.update({"sampler": sampler, "seed": int(seed), "scheme": scheme, "bag_fraction": float(bag_fraction)})
         return out
 
     # ------------------------------------------------------------------ Hamiltonian Monte Carlo (new)

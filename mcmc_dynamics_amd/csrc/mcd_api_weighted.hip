@@ -1,9 +1,12 @@
 // mcd_api_weighted.hip -- C-ABI of the MI355X log-likelihood library (see include/mcd.h; mcd_host.h lists the host units):
 // host driver of the weighted value and gradient.  mcd_weighted_loglike_grad: R parameter rows against the whole catalogue
 // in one launch, every row under the star weights of its own replicate (kernel: mcd_weighted.hip; loop: mcd_weighted.h;
-// generator: mcd_weights.h).  mcd_bootstrap_weights: the generated weights on the host.
+// generator: mcd_weights.h).  mcd_weighted_loglike: the value alone (kernel: mcd_weighted_value.hip; loop:
+// mcd_weighted_value.h), behind the same validation and the same explicit-table pass.  mcd_bootstrap_weights: the generated
+// weights on the host.
 #include "mcd_host.h"
 #include "mcd_weighted.h"
+#include "mcd_weighted_value.h"
 
 using namespace mcd::host;
 
@@ -30,6 +33,8 @@ static void free_weighted_work(WeightedWork& w) {
 void release_weighted(mcd_catalog* cat) {
     for (auto& kv : cat->weighted) free_weighted_work(kv.second);
     cat->weighted.clear();
+    for (auto& kv : cat->weighted_value) free_weighted_work(kv.second);
+    cat->weighted_value.clear();
     if (cat->d_weights) (void)hipFree(cat->d_weights);
     cat->d_weights = nullptr;
     cat->d_weights_bytes = 0;
@@ -40,13 +45,15 @@ MCD_HOST_END
 
 namespace {
 
-// The chunk table over `records` for n_rows rows and its buffers, from the catalogue's cache or built now
-int weighted_work(mcd_catalog* cat, const Shard& sh, int64_t n_rows, WeightedWork** out) {
-    auto it = cat->weighted.find(n_rows);
-    if (it != cat->weighted.end()) { *out = &it->second; return MCD_OK; }
-    if (cat->weighted.size() >= 8) {                                   // bound the cache (a bootstrap uses one row count)
-        for (auto& kv : cat->weighted) free_weighted_work(kv.second);
-        cat->weighted.clear();
+// The chunk table over `records` for n_rows rows and its buffers, from `cache` (the catalogue's for the gradient call,
+// 1 + K fields per row, or the one for the value call, one field) or built now
+int weighted_work(mcd_catalog* cat, std::map<int64_t, WeightedWork>& cache, size_t fields, const Shard& sh, int64_t n_rows,
+                  WeightedWork** out) {
+    auto it = cache.find(n_rows);
+    if (it != cache.end()) { *out = &it->second; return MCD_OK; }
+    if (cache.size() >= 8) {                                           // bound the cache (a bootstrap, a bagged run use one row count)
+        for (auto& kv : cache) free_weighted_work(kv.second);
+        cache.clear();
     }
     // catalogue order always: the weights are indexed by the star's position in `records`, so the verr-sorted copy and
     // the plans made for it are not used
@@ -54,7 +61,7 @@ int weighted_work(mcd_catalog* cat, const Shard& sh, int64_t n_rows, WeightedWor
     WeightedWork w;
     w.n_rows = n_rows;
     w.n_chunks = (int64_t)plan.chunks.size();
-    const size_t fields = (size_t)(1 + cat->k), padded = (size_t)mcd::padded_walkers(n_rows);
+    const size_t padded = (size_t)mcd::padded_walkers(n_rows);
     // (a failure half-way releases what it got)
     auto build = [&]() -> int {
         MCD_HIP(hipMalloc(&w.d_chunks, std::max<size_t>(1, plan.chunks.size()) * sizeof(mcd::Chunk)));
@@ -75,13 +82,13 @@ int weighted_work(mcd_catalog* cat, const Shard& sh, int64_t n_rows, WeightedWor
         return MCD_OK;
     };
     if (int rc = build()) { free_weighted_work(w); return rc; }
-    *out = &(cat->weighted[n_rows] = w);
+    *out = &(cache[n_rows] = w);
     return MCD_OK;
 }
 
-int weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* wd,
-                          double* out, double* grad) {
-    const std::string name("mcd_weighted_loglike_grad");
+// What both entry points refuse, in the order of include/mcd.h; `name` opens the message
+int weighted_usable(mcd_catalog* cat, const std::string& name, int64_t n_rows, int32_t k, const double* params,
+                    const mcd_weight_desc* wd) {
     if (!cat || !params || !wd) return fail(MCD_ERR_INVALID, name + ": null catalogue, params or weight description");
     if (int rc = ctx_usable(cat->ctx)) return rc;
     if (cat->n_psets != 1) return fail(MCD_ERR_INVALID, name + ": defined for un-binned catalogues only");
@@ -110,79 +117,99 @@ int weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const dou
             return fail(MCD_ERR_INVALID, name + ": row_replicate[" + std::to_string(r) + "] = " + std::to_string(b) +
                                              (explicit_w ? " is outside [0, n_replicates)" : " is negative"));
     }
-    if (!out && !grad) return MCD_OK;
-    // explicit weights: every call checks them and fingerprints their contents in one sequential pass (two independent
-    // 64-bit mixes of the bit patterns, with the shape): the transposed copy on the device is kept while the fingerprint
-    // stands, whatever the address, so that the trial steps of an optimiser pay the pass and not the upload
-    uint64_t print[2] = {0x6d63645f776768ull, 0x9E3779B97F4A7C15ull};
-    if (explicit_w) {
-        const size_t total = (size_t)(B * N);
-        for (size_t at = 0; at < total; ++at) {
-            const double x = wd->weights[at];
-            if (!(x >= 0.0) || !std::isfinite(x))
-                return fail(MCD_ERR_INVALID, name + ": weight [" + std::to_string(at / (size_t)N) + "][" +
-                                                 std::to_string(at % (size_t)N) + "] is negative or not finite");
-            uint64_t bits;
-            std::memcpy(&bits, &x, sizeof bits);
-            print[0] = (print[0] ^ bits) * 0xD2E7470EE14C6C93ull;
-            print[0] ^= print[0] >> 32;
-            print[1] = (print[1] + bits) * 0xCA5A826395121157ull;
-            print[1] = (print[1] << 23) | (print[1] >> 41);
+    return MCD_OK;
+}
+
+// explicit weights: every call checks them and fingerprints their contents in one sequential pass (two independent
+// 64-bit mixes of the bit patterns, with the shape): the transposed copy on the device is kept while the fingerprint
+// stands, whatever the address and whichever of the two calls uploaded it, so that the trial steps of an optimiser and
+// the half steps of a chain pay the pass and not the upload
+int weights_fingerprint(const mcd_catalog* cat, const std::string& name, const mcd_weight_desc* wd, uint64_t print[2]) {
+    print[0] = 0x6d63645f776768ull;
+    print[1] = 0x9E3779B97F4A7C15ull;
+    if (wd->scheme != MCD_WEIGHT_EXPLICIT) return MCD_OK;
+    const int64_t B = wd->n_replicates, N = cat->n_stars;
+    const size_t total = (size_t)(B * N);
+    for (size_t at = 0; at < total; ++at) {
+        const double x = wd->weights[at];
+        if (!(x >= 0.0) || !std::isfinite(x))
+            return fail(MCD_ERR_INVALID, name + ": weight [" + std::to_string(at / (size_t)N) + "][" +
+                                             std::to_string(at % (size_t)N) + "] is negative or not finite");
+        uint64_t bits;
+        std::memcpy(&bits, &x, sizeof bits);
+        print[0] = (print[0] ^ bits) * 0xD2E7470EE14C6C93ull;
+        print[0] ^= print[0] >> 32;
+        print[1] = (print[1] + bits) * 0xCA5A826395121157ull;
+        print[1] = (print[1] << 23) | (print[1] >> 41);
+    }
+    return MCD_OK;
+}
+
+// ... and the device copy of the table with fingerprint `print`: kept, or transposed and uploaded now (the device is
+// current, its stream idle)
+int weights_on_device(mcd_catalog* cat, const mcd_weight_desc* wd, const uint64_t print[2]) {
+    const int64_t B = wd->n_replicates, N = cat->n_stars;
+    if (cat->d_weights && cat->weights_replicates == B && cat->weights_print[0] == print[0] && cat->weights_print[1] == print[1])
+        return MCD_OK;
+    // transposed to [star][replicate], in blocks of stars whose rows of the copy stay in cache
+    std::vector<double> transposed((size_t)(B * N));
+    constexpr int64_t kBlockStars = 256;
+    for (int64_t i0 = 0; i0 < N; i0 += kBlockStars) {
+        const int64_t i1 = std::min(N, i0 + kBlockStars);
+        for (int64_t b = 0; b < B; ++b) {
+            const double* row = wd->weights + (size_t)(b * N);
+            for (int64_t i = i0; i < i1; ++i) transposed[(size_t)(i * B + b)] = row[i];
         }
     }
+    cat->weights_replicates = -1;                                   // (nothing is cached while the copy is in the making)
+    const size_t bytes = std::max<size_t>(8, transposed.size() * sizeof(double));
+    if (bytes > cat->d_weights_bytes) {
+        if (cat->d_weights) MCD_HIP(hipFree(cat->d_weights));
+        cat->d_weights = nullptr;
+        cat->d_weights_bytes = 0;
+        MCD_HIP(hipMalloc(&cat->d_weights, bytes));
+        cat->d_weights_bytes = bytes;
+    }
+    // (from pageable memory: the copy has left `transposed` when the call returns)
+    if (!transposed.empty())
+        MCD_HIP(hipMemcpy(cat->d_weights, transposed.data(), transposed.size() * sizeof(double), hipMemcpyHostToDevice));
+    cat->weights_replicates = B;
+    cat->weights_print[0] = print[0];
+    cat->weights_print[1] = print[1];
+    return MCD_OK;
+}
+
+// What both calls do between their validation and their kernel: the explicit table's pass, the plan and buffers of the
+// row count from `cache` (`fields` sums per row), the table's device copy, params and replicates H2D, walker prep; the
+// device is current and the first timing event recorded when this returns
+int weighted_stage(mcd_catalog* cat, const std::string& name, std::map<int64_t, WeightedWork>& cache, size_t fields,
+                   int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* wd, WeightedWork** out) {
+    uint64_t print[2];
+    if (int rc = weights_fingerprint(cat, name, wd, print)) return rc;
     Shard& sh = cat->shards[0];
     const DeviceSlot& slot = cat->ctx->slots[sh.slot];
     MCD_HIP(hipSetDevice(slot.device));
     // (an earlier pipelined evaluation may still be in flight on the stream the plans are released and built on)
-    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, "mcd_weighted_loglike_grad (previous evaluation)");
-    WeightedWork* wp = nullptr;
-    if (int rc = weighted_work(cat, sh, n_rows, &wp)) return rc;
-    WeightedWork& w = *wp;
-    const bool cached = explicit_w && cat->d_weights && cat->weights_replicates == B && cat->weights_print[0] == print[0] &&
-                        cat->weights_print[1] == print[1];
-    if (explicit_w && !cached) {
-        // transposed to [star][replicate], in blocks of stars whose rows of the copy stay in cache
-        std::vector<double> transposed((size_t)(B * N));
-        constexpr int64_t kBlockStars = 256;
-        for (int64_t i0 = 0; i0 < N; i0 += kBlockStars) {
-            const int64_t i1 = std::min(N, i0 + kBlockStars);
-            for (int64_t b = 0; b < B; ++b) {
-                const double* row = wd->weights + (size_t)(b * N);
-                for (int64_t i = i0; i < i1; ++i) transposed[(size_t)(i * B + b)] = row[i];
-            }
-        }
-        cat->weights_replicates = -1;                                   // (nothing is cached while the copy is in the making)
-        const size_t bytes = std::max<size_t>(8, transposed.size() * sizeof(double));
-        if (bytes > cat->d_weights_bytes) {
-            if (cat->d_weights) MCD_HIP(hipFree(cat->d_weights));
-            cat->d_weights = nullptr;
-            cat->d_weights_bytes = 0;
-            MCD_HIP(hipMalloc(&cat->d_weights, bytes));
-            cat->d_weights_bytes = bytes;
-        }
-        // (from pageable memory: the copy has left `transposed` when the call returns)
-        if (!transposed.empty())
-            MCD_HIP(hipMemcpy(cat->d_weights, transposed.data(), transposed.size() * sizeof(double), hipMemcpyHostToDevice));
-        cat->weights_replicates = B;
-        cat->weights_print[0] = print[0];
-        cat->weights_print[1] = print[1];
-    }
+    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, (name + " (previous evaluation)").c_str());
+    if (int rc = weighted_work(cat, cache, fields, sh, n_rows, out)) return rc;
+    WeightedWork& w = **out;
+    if (wd->scheme == MCD_WEIGHT_EXPLICIT)
+        if (int rc = weights_on_device(cat, wd, print)) return rc;
     // the gradient path's staging: params H2D, walker prep
-    const size_t fields = (size_t)(1 + k), padded = (size_t)mcd::padded_walkers(n_rows);
     std::memcpy(w.h_params, params, (size_t)n_rows * k * sizeof(double));
     std::memcpy(w.h_replicate, wd->row_replicate, (size_t)n_rows * sizeof(int64_t));
     MCD_HIP(hipMemcpyAsync(w.d_params, w.h_params, (size_t)n_rows * k * sizeof(double), hipMemcpyHostToDevice, slot.stream));
     MCD_HIP(hipMemcpyAsync(w.d_replicate, w.h_replicate, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, slot.stream));
     MCD_HIP(mcd::launch_prepare_walkers(slot.stream, w.d_params, n_rows, k, cat->model, cat->free_centre, cat->precision,
                                         w.d_wpar));
-    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
     if (cat->timing) MCD_HIP(hipEventRecord(w.e0, slot.stream));
-    MCD_HIP(mcd::launch_weighted_grad(slot.stream, shape, scheme, sh.records, w.d_chunks, w.n_chunks, w.d_params, w.d_wpar,
-                                      w.d_replicate, wd->seed, explicit_w ? cat->d_weights : nullptr, B, w.d_partials, n_rows));
-    if (cat->timing) MCD_HIP(hipEventRecord(w.e1, slot.stream));
-    MCD_HIP(mcd::launch_grad_reduce(slot.stream, shape, w.d_partials, w.n_chunks, w.d_offsets, 1, w.n_chunks, n_rows, w.d_out));
-    MCD_HIP(hipMemcpyAsync(w.h_out, w.d_out, fields * padded * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
-    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, "mcd_weighted_loglike_grad");
+    return MCD_OK;
+}
+
+// ... and after the D2H copy of their results is enqueued: the wait, option "timing", the launch record
+int weighted_finish(mcd_catalog* cat, const std::string& name, WeightedWork& w, int64_t n_rows) {
+    const DeviceSlot& slot = cat->ctx->slots[cat->shards[0].slot];
+    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, name.c_str());
     if (cat->timing) {
         float ms = 0.f;
         MCD_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
@@ -191,12 +218,58 @@ int weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const dou
     }
     cat->last_chunks = w.n_chunks;
     cat->last_grid = mcd::main_grid(w.n_chunks, n_rows);
+    return MCD_OK;
+}
+
+int weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* wd,
+                          double* out, double* grad) {
+    const std::string name("mcd_weighted_loglike_grad");
+    if (int rc = weighted_usable(cat, name, n_rows, k, params, wd)) return rc;
+    if (!out && !grad) return MCD_OK;
+    WeightedWork* wp = nullptr;
+    if (int rc = weighted_stage(cat, name, cat->weighted, (size_t)(1 + k), n_rows, k, params, wd, &wp)) return rc;
+    WeightedWork& w = *wp;
+    const Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    const bool explicit_w = wd->scheme == MCD_WEIGHT_EXPLICIT;
+    const size_t fields = (size_t)(1 + k), padded = (size_t)mcd::padded_walkers(n_rows);
+    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+    MCD_HIP(mcd::launch_weighted_grad(slot.stream, shape, wd->scheme, sh.records, w.d_chunks, w.n_chunks, w.d_params, w.d_wpar,
+                                      w.d_replicate, wd->seed, explicit_w ? cat->d_weights : nullptr,
+                                      explicit_w ? wd->n_replicates : 0, w.d_partials, n_rows));
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e1, slot.stream));
+    MCD_HIP(mcd::launch_grad_reduce(slot.stream, shape, w.d_partials, w.n_chunks, w.d_offsets, 1, w.n_chunks, n_rows, w.d_out));
+    MCD_HIP(hipMemcpyAsync(w.h_out, w.d_out, fields * padded * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+    if (int rc = weighted_finish(cat, name, w, n_rows)) return rc;
     if (out) std::memcpy(out, w.h_out, (size_t)n_rows * sizeof(double));
     if (grad)
         for (int64_t j = 0; j < k; ++j) {
             const double* col = w.h_out + (1 + j) * padded;
             for (int64_t i = 0; i < n_rows; ++i) grad[i * k + j] = col[i];
         }
+    return MCD_OK;
+}
+
+// The value alone: the value kernel (one sum per row) and the value path's reduction of one range
+int weighted_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* wd, double* out) {
+    const std::string name("mcd_weighted_loglike");
+    if (int rc = weighted_usable(cat, name, n_rows, k, params, wd)) return rc;
+    if (!out) return MCD_OK;
+    WeightedWork* wp = nullptr;
+    if (int rc = weighted_stage(cat, name, cat->weighted_value, 1, n_rows, k, params, wd, &wp)) return rc;
+    WeightedWork& w = *wp;
+    const Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    const bool explicit_w = wd->scheme == MCD_WEIGHT_EXPLICIT;
+    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+    MCD_HIP(mcd::launch_weighted_value(slot.stream, shape, wd->scheme, sh.records, w.d_chunks, w.n_chunks, w.d_wpar, w.d_replicate,
+                                       wd->seed, explicit_w ? cat->d_weights : nullptr, explicit_w ? wd->n_replicates : 0,
+                                       w.d_partials, n_rows));
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e1, slot.stream));
+    MCD_HIP(mcd::launch_reduce(slot.stream, w.d_partials, w.d_offsets, 1, w.n_chunks, w.n_chunks, n_rows, nullptr, w.d_out));
+    MCD_HIP(hipMemcpyAsync(w.h_out, w.d_out, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+    if (int rc = weighted_finish(cat, name, w, n_rows)) return rc;
+    std::memcpy(out, w.h_out, (size_t)n_rows * sizeof(double));
     return MCD_OK;
 }
 
@@ -209,6 +282,13 @@ int mcd_weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const
     try {
     return weighted_loglike_grad(cat, n_rows, k, params, w, out, grad);
     } catch (...) { return on_exception("mcd_weighted_loglike_grad"); }
+}
+
+int mcd_weighted_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* w,
+                         double* out) {
+    try {
+    return weighted_loglike(cat, n_rows, k, params, w, out);
+    } catch (...) { return on_exception("mcd_weighted_loglike"); }
 }
 
 int mcd_bootstrap_weights(int32_t scheme, uint64_t seed, int64_t rep0, int64_t n_reps, int64_t star0, int64_t n_stars,

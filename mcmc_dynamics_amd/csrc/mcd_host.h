@@ -13,7 +13,8 @@
 //   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
 //   mcd_api_mmatch.hip     mcd_moment_match: the decision loop of moment matching around the hold-out evaluation
 //   mcd_api_replicate.hip  mcd_replicate_check, mcd_replicate_numbers: replicated-data predictive checks per range of stars
-//   mcd_api_weighted.hip   mcd_weighted_loglike_grad, mcd_bootstrap_weights: value and gradient under per-row star weights
+//   mcd_api_weighted.hip   mcd_weighted_loglike_grad, mcd_weighted_loglike, mcd_bootstrap_weights: value and gradient, or
+//                          the value alone, under per-row star weights
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -206,8 +207,8 @@ struct HoldoutWork {
     hipEvent_t e0 = nullptr, e1 = nullptr;   // option "timing": around the main kernel
 };
 
-// mcd_weighted_loglike_grad: the chunk table over `records` for one row count and its buffers (mcd_api_weighted.hip), kept
-// by the catalogue
+// mcd_weighted_loglike_grad, mcd_weighted_loglike: the chunk table over `records` for one row count and its buffers
+// (mcd_api_weighted.hip), kept by the catalogue; the value call's have one field where the gradient call's have 1 + K
 struct WeightedWork {
     int64_t n_rows = 0;
     int64_t n_chunks = 0;
@@ -381,6 +382,7 @@ struct mcd_catalog {
     // of the last call ([n_stars][n_replicates], grown as needed) with the fingerprint of their contents (-1 replicates:
     // none), released with the catalogue
     std::map<int64_t, mcd::host::WeightedWork> weighted;
+    std::map<int64_t, mcd::host::WeightedWork> weighted_value;   // mcd_weighted_loglike's, a cache of its own
     double* d_weights = nullptr;
     size_t d_weights_bytes = 0;
     int64_t weights_replicates = -1;
