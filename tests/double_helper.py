@@ -22,7 +22,7 @@ L = vh.L
 DOUBLE, DOUBLE_GB = 7, 8
 MODELS = (DOUBLE, DOUBLE_GB)
 BASE = {DOUBLE: 3, DOUBLE_GB: 4}                 # the single-component model each one reduces to
-HEAD = ["v_sys", "sigma_max", "a", "v_maxx", "v_maxy", "r_peak", "v_maxx_c", "v_maxy_c", "r_peak_ratio"]
+HEAD = eh.DOUBLE_HEAD                             # the column list exists once, in emul_helper
 GEOMETRY_COLUMNS = ("v_maxx", "v_maxy", "r_peak", "v_maxx_c", "v_maxy_c", "r_peak_ratio", "ra_center", "dec_center")
 
 
@@ -224,19 +224,4 @@ def pack_records(cat, model, centre):
 
 def pack_walkers(params, model, free, kd):
     """csrc/mcd_prep.h: walker_constants for the double models, on a row of `kd` values."""
-    params = np.atleast_2d(np.asarray(params, dtype=np.float64))
-    w = np.zeros((params.shape[0], kd))
-    a, rp = params[:, 2], params[:, 5]
-    w[:, 0], w[:, 1], w[:, 2], w[:, 3] = params[:, 0], params[:, 1] * params[:, 1], params[:, 3], params[:, 4]
-    w[:, 11], w[:, 12], w[:, 13], w[:, 14] = a * a, params[:, 1] * params[:, 1] * a, rp * rp, 2.0 * rp
-    rc = params[:, 8] * rp
-    w[:, 15], w[:, 16], w[:, 17], w[:, 18] = params[:, 6], params[:, 7], rc * rc, 2.0 * rc
-    w[:, 5] = w[:, 7] = 1.0
-    j = 9
-    if free:
-        w[:, 4], w[:, 5] = np.sin(params[:, j] * eh.DEG), np.cos(params[:, j] * eh.DEG)
-        w[:, 6], w[:, 7] = np.sin(params[:, j + 1] * eh.DEG), np.cos(params[:, j + 1] * eh.DEG)
-        j += 2
-    if model == DOUBLE_GB:
-        w[:, 8], w[:, 9], w[:, 10] = params[:, j], params[:, j + 1] ** 2, params[:, j + 2]
-    return np.ascontiguousarray(w)
+    return eh.pack_double_walkers(params, model, free, kd)

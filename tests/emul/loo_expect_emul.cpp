@@ -152,7 +152,7 @@ extern "C" int emul_loo_expect(int64_t n, int64_t S, const double* lnl, double r
 // the whole call from records and derived sample rows: out[2 + 4 (+ 1 with mix)][n], rows in LooxRow order after lnL
 extern "C" int emul_loo_expect_model(int model, int free_centre, int mix, int f32, int64_t n, const double* recs,
                                      const double* wrows, int64_t S, double r_eff, double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         if constexpr (bg_kind(MODEL) == BG_GAUSS) {

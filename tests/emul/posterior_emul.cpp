@@ -67,7 +67,7 @@ void run(int64_t n, const double* recs, const double* wrows, int64_t S, int64_t 
 // out[4][n] = lppd, lnl_var, pmem_mean, pmem_std; n_slices <= 0: the library's slice plan
 extern "C" int emul_posterior(int model, int free_centre, int mem, int64_t n, const double* recs, const double* wrows,
                               int64_t S, int64_t n_slices, double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         if constexpr (bg_kind(MODEL) != BG_NONE) {

@@ -66,7 +66,7 @@ void run_precision(int f32, int64_t n, const double* recs, const double* wrows, 
 // out[9][n] in PredOut order (the ninth field, pit_mix, is written with mix only); n_slices <= 0: the library's slice plan
 extern "C" int emul_predictive(int model, int free_centre, int mix, int f32, int64_t n, const double* recs,
                                const double* wrows, int64_t S, int64_t n_slices, double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         if constexpr (bg_kind(MODEL) == BG_GAUSS) {

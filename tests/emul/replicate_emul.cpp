@@ -49,7 +49,7 @@ extern "C" {
 int emul_replicate(int model, int free_centre, const double* recs, const double* wrows, int64_t S, uint64_t seed,
                    int64_t row0, int64_t R, const int64_t* offs, const int64_t* order, double bg_mean, double bg_sigma,
                    int64_t forced_len, double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         run<decltype(M)::value, decltype(FREE)::value>(recs, wrows, S, seed, row0, R, offs, order, bg_mean, bg_sigma,
                                                        forced_len, out);
         return 0;
@@ -107,7 +107,7 @@ int64_t emul_rep_scratch_bytes() { return kRepScratchBytes; }
 
 // (cos, sin) of star_unit for n records and one walker row
 int emul_star_unit(int model, int free_centre, int64_t n, const double* recs, const double* wrow, double* c, double* s) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         constexpr int ND = record_doubles(MODEL, kFree);

@@ -57,7 +57,7 @@ extern "C" {
 int emul_weighted_value(int model, int free_centre, int scheme, int64_t n, const double* recs, const double* wpar, int64_t R,
                         const int64_t* row_replicate, uint64_t seed, const double* weights_t, int64_t n_replicates,
                         int64_t chunk_len, double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         if (scheme == kWeightExponential)
@@ -74,7 +74,7 @@ int emul_weighted_value(int model, int free_centre, int scheme, int64_t n, const
 
 int emul_plain_value(int model, int free_centre, int64_t n, const double* recs, const double* wpar, int64_t R, int64_t chunk_len,
                      double* out) {
-    return dispatch_model(model, free_centre != 0, [&](auto M, auto FREE) {
+    return dispatch_any_model(model, free_centre != 0, [&](auto M, auto FREE) {
         run_plain<decltype(M)::value, decltype(FREE)::value>(n, recs, wpar, R, chunk_len, out);
         return 0;
     }, -1);

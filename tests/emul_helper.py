@@ -37,10 +37,14 @@ def lib():
 
 
 PROFILE_MODELS = (3, 4, 5, 6)
-BG_OF = {0: 0, 1: 1, 2: 2, 3: 0, 4: 2, 5: 3, 6: 1}
+DOUBLE_MODELS = (7, 8)                           # the double Lynden-Bell models: records of models 3 / 4
+RECORD_MODEL = {7: 3, 8: 4}
+BG_OF = {0: 0, 1: 1, 2: 2, 3: 0, 4: 2, 5: 3, 6: 1, 7: 0, 8: 2}
+DOUBLE_HEAD = ["v_sys", "sigma_max", "a", "v_maxx", "v_maxy", "r_peak", "v_maxx_c", "v_maxy_c", "r_peak_ratio"]
 
 
 def pack_records(cat, model, centre):
+    model = RECORD_MODEL.get(model, model)
     n = len(cat["v"])
     cols = [cat["v"], cat["verr"] * cat["verr"]]
     if centre is None:
@@ -72,8 +76,43 @@ def pack_records(cat, model, centre):
     return np.ascontiguousarray(np.stack(cols, axis=1), dtype=np.float64)
 
 
+def pack_double_walkers(params, model, free, kd):
+    """csrc/mcd_prep.h: walker_constants for the double models (7, 8), on rows of `kd` values: the profile models' slots
+    and, in slots 15..18, the second component's amplitudes and its squared / doubled peak radius r_peak_ratio * r_peak."""
+    params = np.atleast_2d(np.asarray(params, dtype=np.float64))
+    w = np.zeros((params.shape[0], kd))
+    a, rp = params[:, 2], params[:, 5]
+    w[:, 0], w[:, 1], w[:, 2], w[:, 3] = params[:, 0], params[:, 1] * params[:, 1], params[:, 3], params[:, 4]
+    w[:, 11], w[:, 12], w[:, 13], w[:, 14] = a * a, params[:, 1] * params[:, 1] * a, rp * rp, 2.0 * rp
+    rc = params[:, 8] * rp
+    w[:, 15], w[:, 16], w[:, 17], w[:, 18] = params[:, 6], params[:, 7], rc * rc, 2.0 * rc
+    w[:, 5] = w[:, 7] = 1.0
+    j = 9
+    if free:
+        w[:, 4], w[:, 5] = np.sin(params[:, j] * DEG), np.cos(params[:, j] * DEG)
+        w[:, 6], w[:, 7] = np.sin(params[:, j + 1] * DEG), np.cos(params[:, j + 1] * DEG)
+        j += 2
+    if BG_OF[model] == 2:
+        w[:, 8], w[:, 9], w[:, 10] = params[:, j], params[:, j + 1] ** 2, params[:, j + 2]
+    return np.ascontiguousarray(w)
+
+
+def abi_names(model, free):
+    """The C-ABI column names of `model` (include/mcd.h: mcd_catalog_param_count)."""
+    if model in DOUBLE_MODELS:
+        order = list(DOUBLE_HEAD)
+    else:
+        prof = model in PROFILE_MODELS
+        order = ["v_sys", "sigma_max"] + (["a"] if prof else []) + ["v_maxx", "v_maxy"] + (["r_peak"] if prof else [])
+    if free:
+        order += ["ra_center", "dec_center"]
+    return order + {0: [], 1: [], 2: ["v_back", "sigma_back", "f_back"], 3: ["f_back"]}[BG_OF[model]]
+
+
 def pack_walkers(params, model, free):
     """params in the C-ABI column order (include/mcd.h: mcd_catalog_param_count)."""
+    if model in DOUBLE_MODELS:
+        return pack_double_walkers(params, model, free, lib().emul_kd())
     params = np.atleast_2d(np.asarray(params, dtype=np.float64))
     w = np.zeros((params.shape[0], lib().emul_kd()))
     prof = model in PROFILE_MODELS
@@ -98,13 +137,8 @@ def pack_walkers(params, model, free):
 
 def abi_columns(names, values, model, free):
     """Re-order golden `values` (columns named `names`, the reference's own ordering) into the C-ABI order."""
-    prof = model in PROFILE_MODELS
-    order = ["v_sys", "sigma_max"] + (["a"] if prof else []) + ["v_maxx", "v_maxy"] + (["r_peak"] if prof else [])
-    if free:
-        order += ["ra_center", "dec_center"]
-    order += {0: [], 1: [], 2: ["v_back", "sigma_back", "f_back"], 3: ["f_back"]}[BG_OF[model]]
     names = [str(n) for n in names]
-    return np.ascontiguousarray(np.asarray(values)[:, [names.index(k) for k in order]])
+    return np.ascontiguousarray(np.asarray(values)[:, [names.index(k) for k in abi_names(model, free)]])
 
 
 def loglike(cat, params, model, centre, fast, chunk_len=248):

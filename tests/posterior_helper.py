@@ -76,21 +76,31 @@ def plan(n, S):
 
 # ---- NumPy restatement ------------------------------------------------------------------------------------------
 PROFILE = (3, 4, 5, 6)
+DOUBLE = emul.DOUBLE_MODELS                     # the double Lynden-Bell models: profile models with a second rotation term
 BG = emul.BG_OF
 
 
 def abi_names(model, free):
-    prof = model in PROFILE
-    names = ["v_sys", "sigma_max"] + (["a"] if prof else []) + ["v_maxx", "v_maxy"] + (["r_peak"] if prof else [])
-    if free:
-        names += ["ra_center", "dec_center"]
-    return names + {0: [], 1: [], 2: ["v_back", "sigma_back", "f_back"], 3: ["f_back"]}[BG[model]]
+    return emul.abi_names(model, free)
 
 
-def star_terms(cat, row, model, centre):
+def double_rotation(ra, dec, P, rc, dc):
+    """v_los of the double Lynden-Bell models the way the golden vectors were made: TWO calls of the oracle's
+    model_rotation, the second with v_sys = 0, the ``_c`` amplitudes and the peak radius r_peak_ratio * r_peak.  Runs in
+    the precision of its inputs."""
+    zero = P["v_sys"] * 0
+    return oracle.model_rotation(ra, dec, P["v_sys"], P["v_maxx"], P["v_maxy"], P["r_peak"], rc, dc) + \
+        oracle.model_rotation(ra, dec, zero, P["v_maxx_c"], P["v_maxy_c"], P["r_peak_ratio"] * P["r_peak"], rc, dc)
+
+
+def star_terms(cat, row, model, centre, dtype=np.float64):
     """(lnL_i, p_i) of one parameter row (C-ABI order) from the oracle's per-star functions: the star's term of lnlike
     (runner.py:280-284, constant.py:320-364, model.py:391-623) and its membership probability (constant.py:366-374,
-    model.py:505-510, 680-687); p is None for the models without a background."""
+    model.py:505-510, 680-687); p is None for the models without a background.  `dtype` other than float64 (the double
+    models only): every input cast to it."""
+    if model in DOUBLE:
+        return double_star_terms(cat, row, model, centre, dtype)
+    assert dtype is np.float64
     P = dict(zip(abi_names(model, centre is None), row))
     rc, dc = (P["ra_center"], P["dec_center"]) if centre is None else centre
     ra, dec, v, verr = cat["ra"], cat["dec"], cat["v"], cat["verr"]
@@ -122,6 +132,27 @@ def star_terms(cat, row, model, centre):
     else:
         p = m * np.exp(lc) / (m * np.exp(lc) + (1. - m) * np.exp(lb))
     return x, p
+
+
+def double_star_terms(cat, row, model, centre, dtype=np.float64):
+    """star_terms of models 7 and 8 in `dtype` (float64 or numpy.longdouble)."""
+    P = {k: dtype(x) for k, x in zip(abi_names(model, centre is None), row)}
+    rc, dc = (P["ra_center"], P["dec_center"]) if centre is None else (dtype(centre[0]), dtype(centre[1]))
+    ra, dec, v, verr = (np.asarray(cat[k]).astype(dtype) for k in ("ra", "dec", "v", "verr"))
+    v_los = double_rotation(ra, dec, P, rc, dc)
+    sigma = oracle.model_dispersion(ra, dec, P["sigma_max"], P["a"], rc, dc)
+    norm = verr * verr + sigma * sigma
+    lc = -0.5 * np.log(2. * np.pi * norm) - 0.5 * np.power(v - v_los, 2) / norm
+    assert lc.dtype == dtype
+    if BG[model] == 0:
+        return lc, None
+    lb = oracle.gaussian_background(v, verr, P["v_back"], P["sigma_back"])
+    rho = np.asarray(cat["density"]).astype(dtype)
+    m = rho / (rho + P["f_back"])
+    mx = np.max([lc, lb], axis=0)
+    ec, eb = m * np.exp(lc - mx), (1. - m) * np.exp(lb - mx)
+    assert ec.dtype == dtype
+    return mx + np.log(ec + eb), ec / (ec + eb)
 
 
 def numpy_posterior(cat, table, model, centre):
@@ -160,7 +191,7 @@ def model_catalog(n, model, seed=7):
 CENTRE = (synthetic.CENTER_RA_DEG, synthetic.CENTER_DEC_DEG)
 
 
-TRUTH_EXTRA = {"a": 60.0, "r_peak": 90.0}
+TRUTH_EXTRA = {"a": 60.0, "r_peak": 90.0, "v_maxx_c": 2.0, "v_maxy_c": -1.5, "r_peak_ratio": 0.4}
 
 
 def samples(cat, model, free, S, seed=3):

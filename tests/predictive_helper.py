@@ -29,7 +29,7 @@ INC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 OUT = os.path.join(ROOT, "tests", "emul", "libpredictive_emul.so")
 L = np.longdouble
 FIELDS = ("z_mean", "z_std", "tail_p", "pit", "vlos_mean", "vlos_std", "sigma_mean", "sigma_std")
-MIX_MODELS = (2, 4)
+MIX_MODELS = (2, 4, 8)
 _lib = None
 
 
@@ -89,7 +89,10 @@ def star_terms(cat, row, model, centre, dtype=np.float64):
     P = {k: dtype(x) for k, x in zip(ph.abi_names(model, centre is None), row)}
     rc, dc = (P["ra_center"], P["dec_center"]) if centre is None else (dtype(centre[0]), dtype(centre[1]))
     ra, dec, v, verr = (np.asarray(cat[k]).astype(dtype) for k in ("ra", "dec", "v", "verr"))
-    if model in ph.PROFILE:
+    if model in ph.DOUBLE:
+        v_los = ph.double_rotation(ra, dec, P, rc, dc)                # both components
+        sigma = oracle.model_dispersion(ra, dec, P["sigma_max"], P["a"], rc, dc)
+    elif model in ph.PROFILE:
         v_los = oracle.model_rotation(ra, dec, P["v_sys"], P["v_maxx"], P["v_maxy"], P["r_peak"], rc, dc)
         sigma = oracle.model_dispersion(ra, dec, P["sigma_max"], P["a"], rc, dc)
     else:

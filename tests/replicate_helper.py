@@ -162,7 +162,10 @@ def star_terms(cat, row, model, centre, g, u, bg, dtype=np.float64):
     P = {k: dtype(x) for k, x in zip(ph.abi_names(model, centre is None), row)}
     rc, dc = (P["ra_center"], P["dec_center"]) if centre is None else (dtype(centre[0]), dtype(centre[1]))
     ra, dec, v, verr = (np.asarray(cat[k]).astype(dtype) for k in ("ra", "dec", "v", "verr"))
-    if model in ph.PROFILE:
+    if model in ph.DOUBLE:
+        v_los = ph.double_rotation(ra, dec, P, rc, dc)                # both components
+        sigma = oracle.model_dispersion(ra, dec, P["sigma_max"], P["a"], rc, dc)
+    elif model in ph.PROFILE:
         v_los = oracle.model_rotation(ra, dec, P["v_sys"], P["v_maxx"], P["v_maxy"], P["r_peak"], rc, dc)
         sigma = oracle.model_dispersion(ra, dec, P["sigma_max"], P["a"], rc, dc)
     else:

@@ -8,7 +8,10 @@
   summary launchers (pointwise posterior, PSIS-LOO, posterior predictive, replicate check);
 * edges: a star on the centre, r_peak_ratio at both bounds, f_back = 0, rows outside the box, the float32 refusal;
 * the resident stretch move (P = 9, and P = 14 with a normal prior), HMC and tempering blocks against their host-driven
-  loops, bit for bit; hold-out refits and moment matching run and repeat bit for bit."""
+  loops, bit for bit; hold-out refits and moment matching run and repeat bit for bit.
+
+The summary, hold-out, moment-matching and weighted launchers with the second component LIVE (nothing here but value and
+gradient feels slots 15 .. 18 of the walker row): tests/test_gpu_double_live.py."""
 import os
 
 import numpy as np

@@ -96,16 +96,31 @@ def test_repeated_row_gives_the_posterior_means(model, free):
     assert np.all(np.abs(got["n_eff"] - 48.0) <= 1e-9)
 
 
+def _model_against_oracle(model, free):
+    centre = None if free else ph.CENTRE
+    mix = model in pr.MIX_MODELS
+    cat = pr.head(ph.model_catalog(80, 0, seed=7), 65)
+    table = ph.samples(cat, model, free, 257)
+    if free:
+        cat = pr.clear_of_centres(cat, *pr.sample_centres(table, model))
+    got = lh.emul_model(cat, table, model, centre, mix=mix)
+    lnl = lh.lnl_rows(cat, table, model, centre)
+    x, keys = lh.term_rows(cat, table, model, centre, mix=mix)
+    rows = {"rows": np.stack([got[k] for k in keys], axis=1), "pareto_k": got["pareto_k"]}
+    lh.check_expect(rows, lnl, x, unit_rows=(0, 4) if mix else (0,), what="model {0}".format(model))
+
+
 def test_model_emulation_matches_oracle():
     """The whole call (terms and weights from the catalogue) against the oracle fed with the emulation's own lnL."""
-    model, centre = 2, ph.CENTRE
-    cat = pr.head(ph.model_catalog(80, 0, seed=7), 65)
-    table = ph.samples(cat, model, False, 257)
-    got = lh.emul_model(cat, table, model, centre, mix=True)
-    lnl = lh.lnl_rows(cat, table, model, centre)
-    x, keys = lh.term_rows(cat, table, model, centre, mix=True)
-    rows = {"rows": np.stack([got[k] for k in keys], axis=1), "pareto_k": got["pareto_k"]}
-    lh.check_expect(rows, lnl, x, unit_rows=(0, 4), what="model 2")
+    _model_against_oracle(2, False)
+
+
+@pytest.mark.parametrize("free", [False, True])
+@pytest.mark.parametrize("model", [7, 8])
+def test_double_model_emulation_matches_oracle(model, free):
+    """The same for the double Lynden-Bell models with a live second component (posterior_term<7 | 8>, predictive_term<7 | 8,
+    ..., MIX>): the oracle's lnL and rows hold both rotation terms."""
+    _model_against_oracle(model, free)
 
 
 def test_tile_plan_with_rows():

@@ -12,7 +12,7 @@ import predictive_helper as pr
 from mcmc_dynamics_amd.analysis.runner import ppc_summary
 from test_posterior_cpu import var_ok
 
-MODELS = [0, 1, 2, 3, 4, 5, 6]
+MODELS = [0, 1, 2, 3, 4, 5, 6, 7, 8]               # 7, 8: the double Lynden-Bell models, second component live
 
 
 @pytest.fixture(scope="module")

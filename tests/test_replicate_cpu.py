@@ -106,6 +106,19 @@ def test_emulation_follows_the_rule(model, free):
                          rh.replicate(cat, table, model, centre, rh.SEED, offs, order))
 
 
+@pytest.mark.parametrize("free", [False, True])
+@pytest.mark.parametrize("model", [7, 8])
+def test_double_models_follow_the_rule(model, free):
+    """The double Lynden-Bell models with a live second component at the matrix's N = 65, S = 65 cell, the three layouts."""
+    cat, table, centre = rh.matrix_case(model, free)
+    cat, table = pr.head(cat, 65), table[:65]
+    ref = rh.Reference(cat, table, model, centre)
+    for kind in rh.LAYOUTS:
+        offs, order = rh.layout(kind, 65)
+        got = rh.replicate(cat, table, model, centre, rh.SEED, offs, order)
+        rh.check_rule(got, *ref.at(offs, order), cell=(model, free, kind))
+
+
 def test_star_unit_is_the_models_position_angle():
     for model in (0, 3):
         for free in (False, True):

@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+import double_helper as dh
 import variant_helper as vh
 import weighted_helper as wh
 import weighted_value_helper as wv
@@ -26,7 +27,7 @@ needs_longdouble = pytest.mark.skipif(not vh.HAVE_LONGDOUBLE, reason="numpy.long
 
 # ------------------------------------------------------------------------------------------ 1. the loop
 def _check_cell(model, free, n, n_rows, scheme):
-    case = vh.make_case(model, free, n)
+    case = dh.make_case(model, free, n) if model in dh.MODELS else vh.make_case(model, free, n)
     rows = list(range(n_rows))
     rep = wh.row_replicates(n_rows) if n_rows > 1 else np.array([3], dtype=np.int64)
     explicit = None
@@ -57,6 +58,17 @@ def test_emulation_follows_the_value_rule(model, free):
             for scheme in ("exponential", "poisson", "explicit"):
                 worst = max(worst, _check_cell(model, free, n, n_rows, scheme))
     print("model", model, "free" if free else "fixed", "largest value error", worst)
+
+
+@needs_longdouble
+@pytest.mark.parametrize("free", [False, True])
+@pytest.mark.parametrize("model", dh.MODELS)
+def test_emulation_follows_the_value_rule_for_the_double_models(model, free):
+    """chunk_weighted_value<7 | 8> with a live second component against double_helper's longdouble terms: the matrix's
+    smallest cell, and N = 33 stars under 65 rows."""
+    for n, n_rows in ((1, 1), (33, 65)):
+        for scheme in ("exponential", "poisson", "explicit"):
+            print(model, free, n, n_rows, scheme, "largest value error", _check_cell(model, free, n, n_rows, scheme))
 
 
 # ------------------------------------------------------------------------------------------ 2, 3. bits

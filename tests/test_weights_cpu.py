@@ -15,6 +15,7 @@
 import numpy as np
 import pytest
 
+import double_helper as dh
 import grad_bounds as gb
 import variant_helper as vh
 import weighted_helper as wh
@@ -105,7 +106,7 @@ needs_longdouble = pytest.mark.skipif(not vh.HAVE_LONGDOUBLE, reason="numpy.long
 
 
 def _check_cell(model, free, n, n_rows, scheme):
-    case = vh.make_case(model, free, n)
+    case = dh.make_case(model, free, n) if model in dh.MODELS else vh.make_case(model, free, n)
     rows = list(range(n_rows))
     rep = wh.row_replicates(n_rows) if n_rows > 1 else np.array([3], dtype=np.int64)
     explicit = None
@@ -117,7 +118,7 @@ def _check_cell(model, free, n, n_rows, scheme):
     else:
         w_rows = wh.weights_of_rows(scheme, wh.SEED, rep, n)
     value, grad = wh.emul_weighted(case, rows, rep, scheme, explicit=explicit)
-    floors = gb.floors(model, free, n)
+    floors = dh.floors(model, free, n) if model in dh.MODELS else gb.floors(model, free, n)
     worst = 0.0
     for j in vh.sample_rows(n_rows):                            # the longdouble reference costs: a sample of the rows
         ref = wh.reference(model, case["cat"], case["params"][j], case["centre"], w_rows[j])
@@ -133,6 +134,17 @@ def test_emulation_follows_the_rule(model, free):
         for n_rows in (1, 65, 257):
             for scheme in ("exponential", "poisson", "explicit"):
                 _check_cell(model, free, n, n_rows, scheme)
+
+
+@needs_longdouble
+@pytest.mark.parametrize("free", [False, True])
+@pytest.mark.parametrize("model", dh.MODELS)
+def test_emulation_follows_the_rule_for_the_double_models(model, free):
+    """chunk_weighted<7 | 8> with a live second component against double_helper's longdouble terms: the matrix's smallest
+    cell, and N = 33 stars under 65 rows."""
+    for n, n_rows in ((1, 1), (33, 65)):
+        for scheme in ("exponential", "poisson", "explicit"):
+            print(model, free, n, n_rows, scheme, "largest column error", _check_cell(model, free, n, n_rows, scheme))
 
 
 def test_unit_weights_give_the_unweighted_gradient_bits():

@@ -17,6 +17,7 @@ import subprocess
 
 import numpy as np
 
+import double_helper as dh
 import emul_helper as eh
 import grad_bounds as gb
 import grad_helper as gh
@@ -134,7 +135,7 @@ def emul_weighted(case, rows, rep, scheme, seed=SEED, explicit=None, chunk_len=9
     params = np.ascontiguousarray(case["params"][rows])
     rec = eh.pack_records(case["cat"], model, case["centre"])
     wp = eh.pack_walkers(params, model, free)
-    k = gh.n_columns(model, free)
+    k = dh.n_columns(model, free) if model in dh.MODELS else gh.n_columns(model, free)
     rep = np.ascontiguousarray(rep, dtype=np.int64)
     assert rep.size == len(rows) and params.shape[1] == k
     wt = None if explicit is None else np.ascontiguousarray(np.asarray(explicit, dtype=np.float64).T)
@@ -153,6 +154,9 @@ _terms = {}
 def star_terms(model, cat, row, centre):
     """{"v80", "v64": (N,) value terms; "g80", "g64": (K, N) gradient terms} of one parameter row, computed once."""
     key = (model, centre, np.asarray(row).tobytes(), tuple(sorted((k, np.asarray(v).tobytes()) for k, v in cat.items())))
+    if key not in _terms and model in dh.MODELS:               # the double models: double_helper's restatements
+        _terms[key] = {"v80": dh.per_star(model, cat, row, centre, L)[0], "v64": dh.per_star(model, cat, row, centre, np.float64)[0],
+                       "g80": dh.grad_terms(model, cat, row, centre, L), "g64": dh.grad_terms(model, cat, row, centre, np.float64)}
     if key not in _terms:
         _terms[key] = {"v80": vh.per_star(model, cat, row, centre, L)[0],
                        "v64": vh.per_star(model, cat, row, centre, np.float64)[0],
