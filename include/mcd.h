@@ -371,6 +371,43 @@ int mcd_weighted_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const doub
 int mcd_bootstrap_weights(int32_t scheme, uint64_t seed, int64_t rep0, int64_t n_reps, int64_t star0, int64_t n_stars,
                           double* w /* [n_reps][n_stars] */);
 
+/* Simulated catalogues, resident on the device: every parameter row sees the catalogue with the velocities of its own
+ * simulation (simulation-based calibration: Cook, Gelman & Rubin 2006; Talts et al. 2018; injection-recovery).  Positions
+ * and verr stay the observed ones; only the velocities are replaced, by a set of n_sims velocity columns kept on the
+ * catalogue's device.
+ * mcd_simulate draws simulation sim0 + e at the truth row truths[e] (row-major [E][K], the kernel columns of
+ * mcd_loglike_batch).  For star i (index in catalogue order), with (d*, n*) of that row as for mcd_posterior_predictive and
+ * g, u the numbers of mcd_replicate_check's stream at (seed, sim0 + e, i) (mcd_replicate_numbers gives both, bit for bit):
+ *   v' = (v_i - d*) + sqrt(n*) g                         the model has no background, or u < m* (a cluster star)
+ *      = mu_b + sqrt(verr_i^2 + sigma_b^2) g             otherwise (a background star)
+ * with m* and (mu_b, sigma_b) as for mcd_replicate_check: the truth row's membership prior and (v_back, sigma_back), or
+ * (bg_mean, bg_sigma) for the fixed-background models (ignored otherwise; NaN: none).  A velocity is a function of
+ * (seed, sim0 + e, i, truth row) alone: n_sims, the chunk plan and the launch shape never change it.  The set stays
+ * resident and replaces the previous one; with `velocities` it is also copied back, row-major [E][n_stars].  A non-finite
+ * generated velocity (a truth row outside the model's domain) is MCD_ERR_NONFINITE: the message names the first
+ * (simulation, star), and no set is left resident.
+ * mcd_simulated_set makes the caller's own velocities (row-major [E][n_stars], finite) the resident set, with the
+ * (bg_mean, bg_sigma) the fixed-background models evaluate them under.
+ * mcd_simulated_loglike: out[r] = sum_i l_i(theta[r]; v'(row_sim[r], i)), l_i the star's plain term (what
+ * mcd_loglike_per_star returns) with v' in place of v_i, added per chunk in star order and over the chunks in a fixed
+ * order.  The background term of the fixed-background models is the Gaussian (bg_mean, bg_sigma) of the set at v'; the
+ * catalogue's lnlike_bg column, which belongs to the observed velocities, is not read.  A set that holds the observed
+ * velocities gives mcd_loglike_per_star's sum for the other families.  Several rows may share a simulation; out = NULL is
+ * MCD_OK without work.  Synchronous and deterministic: given the resident set, bit-identical from run to run.
+ * mcd_simulated_info: the simulations of the resident set, 0 when there is none.
+ * MCD_ERR_INVALID, with a message, nothing written and the resident set untouched: a binned or a float32 catalogue;
+ * several devices or a communicator; a foreign k; n_sims < 1; sim0 < 0; n_sims x n_stars x 8 bytes beyond 1 GiB; n_rows
+ * < 1 or > 65536; no resident set; a row_sim outside [0, n_sims); a fixed-background model without finite bg_mean and
+ * bg_sigma >= 0; a non-finite explicit velocity.  A set is released with the catalogue.  All three wait under the
+ * context's deadline and honour option "timing" (mcd_last_kernel_ms: the main kernel) and option "chunk_len". */
+int mcd_simulate(mcd_catalog* cat, int64_t n_sims, int32_t k, const double* truths /* [E][K] */, uint64_t seed, int64_t sim0,
+                 double bg_mean, double bg_sigma /* NaN: none */, double* velocities /* [E][n_stars], may be NULL */);
+int mcd_simulated_set(mcd_catalog* cat, int64_t n_sims, const double* velocities /* [E][n_stars] */, double bg_mean,
+                      double bg_sigma);
+int mcd_simulated_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
+                          const int64_t* row_sim /* [R] */, double* out /* [R], may be NULL */);
+int mcd_simulated_info(const mcd_catalog* cat, int64_t* n_sims);
+
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute
  * whose output is the `lnlike_bg` column of a MCD_MODEL_CONST_BGFIXED / _PROFILE_BGDENS catalogue (runner.py:96-106).

@@ -73,6 +73,12 @@ SYMBOLS = {
                                                  _c_double_p, _c_double_p]),
     "mcd_weighted_loglike": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_void_p,
                                             _c_double_p]),
+    "mcd_simulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, ctypes.c_uint64, ctypes.c_int64,
+                                    ctypes.c_double, ctypes.c_double, _c_double_p]),
+    "mcd_simulated_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_double]),
+    "mcd_simulated_loglike": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_int64_p,
+                                             _c_double_p]),
+    "mcd_simulated_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p]),
     "mcd_bootstrap_weights": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, _c_double_p]),
     "mcd_moment_match": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p,
@@ -833,6 +839,69 @@ class Catalog(object):
         rc = self.lib.mcd_weighted_loglike(self.handle, p.shape[0], self.k, _ptr(p), ctypes.byref(d), _ptr(out))
         _check(self.lib, rc, "mcd_weighted_loglike")
         return out
+
+    def simulate(self, truth_table, seed, sim0=0, bg_mean=float("nan"), bg_sigma=float("nan"), want_velocities=True):
+        """Simulated catalogues drawn on the device (include/mcd.h: mcd_simulate): ``truth_table`` (E, K) kernel rows ->
+        (E, n_stars) velocities, simulation ``sim0 + e`` drawn from the model at row e on the observed positions and
+        ``verr``, with the numbers ``replicate_numbers(seed, sim0 + e, 1, 0, n_stars)``.  The set stays resident on the
+        catalogue's device for ``simulated_loglike`` and replaces the previous one.  ``bg_mean`` / ``bg_sigma``: the
+        background's Gaussian for the fixed-background models.  ``want_velocities`` = False passes a null pointer and
+        returns None.  Un-binned float64 catalogues on one device; synchronous and bit-identical from run to run."""
+        self._alive()
+        p = _f64(truth_table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("truth_table must have shape (E, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        out = np.empty((p.shape[0], self.n_stars), dtype=np.float64) if want_velocities else None
+        rc = self.lib.mcd_simulate(self.handle, p.shape[0], self.k, _ptr(p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sim0),
+                                   float(bg_mean), float(bg_sigma), _ptr(out))
+        _check(self.lib, rc, "mcd_simulate")
+        return out
+
+    def simulated_set(self, velocities, bg_mean=float("nan"), bg_sigma=float("nan")):
+        """Make the caller's own mock velocities the resident set (include/mcd.h: mcd_simulated_set): ``velocities``
+        (E, n_stars), finite -- an N-body snapshot, or a catalogue with injected binaries that the model cannot draw.
+        ``bg_mean`` / ``bg_sigma``: the Gaussian the fixed-background models evaluate the background term with."""
+        self._alive()
+        v = _f64(velocities)
+        if v.ndim == 1:
+            v = v[None, :]
+        if v.ndim != 2 or v.shape[1] != self.n_stars:
+            raise ValueError("velocities must have shape (E, {0})".format(self.n_stars))
+        v = np.ascontiguousarray(v)
+        rc = self.lib.mcd_simulated_set(self.handle, v.shape[0], _ptr(v), float(bg_mean), float(bg_sigma))
+        _check(self.lib, rc, "mcd_simulated_set")
+
+    def simulated_loglike(self, table, row_sim):
+        """Every row against the velocities of its own simulation (include/mcd.h: mcd_simulated_loglike): ``table`` (R, K)
+        kernel rows, ``row_sim`` (R,) int64 the simulation of the resident set that every row is evaluated on -> (R,)
+        sum_i l_i with the simulated velocity in place of the observed one: what the lock-stepped fits of
+        ``Runner.simulated_fits`` evaluate twice per step.  Several rows may share a simulation.  Un-binned float64
+        catalogues on one device; synchronous and, given the resident set, bit-identical from run to run."""
+        self._alive()
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (R, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        sim = np.ascontiguousarray(row_sim, dtype=np.int64).reshape(-1)
+        if sim.size != p.shape[0]:
+            raise ValueError("row_sim must hold one simulation per row of the table")
+        out = np.empty(p.shape[0], dtype=np.float64)
+        rc = self.lib.mcd_simulated_loglike(self.handle, p.shape[0], self.k, _ptr(p), sim.ctypes.data_as(_c_int64_p), _ptr(out))
+        _check(self.lib, rc, "mcd_simulated_loglike")
+        return out
+
+    @property
+    def simulated_sims(self):
+        """Simulations of the resident set (include/mcd.h: mcd_simulated_info), 0 when there is none."""
+        self._alive()
+        n = ctypes.c_int64(0)
+        _check(self.lib, self.lib.mcd_simulated_info(self.handle, ctypes.byref(n)), "mcd_simulated_info")
+        return int(n.value)
 
     REPLICATE_FIELDS = ("s1", "s2", "s3", "s4", "sin", "cos", "max", "tail3")
 

@@ -313,6 +313,29 @@ class BinnedConstantFit(ConstantFit):
     def lnprob_weighted_batch(self, *args, **kwargs):
         return self.bagged()
 
+    def simulated_fits(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: fits of simulated catalogues (sample_prior, simulate, simulated_set, "
+                                  "lnprob_simulated_batch, simulated_fits, sbc, recovery) are defined for un-binned fits "
+                                  "only; fit the bins' stars with ConstantFit")
+
+    def sample_prior(self, *args, **kwargs):
+        return self.simulated_fits()
+
+    def simulate(self, *args, **kwargs):
+        return self.simulated_fits()
+
+    def simulated_set(self, *args, **kwargs):
+        return self.simulated_fits()
+
+    def lnprob_simulated_batch(self, *args, **kwargs):
+        return self.simulated_fits()
+
+    def sbc(self, *args, **kwargs):
+        return self.simulated_fits()
+
+    def recovery(self, *args, **kwargs):
+        return self.simulated_fits()
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

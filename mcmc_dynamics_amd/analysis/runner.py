@@ -496,6 +496,141 @@ def bagged_summary(chain, n_burn, names, thin=1):
             "names": list(names)}
 
 
+SIMULATED_PERCENTILES = (2.275, 2.5, 15.865, 50.0, 84.135, 97.5, 97.725)     # the central 68.27 % and 95.45 % intervals' ends
+
+
+def _simulated_kept(chain, n_burn, thin, who):
+    chain = np.asarray(chain, dtype=np.float64)
+    if chain.ndim != 4:
+        raise ValueError("{0}: chain must have shape (E, W, steps, P)".format(who))
+    if int(thin) < 1:
+        raise ValueError("{0}: thin must be >= 1".format(who))
+    if not 0 <= int(n_burn) < chain.shape[2]:
+        raise ValueError("{0}: n_burn must lie in [0, steps)".format(who))
+    return chain[:, :, int(n_burn)::int(thin), :]
+
+
+def simulated_fit_summary(chain, n_burn, truths=None, thin=1):
+    """Per-fit summaries of the lock-stepped fits of ``Runner.simulated_fits`` from their chains ``chain`` (E, W, steps, P),
+    over every ``thin``-th step after ``n_burn``: ``mean``, ``std`` (E, P), ``percentiles`` ({q: (E, P)} for
+    ``SIMULATED_PERCENTILES``), ``tau`` (E, P) the integrated autocorrelation times in kept steps and ``converged`` (E,)
+    whether the fit keeps 50 of its largest (``diagnostics.summary`` on the host), ``n_samples`` per fit and, with
+    ``truths`` (E, P), ``z`` = (mean - truth) / std."""
+    from .. import diagnostics
+    kept = _simulated_kept(chain, n_burn, thin, "simulated_fit_summary")
+    n_e, n_w, n_t, n_p = kept.shape
+    draws = kept.reshape(n_e, n_w * n_t, n_p)
+    mean, std = draws.mean(axis=1), draws.std(axis=1, ddof=1)
+    diag = diagnostics.summary(np.ascontiguousarray(np.transpose(kept, (2, 0, 1, 3))), context=None)
+    tau = np.atleast_2d(diag["tau"]).reshape(n_e, n_p)
+    out = {"mean": mean, "std": std, "percentiles": {q: np.percentile(draws, q, axis=1) for q in SIMULATED_PERCENTILES},
+           "tau": tau, "converged": np.all(np.atleast_2d(diag["converged"]).reshape(n_e, -1), axis=1), "n_samples": int(n_w * n_t)}
+    if truths is not None:
+        truths = np.asarray(truths, dtype=np.float64).reshape(n_e, n_p)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["z"] = (mean - truths) / std
+    return out
+
+
+def sbc_summary(chain, truths, n_burn, thin=None, n_bins=8, prior_variance=None):
+    """Simulation-based calibration (Cook, Gelman & Rubin 2006; Talts et al. 2018) of the fits ``chain`` (E, W, steps, P)
+    of E catalogues simulated at ``truths`` (E, P), themselves draws from the prior: if sampler, likelihood and prior
+    handling are right, the rank of a truth among the posterior draws of its own catalogue is uniform.
+
+    * ``rank`` (E, P): the number of pooled draws below the truth; the draws are all walkers of every ``thin``-th step
+      after ``n_burn``, ``n_draws`` of them per fit.  ``thin`` = None: the largest integrated autocorrelation time over fits
+      and parameters, rounded up (``thin`` in the result tells), so that the draws of a walker are nearly independent;
+    * ``hist`` (P, n_bins): the ranks 0 .. n_draws in ``n_bins`` bins of equal width, ``expected`` (n_bins,) the uniform
+      expectation of every bin, ``chi2`` (P,) against it, ``dof`` = n_bins - 1 and ``p_value`` (P,) its upper tail;
+    * ``ecdf_max`` (P,): the largest distance between the ranks' empirical distribution function and the uniform one;
+    * ``contraction`` (P,): 1 - mean posterior variance / ``prior_variance`` (P,), NaN where that is not finite or not given.
+
+    Too narrow posteriors (or a fit told too small errors) pile the ranks up at both ends (a U shape), too wide ones in the
+    middle; a biased fit tilts the histogram."""
+    from scipy.special import gammaincc
+    from .. import diagnostics
+    truths = np.atleast_2d(np.asarray(truths, dtype=np.float64))
+    if int(n_bins) < 2:
+        raise ValueError("sbc_summary: n_bins must be >= 2")
+    n_bins = int(n_bins)
+    if thin is None:
+        full = _simulated_kept(chain, n_burn, 1, "sbc_summary")
+        diag = diagnostics.summary(np.ascontiguousarray(np.transpose(full, (2, 0, 1, 3))), context=None)
+        tau = np.asarray(diag["tau"], dtype=np.float64)
+        worst = np.nanmax(tau) if np.any(np.isfinite(tau)) else 1.0
+        thin = max(1, int(np.ceil(worst)))
+    kept = _simulated_kept(chain, n_burn, thin, "sbc_summary")
+    n_e, n_w, n_t, n_p = kept.shape
+    if truths.shape != (n_e, n_p):
+        raise ValueError("sbc_summary: truths must have shape {0}".format((n_e, n_p)))
+    draws = kept.reshape(n_e, n_w * n_t, n_p)
+    n_draws = n_w * n_t
+    rank = np.count_nonzero(draws < truths[:, None, :], axis=1).astype(np.int64)
+    bin_of = np.arange(n_draws + 1, dtype=np.int64) * n_bins // (n_draws + 1)
+    expected = np.bincount(bin_of, minlength=n_bins) * (float(n_e) / (n_draws + 1))
+    hist = np.stack([np.bincount(bin_of[rank[:, p]], minlength=n_bins) for p in range(n_p)])
+    chi2 = ((hist - expected) ** 2 / expected).sum(axis=1)
+    u = np.sort((rank + 0.5) / (n_draws + 1.0), axis=0)
+    i = np.arange(1, n_e + 1, dtype=np.float64)[:, None]
+    ecdf_max = np.maximum(np.max(i / n_e - u, axis=0), np.max(u - (i - 1.0) / n_e, axis=0))
+    contraction = np.full(n_p, np.nan)
+    if prior_variance is not None:
+        pv = np.asarray(prior_variance, dtype=np.float64).reshape(n_p)
+        good = np.isfinite(pv) & (pv > 0)
+        contraction[good] = 1.0 - draws.var(axis=1, ddof=1).mean(axis=0)[good] / pv[good]
+    return {"rank": rank, "n_draws": int(n_draws), "thin": int(thin), "hist": hist, "expected": expected, "chi2": chi2,
+            "dof": n_bins - 1, "p_value": gammaincc(0.5 * (n_bins - 1), 0.5 * chi2), "ecdf_max": ecdf_max,
+            "contraction": contraction, "n_sims": int(n_e), "n_bins": n_bins}
+
+
+def _recovery_stats(samples, truth):
+    """samples (E, n) of one scalar per fit, its true value -> the recovery figures of that scalar."""
+    n_e = samples.shape[0]
+    mean, std = samples.mean(axis=1), samples.std(axis=1, ddof=1)
+    q = np.percentile(samples, [2.275, 15.865, 84.135, 97.725, 2.5], axis=1)
+    c68 = float(np.mean((q[1] <= truth) & (truth <= q[2])))
+    c95 = float(np.mean((q[0] <= truth) & (truth <= q[3])))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = (mean - truth) / std
+    return {"truth": float(truth), "bias": float(np.mean(mean - truth)), "scatter": float(np.std(mean, ddof=1)) if n_e > 1 else np.nan,
+            "rmse": float(np.sqrt(np.mean((mean - truth) ** 2))),
+            "coverage": {68: c68, 95: c95},
+            "coverage_se": {68: float(np.sqrt(c68 * (1.0 - c68) / n_e)), 95: float(np.sqrt(c95 * (1.0 - c95) / n_e))},
+            "z_mean": float(np.mean(z)), "z_std": float(np.std(z, ddof=1)) if n_e > 1 else np.nan, "q2.5": q[4]}
+
+
+def recovery_summary(chain, truth, n_burn, names, thin=1, functions=None, null=None):
+    """Injection-recovery figures of the fits ``chain`` (E, W, steps, P) of E catalogues simulated at the one ``truth`` (P,),
+    over every ``thin``-th step after ``n_burn``.  Per parameter, as (P,) arrays: ``bias`` (the mean over the fits of
+    posterior mean - truth), ``scatter`` (the standard deviation of the posterior means), ``rmse``, ``coverage`` ({68, 95}:
+    the share of fits whose central 68.27 % / 95.45 % interval holds the truth) with ``coverage_se`` (binomial, from the
+    share itself), and ``z_mean`` / ``z_std`` of z = (mean - truth) / std (0 and 1 for a calibrated fit).
+
+    ``functions``: {name: f}, f maps draws (n, P) to (n,) (e.g. a rotation amplitude); ``functions[name]`` in the result
+    holds the same figures as scalars for f, with its value at the truth, and, with ``null`` (a parameter row, P), ``exceeds``:
+    the share of fits whose 2.5 % quantile of f lies above f(null) -- how often the effect is detected."""
+    kept = _simulated_kept(chain, n_burn, thin, "recovery_summary")
+    n_e, n_w, n_t, n_p = kept.shape
+    truth = np.asarray(truth, dtype=np.float64).reshape(-1)
+    if truth.size != n_p or len(names) != n_p:
+        raise ValueError("recovery_summary: truth and names must hold one entry per parameter")
+    draws = kept.reshape(n_e, n_w * n_t, n_p)
+    per = [_recovery_stats(draws[:, :, p], truth[p]) for p in range(n_p)]
+    out = {k: np.array([s[k] for s in per]) for k in ("bias", "scatter", "rmse", "z_mean", "z_std")}
+    out["coverage"] = {c: np.array([s["coverage"][c] for s in per]) for c in (68, 95)}
+    out["coverage_se"] = {c: np.array([s["coverage_se"][c] for s in per]) for c in (68, 95)}
+    out.update({"truth": truth, "n_sims": int(n_e), "n_samples": int(n_w * n_t), "names": list(names), "functions": {}})
+    for name, f in (functions or {}).items():
+        samples = np.stack([np.asarray(f(d), dtype=np.float64).reshape(-1) for d in draws])
+        s = _recovery_stats(samples, float(np.asarray(f(truth[None, :])).reshape(-1)[0]))
+        low = s.pop("q2.5")
+        if null is not None:
+            at_null = float(np.asarray(f(np.asarray(null, dtype=np.float64).reshape(1, n_p))).reshape(-1)[0])
+            s["null"], s["exceeds"] = at_null, float(np.mean(low > at_null))
+        out["functions"][name] = s
+    return out
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -1020,6 +1155,241 @@ class Runner(object):
         sampler.run_mcmc(pos, int(n_steps))
         out = bagged_summary(sampler.chain, n_burn, self.fitted_parameters, thin=thin)
         out.update({"sampler": sampler, "seed": int(seed), "scheme": scheme, "bag_fraction": float(bag_fraction)})
+        return out
+
+    # ------------------------------------------------------------------ fits of simulated catalogues: SBC, recovery (new)
+    def _proper_prior(self, who):
+        """(plan, lo, hi, kind, p0, p1) over the free parameters of a fit whose prior can be sampled."""
+        plan = self._plan()
+        if not plan.simple:
+            raise NotImplementedError("Runner.{0}: expr / lnprior-expression parameters have no prior to draw from".format(who))
+        improper = self.improper_parameters()
+        if improper:
+            raise ValueError("Runner.{0}: the prior of {1} is improper (give two finite bounds, or a normal / log-normal "
+                             "prior)".format(who, ", ".join(improper)))
+        n_p = plan.free_idx.size
+        kind, p0, p1 = (np.zeros(n_p, dtype=np.int32), np.zeros(n_p), np.ones(n_p)) if plan.prior is None else \
+            (np.asarray(a) for a in plan.prior)
+        return plan, plan.lo[plan.free_idx], plan.hi[plan.free_idx], kind, p0, p1
+
+    def _prior_quantile(self, u, who):
+        """u (n, P) in (0, 1) -> the prior's quantiles: the inverse CDF of every free parameter's prior, truncated to its box."""
+        from scipy.special import ndtr, ndtri
+        _, lo, hi, kind, p0, p1 = self._proper_prior(who)
+        u = np.asarray(u, dtype=np.float64)
+        out = np.empty_like(u)
+        for j in range(u.shape[1]):
+            if kind[j] == _native.PRIOR_FLAT:
+                x = lo[j] + u[:, j] * (hi[j] - lo[j])
+            else:
+                log = kind[j] == _native.PRIOR_LOGNORMAL
+                with np.errstate(divide="ignore"):
+                    a, b = (np.log(max(lo[j], 0.0)), np.log(hi[j])) if log else (lo[j], hi[j])
+                ca, cb = ndtr((a - p0[j]) / p1[j]), ndtr((b - p0[j]) / p1[j])
+                x = p0[j] + p1[j] * ndtri(ca + u[:, j] * (cb - ca))
+                x = np.exp(x) if log else x
+            out[:, j] = np.clip(x, lo[j], hi[j])
+        return out
+
+    def sample_prior(self, n, seed=None):
+        """``n`` draws from the prior itself, (n, P) free-parameter vectors: a finite box gives a uniform draw, a normal or
+        log-normal prior is truncated to its box by inverse CDF.  Host NumPy, a function of ``seed``.  ValueError, naming
+        ``improper_parameters()``, when a free parameter has no proper prior; NotImplementedError for ``expr`` /
+        ``lnprior``-expression parameters."""
+        n_p = self._proper_prior("sample_prior")[0].free_idx.size
+        rng = np.random.default_rng(seed)
+        # (the open interval: ndtri(0) is -inf)
+        u = (rng.integers(0, 1 << 53, size=(int(n), n_p)).astype(np.float64) + 0.5) * 2.0 ** -53
+        return self._prior_quantile(u, "sample_prior")
+
+    def prior_variance(self, n_nodes=1 << 16):
+        """(P,) variances of the free parameters' priors, by the midpoint rule on ``n_nodes`` quantiles."""
+        n_p = self._proper_prior("prior_variance")[0].free_idx.size
+        u = np.repeat(((np.arange(int(n_nodes)) + 0.5) / int(n_nodes))[:, None], n_p, axis=1)
+        return self._prior_quantile(u, "prior_variance").var(axis=0)
+
+    def _simulated_background(self):
+        try:
+            return self._replicate_background()
+        except NotImplementedError as exc:
+            raise NotImplementedError(str(exc).replace("Runner.replicate_check", "Runner.simulate"))
+
+    def _truth_table(self, truths, who):
+        """truths (E, P) free-parameter vectors inside the prior -> ((E, P) array, the resolved parameter columns)."""
+        n_p = self.n_fitted_parameters
+        truths = np.atleast_2d(np.asarray(truths, dtype=np.float64))
+        if truths.ndim != 2 or truths.shape[1] != n_p:
+            raise ValueError("{0}: truths must have shape (E, {1})".format(who, n_p))
+        pars = self.parameters
+        resolved = pars.resolve_batch(truths)
+        if not np.all(np.isfinite(pars.lnprior_batch(resolved))):
+            raise ValueError("{0}: a truth row lies outside the prior".format(who))
+        return truths, resolved
+
+    def simulate(self, truths, seed, sim0=0):
+        """Simulated catalogues: ``truths`` (E, P) free-parameter vectors -> (E, n_data) velocities in km/s, catalogue e
+        drawn on the device from the model at truths[e], on the observed positions and velocity errors (simulation id
+        ``sim0 + e``; a velocity is a function of (seed, id, star, truth) alone and ``_native.replicate_numbers`` replays
+        its random numbers).  The set stays resident on the device for ``lnprob_simulated_batch``.  Fixed-background
+        classes draw background stars from their ``background.Gaussian``."""
+        self._holdout_check("simulate")
+        _, resolved = self._truth_table(truths, "simulate")
+        bg = self._simulated_background()
+        cat = self._ensure_catalog()
+        return cat.simulate(self._kernel_table(resolved), seed, sim0=sim0, bg_mean=bg[0], bg_sigma=bg[1])
+
+    def simulated_set(self, velocities):
+        """Make the caller's own mock velocities (E, n_data), in km/s, the resident set of ``lnprob_simulated_batch``."""
+        self._holdout_check("simulated_set")
+        bg = self._simulated_background()
+        velocities = np.atleast_2d(np.asarray(velocities, dtype=np.float64))
+        self._ensure_catalog().simulated_set(velocities, bg_mean=bg[0], bg_sigma=bg[1])
+        return velocities
+
+    def lnprob_simulated_batch(self, values, row_sim):
+        """``lnprob_batch`` with every row evaluated on the velocities of its own simulation: ``values`` (..., P)
+        free-parameter vectors and ``row_sim``, one simulation id of the resident set (``simulate``, ``simulated_set``) per
+        row in C order, -> (...) values of  sum_i lnL_i(v' of the row's simulation) + ln prior,  one launch of the device's
+        simulated VALUE kernel (``_native.Catalog.simulated_loglike``).  Box and structured priors as in ``lnprob_batch``:
+        rows outside the prior are -inf and take a donor row for the launch.  Runs on one device in one process, on
+        un-binned float64 catalogues."""
+        self._holdout_check("lnprob_simulated_batch")
+        values = np.asarray(values, dtype=np.float64)
+        n_p = self.n_fitted_parameters
+        if values.ndim < 1 or values.shape[-1] != n_p:
+            raise ValueError("values must have shape (..., {0})".format(n_p))
+        lead = values.shape[:-1]
+        sim = np.ascontiguousarray(row_sim, dtype=np.int64).reshape(-1)
+        rows = values.reshape(-1, n_p)
+        if sim.size != rows.shape[0]:
+            raise ValueError("row_sim must hold one simulation per row of values")
+        pars = self.parameters
+        resolved = pars.resolve_batch(rows)
+        lp = pars.lnprior_batch(resolved)
+        ok = np.isfinite(lp)
+        out = np.full(lp.shape, -np.inf)
+        if ok.any():
+            if not ok.all():
+                donor = int(np.flatnonzero(ok)[0])
+                resolved = OrderedDict((k, np.where(ok, col, col[donor])) for k, col in resolved.items())
+            lnl = self._ensure_catalog().simulated_loglike(self._kernel_table(resolved), sim)
+            out[ok] = lnl[ok] + lp[ok]
+        return out.reshape(lead)
+
+    def _simulated_start(self, truths, n_walkers, seed):
+        """(E, W, P) start positions: a ball about each truth, truth + 0.01 x prior scale x normal, redrawn until inside
+        the prior.  The prior scale: the width of a finite box, the scale of a normal prior, s x truth of a log-normal one,
+        max(|truth|, 1) where there is neither."""
+        plan = self._plan()
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        n_e, n_p = truths.shape
+        scale = np.where(np.isfinite(hi - lo), hi - lo, np.maximum(np.abs(truths), 1.0))
+        scale = np.broadcast_to(scale, truths.shape).copy()
+        if plan.prior is not None:
+            kind, _, p1 = (np.asarray(a) for a in plan.prior)
+            scale[:, kind == _native.PRIOR_NORMAL] = p1[kind == _native.PRIOR_NORMAL]
+            log = kind == _native.PRIOR_LOGNORMAL
+            scale[:, log] = p1[log] * np.maximum(np.abs(truths[:, log]), 1e-300)
+        rng = np.random.default_rng([int(seed) & 0xFFFFFFFFFFFFFFFF, 0x73696D])
+        pars = self.parameters
+        pos = truths[:, None, :] + 0.01 * scale[:, None, :] * rng.normal(size=(n_e, n_walkers, n_p))
+        for _ in range(100):
+            bad = ~np.isfinite(pars.lnprior_batch(pars.resolve_batch(pos.reshape(-1, n_p)))).reshape(n_e, n_walkers)
+            if not bad.any():
+                return pos
+            e, _w = np.nonzero(bad)
+            pos[bad] = truths[e] + 0.01 * scale[e] * rng.normal(size=(int(bad.sum()), n_p))
+        raise ValueError("simulated_fits: no start positions inside the prior around a truth (it sits on a bound)")
+
+    def simulated_fits(self, truths, n_walkers=64, n_steps=600, n_burn=200, seed=None, velocities=None, pos=None, thin=1):
+        """Fit E simulated catalogues in lock step: catalogue e is drawn from the model at ``truths[e]`` (``simulate``), or is
+        row e of the caller's ``velocities`` (E, n_data) in km/s (``simulated_set``).  E ensembles of ``n_walkers`` walkers
+        take ``n_steps`` stretch-move steps (``BinnedSampler``, ``rng="device"``: the chains are a function of ``seed``);
+        one launch of the simulated value kernel (``lnprob_simulated_batch``) evaluates all E W / 2 proposals of a half
+        step, row (e, w) on simulation e.  ``pos``: start positions (E, W, P), default a small ball about each truth.
+        The velocities and the chains take the one ``seed``; their generators have different keys.
+
+        Returns ``simulated_fit_summary`` of the chains (per fit: ``mean``, ``std``, ``percentiles``, ``tau``, ``converged``,
+        ``z`` = (mean - truth) / std) plus ``truths``, ``velocities``, ``sampler`` (``chain``: (E, W, steps, P)) and
+        ``seed``."""
+        self._holdout_check("simulated_fits")
+        from .binned import BinnedSampler
+        n_w, n_p = int(n_walkers), self.n_fitted_parameters
+        if int(thin) < 1:
+            raise ValueError("simulated_fits: thin must be >= 1")
+        if not 0 <= int(n_burn) < int(n_steps):
+            raise ValueError("simulated_fits: n_burn must lie in [0, n_steps)")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        truths, _ = self._truth_table(truths, "simulated_fits")
+        n_e = truths.shape[0]
+        if velocities is None:
+            velocities = self.simulate(truths, seed)
+        else:
+            velocities = np.atleast_2d(np.asarray(velocities, dtype=np.float64))
+            if velocities.shape != (n_e, self.n_data):
+                raise ValueError("simulated_fits: velocities must have shape {0}".format((n_e, self.n_data)))
+            velocities = self.simulated_set(velocities)
+        if pos is None:
+            pos = self._simulated_start(truths, n_w, seed)
+        pos = np.ascontiguousarray(pos, dtype=np.float64)
+        if pos.shape != (n_e, n_w, n_p):
+            raise ValueError("Array with starting values has invalid shape: expected {0}".format((n_e, n_w, n_p)))
+        pars = self.parameters
+        if not np.all(np.isfinite(pars.lnprior_batch(pars.resolve_batch(pos.reshape(-1, n_p))))):
+            raise ValueError("Invalid initial guesses: start positions outside the prior")
+
+        def log_prob(values):
+            # (E, rows, P): the rows of ensemble e on simulation e
+            return self.lnprob_simulated_batch(values, np.repeat(np.arange(n_e, dtype=np.int64), values.shape[1]))
+
+        sampler = BinnedSampler(n_e, n_w, n_p, log_prob, seed=seed, rng="device")
+        logger.info("simulated fits: %d catalogues, %d walkers each, %d steps", n_e, n_w, n_steps)
+        sampler.reserve(int(n_steps))
+        sampler.run_mcmc(pos, int(n_steps))
+        out = simulated_fit_summary(sampler.chain, n_burn, truths, thin=thin)
+        out.update({"truths": truths, "velocities": velocities, "sampler": sampler, "seed": int(seed),
+                    "names": list(self.fitted_parameters)})
+        return out
+
+    def sbc(self, n_sims=256, n_walkers=32, n_steps=600, n_burn=200, seed=None, n_bins=8, thin=None, truths=None):
+        """Simulation-based calibration of this fit: ``n_sims`` truths drawn from the prior (``sample_prior(n_sims, seed)``;
+        or the caller's ``truths``), one simulated catalogue each, all fitted in lock step (``simulated_fits``), and the
+        rank statistics of ``sbc_summary`` (``thin`` = None: the largest autocorrelation time).  Returns that summary plus
+        ``fits`` (what ``simulated_fits`` returned), ``truths``, ``names`` and ``seed``."""
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        if truths is None:
+            truths = self.sample_prior(int(n_sims), seed=seed)
+        fits = self.simulated_fits(truths, n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed)
+        try:
+            prior_variance = self.prior_variance()
+        except (ValueError, NotImplementedError):
+            prior_variance = None
+        out = sbc_summary(fits["sampler"].chain, fits["truths"], n_burn, thin=thin, n_bins=n_bins, prior_variance=prior_variance)
+        out.update({"fits": fits, "truths": fits["truths"], "names": fits["names"], "seed": int(seed)})
+        return out
+
+    def recovery(self, truth, n_sims=64, n_walkers=32, n_steps=600, n_burn=200, seed=None, thin=1, functions=None, null=None):
+        """Injection-recovery: ``n_sims`` catalogues simulated at the one ``truth`` (P,) -- or at every row of a grid (G, P),
+        ``n_sims`` each -- on the data's positions and velocity errors, fitted in lock step (``simulated_fits``), and
+        ``recovery_summary`` per truth: bias, scatter, interval coverage, z scores, and for every entry of ``functions`` the
+        same plus ``exceeds``, the share of fits whose 2.5 % quantile of the function lies above its value at the
+        parameter row ``null`` (the detection rate).  Returns the summary of a single truth, or ``{"grid": [summary per
+        row]}`` for a grid; both carry ``fits`` and ``seed``."""
+        truth = np.asarray(truth, dtype=np.float64)
+        grid = np.atleast_2d(truth)
+        n_s = int(n_sims)
+        if n_s < 1:
+            raise ValueError("recovery: n_sims must be >= 1")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        fits = self.simulated_fits(np.repeat(grid, n_s, axis=0), n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed)
+        chain = fits["sampler"].chain
+        per = [recovery_summary(chain[g * n_s:(g + 1) * n_s], grid[g], n_burn, fits["names"], thin=thin, functions=functions,
+                                null=null) for g in range(grid.shape[0])]
+        out = dict(per[0]) if truth.ndim == 1 else {"grid": per}
+        out.update({"fits": fits, "seed": int(seed)})
         return out
 
     # ------------------------------------------------------------------ Hamiltonian Monte Carlo (new)

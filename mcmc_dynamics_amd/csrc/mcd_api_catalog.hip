@@ -481,6 +481,7 @@ int mcd_catalog_destroy(mcd_catalog* cat) {
     }
     release_holdout(cat);
     release_weighted(cat);
+    release_simulated(cat);
     for (hipEvent_t e : cat->chain_events) (void)hipEventDestroy(e);
     if (cat->chain.d) (void)hipFree(cat->chain.d);
     if (cat->chain.h) (void)hipHostFree(cat->chain.h);
@@ -554,6 +555,7 @@ int mcd_set_option(mcd_catalog* cat, const char* key, int64_t value) {
             }
             release_holdout(cat);
             release_weighted(cat);
+            release_simulated(cat, true);              // (the plans go, the resident set stays)
             cat->cur_walkers = 0;
         }
         return MCD_OK;

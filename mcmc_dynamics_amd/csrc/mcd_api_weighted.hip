@@ -12,7 +12,7 @@ using namespace mcd::host;
 
 MCD_HOST_BEGIN
 
-static void free_weighted_work(WeightedWork& w) {
+void free_weighted_work(WeightedWork& w) {
     if (w.d_chunks) (void)hipFree(w.d_chunks);
     if (w.d_offsets) (void)hipFree(w.d_offsets);
     if (w.d_params) (void)hipFree(w.d_params);
@@ -41,12 +41,8 @@ void release_weighted(mcd_catalog* cat) {
     cat->weights_replicates = -1;
 }
 
-MCD_HOST_END
-
-namespace {
-
 // The chunk table over `records` for n_rows rows and its buffers, from `cache` (the catalogue's for the gradient call,
-// 1 + K fields per row, or the one for the value call, one field) or built now
+// 1 + K fields per row, the one for the value call or the one of mcd_simulated_loglike, one field) or built now
 int weighted_work(mcd_catalog* cat, std::map<int64_t, WeightedWork>& cache, size_t fields, const Shard& sh, int64_t n_rows,
                   WeightedWork** out) {
     auto it = cache.find(n_rows);
@@ -85,6 +81,25 @@ int weighted_work(mcd_catalog* cat, std::map<int64_t, WeightedWork>& cache, size
     *out = &(cache[n_rows] = w);
     return MCD_OK;
 }
+
+// After the D2H copy of a call's results is enqueued: the wait, option "timing", the launch record
+int weighted_finish(mcd_catalog* cat, const std::string& name, WeightedWork& w, int64_t n_rows) {
+    const DeviceSlot& slot = cat->ctx->slots[cat->shards[0].slot];
+    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, name.c_str());
+    if (cat->timing) {
+        float ms = 0.f;
+        MCD_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
+        cat->last_kernel_ms = ms;
+        cat->timing_pending = false;
+    }
+    cat->last_chunks = w.n_chunks;
+    cat->last_grid = mcd::main_grid(w.n_chunks, n_rows);
+    return MCD_OK;
+}
+
+MCD_HOST_END
+
+namespace {
 
 // What both entry points refuse, in the order of include/mcd.h; `name` opens the message
 int weighted_usable(mcd_catalog* cat, const std::string& name, int64_t n_rows, int32_t k, const double* params,
@@ -206,20 +221,7 @@ int weighted_stage(mcd_catalog* cat, const std::string& name, std::map<int64_t, 
     return MCD_OK;
 }
 
-// ... and after the D2H copy of their results is enqueued: the wait, option "timing", the launch record
-int weighted_finish(mcd_catalog* cat, const std::string& name, WeightedWork& w, int64_t n_rows) {
-    const DeviceSlot& slot = cat->ctx->slots[cat->shards[0].slot];
-    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, name.c_str());
-    if (cat->timing) {
-        float ms = 0.f;
-        MCD_HIP(hipEventElapsedTime(&ms, w.e0, w.e1));
-        cat->last_kernel_ms = ms;
-        cat->timing_pending = false;
-    }
-    cat->last_chunks = w.n_chunks;
-    cat->last_grid = mcd::main_grid(w.n_chunks, n_rows);
-    return MCD_OK;
-}
+// ... and after the D2H copy of their results is enqueued: weighted_finish (above)
 
 int weighted_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const mcd_weight_desc* wd,
                           double* out, double* grad) {

@@ -15,6 +15,8 @@
 //   mcd_api_replicate.hip  mcd_replicate_check, mcd_replicate_numbers: replicated-data predictive checks per range of stars
 //   mcd_api_weighted.hip   mcd_weighted_loglike_grad, mcd_weighted_loglike, mcd_bootstrap_weights: value and gradient, or
 //                          the value alone, under per-row star weights
+//   mcd_api_simulated.hip  mcd_simulate, mcd_simulated_set, mcd_simulated_loglike, mcd_simulated_info: simulated catalogues
+//                          resident on the device, and every parameter row against the velocities of its own simulation
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -207,8 +209,9 @@ struct HoldoutWork {
     hipEvent_t e0 = nullptr, e1 = nullptr;   // option "timing": around the main kernel
 };
 
-// mcd_weighted_loglike_grad, mcd_weighted_loglike: the chunk table over `records` for one row count and its buffers
-// (mcd_api_weighted.hip), kept by the catalogue; the value call's have one field where the gradient call's have 1 + K
+// mcd_weighted_loglike_grad, mcd_weighted_loglike, mcd_simulated_loglike: the chunk table over `records` for one row count
+// and its buffers (mcd_api_weighted.hip), kept by the catalogue; the value calls' have one field where the gradient call's
+// have 1 + K
 struct WeightedWork {
     int64_t n_rows = 0;
     int64_t n_chunks = 0;
@@ -282,6 +285,12 @@ int holdout_device_plan(mcd_catalog* cat, const std::vector<int64_t>& ranges, in
 int holdout_device_eval(mcd_catalog* cat, HoldoutWork& w, int64_t n_walkers, const int64_t* d_set_range);
 // mcd_api_weighted.hip
 void release_weighted(mcd_catalog* cat);
+void free_weighted_work(WeightedWork& w);
+int weighted_work(mcd_catalog* cat, std::map<int64_t, WeightedWork>& cache, size_t fields, const Shard& sh, int64_t n_rows,
+                  WeightedWork** out);
+int weighted_finish(mcd_catalog* cat, const std::string& name, WeightedWork& w, int64_t n_rows);
+// mcd_api_simulated.hip
+void release_simulated(mcd_catalog* cat, bool keep_set = false);
 
 MCD_HOST_END
 
@@ -387,6 +396,14 @@ struct mcd_catalog {
     size_t d_weights_bytes = 0;
     int64_t weights_replicates = -1;
     uint64_t weights_print[2] = {0, 0};
+    // simulated catalogues (mcd_simulate, mcd_simulated_set): the resident velocity table [n_stars][n_sims] (grown as needed;
+    // sim_count 0: no set is resident) with the fixed-background models' (mean, sigma^2), and mcd_simulated_loglike's plan
+    // and buffers per row count (d_replicate holds row_sim), released with the catalogue
+    double* d_sim = nullptr;
+    size_t d_sim_bytes = 0;
+    int64_t sim_count = 0;
+    double sim_bg_mean = 0.0, sim_bg_sigma2 = 0.0;
+    std::map<int64_t, mcd::host::WeightedWork> simulated;
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
