@@ -760,6 +760,11 @@ double mcd_last_device_ms(const mcd_catalog* cat);
  *                      instruction per term fewer, relative error of the root <= 4.9e-16, results equal to rounding.  0: never
  *                      (the results of a library without this option, bit for bit).  mcd_last_root_quad tells,
  *                      mcd_last_quad_chunks counts the chunks.
+ *   "block_step"    1 (default): a launch of the bounded narrow-range loop (R = 32) that offers the quadratic form runs the
+ *                      kernel whose quadratic loop does its per-band work -- the fold of the coefficients, the rescale of the
+ *                      running product and the prefetch of a whole band of records -- in one block per 32 stars; admitted
+ *                      per call where 56 raw factors fit between two rescales.  The same results, bit for bit.  0: never
+ *                      (the kernels of a library without this option).  mcd_last_block_step tells.
  *   "target_waves"  number of waves the chunking aims for per device (default 10240)
  *   "chunk_len"     explicit nominal chunk length in stars (rounded up to a multiple of 32; 0, the default: derived from
  *                      "target_waves"); tuning aid
@@ -816,6 +821,9 @@ int mcd_last_root_quad(const mcd_catalog* cat);
 /* ... and the chunks in which every wave took it, counted as mcd_last_direct_chunks is and never more than that; 0 and -1
  * as there. */
 int64_t mcd_last_quad_chunks(const mcd_catalog* cat);
+/* 1 when the most recent main-kernel launch ran the kernel with one block step per 32-star band (option "block_step"), 0 when
+ * not (option off, refused by the guard, no bounded launch with the quadratic form), -1 before the first launch. */
+int mcd_last_block_step(const mcd_catalog* cat);
 /* Kernel family the range guard chose for the batch staged last: 0 plain, 1 fast formulation, 2 narrow-range variant of
  * the mixture kernels (no per-star exponent bookkeeping; chunks holding a star outside its domain -- a certain member, an
  * extreme background likelihood, an empty component -- still run the fast formulation); -1 before any call. */

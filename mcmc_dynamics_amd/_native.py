@@ -138,6 +138,7 @@ SYMBOLS = {
     "mcd_last_exp_split": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_root_quad": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_quad_chunks": (ctypes.c_int64, [ctypes.c_void_p]),
+    "mcd_last_block_step": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_fast_level": (ctypes.c_int, [ctypes.c_void_p]),
     "mcd_last_f32_domain": (ctypes.c_int, [ctypes.c_void_p, _c_double_p, _c_double_p]),
     "mcd_f32_outside": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_double_p, _c_double_p, ctypes.POINTER(ctypes.c_char_p)]),
@@ -1091,6 +1092,13 @@ class Catalog(object):
         0 none; -1 before any launch."""
         return self.lib.mcd_last_quad_chunks(self.handle)
 
+    @property
+    def last_block_step(self):
+        """1: the last main-kernel launch ran the bounded kernel whose quadratic loop takes one block step per 32-star band
+        (option ``block_step`` on a bounded launch with R = 32 that offers the quadratic form, where 56 raw factors fit
+        between two rescales); 0 not; -1 before any launch."""
+        return self.lib.mcd_last_block_step(self.handle)
+
     def hmc_block(self, plan, chol, step_size, n_leap, pos, lnp, seed, step0, n_steps, chain=None, lnprob_chain=None,
                   accepted=None, energy_error=None, jitter=0.1):
         """``mcd_hmc_block``: advance W independent chains by ``n_steps`` Hamiltonian Monte Carlo steps of ``n_leap``
@@ -1249,7 +1257,8 @@ class Catalog(object):
                                                        ctypes.byref(ch), ctypes.byref(rb)), "mcd_last_launch_info")
         return {"workgroups": wg.value, "walker_tile": tile.value, "chunks": ch.value, "record_bytes": rb.value,
                 "series_chunks": self.last_series_chunks, "direct_chunks": self.last_direct_chunks,
-                "exp_split": self.last_exp_split, "root_quad": self.last_root_quad, "quad_chunks": self.last_quad_chunks}
+                "exp_split": self.last_exp_split, "root_quad": self.last_root_quad, "quad_chunks": self.last_quad_chunks,
+                "block_step": self.last_block_step}
 
     def close(self):
         if getattr(self, "handle", None):

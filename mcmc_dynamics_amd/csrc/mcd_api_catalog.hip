@@ -160,6 +160,7 @@ const Option kOptions[] = {
     {"root_series", 0, 1, "root_series: 1 (series root on the narrow chunks of verr-sorted records, default) or 0 (never)", false, false, MCD_SET(c->root_series = (int)v)},
     {"exp_split", 0, 1, "exp_split: 1 (split exponent offset in the direct chunks where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->exp_split = (int)v)},
     {"root_quad", 0, 1, "root_quad: 1 (quadratic series root on 32-star bands where a direct chunk admits it, default) or 0 (never)", false, false, MCD_SET(c->root_quad = (int)v)},
+    {"block_step", 0, 1, "block_step: 1 (one block step per 32-star band in the bounded quadratic loop where the guard admits it, default) or 0 (never)", false, false, MCD_SET(c->block_step = (int)v)},
     {"root_direct", 0, 1, "root_direct: 1 (direct form of the series root where a chunk admits it, default) or 0 (delta form only)", false, false, MCD_SET(c->root_direct = (int)v)},
     {"prefetch", -1, 1, "prefetch: -1 (by record volume, default), 0 (off) or 1 (on)", false, false, MCD_SET(c->prefetch = (int)v)},
     {"spin_us", 0, kMax, "spin_us must be >= 0", false, false, MCD_SET(c->spin_us = v)},
@@ -604,6 +605,7 @@ int64_t mcd_last_direct_chunks(const mcd_catalog* cat) { return cat ? cat->last_
 int mcd_last_narrow_bounded(const mcd_catalog* cat) { return cat ? cat->last_narrow_bounded : -1; }
 int mcd_last_exp_split(const mcd_catalog* cat) { return cat ? cat->last_exp_split : -1; }
 int mcd_last_root_quad(const mcd_catalog* cat) { return cat ? cat->last_root_quad : -1; }
+int mcd_last_block_step(const mcd_catalog* cat) { return cat ? cat->last_block_step : -1; }
 int64_t mcd_last_quad_chunks(const mcd_catalog* cat) { return cat ? cat->last_quad_chunks : -1; }
 
 int mcd_last_f32_domain(const mcd_catalog* cat, double* kappa_v, double* kappa_theta) {

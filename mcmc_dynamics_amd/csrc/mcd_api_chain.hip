@@ -262,6 +262,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     cat->last_direct_chunks = 0;
     cat->last_exp_split = 0;                           // (... and the direct form without the split exponent offset)
     cat->last_root_quad = 0;
+    cat->last_block_step = 0;
     cat->last_quad_chunks = 0;
     const double* pset_const = fast_pset_const(cat, sh, level);
     // launches with few partial sums per walker (balanced plans of small catalogues, radial bins of a few chunks): no

@@ -121,6 +121,8 @@ int stage_params_impl(mcd_catalog* cat, int64_t n_walkers, int32_t k, const doub
             w->exp_split[b] = fast == 2 && cat->precision == MCD_F64 && (b == 0 || narrow_rescale != 0) &&
                               mcd::exp_split_admitted(cat->stats, cat->model, cat->free_centre, cat->k, params, n_rows,
                                                       b ? narrow_rescale : 0);
+        w->block_step = w->exp_split[1] && narrow_rescale == 32 &&
+                        mcd::block_step_admitted(cat->stats, cat->model, cat->free_centre, cat->k, params, n_rows);
         w->series_chunks = series_chunk_count(cat, *w, fast, params, n_rows);
         w->direct_chunks = direct_chunk_count(cat, *w, fast, params, n_rows);
         w->quad_chunks = quad_chunk_count(cat, *w, fast, params, n_rows);
@@ -226,6 +228,8 @@ int enqueue(mcd_catalog* cat, bool pipelined) {
         }
         cat->last_exp_split = mcd::exp_split_launch(shape) ? 1 : 0;
         cat->last_root_quad = mcd::root_quad_launch(shape) ? 1 : 0;
+        shape.block_step = cat->block_step != 0 && w.block_step && mcd::block_step_fits_l2(w.n_chunks, W);
+        cat->last_block_step = mcd::block_step_launch(shape) ? 1 : 0;
         if (&sh == &cat->shards.front()) cat->last_series_chunks = cat->last_direct_chunks = cat->last_quad_chunks = 0;
         cat->last_quad_chunks += cat->last_root_quad && shape.fast == 2 ? w.quad_chunks : 0;
         cat->last_series_chunks += shape.root_series && shape.fast == 2 ? w.series_chunks : 0;

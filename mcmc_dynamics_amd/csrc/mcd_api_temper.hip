@@ -165,6 +165,7 @@ int temper_block_device(mcd_catalog* cat, const mcd::TemperShared& ts, int64_t n
     cat->last_direct_chunks = 0;
     cat->last_exp_split = 0;
     cat->last_root_quad = 0;
+    cat->last_block_step = 0;
     cat->last_quad_chunks = 0;
     if (*(const int32_t*)(a.h + o_status) != 0)
         return fail(MCD_ERR_NONFINITE, "mcd_temper_block: the log-likelihood returned NaN");

@@ -365,6 +365,22 @@ MCD_HD bool exp_split_admitted(const StatsScalars& st, int model, bool free_cent
     return rescale * (hi2 + kExpSplitLog2KappaMax) <= 1000.0;
 }
 
+// Block step of the bounded quadratic loop (option "block_step"; mcd_math.h: chunk_bgfixed_fast<.., BOUNDED, BLOCK>): its
+// rescale moves from every R-th star of the chunk to the multiples of 32 of the absolute record index.  The loop runs with
+// the split exponent offset, so a launch takes it only where kBlockStepFactors = 56 raw factors of at most kappa_max y_hi and
+// at least y_lo fit between two rescales -- bounded_rescale's and exp_split_admitted's conditions with R = 56: a chunk's
+// first, partial band (up to 24 stars) and a whole one, with room to spare over the 32 the loop lets pass as it stands.
+// Where this refuses, the launch keeps the bounded loop as it is.
+constexpr int kBlockStepFactors = 56;
+MCD_HD bool block_step_admitted(const StatsScalars& st, int model, bool free_centre, int64_t n_rows, const ParamRanges& pr) {
+    if (bounded_rescale(st, model, free_centre, n_rows, pr) != 32) return false;
+    GuardRanges g;
+    if (!guard_verdict(st, model, false, n_rows, pr, &g)) return false;
+    const double lo2 = -log2(1.0 - st.pm_max);                        // (bounded_rescale's)
+    const double hi2 = log2(1.0 + exp(st.nbp_max) / sqrt(g.n_min));
+    return kBlockStepFactors * (hi2 + kExpSplitLog2KappaMax) <= 1000.0 && 1.0 + kBlockStepFactors * lo2 <= 1000.0;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // float32 accuracy domain (MCD_F32, MCD_F32_ACC64; host only -- the resident chain is float64).  The float32 kernels round
 // every record field and every walker constant to 24 bits before the first operation, so what they can deliver is set by
@@ -452,6 +468,9 @@ inline int fast_level(const CatalogStats& st, int model, bool free_centre, bool 
 
 inline int bounded_rescale(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows) {
     return bounded_rescale(st, model, free_centre, n_rows, table_ranges(model, free_centre, k, params, n_rows));
+}
+inline bool block_step_admitted(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows) {
+    return block_step_admitted(st, model, free_centre, n_rows, table_ranges(model, free_centre, k, params, n_rows));
 }
 inline bool exp_split_admitted(const CatalogStats& st, int model, bool free_centre, int k, const double* params, int64_t n_rows,
                                int rescale) {

@@ -148,6 +148,7 @@ struct WorkSet {
     int narrow_rescale = 0;            // its bounded narrow-range verdict (mcd_guard.h: bounded_rescale; R or 0)
     bool exp_split[2] = {false, false};   // mcd_guard.h: exp_split_admitted for the staged batch: [0] in the loops that keep the
                                           // clamp, [1] in the bounded loop with R = narrow_rescale
+    bool block_step = false;           // mcd_guard.h: block_step_admitted for the staged batch (56 raw factors fit the bounded loop)
     bool staged = false;
     bool sorted = false;               // planned on, and launched with, the shard's verr-sorted records (Shard::records_sorted)
     std::vector<double> series_need;   // sorted: per chunk outside chunk_general, the smallest sigma^2 with which its verr^2
@@ -345,6 +346,8 @@ struct mcd_catalog {
                                        // delta form on every series chunk
     int root_quad = 1;                 // option "root_quad": 1 the quadratic form on 32-star bands where a direct chunk of a
                                        // launch with the split exponent offset admits it (mcd_math.h: RootQuad), 0 never
+    int block_step = 1;                // option "block_step": 1 the bounded quadratic loop takes one block step per 32-star band
+                                       // (fold, rescale and prefetch together) where the guard admits it, 0 never
     int balance = -1;                  // option "balance": one round of equal waves (mcd_chunks.h): -1 when the catalogue is
                                        // small enough, 0 never, m > 0 forced with m workgroups per CU
     int two_lanes = 1;                 // option "two_lanes": pipelined evaluations of one device alternate between two streams
@@ -411,6 +414,8 @@ struct mcd_catalog {
                                        // 0 not (-1: no launch yet)
     int last_root_quad = -1;           // 1: the last main-kernel launch held the third vote (option "root_quad" on a launch with
                                        // the split exponent offset), 0 not (-1: no launch yet)
+    int last_block_step = -1;          // 1: the last main-kernel launch ran the block-step kernel (option "block_step" on a
+                                       // bounded launch with R = 32 that holds the third vote), 0 not (-1: no launch yet)
     int64_t last_quad_chunks = -1;     // chunks of that launch in the quadratic form (host count), -1: no launch yet
     int last_narrow_bounded = -1;      // R of the bounded narrow-range loop the last main-kernel launch ran, 0 none (-1: no launch yet)
 };

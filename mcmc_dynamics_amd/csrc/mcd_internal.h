@@ -35,6 +35,9 @@ struct LaunchShape {
                                             // null: the direct form as it is
     bool root_quad = false;         // ... and of those the chunks that admit it run the quadratic form on 32-star bands
                                     // (option "root_quad"; mcd_math.h: RootQuad); acts only where exp_split_launch holds
+    bool block_step = false;        // ... in the bounded loop with one block step per band: fold, rescale and prefetch together
+                                    // (option "block_step"; mcd_guard.h: block_step_admitted); acts only where
+                                    // block_step_launch holds
     double* rerun_flag = nullptr;   // device word the fast mixture kernels set to `launch_tag` in the denormal regime
     double launch_tag = 0.0;
 };
@@ -71,6 +74,27 @@ inline bool exp_split_launch(const LaunchShape& sh) {
 
 // ... and those that admit it in the quadratic form on 32-star bands (what mcd_last_root_quad reports)
 inline bool root_quad_launch(const LaunchShape& sh) { return sh.root_quad && exp_split_launch(sh); }
+
+// The block step touches a 32-star band (2 KiB) while the band before it is still being read, and a chunk's first 4 KiB at
+// once: up to 4 KiB per chunk in flight, against 1 KiB with the prefetch per 8-star iteration.  What it touched must still
+// be in the L2 of the chunk's XCD (4 MiB, shared by 32 CUs x 32 resident waves) when the scalar loads come for it.  Chunks
+// in flight per XCD: an eighth of the launch's, at most 1024 waves over the waves that share a chunk (its walker tiles).
+// Measured on C3's records (1e6 stars, profiles/r14_c3_ab.txt): 256 chunks x 4 KiB = 1 MiB (256 walkers) -1.5 % per step,
+// 376 x 4 KiB = 1.5 MiB (128 walkers) -0.8 to -1.4 %, 1024 x 4 KiB = 4 MiB (64 walkers, one wave per chunk) +41 %, whatever
+// the plan (8- or 4-wave workgroups, one round or several) and whether the band is touched one or two bands ahead, in 64- or
+// 128-byte steps -- what a kernel without any prefetch costs there (mcd_math.h: RecordPrefetch).  That the bands are evicted
+// before they are read is what these figures suggest; it was not measured directly.  Admitted up to 1.5 MiB, the largest
+// footprint measured as a gain.
+inline bool block_step_fits_l2(int64_t n_chunks, int64_t n_walkers) {
+    const int64_t n_wtiles = (n_walkers + 63) / 64;
+    const int64_t per_xcd = (n_chunks + 7) / 8, resident = 1024 / (n_wtiles < 1 ? 1 : (n_wtiles > 1024 ? 1024 : n_wtiles));
+    return (per_xcd < resident ? per_xcd : resident) * 4096 <= (int64_t)3 << 19;
+}
+
+// ... in the bounded kernel whose quadratic loop takes one block step per 32-star band (what mcd_last_block_step reports)
+inline bool block_step_launch(const LaunchShape& sh) {
+    return sh.block_step && narrow_bounded_launch(sh) && sh.narrow_rescale == 32 && root_quad_launch(sh);
+}
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& shape, const void* records, const Chunk* chunks,
                           int64_t n_chunks, const void* wpar, double* partials, int64_t n_walkers);

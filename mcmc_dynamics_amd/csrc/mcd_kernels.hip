@@ -119,18 +119,20 @@ __device__ const double kExpTabSqrt2Device[kExpTabSize] = {MCD_EXP_TABLE_SQRT2_V
 // recs_split (null: none): the split-offset records of a launch with option "exp_split" (mcd_exp_split.h), in the order and
 // stride of `recs`, read by the direct chunks in its place; split_const[2 chunk]: what such a chunk adds to its sum,
 // split_const[2 chunk + 1]: the largest half-width of a 32-star block it touches (mcd_exp_split.h: exp_split_chunk_consts).
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
-__global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(const T* __restrict__ recs,
-                                                                 const Chunk* __restrict__ chunks,
-                                                                 const T* __restrict__ wpar,
-                                                                 double* __restrict__ partials, int64_t n_tasks,
-                                                                 int n_wtiles, int64_t n_walkers, int64_t n_chunks,
-                                                                 int uniform_len, int uniform_extra, int64_t n_records,
-                                                                 double* __restrict__ rerun_flag, double launch_tag,
-                                                                 const uint8_t* __restrict__ chunk_general,
-                                                                 int64_t n_slots, int narrow_iters, int root_series,
-                                                                 const T* __restrict__ recs_split,
-                                                                 const double* __restrict__ split_const) {
+// BLOCK: the bounded kernel whose quadratic loop takes one block step per 32-star band (option "block_step";
+// chunk_bgfixed_fast<.., BOUNDED, BLOCK>) -- a kernel of its own, loglike_block_kernel below, so that a launch without the
+// option runs the code it ran before.  Both kernels are this one body.
+#define MCD_MAIN_KERNEL_PARAMS                                                                                               \
+    const T* __restrict__ recs, const Chunk* __restrict__ chunks, const T* __restrict__ wpar, double* __restrict__ partials, \
+    int64_t n_tasks, int n_wtiles, int64_t n_walkers, int64_t n_chunks, int uniform_len, int uniform_extra,                  \
+    int64_t n_records, double* __restrict__ rerun_flag, double launch_tag, const uint8_t* __restrict__ chunk_general,        \
+    int64_t n_slots, int narrow_iters, int root_series, const T* __restrict__ recs_split,                                    \
+    const double* __restrict__ split_const
+#define MCD_MAIN_KERNEL_ARGS                                                                                                 \
+    recs, chunks, wpar, partials, n_tasks, n_wtiles, n_walkers, n_chunks, uniform_len, uniform_extra, n_records, rerun_flag, \
+    launch_tag, chunk_general, n_slots, narrow_iters, root_series, recs_split, split_const
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED, bool BLOCK>
+__device__ __forceinline__ void loglike_body(MCD_MAIN_KERNEL_PARAMS) {
     constexpr int ND = record_doubles(MODEL, FREE);
     constexpr int kThreads = WAVES * kWave;
     constexpr bool kCombine = WAVES > kWavesPerBlock;
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
                     quad.park = (QuadParkPtr)quad_lds + wave * kWave;
                     quad.stride = kThreads;
                 }
-                result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED>(
+                result = chunk_loglike<MODEL, FREE, T, A, 2, PF, kTabBiased, BOUNDED, BLOCK>(
                          chunk_recs, ch.count, w, denormal, exptab_lds, narrow_iters, root_series != 0, root_series > 1,
                          recs_split ? (RecPtr<T>)(recs_split + ch.begin * ND) : (RecPtr<T>) nullptr, split_const + 2 * chunk_id, quad);
             }
@@ -261,6 +263,17 @@ __global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kern
     }
 #endif
 }
+
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF, int WAVES, bool BOUNDED = false>
+__global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_kernel(MCD_MAIN_KERNEL_PARAMS) {
+    loglike_body<MODEL, FREE, T, A, FAST, PF, WAVES, BOUNDED, false>(MCD_MAIN_KERNEL_ARGS);
+}
+template <int MODEL, bool FREE, class T, class A, int WAVES>
+__global__ __launch_bounds__(WAVES * kWave, WAVES > 4 ? 4 : 1) void loglike_block_kernel(MCD_MAIN_KERNEL_PARAMS) {
+    loglike_body<MODEL, FREE, T, A, 2, true, WAVES, true, true>(MCD_MAIN_KERNEL_ARGS);
+}
+#undef MCD_MAIN_KERNEL_PARAMS
+#undef MCD_MAIN_KERNEL_ARGS
 
 // ------------------------------------------------------------------------------------------------
 // final reduction: one block per (parameter set, group of 8 walkers).  The group's partial sums are one contiguous
@@ -368,21 +381,30 @@ hipError_t launch_one(hipStream_t s, const LaunchShape& sh, const void* records,
     const bool bounded = kCanBound && sh.prefetch && narrow_bounded_launch(sh);
     const int narrow_iters = bounded ? sh.narrow_rescale / 8 : 1;
     const int root_level = sh.root_series ? (sh.root_direct ? (root_quad_launch(sh) ? 3 : 2) : 1) : 0;     // (loglike_kernel: root_series)
-#define MCD_LAUNCH_MAIN(PF_, WAVES_, BOUNDED_)                                                                               \
-    hipLaunchKernelGGL((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), dim3((unsigned)grid),               \
+#define MCD_LAUNCH_AS(KERNEL_, WAVES_)                                                                                       \
+    hipLaunchKernelGGL(KERNEL_, dim3((unsigned)grid),                                                                        \
                        dim3(WAVES_ * kWave), 0, s, (const T*)records, chunks, (const T*)wpar, partials, n_tasks, n_wtiles,   \
                        n_walkers, n_chunks, sh.uniform_len, sh.uniform_extra, sh.n_records, sh.rerun_flag, sh.launch_tag,    \
                        sh.chunk_general, n_slots, narrow_iters, root_level,                                                   \
                        (const T*)(exp_split_launch(sh) ? sh.records_split : nullptr), sh.split_const)
+#define MCD_LAUNCH_MAIN(PF_, WAVES_, BOUNDED_)                                                                               \
+    MCD_LAUNCH_AS((loglike_kernel<MODEL, FREE, T, A, FAST, PF_, WAVES_, BOUNDED_>), WAVES_)
     // bounded, else prefetch, else plain -- once, for a workgroup of decltype(waves)::value waves
     auto launch = [&](auto waves) {
         constexpr int W = decltype(waves)::value;
+        if constexpr (kCanBound) {
+            if (bounded && block_step_launch(sh)) {
+                MCD_LAUNCH_AS((loglike_block_kernel<MODEL, FREE, T, A, W>), W);
+                return hipGetLastError();
+            }
+        }
         if (bounded) MCD_LAUNCH_MAIN(true, W, kCanBound);
         else if (FAST != 0 && sh.prefetch) MCD_LAUNCH_MAIN((FAST != 0), W, false);
         else MCD_LAUNCH_MAIN(false, W, false);
         return hipGetLastError();
     };
 #undef MCD_LAUNCH_MAIN
+#undef MCD_LAUNCH_AS
     if constexpr (kCanCombine) {
         if (combine && sh.waves == 8) return launch(std::integral_constant<int, 8>());
         // 16 waves: 1024 threads, at most 128 VGPRs -- the kernels of the per-walker Gaussian background need more

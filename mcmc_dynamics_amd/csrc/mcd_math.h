@@ -43,6 +43,11 @@ namespace mcd { template <class T> using RecPtr = const T MCD_CONST_AS*; }
 #else
 #define MCD_KEEP_BRANCH() ((void)0)
 #endif
+// bands between a block step of the bounded quadratic loop and the band whose records it prefetches (chunk_bgfixed_fast;
+// -D for A/B builds, csrc/Makefile: variant)
+#ifndef MCD_BLOCK_STEP_AHEAD
+#define MCD_BLOCK_STEP_AHEAD 1
+#endif
 
 namespace mcd {
 
@@ -1451,7 +1456,7 @@ MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<d
 // BG_FIXED, f64 fast forms.  MODEL_BGFIXED has norm = verr^2 + sigma^2 (constant.py:52-74): the accumulator takes 2 norm
 // (HALVED form; 8 norm for the narrow-range variant's one-step Newton reciprocal root) and `exptab` is then the
 // sqrt(2)-scaled table; star_d_n's own norm is dead code there.
-template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED>
+template <int MODEL, bool FREE, int FAST, bool PF, bool TAB_BIASED, bool BOUNDED, bool BLOCK = false>
 MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts<double>& w, bool& denormal,
                                  const double* __restrict__ exptab, int rescale_iters, bool series, bool direct,
                                  RecPtr<double> r_split, const double* __restrict__ split_const, const QuadArgs& quad) {
@@ -1488,6 +1493,7 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     };
     const int n4 = count >> 2;
     static_assert(!BOUNDED || (NARROW && PF && TAB_BIASED && !FREE), "the bounded loop is the prefetching BGFIXED one");
+    static_assert(!BLOCK || BOUNDED, "the block step belongs to the bounded loop");
     auto four = [&](RecPtr<double> r4, auto SERIES) {
         if constexpr (std::is_same<decltype(SERIES), RootDirectSplit>::value || std::is_same<decltype(SERIES), const RootQuad*>::value) {
             // (the linear coefficient of the scaled polynomial in place of the rsq loops' variance scale)
@@ -1534,7 +1540,92 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
     };
     auto run = [&](auto SERIES) {
         constexpr bool QUAD = std::is_same<decltype(SERIES), const RootQuad*>::value;
-        if constexpr (BOUNDED) {
+        if constexpr (BOUNDED && BLOCK && QUAD) {
+            // Block step (option "block_step"): the bounded quadratic loop with ONE block outside the loop body, taken
+            // where the absolute record index reaches a multiple of 32.  It holds the fold (where a block starts there),
+            // the rescale and the prefetch of a whole block, so the loop body is the per-term arithmetic alone.
+            //   Rescale: at most 32 raw factors lie between two rescales here (the stars up to the chunk's first boundary,
+            //   then whole blocks; a boundary inside the array's last block, which starts no block, rescales all the
+            //   same).  The launch admits this loop only where 56 fit (mcd_guard.h: block_step_admitted).  Rescaling
+            //   multiplies by a power of two: the bits of the loop below, whose rescales count from the chunk's start.
+            //   Prefetch: one vector load whose lane l < 32 touches the 64-byte record l of the band BEHIND the one that
+            //   starts here (MCD_BLOCK_STEP_AHEAD = 1; two bands ahead and 16 lanes on 128-byte lines measured the same at 256
+            //   walkers and worse at 128, profiles/r14_c3_ab.txt), clamped to the chunk's own records -- the lanes are
+            //   switched off through the exec mask, from scalar arithmetic -- so it addresses nothing outside the array.
+            //   The chunk's records up to there, at most 64, are touched once in front of the loop.  The touched word is
+            //   dead: it is retired in the NEXT block step (and behind the loop), where the wait has long been served.
+            //   A band is touched 32 stars before it is read instead of 8: the launch takes this loop only where that
+            //   much more in flight still fits the L2 (mcd_internal.h: block_step_fits_l2).
+            //   `col`: the lane's column in the parked planes as an LDS address, kept in one VGPR across the loop; shifted
+            //   by three it is the lane's record in the prefetch, less what `line0` takes off the scalar base.
+            uint32_t touched = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+            uint32_t col = (uint32_t)(uintptr_t)quad.park +
+                           8u * __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            asm volatile("" : "+v"(col));
+            const uint64_t line0 = (uint64_t)(uint32_t)(uintptr_t)quad.park << 3;
+#endif
+            auto touch = [&](RecPtr<double> at, int records, int max_lines) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                // (the lanes' mask by a select, not a clamp: hipcc takes a two-sided clamp of a wave-uniform int to v_med3_i32)
+                const int lines = records > max_lines ? max_lines : records;
+                const uint64_t lanes = lines > 0 ? (lines < 64 ? ~(~0ull << lines) : ~0ull) : 0;
+                typedef const uint32_t __attribute__((address_space(1)))* global_word_ptr;
+                asm volatile("" :: "v"(touched));
+                // (the scalar base and the shift behind volatile asm: left in sight, the address becomes an induction
+                // variable of the loop, a 64-bit vector add per iteration and a register pair across it)
+                uint64_t base = (uint64_t)at - line0;
+                asm volatile("" : "+s"(base));
+                uint32_t line;
+                asm volatile("v_lshlrev_b32 %0, 3, %1" : "=v"(line) : "v"(col));
+                if (__builtin_amdgcn_inverse_ballot_w64(lanes)) touched = *(global_word_ptr)(base + (uint64_t)line);
+#else
+                (void)at; (void)records; (void)max_lines; (void)touched;
+#endif
+            };
+            const int n8 = count >> 3;
+            constexpr int kAhead = 32 * MCD_BLOCK_STEP_AHEAD;             // stars between a block step and the band it touches
+            static_assert(ND * 8 == 64 && 32 + kAhead <= 64, "one lane per 64-byte record, a chunk's first bands in one load");
+            touch(r, count < to_boundary + kAhead ? count : to_boundary + kAhead, 64);
+            for (int g = 0; g < n8; ++g, r += 8 * ND) {
+                if (to_boundary == 0) {
+                    to_boundary = 32;
+                    MCD_KEEP_BRANCH();
+                    if (folds > 0) {
+                        --folds;
+#if defined(__HIP_DEVICE_COMPILE__)
+                        RootQuadCentre c;
+                        c.c3 = qc.c3;
+                        const volatile __attribute__((address_space(3))) double* park =
+                            (const volatile __attribute__((address_space(3))) double*)col;
+                        c.c1 = park[0];
+                        c.c2 = park[quad.stride];
+                        c.G0s = park[2 * quad.stride];
+                        c.A = park[3 * quad.stride];
+                        c.k3 = park[4 * quad.stride];
+                        sq.fold(c, r[XB + 2], r[XB + 3], r[ND + XB + 2]);
+#else
+                        fold_at(r);
+#endif
+                    }
+                    acc.rescale_narrow();
+                    touch(r + kAhead * ND, count - 8 * g - kAhead, 32);
+                }
+                to_boundary -= 8;
+                four(r, SERIES);
+                four(r + 4 * ND, SERIES);
+            }
+#if defined(__HIP_DEVICE_COMPILE__)
+            asm volatile("" :: "v"(touched));
+#endif
+            acc.rescale_narrow();
+            if (n4 & 1) {
+                boundary(r, 4);
+                four(r, SERIES);
+                r += 4 * ND;
+                acc.rescale_narrow();
+            }
+        } else if constexpr (BOUNDED) {
             // bounded sub-variant: every mixture value lies in [y_lo, y_hi] with R log2(y_hi) <= 1000 and
             // 1 + R (-log2 y_lo) <= 1000 (mcd_guard.h: bounded_rescale), so R = 8 rescale_iters raw factors fit between
             // two rescales.  A scalar countdown sends every rescale_iters-th iteration to the rescale, a block outside
@@ -1698,11 +1789,14 @@ MCD_HD double chunk_bgfixed_fast(RecPtr<double> r, int count, const WalkerConsts
 // TAB_BIASED: `exptab` is the exponent-biased table (exp_tab_bias; MODEL_BGFIXED kernels with the narrow-range variant).
 // BOUNDED (MODEL_BGFIXED, fixed centre, FAST == 2, PF, TAB_BIASED; host guard mcd_guard.h: bounded_rescale): the
 // narrow-range loop without the exponent clamp, rescaling after every `rescale_iters` 8-star iterations (R / 8).
+// BLOCK (with BOUNDED; option "block_step", host guard mcd_guard.h: block_step_admitted): the bounded quadratic loop does its
+// fold, its rescale and its prefetch in one block per 32-star band (chunk_bgfixed_fast: block step); no other loop changes.
 // `series` (MODEL_BGFIXED, fixed centre, FAST == 2, f64): the records are sorted by verr, so a chunk whose verr^2 band is
 // narrow for every walker of the wave takes the reciprocal root from a per-chunk series (RootSeries) -- a wave-wide vote;
 // with `direct` (option "root_direct") such a chunk takes the direct form of the series (RootDirect) where the chunk's
 // verr^2 is at most 1/8 of every walker's variance -- a second vote.
-template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false>
+template <int MODEL, bool FREE, class T, class A, int FAST, bool PF = false, bool TAB_BIASED = false, bool BOUNDED = false,
+          bool BLOCK = false>
 MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bool& denormal,
                             const double* __restrict__ exptab, int rescale_iters = 1, bool series = false, bool direct = false,
                             RecPtr<T> r_split = nullptr, const double* __restrict__ split_const = nullptr,
@@ -1719,7 +1813,7 @@ MCD_HD double chunk_loglike(RecPtr<T> r, int count, const WalkerConsts<T>& w, bo
         if constexpr (FAST == 2 && MODEL == MODEL_PROFILE && !FREE) return chunk_profile_narrow<PF>(r, count, w);
         else return chunk_const_fast<MODEL, FREE, PF>(r, count, w);
     } else if constexpr (BG == BG_FIXED) {
-        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED>(r, count, w, denormal, exptab, rescale_iters, series, direct, r_split, split_const, quad);
+        return chunk_bgfixed_fast<MODEL, FREE, FAST, PF, TAB_BIASED, BOUNDED, BLOCK>(r, count, w, denormal, exptab, rescale_iters, series, direct, r_split, split_const, quad);
     } else if constexpr (BG == BG_FIXED_DENSITY) {
         // BG_FIXED_DENSITY, f64 fast forms
         constexpr int ND = record_doubles(MODEL, FREE);

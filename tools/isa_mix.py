@@ -18,7 +18,10 @@ and the direct loop once more with the split exponent offset (option "exp_split"
 The split loop exists once more with the quadratic series root on 32-star bands (option "root_quad", mcd_math.h: RootQuad):
 rows "..., quad", 10 fused multiply-adds per term against the split rows' 11.  Its coefficients are folded once per 32
 stars in a block of its own (five ds_read_b64 and four FMAs), which the count adds once per 32 terms.  The bounded quad
-loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded split loop keeps
+loop keeps its row under "bgfixed_quad_bounded".  With option "block_step" the launch runs loglike_block_kernel, the bounded
+kernel whose quadratic loop takes ONE block per 32 stars for the fold, the rescale and the prefetch of a whole band (row
+"..., quad, block step": 4 x loop body + that block, which is whatever the enclosing loop holds beside the 8-star body).
+That loop is what nearly all of C3's chunks run, so it gives the "bgfixed" key's prefetch fields; the bounded split loop keeps
 its row under "bgfixed_split_bounded", the bounded direct loop without the split under "bgfixed_direct_bounded", the bounded
 delta series loop under "bgfixed_series_bounded".
 
@@ -109,11 +112,14 @@ SERIES = [
      _sel(rsq=0, frexp=0, add=8, fma=40), False, False, True),
     ("ILi1ELb0EddLi2ELb1ELi4ELb0EE", "BGFIXED fixed, narrow, prefetch, quad", "bgfixed_quad", 8, 1,
      _sel(rsq=0, frexp=1, add=16, fma=80), True, False, True),
-    # what C3's timed launches run on the chunks that qualify: the "bgfixed" key's prefetch fields
-    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, quad", "bgfixed", 8, 4,
+    ("ILi1ELb0EddLi2ELb1ELi4ELb1EE", "BGFIXED fixed, narrow, prefetch, bounded, quad", "bgfixed_quad_bounded", 8, 4,
      _sel(rsq=0, frexp=0, add=16, fma=80), True, True, True),
 ]
 QUAD_BLOCK = 32      # stars per fold of the quadratic loops
+# what C3's timed launches run on the chunks that qualify: the "bgfixed" key's prefetch fields.  The kernel of
+# option "block_step" (mcd_kernels.hip: loglike_block_kernel): name of the function, name, key, stars, selector
+BLOCK_STEP = ("20loglike_block_kernelILi1ELb0EddLi4EE", "BGFIXED fixed, narrow, prefetch, bounded, quad, block step", "bgfixed", 8,
+              _sel(rsq=0, frexp=0, add=16, fma=80))
 
 
 def _ops(lines):
@@ -147,6 +153,24 @@ def body_lines(k, sp):
     if blk and blk[1] <= sp[1] + 1:
         return k[sp[0]:blk[0]] + k[blk[1]:sp[1] + 1]
     return k[sp[0]:sp[1] + 1]
+
+
+def block_step_lines(k, labels, spans, best):
+    """the lines of the block step of loop `best` (the 8-star body of the block-step kernel's quadratic loop): what the
+    smallest loop around it holds beside it -- the fold, the rescale and the prefetch of a 32-star band -- or None"""
+    around = [sp for sp in spans if sp != best and sp[0] <= best[0] and best[1] <= sp[1]]
+    if not around:
+        return None
+    outer = min(around, key=lambda sp: sp[1] - sp[0])
+    # ... and the blocks laid out behind its closing branch that jump back into it (the predicated prefetch load)
+    end = outer[1] + 1
+    while True:
+        j = next((j for j in range(end, min(end + 24, len(k))) if re.match(r"\s*s_branch |^\.LBB", k[j])), None)
+        m = re.match(r"\s*s_branch (\.LBB\d+_\d+)", k[j]) if j is not None else None
+        if not (m and m.group(1) in labels and outer[0] <= labels[m.group(1)] <= outer[1]):
+            break
+        end = j + 1
+    return k[outer[0]:best[0]] + k[best[1] + 1:end]
 
 
 def rescale_block(k, labels, best, bounded, trips):
@@ -198,8 +222,10 @@ def analyse(out="/tmp/isa_mix"):
     variants.append(BOUNDED + (True, True))
     variants += [v + (False,) * (9 - len(v)) for v in SERIES]
     variants = [v + (False,) * (9 - len(v)) for v in variants]
-    for tag, name, key, per, trips, selector, with_prefetch, bounded, quad in variants:
-        starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_114loglike_kernel" + tag)]
+    variants = [("14loglike_kernel" + v[0],) + v[1:] + (False,) for v in variants]
+    variants.append(BLOCK_STEP[:4] + (QUAD_BLOCK // BLOCK_STEP[3], BLOCK_STEP[4], True, True, True, True))
+    for tag, name, key, per, trips, selector, with_prefetch, bounded, quad, block_step in variants:
+        starts = [i for i, l in enumerate(asm) if l.startswith("_ZN3mcd12_GLOBAL__N_1" + tag)]
         if not starts:
             continue
         a = starts[0]
@@ -212,6 +238,20 @@ def analyse(out="/tmp/isa_mix"):
             if m and m.group(1) in labels and labels[m.group(1)] < i:
                 spans.append((labels[m.group(1)], i))
         inner = [sp for sp in spans if not any(o != sp and sp[0] <= o[0] and o[1] <= sp[1] for o in spans)]
+        if block_step:
+            # (the loop body holds no fold block and no rescale block of the other kinds: count it as it stands)
+            hits = [sp for sp in sorted(inner, key=lambda sp: sp[1] - sp[0], reverse=True)
+                    if selector(Counter(_ops(k[sp[0]:sp[1]]))) and sp[1] - sp[0] >= 8 * per]
+            step = block_step_lines(k, labels, spans, hits[0]) if hits else None
+            if step is None:
+                continue
+            total = Counter()
+            for op, v in Counter(_ops(k[hits[0][0]:hits[0][1] + 1])).items():
+                total[op] += v * trips
+            for op, v in Counter(_ops(step)).items():
+                total[op] += v
+            rows.append(_row(name, key, with_prefetch, per * trips, total))
+            continue
         ranked = sorted(inner, key=lambda sp: sp[1] - sp[0], reverse=True)
         best = None
         if selector is not None:
@@ -242,21 +282,25 @@ def analyse(out="/tmp/isa_mix"):
             terms = QUAD_BLOCK
             for op, v in Counter(_ops(k[fold[0]:fold[1]])).items():
                 total[op] += v
-
-        def is_f64(o):
-            return "f64" in o
-        valu = sum(v for o, v in total.items() if o.startswith("v_"))
-        f64 = sum(v for o, v in total.items() if o.startswith("v_") and is_f64(o) and not o.startswith(("v_ldexp", "v_frexp")))
-        trans = sum(v for o, v in total.items() if o.startswith(("v_rsq_f64", "v_rcp_f64")))
-        slots = sum(v * (2.9 if o.startswith(("v_rsq_f64", "v_rcp_f64")) else
-                         1.0 if (is_f64(o) and not o.startswith(("v_ldexp", "v_frexp"))) else 0.5)
-                    for o, v in total.items() if o.startswith("v_"))
-        rows.append({"name": name, "model": key, "prefetch": with_prefetch, "stars_per_iteration": terms,
-                     "valu_per_term": valu / terms, "f64_per_term": f64 / terms, "trans_f64_per_term": trans / terms,
-                     "other_per_term": (valu - f64) / terms, "slots_per_term": slots / terms,
-                     "lds_per_term": sum(v for o, v in total.items() if o.startswith("ds_")) / terms,
-                     "salu_smem_per_term": sum(v for o, v in total.items() if o.startswith("s_")) / terms})
+        rows.append(_row(name, key, with_prefetch, terms, total))
     return rows
+
+
+def _row(name, key, with_prefetch, terms, total):
+    """one table row from the instruction tally `total` of `terms` star-walker terms"""
+    def is_f64(o):
+        return "f64" in o
+    valu = sum(v for o, v in total.items() if o.startswith("v_"))
+    f64 = sum(v for o, v in total.items() if o.startswith("v_") and is_f64(o) and not o.startswith(("v_ldexp", "v_frexp")))
+    trans = sum(v for o, v in total.items() if o.startswith(("v_rsq_f64", "v_rcp_f64")))
+    slots = sum(v * (2.9 if o.startswith(("v_rsq_f64", "v_rcp_f64")) else
+                     1.0 if (is_f64(o) and not o.startswith(("v_ldexp", "v_frexp"))) else 0.5)
+                for o, v in total.items() if o.startswith("v_"))
+    return {"name": name, "model": key, "prefetch": with_prefetch, "stars_per_iteration": terms,
+            "valu_per_term": valu / terms, "f64_per_term": f64 / terms, "trans_f64_per_term": trans / terms,
+            "other_per_term": (valu - f64) / terms, "slots_per_term": slots / terms,
+            "lds_per_term": sum(v for o, v in total.items() if o.startswith("ds_")) / terms,
+            "salu_smem_per_term": sum(v for o, v in total.items() if o.startswith("s_")) / terms}
 
 
 def merge_variants(rows):
