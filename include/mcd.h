@@ -407,6 +407,19 @@ int mcd_simulated_set(mcd_catalog* cat, int64_t n_sims, const double* velocities
 int mcd_simulated_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
                           const int64_t* row_sim /* [R] */, double* out /* [R], may be NULL */);
 int mcd_simulated_info(const mcd_catalog* cat, int64_t* n_sims);
+/* mcd_simulated_loglike with its gradient (MAP fits of simulated catalogues: the parametric bootstrap, a simulated null
+ * distribution of a likelihood-ratio statistic): out[r] as above, and
+ *   grad[r][k] = sum_i dl_i/dtheta_k(theta[r]; v'(row_sim[r], i))
+ * with respect to the K kernel columns, in their units (as mcd_loglike_grad_batch; the partials of the residual and of the
+ * variance do not depend on the velocity).  out[r] has mcd_simulated_loglike's bits.  Un-binned MCD_F64 catalogues, one
+ * device, no communicator.  MCD_ERR_INVALID, with a message, out and grad untouched and the resident set as it was: the
+ * refusals of mcd_simulated_loglike, and a null grad.  out = NULL gives the same gradient.  Synchronous and deterministic:
+ * given the resident set, bit-identical from run to run.  The work buffers of a row count stay with the catalogue, in a
+ * cache apart from the value call's.  Waits under the context's deadline; honours options "timing" (mcd_last_kernel_ms:
+ * the main kernel) and "chunk_len". */
+int mcd_simulated_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params /* [R][K] */,
+                               const int64_t* row_sim /* [R] */, double* out /* [R], may be NULL */,
+                               double* grad /* [R][K] */);
 
 /* Background log-likelihood of n test stars against the kernel-density estimate built from n_comp comparison
  * stars: replaces background.SingleStars.__call__ (background/single_stars.py:42-77), the O(n * n_comp) precompute

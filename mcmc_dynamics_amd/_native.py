@@ -78,6 +78,8 @@ SYMBOLS = {
     "mcd_simulated_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, _c_double_p, ctypes.c_double, ctypes.c_double]),
     "mcd_simulated_loglike": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_int64_p,
                                              _c_double_p]),
+    "mcd_simulated_loglike_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, _c_double_p, _c_int64_p,
+                                                  _c_double_p, _c_double_p]),
     "mcd_simulated_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p]),
     "mcd_bootstrap_weights": (ctypes.c_int, [ctypes.c_int32, ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                              ctypes.c_int64, _c_double_p]),
@@ -895,6 +897,30 @@ class Catalog(object):
         rc = self.lib.mcd_simulated_loglike(self.handle, p.shape[0], self.k, _ptr(p), sim.ctypes.data_as(_c_int64_p), _ptr(out))
         _check(self.lib, rc, "mcd_simulated_loglike")
         return out
+
+    def simulated_loglike_grad(self, table, row_sim, want_value=True):
+        """``simulated_loglike`` with its gradient (include/mcd.h: mcd_simulated_loglike_grad): ``table`` (R, K) kernel rows,
+        ``row_sim`` (R,) -> (values (R,), grad (R, K)) with respect to the kernel columns, in their units, every row on the
+        velocities of its own simulation: what a MAP fit per simulated catalogue climbs (``Runner.simulated_maximize``).
+        The values have ``simulated_loglike``'s bits.  ``want_value=False`` passes no value buffer and returns (None,
+        grad) with the same gradient.  Un-binned float64 catalogues on one device; synchronous and, given the resident
+        set, bit-identical from run to run."""
+        self._alive()
+        p = _f64(table)
+        if p.ndim == 1:
+            p = p[None, :]
+        if p.ndim != 2 or p.shape[1] != self.k:
+            raise ValueError("table must have shape (R, {0})".format(self.k))
+        p = np.ascontiguousarray(p)
+        sim = np.ascontiguousarray(row_sim, dtype=np.int64).reshape(-1)
+        if sim.size != p.shape[0]:
+            raise ValueError("row_sim must hold one simulation per row of the table")
+        out = np.empty(p.shape[0], dtype=np.float64) if want_value else None
+        grad = np.empty((p.shape[0], self.k), dtype=np.float64)
+        rc = self.lib.mcd_simulated_loglike_grad(self.handle, p.shape[0], self.k, _ptr(p), sim.ctypes.data_as(_c_int64_p),
+                                                 _ptr(out) if want_value else None, _ptr(grad))
+        _check(self.lib, rc, "mcd_simulated_loglike_grad")
+        return out, grad
 
     @property
     def simulated_sims(self):

@@ -336,6 +336,23 @@ class BinnedConstantFit(ConstantFit):
     def recovery(self, *args, **kwargs):
         return self.simulated_fits()
 
+    def simulated_maximize(self, *args, **kwargs):
+        raise NotImplementedError("BinnedConstantFit: MAP fits of simulated catalogues (lnprob_simulated_grad_batch, "
+                                  "simulated_maximize, parametric_bootstrap, lrt) are defined for un-binned fits only; fit "
+                                  "the bins' stars with ConstantFit")
+
+    def lnprob_simulated_grad_batch(self, *args, **kwargs):
+        return self.simulated_maximize()
+
+    def simulated_sims(self, *args, **kwargs):
+        return self.simulated_maximize()
+
+    def parametric_bootstrap(self, *args, **kwargs):
+        return self.simulated_maximize()
+
+    def lrt(self, *args, **kwargs):
+        return self.simulated_maximize()
+
     def hmc(self, *args, **kwargs):
         raise NotImplementedError("BinnedConstantFit: Hamiltonian Monte Carlo is defined for un-binned fits only (the "
                                   "lock-stepped ensembles of the bins have no HMC block)")

@@ -631,6 +631,56 @@ def recovery_summary(chain, truth, n_burn, names, thin=1, functions=None, null=N
     return out
 
 
+def parametric_bootstrap_summary(x, x_hat, converged, names, laplace_covariance=None):
+    """Moments of the refits ``x`` (E, P) of ``Runner.parametric_bootstrap`` -- the maxima of E catalogues simulated at the
+    estimate ``x_hat`` (P,) -- over the CONVERGED refits only: ``mean``, ``bias`` = mean - x_hat (the bias of the estimator
+    under the fitted model), ``covariance`` (sample, E - 1: the model-based sampling covariance of the estimate), ``std``,
+    ``percentiles`` ({2.5, 16, 50, 84, 97.5} -> (P,)), ``n_converged``, ``n_sims``, ``names``, and with
+    ``laplace_covariance`` (``Runner.laplace(x_hat)["covariance"]``) ``std_ratio`` = std / sqrt(diag laplace_covariance):
+    about 1 where the likelihood is quadratic over the estimate's scatter.  Against ``bootstrap_summary``'s ``std``, which
+    makes no use of the model, the ratio tells whether the model describes the scatter of the data.  Warns when fewer than
+    90 % of the refits converged."""
+    out = bootstrap_summary(x, x_hat, converged, names, laplace_covariance)
+    out["n_sims"] = out.pop("n_replicates")
+    return out
+
+
+LRT_QUANTILES = (50.0, 90.0, 95.0, 99.0, 99.9)
+
+
+def lrt_summary(lnprob_null, lnprob_full, converged_null, converged_full, stat_obs, df, tolerance=0.0):
+    """The simulated null distribution of a likelihood-ratio statistic (``Runner.lrt``): ``lnprob_null`` / ``lnprob_full``
+    (E,) the maxima of the null and of the full fit on E catalogues simulated under the null, ``converged_*`` (E,) whether
+    each fit converged, ``stat_obs`` the statistic of the data and ``df`` the number of parameters the null fixes.
+
+    ``stat`` (E,) = 2 (lnprob_full - lnprob_null); ``used`` (E,): both fits converged; ``n_used``; ``p_value`` =
+    (1 + #{used, stat >= stat_obs}) / (1 + n_used), the Monte-Carlo p-value that counts the data among the draws (Davison &
+    Hinkley 1997), never 0; ``p_se`` its binomial standard error; ``p_asymptotic`` the upper tail of chi2(``df``) at
+    ``stat_obs`` (Wilks), for comparison; ``quantiles`` ({50, 90, 95, 99, 99.9} -> the null statistic's quantile over the
+    used simulations); ``n_negative``: used statistics below -``tolerance`` -- nested models cannot give one, so a count
+    above 0 is a defect of the fits (a full fit stuck below its null)."""
+    from scipy.special import gammaincc
+    l0, l1 = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (lnprob_null, lnprob_full))
+    c0, c1 = (np.asarray(a, dtype=bool).reshape(-1) for a in (converged_null, converged_full))
+    if not (l0.size == l1.size == c0.size == c1.size):
+        raise ValueError("lrt_summary: the four arrays must hold one entry per simulation")
+    if int(df) < 1:
+        raise ValueError("lrt_summary: df must be >= 1")
+    stat = 2.0 * (l1 - l0)
+    used = c0 & c1 & np.isfinite(stat)
+    n_used = int(np.count_nonzero(used))
+    if n_used < 0.9 * stat.size:
+        warnings.warn("lrt_summary: only {0} of {1} simulations have both fits converged; the p-value is taken over "
+                      "those".format(n_used, stat.size))
+    stat_obs = float(stat_obs)
+    p = (1.0 + np.count_nonzero(stat[used] >= stat_obs)) / (1.0 + n_used)
+    quantiles = {q: (float(np.percentile(stat[used], q)) if n_used else np.nan) for q in LRT_QUANTILES}
+    return {"stat": stat, "used": used, "n_used": n_used, "stat_obs": stat_obs, "p_value": float(p),
+            "p_se": float(np.sqrt(p * (1.0 - p) / (1.0 + n_used))), "df": int(df),
+            "p_asymptotic": float(gammaincc(0.5 * int(df), 0.5 * max(stat_obs, 0.0))), "quantiles": quantiles,
+            "n_negative": int(np.count_nonzero(stat[used] < -float(tolerance))), "n_sims": int(stat.size)}
+
+
 class Runner(object):
     """Parent of the analysis classes.  Sub-classes name the observables and model parameters they
     need (``OBSERVABLES``, ``MODEL_PARAMETERS``) and implement ``_lnlike_batch``."""
@@ -1390,6 +1440,209 @@ class Runner(object):
                                 null=null) for g in range(grid.shape[0])]
         out = dict(per[0]) if truth.ndim == 1 else {"grid": per}
         out.update({"fits": fits, "seed": int(seed)})
+        return out
+
+    # ------------------------------------------------------------------ MAP fits of simulated catalogues (new)
+    def simulated_sims(self):
+        """Simulations of the set resident on the device (``simulate``, ``simulated_set``), 0 when there is none."""
+        self._holdout_check("simulated_sims")
+        return self._ensure_catalog().simulated_sims
+
+    def lnprob_simulated_grad_batch(self, values, row_sim):
+        """``lnprob_grad_batch`` with every row evaluated on the velocities of its own simulation: (R, P) free-parameter
+        vectors and ``row_sim`` (R,), one simulation id of the resident set per row, -> ((R,) values, (R, P) gradients) of
+        sum_i lnL_i(v' of the row's simulation) + ln prior,  one launch of the device's simulated value-and-gradient kernel
+        (``_native.Catalog.simulated_loglike_grad``).  The chain rule, the prior handling, the donor rows and the refusals
+        are ``lnprob_grad_batch``'s.  Runs on one device in one process, on un-binned float64 catalogues."""
+        self._holdout_check("lnprob_simulated_grad_batch")
+        values = np.atleast_2d(np.asarray(values, dtype=np.float64))
+        sim = np.ascontiguousarray(row_sim, dtype=np.int64).reshape(-1)
+        if sim.size != values.shape[0]:
+            raise ValueError("row_sim must hold one simulation per row of values")
+        plan = self._grad_plan()
+
+        def lnlike_grad(rows):
+            return self._lnlike_grad_rows(rows, lambda cat, table: cat.simulated_loglike_grad(table, sim))
+        if plan.prior is None:
+            return lnlike_grad(values)
+        return self._lnprob_grad_rows(values, plan, lnlike_grad)
+
+    def _inside_box(self, x, plan):
+        """x clipped strictly inside the box of the free parameters: 1e-6 of a finite width (of max(|bound|, 1) on a
+        one-sided one) away from every bound."""
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        room = 1e-6 * np.where(np.isfinite(hi - lo), hi - lo,
+                               np.maximum(np.where(np.isfinite(lo), np.abs(lo), 0.0), np.where(np.isfinite(hi), np.abs(hi), 0.0)) + 1.0)
+        return np.clip(x, lo + room, hi - room)
+
+    def simulated_maximize(self, truths=None, velocities=None, seed=None, x0=None, max_iter=200, gtol=1e-8):
+        """MAP fits of E simulated catalogues in lock step: catalogue e is drawn from the model at ``truths[e]``
+        (``simulate(truths, seed)``), or is row e of the caller's ``velocities`` (E, n_data) in km/s (``simulated_set``); with
+        neither, the set already resident on the device is fitted.  ``x0``: the starts, (P,) for all, (E, P) one per
+        catalogue, or (E, S, P) S per catalogue; default the truths, clipped strictly inside the box.  All E S rows climb
+        ``lnprob_simulated_grad_batch`` in ONE ``optimize.maximize_batch`` run, row (e, s) on simulation e: one launch of
+        the simulated value-and-gradient kernel per trial step.  Per catalogue the best converged start wins (the best of
+        all where none converged).
+
+        Returns ``x`` (E, P), ``lnprob`` (E,), ``converged`` (E,), ``n_iter`` (E,) of the winning starts, ``all_x`` (E, S, P),
+        ``all_lnprob`` (E, S), ``all_converged`` (E, S), ``names``, ``seed`` and, when they were drawn here, ``velocities``.
+        A few dozen launches per fit where ``simulated_fits`` takes two per step of a chain."""
+        from ..optimize import maximize_batch
+        self._holdout_check("simulated_maximize")
+        plan = self._grad_plan()
+        n_p = plan.free_idx.size
+        out = {}
+        if truths is not None:
+            truths, _ = self._truth_table(truths, "simulated_maximize")
+        if velocities is not None:
+            velocities = np.atleast_2d(np.asarray(velocities, dtype=np.float64))
+            if velocities.ndim != 2 or velocities.shape[1] != self.n_data or \
+                    (truths is not None and velocities.shape[0] != truths.shape[0]):
+                raise ValueError("simulated_maximize: velocities must have shape (E, {0})".format(self.n_data))
+            self.simulated_set(velocities)
+            n_e = velocities.shape[0]
+        elif truths is not None:
+            if seed is None:
+                seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+            out["velocities"] = self.simulate(truths, seed)
+            n_e = truths.shape[0]
+        else:
+            n_e = int(self.simulated_sims())
+            if n_e < 1:
+                raise ValueError("simulated_maximize: no simulated set is resident (give truths or velocities)")
+        if x0 is None:
+            if truths is None:
+                raise ValueError("simulated_maximize: x0 is needed where there are no truths to start from")
+            x0 = self._inside_box(truths, plan)
+        x0 = np.asarray(x0, dtype=np.float64)
+        if x0.ndim == 1:
+            x0 = np.broadcast_to(x0, (n_e, 1, x0.size))
+        elif x0.ndim == 2:
+            x0 = x0[:, None, :]
+        if x0.ndim != 3 or x0.shape[0] != n_e or x0.shape[1] < 1 or x0.shape[2] != n_p:
+            raise ValueError("simulated_maximize: x0 must have shape ({1},), ({0}, {1}) or ({0}, S, {1})".format(n_e, n_p))
+        n_s = x0.shape[1]
+        sim = np.repeat(np.arange(n_e, dtype=np.int64), n_s)
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        logger.info("simulated MAP fits: %d catalogues, %d start(s) each", n_e, n_s)
+        res = maximize_batch(lambda x: self.lnprob_simulated_grad_batch(x, sim), np.ascontiguousarray(x0).reshape(n_e * n_s, n_p),
+                             lo, hi, max_iter=max_iter, gtol=gtol)
+        f = np.where(np.isfinite(res["f"]), res["f"], -np.inf).reshape(n_e, n_s)
+        conv = np.asarray(res["converged"], dtype=bool).reshape(n_e, n_s)
+        # per catalogue the best converged start, or the best of all where none converged
+        pool = np.where(conv.any(axis=1)[:, None], conv, True)
+        best = np.argmax(np.where(pool, f, -np.inf), axis=1)
+        rows = np.arange(n_e)
+        all_x = res["x"].reshape(n_e, n_s, n_p)
+        out.update({"x": all_x[rows, best].copy(), "lnprob": f[rows, best].copy(), "converged": conv[rows, best].copy(),
+                    "n_iter": np.asarray(res["n_iter"]).reshape(n_e, n_s)[rows, best].copy(), "all_x": all_x, "all_lnprob": f,
+                    "all_converged": conv, "names": list(self.fitted_parameters), "seed": None if seed is None else int(seed)})
+        return out
+
+    def parametric_bootstrap(self, n_sims=256, x_hat=None, seed=None, max_iter=200, gtol=1e-8):
+        """Parametric bootstrap of the maximum (Efron & Tibshirani 1993, ch. 6): ``n_sims`` catalogues simulated from the
+        model at ``x_hat`` (default: ``maximize()["x"]``) on the data's positions and velocity errors, each refitted from
+        ``x_hat`` (``simulated_maximize``: one lock-stepped run), and ``parametric_bootstrap_summary`` of the refits: the bias
+        and the covariance of the estimator UNDER THE FITTED MODEL, with ``std_ratio`` against ``laplace(x_hat)`` where that
+        exists.  ``bootstrap()`` gives the same moments without the model (resampled stars); the ratio of the two ``std``
+        tells whether the model describes the scatter of the data.  ``covariance`` is accepted wherever
+        ``laplace()["covariance"]`` is.  Also returns ``x`` (E, P), ``converged``, ``n_iter``, ``lnprob``, ``x_hat``, ``seed``."""
+        self._holdout_check("parametric_bootstrap")
+        plan = self._grad_plan()
+        n_e = int(n_sims)
+        if n_e < 1:
+            raise ValueError("parametric_bootstrap: n_sims must be >= 1")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        x_hat = self.maximize(max_iter=max_iter, gtol=gtol)["x"] if x_hat is None else \
+            np.asarray(x_hat, dtype=np.float64).reshape(-1)
+        if x_hat.size != plan.free_idx.size:
+            raise ValueError("parametric_bootstrap: x_hat must hold the {0} free parameters".format(plan.free_idx.size))
+        fits = self.simulated_maximize(np.tile(x_hat, (n_e, 1)), seed=seed, x0=self._inside_box(x_hat, plan), max_iter=max_iter,
+                                       gtol=gtol)
+        try:
+            laplace = self.laplace(x_hat)["covariance"]
+        except ValueError:
+            laplace = None
+        out = parametric_bootstrap_summary(fits["x"], x_hat, fits["converged"], fits["names"], laplace)
+        out.update({"x": fits["x"], "converged": fits["converged"], "n_iter": fits["n_iter"], "lnprob": fits["lnprob"],
+                    "x_hat": x_hat, "seed": int(seed)})
+        return out
+
+    def _lrt_embedding(self, null):
+        """What makes ``null`` a sub-model of this fit: (positions of null's free parameters among this fit's free ones,
+        positions of the others, null's fixed values there), or ValueError with the reason."""
+        if type(null) is not type(self):
+            raise ValueError("lrt: the null fit is a {0}, this one a {1}".format(type(null).__name__, type(self).__name__))
+        if null.n_data != self.n_data:
+            raise ValueError("lrt: the null fit has {0} stars, this one {1}".format(null.n_data, self.n_data))
+        for col in list(self.OBSERVABLES) + ["pmember", "lnlike_background"]:
+            a, b = getattr(self, col, None), getattr(null, col, None)
+            if (a is None) != (b is None) or (a is not None and not np.array_equal(np.asarray(a), np.asarray(b))):
+                raise ValueError("lrt: the null fit's data column '{0}' differs from this fit's".format(col))
+        free, free0 = list(self.fitted_parameters), list(null.fitted_parameters)
+        for name in free0:
+            if name not in free:
+                raise ValueError("lrt: '{0}' is free in the null fit but not in this one (the models are not nested)".format(name))
+        if len(free0) == len(free):
+            raise ValueError("lrt: the null fit fixes no parameter that is free here")
+        plan = self._grad_plan()
+        lo, hi = plan.lo[plan.free_idx], plan.hi[plan.free_idx]
+        extra = [j for j, name in enumerate(free) if name not in free0]
+        fixed = np.array([float(null.parameters[free[j]]._value) for j in extra])
+        for j, val in zip(extra, fixed):
+            if not lo[j] <= val <= hi[j]:
+                raise ValueError("lrt: the null fit fixes '{0}' at {1}, outside this fit's box [{2}, {3}]".format(
+                    free[j], val, lo[j], hi[j]))
+        for name, par in self.parameters.items():
+            if par.fixed and par._expr is None and float(par._value) != float(null.parameters[name]._value):
+                raise ValueError("lrt: '{0}' is fixed at {1} here and at {2} in the null fit".format(
+                    name, float(par._value), float(null.parameters[name]._value)))
+        return np.array([free.index(name) for name in free0], dtype=np.intp), np.array(extra, dtype=np.intp), fixed
+
+    def lrt(self, null, n_sims=1024, seed=None, max_iter=200, gtol=1e-8):
+        """Likelihood-ratio test of this fit against the nested fit ``null`` -- the same class on the same stars, its free
+        parameters a subset of this fit's and the others fixed (rotation amplitudes at zero: "does the cluster rotate?")
+        -- with the null distribution of the statistic SIMULATED at the data's own positions and velocity errors (a
+        parametric bootstrap of the test, Davison & Hinkley 1997 ch. 4), because Wilks' chi2 is not to be trusted with a
+        few hundred stars, a background mixture or a parameter near a bound.
+
+        x0 = ``null.maximize()``, x1 = ``self.maximize()``, ``stat_obs`` = 2 (lnprob1 - lnprob0); ``n_sims`` catalogues are
+        drawn from the null at x0 (``null.simulate``) and handed to this fit (``simulated_set``); the null refits them
+        from x0 and this fit from two starts each -- x0 embedded (the null's fixed values in the other coordinates), so
+        that the full fit starts where the null ends and the statistic cannot be negative, and x1 -- by
+        ``simulated_maximize``.  Returns ``lrt_summary`` (``stat``, ``used``, ``p_value``, ``p_se``, ``df``,
+        ``p_asymptotic``, ``quantiles``, ``n_negative``) plus ``x_null``, ``x_full``, ``lnprob_null``, ``lnprob_full``,
+        ``fits_null``, ``fits_full``, ``tolerance`` and ``seed``.  ValueError, with the reason, when ``null`` is not a
+        sub-model of this fit."""
+        self._holdout_check("lrt")
+        if not isinstance(null, Runner):
+            raise ValueError("lrt: null must be a fit of the same class on the same stars")
+        shared, extra, fixed = self._lrt_embedding(null)
+        n_e = int(n_sims)
+        if n_e < 1:
+            raise ValueError("lrt: n_sims must be >= 1")
+        if seed is None:
+            seed = int(np.random.SeedSequence().entropy % (2 ** 63))
+        plan = self._grad_plan()
+        fit0 = null.maximize(max_iter=max_iter, gtol=gtol)
+        fit1 = self.maximize(max_iter=max_iter, gtol=gtol)
+        x0, x1 = fit0["x"], fit1["x"]
+        embedded = np.empty(plan.free_idx.size)
+        embedded[shared], embedded[extra] = x0, fixed
+        lnprob1 = float(fit1["lnprob"])
+        stat_obs = 2.0 * (lnprob1 - float(fit0["lnprob"]))
+        vel = null.simulate(np.tile(x0, (n_e, 1)), seed)
+        fits_null = null.simulated_maximize(x0=null._inside_box(x0, null._grad_plan()), max_iter=max_iter, gtol=gtol)
+        self.simulated_set(vel)
+        starts = np.stack([self._inside_box(embedded, plan), self._inside_box(x1, plan)])
+        fits_full = self.simulated_maximize(x0=np.broadcast_to(starts, (n_e,) + starts.shape), max_iter=max_iter, gtol=gtol)
+        scale = max(float(np.max(np.abs(fits_null["lnprob"]))), float(np.max(np.abs(fits_full["lnprob"]))), float(self.n_data))
+        tolerance = 4e-12 * scale
+        out = lrt_summary(fits_null["lnprob"], fits_full["lnprob"], fits_null["converged"], fits_full["converged"], stat_obs,
+                          len(extra), tolerance=tolerance)
+        out.update({"x_null": x0, "x_full": x1, "lnprob_null": float(fit0["lnprob"]), "lnprob_full": lnprob1,
+                    "fits_null": fits_null, "fits_full": fits_full, "velocities": vel, "tolerance": tolerance, "seed": int(seed)})
         return out
 
     # ------------------------------------------------------------------ Hamiltonian Monte Carlo (new)

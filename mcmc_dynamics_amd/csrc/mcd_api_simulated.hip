@@ -2,9 +2,10 @@
 // host driver of the simulated catalogues.  mcd_simulate draws n_sims catalogues' velocities from the model, one truth row
 // each, into a table resident on the catalogue's device; mcd_simulated_set uploads a caller's own; mcd_simulated_loglike
 // evaluates R parameter rows in one launch, every row against the velocities of its own simulation (kernels:
-// mcd_simulated.hip; velocity rule, term and loop: mcd_simulated.h; generator: mcd_replicate.h).
+// mcd_simulated.hip; velocity rule, term and loop: mcd_simulated.h; generator: mcd_replicate.h);
+// mcd_simulated_loglike_grad adds the gradient (kernel: mcd_simulated_grad.hip; loop: mcd_simulated_grad.h).
 #include "mcd_host.h"
-#include "mcd_simulated.h"
+#include "mcd_simulated_grad.h"
 
 using namespace mcd::host;
 
@@ -15,6 +16,8 @@ MCD_HOST_BEGIN
 void release_simulated(mcd_catalog* cat, bool keep_set) {
     for (auto& kv : cat->simulated) free_weighted_work(kv.second);
     cat->simulated.clear();
+    for (auto& kv : cat->simulated_grad) free_weighted_work(kv.second);
+    cat->simulated_grad.clear();
     if (keep_set) return;
     if (cat->d_sim) (void)hipFree(cat->d_sim);
     cat->d_sim = nullptr;
@@ -225,6 +228,72 @@ int simulated_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const double*
     return MCD_OK;
 }
 
+// What the two evaluations refuse, in the order of include/mcd.h; `name` opens the message, `nulls` names the pointers
+int simulated_rows_usable(mcd_catalog* cat, const std::string& name, int64_t n_rows, int32_t k, bool any_null,
+                          const char* nulls, const int64_t* row_sim) {
+    if (int rc = simulated_usable(cat, name)) return rc;
+    if (any_null) return fail(MCD_ERR_INVALID, name + ": null " + nulls);
+    if (k != cat->k) return fail(MCD_ERR_INVALID, name + ": parameter rows have the wrong number of columns");
+    if (n_rows < 1 || n_rows > mcd::kSimulatedMaxRows)
+        return fail(MCD_ERR_INVALID, name + ": needs 1 .. " + std::to_string(mcd::kSimulatedMaxRows) + " parameter rows");
+    if (cat->sim_count < 1 || !cat->d_sim)
+        return fail(MCD_ERR_INVALID, name + ": no simulated set is resident (mcd_simulate or mcd_simulated_set first)");
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (row_sim[r] < 0 || row_sim[r] >= cat->sim_count)
+            return fail(MCD_ERR_INVALID, name + ": row_sim[" + std::to_string(r) + "] = " + std::to_string(row_sim[r]) +
+                                             " is outside [0, " + std::to_string(cat->sim_count) + ")");
+    return MCD_OK;
+}
+
+// ... and what both do between their validation and their kernel: the plan and buffers of the row count from `cache`
+// (`fields` sums per row), params and simulation ids H2D, walker prep (the weighted path's staging); the device is current
+// and the first timing event recorded when this returns
+int simulated_stage(mcd_catalog* cat, const std::string& name, std::map<int64_t, WeightedWork>& cache, size_t fields,
+                    int64_t n_rows, int32_t k, const double* params, const int64_t* row_sim, WeightedWork** out) {
+    Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    MCD_HIP(hipSetDevice(slot.device));
+    // (an earlier pipelined evaluation may still be in flight on the stream the plans are released and built on)
+    MCD_WAIT(cat->ctx, slot.stream, cat->spin_us, (name + " (previous evaluation)").c_str());
+    if (int rc = weighted_work(cat, cache, fields, sh, n_rows, out)) return rc;
+    WeightedWork& w = **out;
+    std::memcpy(w.h_params, params, (size_t)n_rows * k * sizeof(double));
+    std::memcpy(w.h_replicate, row_sim, (size_t)n_rows * sizeof(int64_t));
+    MCD_HIP(hipMemcpyAsync(w.d_params, w.h_params, (size_t)n_rows * k * sizeof(double), hipMemcpyHostToDevice, slot.stream));
+    MCD_HIP(hipMemcpyAsync(w.d_replicate, w.h_replicate, (size_t)n_rows * sizeof(int64_t), hipMemcpyHostToDevice, slot.stream));
+    MCD_HIP(mcd::launch_prepare_walkers(slot.stream, w.d_params, n_rows, k, cat->model, cat->free_centre, cat->precision,
+                                        w.d_wpar));
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e0, slot.stream));
+    return MCD_OK;
+}
+
+int simulated_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const int64_t* row_sim,
+                           double* out, double* grad) {
+    const std::string name("mcd_simulated_loglike_grad");
+    if (int rc = simulated_rows_usable(cat, name, n_rows, k, !params || !row_sim || !grad, "params, row_sim or grad", row_sim))
+        return rc;
+    WeightedWork* wp = nullptr;
+    if (int rc = simulated_stage(cat, name, cat->simulated_grad, (size_t)(1 + k), n_rows, k, params, row_sim, &wp)) return rc;
+    WeightedWork& w = *wp;
+    const Shard& sh = cat->shards[0];
+    const DeviceSlot& slot = cat->ctx->slots[sh.slot];
+    const size_t fields = (size_t)(1 + k), padded = (size_t)mcd::padded_walkers(n_rows);
+    const mcd::LaunchShape shape{cat->model, cat->free_centre, cat->precision, 0};
+    MCD_HIP(mcd::launch_simulated_grad(slot.stream, shape, sh.records, w.d_chunks, w.n_chunks, w.d_params, w.d_wpar,
+                                       w.d_replicate, cat->d_sim, cat->sim_count, cat->sim_bg_mean, cat->sim_bg_sigma2,
+                                       w.d_partials, n_rows));
+    if (cat->timing) MCD_HIP(hipEventRecord(w.e1, slot.stream));
+    MCD_HIP(mcd::launch_grad_reduce(slot.stream, shape, w.d_partials, w.n_chunks, w.d_offsets, 1, w.n_chunks, n_rows, w.d_out));
+    MCD_HIP(hipMemcpyAsync(w.h_out, w.d_out, fields * padded * sizeof(double), hipMemcpyDeviceToHost, slot.stream));
+    if (int rc = weighted_finish(cat, name, w, n_rows)) return rc;
+    if (out) std::memcpy(out, w.h_out, (size_t)n_rows * sizeof(double));
+    for (int64_t j = 0; j < k; ++j) {
+        const double* col = w.h_out + (1 + j) * padded;
+        for (int64_t i = 0; i < n_rows; ++i) grad[i * k + j] = col[i];
+    }
+    return MCD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -247,6 +316,13 @@ int mcd_simulated_loglike(mcd_catalog* cat, int64_t n_rows, int32_t k, const dou
     try {
     return simulated_loglike(cat, n_rows, k, params, row_sim, out);
     } catch (...) { return on_exception("mcd_simulated_loglike"); }
+}
+
+int mcd_simulated_loglike_grad(mcd_catalog* cat, int64_t n_rows, int32_t k, const double* params, const int64_t* row_sim,
+                               double* out, double* grad) {
+    try {
+    return simulated_loglike_grad(cat, n_rows, k, params, row_sim, out, grad);
+    } catch (...) { return on_exception("mcd_simulated_loglike_grad"); }
 }
 
 int mcd_simulated_info(const mcd_catalog* cat, int64_t* n_sims) {

@@ -75,8 +75,13 @@ template <class T> struct GradRaw {
 };
 
 // g[0 .. K) += dl/dtheta_k of one star for one walker; returns l (the value path's plain term: gauss_lnl / mixture_lnl).
-template <int MODEL, bool FREE, class T = double>
-MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T* __restrict__ g) {
+// SIM (mcd_simulated_grad.h): the star's velocity is v, not the record's -- the residual becomes d + (v - r[0]) as
+// simulated_term (mcd_simulated.h) forms it, the fitted background's v - v_back, and the fixed-background families take
+// the Gaussian (bg_mean, bg_sigma2) at v in place of the stored lnlike_bg.  The partials of d and n do not depend on the
+// velocity.  Without SIM the three arguments are not read.
+template <int MODEL, bool FREE, class T, bool SIM>
+MCD_HD T grad_term_at(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T v, T bg_mean, T bg_sigma2,
+                      T* __restrict__ g) {
     using C = GradCols<MODEL, FREE>;
     constexpr int XB = geometry_doubles(MODEL, FREE);
     constexpr int BG = bg_kind(MODEL);
@@ -103,6 +108,8 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
             const T s = y * inv, c = off_centre ? x * inv : (std::signbit(x) ? T(-1) : T(1));
             const T u = fma_(w.vx, s, -(w.vy * c));
             d = (r[0] - w.vsys) - u;
+            // (the value path rounds this residual otherwise, and a simulated term returns simulated_term's bits)
+            if constexpr (SIM) d = free_centre_residual<false>(r[2], r[3], r[4], w.sac, w.cac, w.sdc, w.cdc, w.vx, w.vy, r[0] - w.vsys);
             d_vx = -s;
             d_vy = c;
             const T d_x = inv * fma_(u, c, w.vy), d_y = inv * fma_(u, s, -w.vx);     // inv = 0 on the centre
@@ -163,6 +170,7 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
             n_dec = n_r * (dy * dy_dec);
         }
     }
+    if constexpr (SIM) d = d + (v - r[0]);
     const T dn = d / n;
     T c_d = -dn;                                                   // dlc/dd
     T c_n = T(0.5) * (dn * dn - T(1) / n);                         // dlc/dn
@@ -171,6 +179,19 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
     // ---- mixture: responsibilities after subtracting max(lc, lb)
     if constexpr (BG != BG_NONE) {
         T lb, p, rho = T(0), db = T(0), nb = T(1);
+        if constexpr (SIM) {
+            if constexpr (BG == BG_GAUSS) {
+                nb = r[1] + w.sb2;
+                db = v - w.vb;
+                lb = gauss_lnl(db, nb);
+                rho = r[XB];
+            } else {
+                lb = gauss_lnl(v - bg_mean, r[1] + bg_sigma2);
+                if constexpr (BG == BG_FIXED) p = r[XB + 1];
+                else rho = r[XB + 2];
+            }
+            if constexpr (BG != BG_FIXED) p = rho / (rho + w.fb);
+        } else
         if (BG == BG_FIXED) { lb = r[XB]; p = r[XB + 1]; }
         else if (BG == BG_FIXED_DENSITY) { lb = r[XB]; rho = r[XB + 2]; p = rho / (rho + w.fb); }
         else {
@@ -220,6 +241,11 @@ MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T
         }
     }
     return l;
+}
+
+template <int MODEL, bool FREE, class T = double>
+MCD_HD T grad_term(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q, T* __restrict__ g) {
+    return grad_term_at<MODEL, FREE, T, false>(r, w, q, T(0), T(0), T(0), g);
 }
 
 // One chunk of stars for one walker: acc[0] += sum of l, acc[1 + k] += sum of dl/dtheta_k (star order).

@@ -15,8 +15,9 @@
 //   mcd_api_replicate.hip  mcd_replicate_check, mcd_replicate_numbers: replicated-data predictive checks per range of stars
 //   mcd_api_weighted.hip   mcd_weighted_loglike_grad, mcd_weighted_loglike, mcd_bootstrap_weights: value and gradient, or
 //                          the value alone, under per-row star weights
-//   mcd_api_simulated.hip  mcd_simulate, mcd_simulated_set, mcd_simulated_loglike, mcd_simulated_info: simulated catalogues
-//                          resident on the device, and every parameter row against the velocities of its own simulation
+//   mcd_api_simulated.hip  mcd_simulate, mcd_simulated_set, mcd_simulated_loglike, mcd_simulated_loglike_grad,
+//                          mcd_simulated_info: simulated catalogues resident on the device, and every parameter row (value,
+//                          or value and gradient) against the velocities of its own simulation
 //   mcd_api_diag.hip       mcd_chain_diagnostics: on the host without a context, on the context's first device with one
 // The kernel units they call share mcd_dispatch.h ((model, free_centre) and term precision -> template arguments, the one
 // list of models) and mcd_launch.h (workgroup shape, padded_walkers, the main kernels' wave mapping and partial-sum address).
@@ -407,6 +408,7 @@ struct mcd_catalog {
     int64_t sim_count = 0;
     double sim_bg_mean = 0.0, sim_bg_sigma2 = 0.0;
     std::map<int64_t, mcd::host::WeightedWork> simulated;
+    std::map<int64_t, mcd::host::WeightedWork> simulated_grad;   // mcd_simulated_loglike_grad's, 1 + K fields per row
     int last_prefetch = -1;            // the last main-kernel launch used the prefetching instantiation (-1: none yet)
     int64_t last_series_chunks = -1;   // chunks of the last main-kernel launch that took the series root (host count), -1: no launch yet
     int64_t last_direct_chunks = -1;   // ... of which in the direct form (host count), -1: no launch yet
