@@ -533,6 +533,48 @@ int mcd_stretch_move_seeded_prior(mcd_catalog* cat, const mcd_stretch_desc* desc
                                   uint64_t seed, int64_t step0, double* chain, double* lnprob_chain, int64_t* accepted,
                                   const mcd_prior_desc* prior);
 
+/* One block of differential-evolution steps (ter Braak 2006; with a jittered scale, Nelson et al. 2013) in place of the
+ * stretch move: the same red / blue half steps, the same launch of W/2 rows per half step, one value evaluation per
+ * proposal.  For slot j of half step h (s = pos[first[j]], first / second the halves of order[i]):
+ *   proposal  s + (x_a - x_b) g, x_a = pos[second[pick_a]], x_b = pos[second[pick_b]], pick_a != pick_b both in 0 .. W/2 - 1
+ *             (a subtraction, a multiplication, an addition per coordinate, never contracted)
+ *   accept    iff thr < lnp_new - lnp_old (thr = log u: the proposal is symmetric, there is no (P - 1) log z term)
+ * `desc` is the stretch move's descriptor and everything it says about the box, fixed_ok, the column map and the B
+ * lock-stepped ensembles of a binned catalogue holds here (desc->n_bins must equal the catalogue's number of parameter
+ * sets); `prior` (may be NULL) as in the *_prior entry points.  Array layouts: pos [B][W][P], lnp [B][W], order
+ * [n_steps][B][W], pick_a / pick_b / gamma / thr [n_steps][2][B][W/2], chain [n_steps][B][W][P] or NULL, lnprob_chain
+ * [n_steps][B][W] or NULL, accepted [B][W] or NULL (added to).  W must be even and >= 4: a half holds two distinct partners.
+ *
+ * A float64 catalogue on one device in one process runs the block RESIDENT (mcmc_dynamics_amd/csrc/mcd_de.hip: one small
+ * kernel per half step accepts, proposes, applies the priors, builds the table rows and their walker constants and judges
+ * the range guard); everything else, and any block in which the device met a NaN, a re-run request, a changed kernel
+ * family or an ensemble without a proposal inside the prior, runs HOST-DRIVEN from the same inputs around mcd_loglike_batch
+ * (mcd_de.h: de_block).  The two give the same chain bit for bit.  Option "device_chain" = 0 forces the host-driven form.
+ *
+ * mcd_de_move_seeded generates the numbers inside the library: g = gamma0 (1 + sigma n), n a standard normal (polar method
+ * with det_log: no libm call decides a bit); the samplers' defaults are gamma0 = 2.38 / sqrt(2 P), sigma = 1e-5.  The
+ * generator is Philox4x64-10 under a key constant of its own -- the stream is independent of mcd_chain_numbers' of the same
+ * seed -- and a number is a function of (seed, step, half step, ensemble, slot) alone: blocks of any length continue each
+ * other through step0, and mcd_de_numbers (needs no device) returns the numbers of steps step0 .. step0 + n_steps - 1 in the
+ * layout mcd_de_move takes, so that mcd_de_move(..., those arrays, ...) gives the same chain bit for bit.
+ *
+ * MCD_ERR_INVALID, nothing written: gamma0 <= 0 or non-finite, sigma < 0 or non-finite, W < 4 or odd (seeded: W > 1048576),
+ * desc->n_bins different from the catalogue's, an index outside its range, a null array.  MCD_ERR_NONFINITE: the
+ * log-probability returned NaN.  (Added entry points: MCD_ABI_VERSION stays at 1.) */
+int mcd_de_move(mcd_catalog* cat, const mcd_stretch_desc* desc, const mcd_prior_desc* prior /* may be NULL */, int64_t n_steps,
+                double* pos, double* lnp, const int32_t* order, const int32_t* pick_a, const int32_t* pick_b,
+                const double* gamma, const double* thr, double* chain, double* lnprob_chain, int64_t* accepted);
+int mcd_de_move_seeded(mcd_catalog* cat, const mcd_stretch_desc* desc, const mcd_prior_desc* prior /* may be NULL */,
+                       double gamma0, double sigma, int64_t n_steps, double* pos, double* lnp, uint64_t seed, int64_t step0,
+                       double* chain, double* lnprob_chain, int64_t* accepted);
+int mcd_de_numbers(uint64_t seed, int64_t step0, int64_t n_steps, int64_t n_bins, int64_t n_walkers, int32_t n_dim,
+                   double gamma0, double sigma, int32_t* order, int32_t* pick_a, int32_t* pick_b, double* gamma, double* thr);
+/* Blocks of mcd_de_move* that ran resident / host-driven, blocks the device discarded (they were then run host-driven and
+ * count there too) and the status bits of the last discarded one, as mcd_stretch_info -- which keeps counting stretch
+ * blocks only.  Any pointer may be NULL. */
+int mcd_de_info(const mcd_catalog* cat, int64_t* device_blocks, int64_t* host_blocks, int64_t* discarded_blocks,
+                int32_t* last_discard_status);
+
 /* One block of Hamiltonian Monte Carlo steps (Duane et al. 1987; Neal 2011) on the gradient of mcd_loglike_grad_batch:
  * W independent chains, each step n_leap leapfrog points, i.e. n_leap value-and-gradient evaluations of W rows.  The
  * reference has no gradient-based sampler -- this stands beside mcd_stretch_move_seeded as a second way to drive the chain

@@ -98,6 +98,18 @@ SYMBOLS = {
                                          ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p,
                                          ctypes.POINTER(ctypes.c_int32)]),
     "mcd_stretch_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p, _c_int64_p, ctypes.POINTER(ctypes.c_int32)]),
+    "mcd_de_move": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
+                                   ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                   ctypes.POINTER(ctypes.c_int32), _c_double_p, _c_double_p, _c_double_p, _c_double_p,
+                                   _c_int64_p]),
+    "mcd_de_move_seeded": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_int64, _c_double_p, _c_double_p, ctypes.c_uint64, ctypes.c_int64,
+                                          _c_double_p, _c_double_p, _c_int64_p]),
+    "mcd_de_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                      ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_int32),
+                                      ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), _c_double_p,
+                                      _c_double_p]),
+    "mcd_de_info": (ctypes.c_int, [ctypes.c_void_p, _c_int64_p, _c_int64_p, _c_int64_p, ctypes.POINTER(ctypes.c_int32)]),
     "mcd_hmc_block": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_double_p, _c_double_p,
                                      ctypes.c_uint64, ctypes.c_int64, _c_double_p, _c_double_p, _c_int64_p, _c_double_p]),
     "mcd_hmc_numbers": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -476,6 +488,27 @@ def chain_numbers(seed, step0, n_steps, n_bins, n_walkers, n_dim, squeeze=False)
     if squeeze:
         return order[:, 0], zz[:, :, 0], thr[:, :, 0], pick[:, :, 0]
     return order, zz, thr, pick
+
+
+def de_numbers(seed, step0, n_steps, n_bins, n_walkers, n_dim, gamma0, sigma, squeeze=False):
+    """``mcd_de_numbers``: the random numbers of steps ``step0 .. step0 + n_steps - 1`` of the seeded differential-evolution
+    chain (host code, no device involved; csrc/mcd_de.h): order (steps, B, W) int32, pick_a / pick_b int32 and gamma / thr
+    float64 (steps, 2, B, W/2), in the layout ``de_move`` takes.  ``squeeze``: drop the ensemble axis (n_bins <= 1)."""
+    lib = load_library()
+    b, w, n = max(int(n_bins), 1), int(n_walkers), int(n_steps)
+    i32 = ctypes.POINTER(ctypes.c_int32)
+    order = np.empty((n, b, w), dtype=np.int32)
+    pick_a = np.empty((n, 2, b, w // 2), dtype=np.int32)
+    pick_b = np.empty_like(pick_a)
+    gamma = np.empty((n, 2, b, w // 2), dtype=np.float64)
+    thr = np.empty_like(gamma)
+    rc = lib.mcd_de_numbers(int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), n, b, w, int(n_dim), float(gamma0), float(sigma),
+                            order.ctypes.data_as(i32), pick_a.ctypes.data_as(i32), pick_b.ctypes.data_as(i32), _ptr(gamma),
+                            _ptr(thr))
+    _check(lib, rc, "mcd_de_numbers")
+    if squeeze:
+        return order[:, 0], pick_a[:, :, 0], pick_b[:, :, 0], gamma[:, :, 0], thr[:, :, 0]
+    return order, pick_a, pick_b, gamma, thr
 
 
 def hmc_numbers(seed, step0, n_steps, n_walkers, n_dim):
@@ -1076,6 +1109,52 @@ class Catalog(object):
             rc = self.lib.mcd_stretch_move_seeded(*head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail)
         _check(self.lib, rc, "mcd_stretch_move_seeded")
         self._walkers = pos.shape[-2] // 2
+
+    def _de_prior(self, plan):
+        """The ``prior`` argument of the DE entry points from a plan's optional ``prior`` entry (and what keeps it alive)."""
+        if plan.get("prior") is None:
+            return None, None
+        pd, keep = _prior_desc(plan["prior"])
+        return ctypes.byref(pd), (pd, keep)
+
+    def de_move(self, plan, pos, lnp, order, pick_a, pick_b, gamma, thr, chain=None, lnprob_chain=None, accepted=None):
+        """``mcd_de_move``: advance the ensemble(s) by ``len(order)`` differential-evolution steps (csrc/mcd_de.h) with the
+        half-step loop inside the library.  ``plan``, ``pos``, ``lnp`` and the outputs as for ``stretch_move`` (a ``prior``
+        entry of the plan is handed on); ``order`` (steps, [B,] W) int32, ``pick_a`` / ``pick_b`` int32 and ``gamma`` / ``thr``
+        float64 (steps, 2, [B,] W/2), as ``de_numbers`` returns them."""
+        head, tail, _keep = self._stretch_args("de_move", plan, pos, lnp, order.shape[0], chain, lnprob_chain, accepted)
+        for a, dt in ((gamma, np.float64), (thr, np.float64), (order, np.int32), (pick_a, np.int32), (pick_b, np.int32)):
+            if a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError("de_move needs C-contiguous arrays of the documented dtypes")
+        half_shape = (order.shape[0], 2) + pos.shape[:-2] + (pos.shape[-2] // 2,)
+        if order.shape != order.shape[:1] + lnp.shape or any(a.shape != half_shape for a in (pick_a, pick_b, gamma, thr)):
+            raise ValueError("de_move: inconsistent array shapes")
+        prior, _keep_prior = self._de_prior(plan)
+        i32 = ctypes.POINTER(ctypes.c_int32)
+        rc = self.lib.mcd_de_move(head[0], head[1], prior, *head[2:], order.ctypes.data_as(i32), pick_a.ctypes.data_as(i32),
+                                  pick_b.ctypes.data_as(i32), _ptr(gamma), _ptr(thr), *tail)
+        _check(self.lib, rc, "mcd_de_move")
+        self._walkers = pos.shape[-2] // 2
+
+    def de_move_seeded(self, plan, pos, lnp, gamma0, sigma, seed, step0, n_steps, chain=None, lnprob_chain=None, accepted=None):
+        """``mcd_de_move_seeded``: the same block with its random numbers generated inside the library -- steps ``step0 ..
+        step0 + n_steps - 1`` of the chain that ``seed`` names; ``de_numbers(seed, step0, n_steps, ...)`` returns them."""
+        if n_steps < 0 or step0 < 0:
+            raise ValueError("de_move_seeded: inconsistent array shapes")
+        head, tail, _keep = self._stretch_args("de_move_seeded", plan, pos, lnp, n_steps, chain, lnprob_chain, accepted)
+        prior, _keep_prior = self._de_prior(plan)
+        rc = self.lib.mcd_de_move_seeded(head[0], head[1], prior, float(gamma0), float(sigma), *head[2:],
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(step0), *tail)
+        _check(self.lib, rc, "mcd_de_move_seeded")
+        self._walkers = pos.shape[-2] // 2
+
+    def de_info(self):
+        """Where the blocks of ``de_move`` / ``de_move_seeded`` ran: {'device_blocks', 'host_blocks', 'discarded_blocks',
+        'last_discard_status'} (``mcd_de_info``; ``stretch_info`` keeps counting stretch blocks only)."""
+        a, b, c, st = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int32(0)
+        _check(self.lib, self.lib.mcd_de_info(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(st)),
+               "mcd_de_info")
+        return {"device_blocks": a.value, "host_blocks": b.value, "discarded_blocks": c.value, "last_discard_status": st.value}
 
     @property
     def last_prefetch(self):

@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from ..sampler import _clear, _host_seed, _reserve, _run_blocks, _setup
+from ..sampler import _clear, _host_seed, _reserve, _run_blocks, _setup, default_gamma0
 from .constant import ConstantFit
 
 logger = logging.getLogger(__name__)
@@ -30,7 +30,8 @@ class BinnedSampler(object):
 
     N_STREAMS = 8          # part of the definition of the random stream (2: 334, 4: 313, 8: 297 us per step at 55 x 512)
 
-    def __init__(self, n_bins, nwalkers, ndim, log_prob_fn, a=2.0, seed=None, block_fn=None, rng="host", seeded_block_fn=None):
+    def __init__(self, n_bins, nwalkers, ndim, log_prob_fn, a=2.0, seed=None, block_fn=None, rng="host", seeded_block_fn=None,
+                 move="stretch", gamma0=None, sigma=1e-5):
         """``rng``: where the move's random numbers come from.
 
         ``"host"``: NumPy's Mersenne twister on the host, as emcee draws (B x W numbers per step cross PCIe: the draws, not
@@ -39,9 +40,12 @@ class BinnedSampler(object):
         ``"device"``: the counter-based generator of csrc/mcd_rng.h: every number is a function of (seed, step, half step,
         bin, walker) alone (``sampler._setup``).  ``seeded_block_fn`` (``Runner._stretch_block_seeded``) runs whole blocks
         with the numbers generated on the device; without it (expression priors) the NumPy loop takes the SAME numbers
-        from ``_native.chain_numbers`` -- one chain whichever way it is run, and however it is cut into blocks."""
+        from ``_native.chain_numbers`` -- one chain whichever way it is run, and however it is cut into blocks.
+
+        ``move``: ``"stretch"`` or ``"de"``, the differential-evolution move (``sampler._setup``; ``gamma0``, ``sigma``); it
+        needs ``rng="device"``, and ``seeded_block_fn`` is then the DE block (``Runner._de_block_seeded``)."""
         self.n_bins = int(n_bins)
-        _setup(self, (self.n_bins,), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn)
+        _setup(self, (self.n_bins,), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn, move, gamma0, sigma)
         self.log_prob_fn = log_prob_fn
         self.block_steps = 64                     # steps whose random numbers are drawn together (defines the stream)
         self.device_block_steps = 256             # rng="device": steps per library call (NOT part of the stream's definition)
@@ -234,12 +238,17 @@ class BinnedConstantFit(ConstantFit):
         return float(self.lnlike_total(np.asarray(values, dtype=np.float64).reshape(1, -1))[0])
 
     RNG = "device"                 # where BinnedSampler's random numbers come from ("host": NumPy's generator, as emcee)
+    MOVE = "stretch"               # the move when ``__call__`` is not told one: "stretch" or "de" (sampler._setup)
 
-    def __call__(self, n_walkers=100, n_steps=100, pos=None, seed=None, rng=None, **kwargs):
+    def __call__(self, n_walkers=100, n_steps=100, pos=None, seed=None, rng=None, move=None, gamma0=None, sigma=1e-5, **kwargs):
         """Run the B ensembles in lockstep; returns a ``BinnedSampler`` (``.chain``: (B, W, steps, P)).  ``rng``: see
-        ``BinnedSampler`` (default: the class attribute ``RNG``)."""
+        ``BinnedSampler`` (default: the class attribute ``RNG``).  ``move``: ``"stretch"`` or ``"de"`` (default: the class
+        attribute ``MOVE``), with ``gamma0`` and ``sigma`` as ``BinnedSampler`` takes them."""
         if kwargs.get("n_threads", 1) != 1:
             raise ValueError("n_threads > 1 is not supported by the GPU backend.")
+        move = move or self.MOVE
+        if move == "de" and self._rank_group() is not None:
+            raise NotImplementedError("move='de' on a multi-rank context: the collective resident DE block is not built")
         if pos is None:
             pos = np.stack([self.get_initials(n_walkers) for _ in range(self.n_bins)])
         pos = np.asarray(pos, dtype=np.float64)
@@ -257,9 +266,15 @@ class BinnedConstantFit(ConstantFit):
         # (library blocks only for the package's own posterior and box priors: a subclass that overrides a posterior method
         # outside the package is driven by the NumPy loop around ITS lnprob_batch -- Runner.resident_ok)
         native_ok = self.resident_ok()[0] and self.n_bins > 1
-        sampler = BinnedSampler(self.n_bins, n_walkers, self.n_fitted_parameters, self.lnprob_batch, seed=seed,
-                                block_fn=self._stretch_block if native_ok else None, rng=rng or self.RNG,
-                                seeded_block_fn=self._stretch_block_seeded if native_ok else None)
+        if move == "de":
+            g0 = default_gamma0(self.n_fitted_parameters) if gamma0 is None else float(gamma0)
+            seeded = (lambda *block: self._de_block_seeded(g0, sigma, *block)) if native_ok else None
+            sampler = BinnedSampler(self.n_bins, n_walkers, self.n_fitted_parameters, self.lnprob_batch, seed=seed,
+                                    rng=rng or self.RNG, seeded_block_fn=seeded, move="de", gamma0=g0, sigma=sigma)
+        else:
+            sampler = BinnedSampler(self.n_bins, n_walkers, self.n_fitted_parameters, self.lnprob_batch, seed=seed,
+                                    block_fn=self._stretch_block if native_ok else None, rng=rng or self.RNG,
+                                    seeded_block_fn=self._stretch_block_seeded if native_ok else None, move=move)
         sampler.run_mcmc(pos, n_steps)
         return sampler
 

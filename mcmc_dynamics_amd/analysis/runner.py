@@ -1156,7 +1156,7 @@ class Runner(object):
         return out.reshape(lead)
 
     def bagged(self, n_bags=64, n_walkers=64, n_steps=600, n_burn=200, scheme="exponential", seed=None, pos=None,
-               bag_fraction=1.0, thin=1):
+               bag_fraction=1.0, thin=1, move="stretch", gamma0=None, sigma=1e-5):
         """The bagged posterior ("BayesBag": Huggins & Miller 2019, 2023): ``n_bags`` posteriors of the same model, bag b on
         the catalogue under the bootstrap weights of replicate b (``scheme`` "exponential": Exp(1), "poisson": Poisson(1)
         counts; the weights of ``bootstrap`` -- a function of (seed, b, star), ``_native.bootstrap_weights`` replays them),
@@ -1169,7 +1169,8 @@ class Runner(object):
         Returns ``bagged_summary`` of the chains -- the pooled moments are the bagged posterior, ``within`` / ``between`` /
         ``mismatch_ratio`` compare the model's own width with the sampling scatter (see there) -- plus ``sampler``
         (``chain``: (B, W, steps, P)), ``seed``, ``scheme`` and ``bag_fraction``.  Unlike every interval taken from one
-        chain, the bagged intervals keep their coverage when the model understates the scatter of the data."""
+        chain, the bagged intervals keep their coverage when the model understates the scatter of the data.
+        ``move``, ``gamma0``, ``sigma``: the sampler's move (``BinnedSampler``: "stretch" or "de")."""
         self._holdout_check("bagged")
         from .binned import BinnedSampler
         n_b, n_w, n_p = int(n_bags), int(n_walkers), self.n_fitted_parameters
@@ -1199,7 +1200,7 @@ class Runner(object):
             rep = np.repeat(np.arange(n_b, dtype=np.int64), values.shape[1])
             return self.lnprob_weighted_batch(values, rep, scheme=scheme, seed=seed, weight_scale=bag_fraction)
 
-        sampler = BinnedSampler(n_b, n_w, n_p, log_prob, seed=seed, rng="device")
+        sampler = BinnedSampler(n_b, n_w, n_p, log_prob, seed=seed, rng="device", move=move, gamma0=gamma0, sigma=sigma)
         logger.info("bagged posterior: %d bags (%s weights), %d walkers each, %d steps", n_b, scheme, n_w, n_steps)
         sampler.reserve(int(n_steps))
         sampler.run_mcmc(pos, int(n_steps))
@@ -1351,7 +1352,8 @@ class Runner(object):
             pos[bad] = truths[e] + 0.01 * scale[e] * rng.normal(size=(int(bad.sum()), n_p))
         raise ValueError("simulated_fits: no start positions inside the prior around a truth (it sits on a bound)")
 
-    def simulated_fits(self, truths, n_walkers=64, n_steps=600, n_burn=200, seed=None, velocities=None, pos=None, thin=1):
+    def simulated_fits(self, truths, n_walkers=64, n_steps=600, n_burn=200, seed=None, velocities=None, pos=None, thin=1,
+                       move="stretch", gamma0=None, sigma=1e-5):
         """Fit E simulated catalogues in lock step: catalogue e is drawn from the model at ``truths[e]`` (``simulate``), or is
         row e of the caller's ``velocities`` (E, n_data) in km/s (``simulated_set``).  E ensembles of ``n_walkers`` walkers
         take ``n_steps`` stretch-move steps (``BinnedSampler``, ``rng="device"``: the chains are a function of ``seed``);
@@ -1361,7 +1363,7 @@ class Runner(object):
 
         Returns ``simulated_fit_summary`` of the chains (per fit: ``mean``, ``std``, ``percentiles``, ``tau``, ``converged``,
         ``z`` = (mean - truth) / std) plus ``truths``, ``velocities``, ``sampler`` (``chain``: (E, W, steps, P)) and
-        ``seed``."""
+        ``seed``.  ``move``, ``gamma0``, ``sigma``: the sampler's move (``BinnedSampler``: "stretch" or "de")."""
         self._holdout_check("simulated_fits")
         from .binned import BinnedSampler
         n_w, n_p = int(n_walkers), self.n_fitted_parameters
@@ -1393,7 +1395,7 @@ class Runner(object):
             # (E, rows, P): the rows of ensemble e on simulation e
             return self.lnprob_simulated_batch(values, np.repeat(np.arange(n_e, dtype=np.int64), values.shape[1]))
 
-        sampler = BinnedSampler(n_e, n_w, n_p, log_prob, seed=seed, rng="device")
+        sampler = BinnedSampler(n_e, n_w, n_p, log_prob, seed=seed, rng="device", move=move, gamma0=gamma0, sigma=sigma)
         logger.info("simulated fits: %d catalogues, %d walkers each, %d steps", n_e, n_w, n_steps)
         sampler.reserve(int(n_steps))
         sampler.run_mcmc(pos, int(n_steps))
@@ -1402,7 +1404,7 @@ class Runner(object):
                     "names": list(self.fitted_parameters)})
         return out
 
-    def sbc(self, n_sims=256, n_walkers=32, n_steps=600, n_burn=200, seed=None, n_bins=8, thin=None, truths=None):
+    def sbc(self, n_sims=256, n_walkers=32, n_steps=600, n_burn=200, seed=None, n_bins=8, thin=None, truths=None, move="stretch", gamma0=None, sigma=1e-5):
         """Simulation-based calibration of this fit: ``n_sims`` truths drawn from the prior (``sample_prior(n_sims, seed)``;
         or the caller's ``truths``), one simulated catalogue each, all fitted in lock step (``simulated_fits``), and the
         rank statistics of ``sbc_summary`` (``thin`` = None: the largest autocorrelation time).  Returns that summary plus
@@ -1411,7 +1413,7 @@ class Runner(object):
             seed = int(np.random.SeedSequence().entropy % (2 ** 63))
         if truths is None:
             truths = self.sample_prior(int(n_sims), seed=seed)
-        fits = self.simulated_fits(truths, n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed)
+        fits = self.simulated_fits(truths, n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed, move=move, gamma0=gamma0, sigma=sigma)
         try:
             prior_variance = self.prior_variance()
         except (ValueError, NotImplementedError):
@@ -1420,7 +1422,8 @@ class Runner(object):
         out.update({"fits": fits, "truths": fits["truths"], "names": fits["names"], "seed": int(seed)})
         return out
 
-    def recovery(self, truth, n_sims=64, n_walkers=32, n_steps=600, n_burn=200, seed=None, thin=1, functions=None, null=None):
+    def recovery(self, truth, n_sims=64, n_walkers=32, n_steps=600, n_burn=200, seed=None, thin=1, functions=None, null=None,
+                 move="stretch", gamma0=None, sigma=1e-5):
         """Injection-recovery: ``n_sims`` catalogues simulated at the one ``truth`` (P,) -- or at every row of a grid (G, P),
         ``n_sims`` each -- on the data's positions and velocity errors, fitted in lock step (``simulated_fits``), and
         ``recovery_summary`` per truth: bias, scatter, interval coverage, z scores, and for every entry of ``functions`` the
@@ -1434,7 +1437,7 @@ class Runner(object):
             raise ValueError("recovery: n_sims must be >= 1")
         if seed is None:
             seed = int(np.random.SeedSequence().entropy % (2 ** 63))
-        fits = self.simulated_fits(np.repeat(grid, n_s, axis=0), n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed)
+        fits = self.simulated_fits(np.repeat(grid, n_s, axis=0), n_walkers=n_walkers, n_steps=n_steps, n_burn=n_burn, seed=seed, move=move, gamma0=gamma0, sigma=sigma)
         chain = fits["sampler"].chain
         per = [recovery_summary(chain[g * n_s:(g + 1) * n_s], grid[g], n_burn, fits["names"], thin=thin, functions=functions,
                                 null=null) for g in range(grid.shape[0])]
@@ -1878,12 +1881,30 @@ class Runner(object):
             return False, "the priors are not plain boxes with flat / normal / log-normal priors (expression priors / constrained parameters)"
         return True, ""
 
-    def _make_sampler(self, n_walkers, seed=None):
+    MOVE = "stretch"               # the built-in sampler's move when ``__call__`` is not told one: "stretch" or "de"
+
+    def _make_sampler(self, n_walkers, seed=None, move=None, gamma0=None, sigma=1e-5):
         if self.SAMPLER not in ("auto", "emcee", "resident", "builtin"):
             raise ValueError("Runner.SAMPLER must be 'auto', 'emcee', 'resident' or 'builtin'")
+        move = move or self.MOVE
         resident, why_not = self.resident_ok()
         if self.SAMPLER == "resident" and not resident:
             raise ValueError("Runner.SAMPLER = 'resident' is not possible here: " + why_not)
+        if move == "de":
+            # the differential-evolution move (csrc/mcd_de.h) is the built-in sampler's: it runs whether or not emcee can be
+            # imported, on the counter-based stream, resident where resident_ok() allows and in the NumPy loop otherwise
+            from ..sampler import EnsembleSampler, default_gamma0
+            if self._context is not None and getattr(self._context, "n_ranks", 1) > 1:
+                raise NotImplementedError("move='de' on a multi-rank context: the collective resident DE block is not built")
+            g0 = default_gamma0(self.n_fitted_parameters) if gamma0 is None else float(gamma0)
+            logger.info("MCMC driver: built-in differential-evolution move (gamma0 = %.4g), %s", g0,
+                        "blocks of steps inside the library, ensemble resident on the device" if resident
+                        else "Python loop around lnprob_batch (" + why_not + ")")
+            seeded = (lambda *block: self._de_block_seeded(g0, sigma, *block)) if resident else None
+            return EnsembleSampler(n_walkers, self.n_fitted_parameters, self.lnprob_batch, vectorize=True, seed=seed,
+                                   rng="device", seeded_block_fn=seeded, move="de", gamma0=g0, sigma=sigma)
+        if move != "stretch":
+            raise ValueError("move must be 'stretch' or 'de'")
         if self.SAMPLER in ("auto", "emcee"):
             try:
                 import emcee
@@ -1957,6 +1978,13 @@ class Runner(object):
         if self._precision != "f64":
             self._note_f32(cat)
 
+    def _de_block_seeded(self, gamma0, sigma, pos, lnp, seed, step0, n_steps, chain, lnprob_chain, accepted):
+        """One block of differential-evolution steps inside the library (``_native.Catalog.de_move_seeded``)."""
+        cat = self._stretch_catalog(pos)
+        cat.de_move_seeded(self._stretch_plan(), pos, lnp, gamma0, sigma, seed, step0, n_steps, chain, lnprob_chain, accepted)
+        if self._precision != "f64":
+            self._note_f32(cat)
+
     def _stretch_block(self, pos, lnp, order, zz, thr, pick, chain, lnprob_chain, accepted):
         """One block of stretch-move steps inside the library (``_native.Catalog.stretch_move``)."""
         cat = self._stretch_catalog(pos)
@@ -1965,10 +1993,12 @@ class Runner(object):
             self._note_f32(cat)
 
     def __call__(self, n_walkers=100, n_steps=500, n_burn=100, n_threads=1, n_out=None, pos=None, lnprob0=None,
-                 plot=False, prefix="sampler", true_values=None, **kwargs):
+                 plot=False, prefix="sampler", true_values=None, move=None, gamma0=None, sigma=1e-5, **kwargs):
         """Run the MCMC (runner.py:332-443).  Same arguments as the reference; ``n_threads`` must be 1
         because the likelihood of all walkers is one GPU launch (a process pool would fork after HIP
-        initialisation and hold W copies of the catalogue)."""
+        initialisation and hold W copies of the catalogue).  ``move``: ``"stretch"`` (the default of the class attribute
+        ``MOVE``; what emcee runs) or ``"de"``, the built-in sampler's differential-evolution move with scale ``gamma0``
+        (None: 2.38 / sqrt(2 P)) and jitter ``sigma`` (``sampler.EnsembleSampler``)."""
         if kwargs:
             if "filename" in kwargs or "plotfilename" in kwargs:
                 logger.warning("Parameters <filename> and <plotfilename> not used anymore. Use <prefix> instead.")
@@ -1999,7 +2029,7 @@ class Runner(object):
                 raise ValueError("Invalid initial guesses for walker {0}: {1}={2}".format(
                     i, self.fitted_parameters, pos[i]))                                      # runner.py:392-395
 
-        sampler = self._make_sampler(n_walkers, seed=seed)
+        sampler = self._make_sampler(n_walkers, seed=seed, move=move, gamma0=gamma0, sigma=sigma)
         logger.info("Running MCMC chain ...")
         if n_out is not None:
             logger.info("Iter. <log like>   " + "".join(" {0:12s}".format("<" + n + ">") for n in self.fitted_parameters))
@@ -2044,10 +2074,11 @@ class Runner(object):
         """Run the MCMC until the integrated autocorrelation time says it is long enough (emcee's documented pattern):
         increments of ``check_every`` steps, after each one ``tau`` from ``diagnostics.integrated_time(..., quiet=True)``;
         stops when ``steps > tol max(tau)`` and ``max |tau - previous tau| / tau < rtol``, or at ``max_steps``.  Works with
-        whichever sampler ``SAMPLER`` selects (it needs ``run_mcmc`` and ``get_chain()``); ``pos`` and ``lnprob0`` as in
-        ``__call__``.  Returns ``(sampler, history)``, ``history`` a list of ``(steps, tau)`` per check."""
+        whichever sampler ``SAMPLER`` selects (it needs ``run_mcmc`` and ``get_chain()``); ``pos``, ``lnprob0``, ``move``,
+        ``gamma0`` and ``sigma`` as in ``__call__``.  Returns ``(sampler, history)``, ``history`` a list of ``(steps, tau)`` per check."""
         from .. import diagnostics
         pos, lnprob0 = call_kwargs.pop("pos", None), call_kwargs.pop("lnprob0", None)
+        move = {k: call_kwargs.pop(k) for k in ("move", "gamma0", "sigma") if k in call_kwargs}
         if call_kwargs:
             raise TypeError("run_converged: unknown argument(s) {0}".format(sorted(call_kwargs)))
         if pos is None:
@@ -2059,7 +2090,7 @@ class Runner(object):
             seed = int(group.bcast_json(int(np.random.SeedSequence().entropy % (2 ** 32)), src=0))
         if not np.all(np.isfinite(self.lnprior_batch(pos))):
             raise ValueError("Invalid initial guesses for some walker(s).")
-        sampler = self._make_sampler(n_walkers, seed=seed)
+        sampler = self._make_sampler(n_walkers, seed=seed, **move)
         history, previous, steps = [], None, 0
         while steps < max_steps:
             n = int(min(check_every, max_steps - steps))
@@ -2286,7 +2317,7 @@ class Runner(object):
         offsets = np.concatenate([[0], np.cumsum([s.size for s in sets])]).astype(np.int64)
         return sets, np.concatenate([held, rest]), offsets
 
-    def holdout_fit(self, sets, n_walkers=64, n_steps=600, n_burn=200, pos=None, seed=None, thin=1):
+    def holdout_fit(self, sets, n_walkers=64, n_steps=600, n_burn=200, pos=None, seed=None, thin=1, move="stretch", gamma0=None, sigma=1e-5):
         """Refit the model once per hold-out set, all refits in lock step, and evaluate every held-out star under the
         refit that left it out (Vehtari, Gelman & Gabry 2017, sections 2.3 and 2.4).  ``sets``: a list of E disjoint
         arrays of star indices.  E ensembles of ``n_walkers`` walkers take ``n_steps`` stretch-move steps
@@ -2299,7 +2330,8 @@ class Runner(object):
         Returns ``elpd`` and ``lnl_var`` (n_data,) in this runner's star order (NaN for stars in no set), ``sets``,
         ``sampler`` (``chain``: (E, W, steps, P)), ``tau`` (E,) the largest integrated autocorrelation time of each
         refit and ``converged`` (E,) whether its post-burn-in chain holds 50 of them (``diagnostics.summary``; logged
-        where not), and ``n_samples`` per set."""
+        where not), and ``n_samples`` per set.  ``move``, ``gamma0``, ``sigma``: the sampler's move (``BinnedSampler``:
+        "stretch" or "de")."""
         self._holdout_check("holdout_fit")
         from .binned import BinnedSampler
         from .. import diagnostics
@@ -2337,7 +2369,7 @@ class Runner(object):
                     out[ok] = train.reshape(-1)[ok] + lp[ok]
                 return out.reshape(lead)
 
-            sampler = BinnedSampler(n_sets, n_walkers, n_p, log_prob, seed=seed, rng="device")
+            sampler = BinnedSampler(n_sets, n_walkers, n_p, log_prob, seed=seed, rng="device", move=move, gamma0=gamma0, sigma=sigma)
             logger.info("hold-out refits: %d sets of %d .. %d stars, %d walkers each, %d steps", n_sets,
                         min(s.size for s in sets), max(s.size for s in sets), n_walkers, n_steps)
             sampler.reserve(n_steps)

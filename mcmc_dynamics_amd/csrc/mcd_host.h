@@ -8,6 +8,7 @@
 //   mcd_api_catalog.hip    catalogues, work sets and chunk plans, the main kernel's launch shape, options, mcd_last_* queries
 //   mcd_api_eval.hip       staging, enqueue, sync, fetch; the per-star outputs of one parameter row
 //   mcd_api_chain.hip      the stretch-move block and the HMC block, each resident on the device or host-driven
+//   mcd_api_de.hip         the differential-evolution block (mcd_de.h), resident on the device or host-driven
 //   mcd_api_temper.hip     the parallel-tempering block in the same two forms
 //   mcd_api_summaries.hip  mcd_pointwise_posterior, mcd_psis_loo, mcd_kde_background
 //   mcd_api_holdout.hip    mcd_holdout_loglike, mcd_holdout_pointwise: the exact leave-out refits
@@ -383,6 +384,13 @@ struct mcd_catalog {
     int64_t chain_device_blocks = 0, chain_host_blocks = 0, chain_discarded = 0;
     int chain_last_status = 0;         // status word of the last discarded block (mcd::ChainStatus bits)
     std::vector<hipEvent_t> chain_events;   // large blocks: parts joined by events (stretch_block_device)
+    // resident differential-evolution chain (mcd_de.hip, mcd_api_de.hip): counted apart from the stretch blocks; it shares
+    // the arena `chain` (a block of either move fills it anew) and the options "device_chain" and "fast_path"
+    int de_hint = -1;                  // kernel family the device's guard asked for when it last disagreed (-1: none)
+    int64_t de_backoff = 0;            // blocks left to run host-driven after a discarded block
+    int de_consecutive = 0;            // discarded blocks in a row (the back-off doubles with each)
+    int64_t de_device_blocks = 0, de_host_blocks = 0, de_discarded = 0;
+    int de_last_status = 0;            // status word of the last discarded block (mcd::ChainStatus bits)
     // Hamiltonian Monte Carlo blocks (mcd_hmc_block): trajectory state and chain rows of the resident block, its pinned mirror
     mcd::host::ChainArena hmc;
     int64_t hmc_device_blocks = 0, hmc_host_blocks = 0;

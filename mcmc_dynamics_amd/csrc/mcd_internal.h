@@ -191,6 +191,23 @@ bool stretch_step_handles(const StretchDevice& d);
 // ... and only that kernel can add up the main kernel's partial sums itself (StretchDevice::fused)
 bool stretch_step_fuses(const StretchDevice& d);
 
+// ---- resident differential-evolution chain (mcd_de.hip; the move: mcd_de.h) ----
+// The block's state, scratch and status words are the stretch block's (`s`; s.zz holds the scales gamma, s.pick the first
+// partner); what the move adds is the second partner.  Members of `s` the general step kernel does not know (fused,
+// defer_guard, force_general, the logs) are ignored.
+struct DeDevice {
+    StretchDevice s;
+    const int32_t* pick_b = nullptr;       // [n_steps][2][B][W/2]
+};
+// One workgroup per ensemble, any W: accept / reject half step (acc_step, acc_h) from the sums `ll` (acc_step < 0: none),
+// judge the table those sums belong to, propose half step (prop_step, prop_h) (prop_step < 0: none).
+hipError_t launch_de_step(hipStream_t s, const DeDevice& d, int64_t acc_step, int acc_h, int64_t prop_step, int prop_h,
+                          const double* ll, double rerun_tag);
+// seeded blocks: the numbers of steps [i0, i1) of a block, generated where an upload would have put them
+hipError_t launch_de_numbers(hipStream_t s, uint64_t seed, int64_t step0, int64_t i0, int64_t i1, int64_t n_bins,
+                             int64_t n_walkers, double gamma0, double sigma, int32_t* order, int32_t* pick_a, int32_t* pick_b,
+                             double* gamma, double* thr);
+
 // background.SingleStars (mcd_kde.hip): slice plan and launch.  part_dmin / part_sum hold [n_slices][n] doubles.
 int kde_slices(int64_t n, int64_t m, int* slice_len);
 hipError_t launch_kde(hipStream_t s, const double* comp, int64_t m, const double* v, const double* verr, int64_t n,

@@ -44,7 +44,15 @@ def _draw_pool():
 # is the shape of the ensemble axis, () for one ensemble without one, (B,) for B ensembles; pos is lead + (W, P), lnp and
 # the acceptance counts lead + (W,), a block's numbers (steps,) + lead + (W,) (order) and (steps, 2) + lead + (W/2,).
 
-def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn):
+MOVES = ("stretch", "de")
+
+
+def default_gamma0(ndim):
+    """The differential-evolution scale ter Braak (2006) derives for a Gaussian target: 2.38 / sqrt(2 P)."""
+    return 2.38 / np.sqrt(2.0 * int(ndim))
+
+
+def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn, move="stretch", gamma0=None, sigma=1e-5):
     """Checks and state common to both samplers.  ``rng="device"``: the move's random numbers come from the counter-based
     generator of csrc/mcd_rng.h (Philox4x64-10) instead of NumPy's Mersenne twister -- a function of (seed, step, half
     step, ensemble, walker) alone, generated on the device (csrc/mcd_stretch.hip: chain_numbers_kernel) by
@@ -54,10 +62,29 @@ def _setup(s, lead, nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn):
     ``rng_step`` is that generator's step counter: it advances with ``iteration`` and ``reset()`` leaves it alone, so the
     steps after a ``reset()`` take the numbers that follow the ones already used (as ``HMCSampler`` and
     ``TemperedSampler``).  ``seed`` may be any Python integer there: it wraps to 64 bits (-1 is 2^64 - 1), as
-    ``_native.Catalog.stretch_move_seeded`` takes it."""
+    ``_native.Catalog.stretch_move_seeded`` takes it.
+
+    ``move``: ``"stretch"`` (Goodman & Weare, emcee's default) or ``"de"``, the differential-evolution move of csrc/mcd_de.h:
+    a walker of one half proposes ``s + g (x_a - x_b)`` from two distinct walkers of the other half, ``g = gamma0 (1 + sigma
+    n)`` with a standard normal ``n`` (``gamma0`` None: ``default_gamma0(ndim)``), accepted with probability min(1, ratio of
+    the posteriors).  Same half steps, same cost per step; on correlated posteriors it decorrelates in about a third of the
+    steps.  It is defined on the counter-based stream (a key of its own: never the stretch move's numbers of the same
+    seed), so it needs ``rng="device"``, and an ensemble of at least 4 walkers.  ``seeded_block_fn`` is then the DE block
+    (``Runner._de_block_seeded``) and the NumPy loop takes its numbers from ``_native.de_numbers``."""
     if rng not in ("host", "device"):
         raise ValueError("rng must be 'host' or 'device'")
-    if rng == "device" and float(a) != 2.0:
+    if move not in MOVES:
+        raise ValueError("move must be 'stretch' or 'de'")
+    s.move, s.gamma0, s.sigma = move, None, float(sigma)
+    if move == "de":
+        if rng != "device":
+            raise ValueError("move='de' is defined on the counter-based stream: it needs rng='device'")
+        if nwalkers < 4:
+            raise ValueError("move='de' needs at least 4 walkers: two distinct partners in each half of the ensemble")
+        s.gamma0 = default_gamma0(ndim) if gamma0 is None else float(gamma0)
+        if not (s.gamma0 > 0.0 and np.isfinite(s.gamma0)) or not (s.sigma >= 0.0 and np.isfinite(s.sigma)):
+            raise ValueError("move='de' needs a finite gamma0 > 0 and a finite sigma >= 0")
+    if rng == "device" and move == "stretch" and float(a) != 2.0:
         raise ValueError("rng='device' implements the stretch move with a = 2 (emcee's default)")
     # rng="device": the 64-bit name of the chain (no seed: from NumPy's global generator, which the reference seeds at
     # analysis/runner.py:59 -- `np.random.seed` before the run makes it reproducible, as with emcee).  Only then: drawing
@@ -116,6 +143,8 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
       was never run.)
     * otherwise the NumPy half-step loop below, around ``evaluate`` (proposals lead + (W/2, P) -> lead + (W/2,); it
       counts its calls in ``n_calls``), with the numbers of ``draw`` -- or, with ``rng="device"``, of ``_native.chain_numbers``: the ones the device generates.
+
+    ``move="de"`` (always ``rng="device"``): the numbers are ``_native.de_numbers``' and ``seeded_block_fn`` is the DE block.
     """
     nsteps = int(nsteps)
     if store and s.iteration + nsteps > s._chain.shape[0]:    # geometric growth: amortised O(1) per stored step
@@ -125,6 +154,9 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
         from . import _native
 
         def draw(n):                                          # noqa: F811 -- the same numbers the device generates
+            if s.move == "de":
+                return _native.de_numbers(s.seed64, s.rng_step, n, lnp.size // s.nwalkers, s.nwalkers, s.ndim, s.gamma0,
+                                          s.sigma, squeeze=not s._lead)
             return _native.chain_numbers(s.seed64, s.rng_step, n, lnp.size // s.nwalkers, s.nwalkers, s.ndim,
                                          squeeze=not s._lead)
     library = s.seeded_block_fn if device else s.block_fn
@@ -161,9 +193,16 @@ def _run_blocks(s, pos, lnp, nsteps, first, chunk, draw, evaluate, store=True):
 
 
 def _half_steps(s, pos, lnp, numbers, evaluate, store):
-    """The stretch move in NumPy, one block of steps: every half step proposes for one half of every ensemble against the
-    other half, in one ``evaluate`` call.  Walkers are addressed as rows of the flat (B * W, P) ensemble."""
-    order_b, zz_b, thr_b, pick_b = numbers
+    """The move in NumPy, one block of steps: every half step proposes for one half of every ensemble against the
+    other half, in one ``evaluate`` call.  Walkers are addressed as rows of the flat (B * W, P) ensemble.  ``move="de"``:
+    ``numbers`` are ``_native.de_numbers``' (order, pick_a, pick_b, gamma, thr); the proposal is ``s + (x_a - x_b) * g`` --
+    three separate roundings, as csrc/mcd_de.h writes them."""
+    de = s.move == "de"
+    pick2_b = None
+    if de:
+        order_b, pick_b, pick2_b, zz_b, thr_b = numbers
+    else:
+        order_b, zz_b, thr_b, pick_b = numbers
     n, W, P = order_b.shape[0], s.nwalkers, s.ndim
     B, half = lnp.size // W, W // 2
     flat_pos, flat_lnp, flat_acc = pos.reshape(B * W, P), lnp.reshape(B * W), s._accepted.reshape(B * W)
@@ -171,6 +210,8 @@ def _half_steps(s, pos, lnp, numbers, evaluate, store):
         raise ValueError("the NumPy loop updates pos and lnp in place: they must be C-contiguous")
     order_b = order_b.reshape(n, B, W) + (W * np.arange(B))[:, None]                 # ensemble b's walkers: rows b * W + j
     pick_b = pick_b.reshape(n, 2, B, half) + (half * np.arange(B))[:, None]          # partner of half-row b * half + j
+    if de:
+        pick2_b = pick2_b.reshape(n, 2, B, half) + (half * np.arange(B))[:, None]
     zz_b, thr_b = zz_b.reshape(n, 2, B * half), thr_b.reshape(n, 2, B * half)
     for i in range(n):
         order = order_b[i]
@@ -179,7 +220,10 @@ def _half_steps(s, pos, lnp, numbers, evaluate, store):
             first, second = halves[h], halves[1 - h]
             s_pos = flat_pos[first]
             partners = flat_pos[second[pick_b[i, h].ravel()]]
-            proposal = partners - (partners - s_pos) * zz_b[i, h][:, None]
+            if de:
+                proposal = s_pos + (partners - flat_pos[second[pick2_b[i, h].ravel()]]) * zz_b[i, h][:, None]
+            else:
+                proposal = partners - (partners - s_pos) * zz_b[i, h][:, None]
             new_lnp = np.reshape(evaluate(proposal.reshape(s._lead + (half, P))), B * half)
             accept = thr_b[i, h] < new_lnp - flat_lnp[first]
             idx = first[accept]
@@ -196,10 +240,11 @@ def _half_steps(s, pos, lnp, numbers, evaluate, store):
 class EnsembleSampler(object):
 
     def __init__(self, nwalkers, ndim, log_prob_fn, pool=None, a=2.0, vectorize=False, seed=None, block_fn=None, rng="host",
-                 seeded_block_fn=None):
+                 seeded_block_fn=None, move="stretch", gamma0=None, sigma=1e-5):
         """``rng``: ``"host"`` (NumPy's Mersenne twister, as emcee) or ``"device"`` (the counter-based generator of
-        csrc/mcd_rng.h, see ``_setup``)."""
-        _setup(self, (), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn)
+        csrc/mcd_rng.h, see ``_setup``).  ``move``: ``"stretch"`` or ``"de"`` (differential evolution with scale ``gamma0``
+        and jitter ``sigma``, see ``_setup``; needs ``rng="device"``)."""
+        _setup(self, (), nwalkers, ndim, a, rng, seed, block_fn, seeded_block_fn, move, gamma0, sigma)
         self.log_prob_fn = log_prob_fn
         self.pool = pool
         self.vectorize = bool(vectorize)
