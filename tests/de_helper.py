@@ -221,38 +221,63 @@ def autocorr_time(x, c=5.0):
 
 # ---- GPU tests: catalogues, walkers and the NumPy loop around the library's evaluation -------------------------------
 CENTRE = (56.345, -26.675)
+DOUBLE_BASE = {7: 3, 8: 4}                      # double_helper.BASE: the single-component model a double model reduces to
 
 
-def gpu_walkers(rng, w, model, sv, free):
-    """(w, K) start rows of ``model`` (include/mcd.h) around a cluster of dispersion ``sv``."""
+def n_columns(model, free):
+    """Kernel columns of ``model`` (include/mcd.h): v_sys, sigma_max [, a], v_maxx, v_maxy [, r_peak] [, v_maxx_c, v_maxy_c,
+    r_peak_ratio] [, ra_center, dec_center] [, v_back, sigma_back, f_back | f_back]."""
+    return (4 if model < 3 else 6) + (3 if model >= 7 else 0) + (2 if free else 0) + {2: 3, 4: 3, 8: 3, 5: 1}.get(model, 0)
+
+
+def gpu_walkers(rng, w, model, sv, free, near_centre=False):
+    """(w, K) start rows of ``model`` (include/mcd.h) around a cluster of dispersion ``sv``.  Models 7 and 8: the row of
+    the single-component counterpart with the second component's three columns of double_helper.make_case behind r_peak,
+    its amplitudes in units of ``sv``; from model 4 on a free centre stays within 0.005 deg (variant_helper.make_case)."""
+    if model >= 7:
+        import double_helper
+        base = gpu_walkers(rng, w, DOUBLE_BASE[model], sv, free, near_centre=True)
+        case = double_helper.make_case(model, free, 1, seed=int(rng.integers(1 << 31)))
+        extra = case["params"][:w, 6:9].copy()
+        assert extra.shape == (w, 3)
+        extra[:, :2] *= sv / case["scale"]
+        return np.ascontiguousarray(np.concatenate([base[:, :6], extra, base[:, 6:]], axis=1))
     cols = [rng.normal(0, 0.2 * sv, w), sv * 10.0 ** rng.uniform(-0.3, 0.3, w)]
     if model >= 3:
         cols.append(10.0 ** rng.uniform(1.0, 2.0, w))
     cols += [rng.normal(0, 0.2 * sv, w), rng.normal(0, 0.2 * sv, w)]
     if model >= 3:
         cols.append(10.0 ** rng.uniform(1.0, 2.0, w))
-    if free:
+    if free and (model >= 4 or near_centre):
+        cols += [CENTRE[0] + rng.uniform(-0.005, 0.005, w), CENTRE[1] + rng.uniform(-0.005, 0.005, w)]
+    elif free:
         cols += [CENTRE[0] + rng.normal(0, 0.002, w), CENTRE[1] + rng.normal(0, 0.002, w)]
     if model in (2, 4):
         cols += [rng.normal(0, 0.3 * sv, w), 3 * sv * 10.0 ** rng.uniform(-0.1, 0.1, w), rng.uniform(0.2, 0.8, w)]
+    if model == 5:
+        cols.append(rng.uniform(0.2, 0.8, w))                          # f_back
     return np.ascontiguousarray(np.stack(cols, axis=1))
 
 
 def gpu_columns(rng, n, model):
     """The columns of a small cluster with a background population: (dict of ra, dec, v, verr [, lnlike_bg, pmember |
-    density]), dispersion)."""
+    density]), dispersion).  From model 4 on the stars keep 0.01 deg from the centre, as the catalogues of
+    variant_helper.make_case do (the position angle next to the centre is ill-conditioned in the reference's own formula:
+    the accuracy floors of tests/test_gpu_variant_matrix.py are stated for such catalogues)."""
     from oracle import lnprob_numpy as oracle
     sv = 12.0
-    sep = np.maximum(np.abs(rng.normal(0, 2.0 / 60.0, n)), 1e-4)
+    sep = np.maximum(np.abs(rng.normal(0, 2.0 / 60.0, n)), 1e-4 if model < 4 else 0.01)
     th = rng.uniform(-np.pi, np.pi, n)
     ra, dec = CENTRE[0] + sep * np.cos(th) / np.cos(np.radians(CENTRE[1])), CENTRE[1] + sep * np.sin(th)
     v, verr = rng.normal(0, sv, n), rng.uniform(0.5, 4.0, n)
     v[::7] = rng.normal(0, 3 * sv, len(v[::7]))                     # a background population
     cols = dict(ra=ra, dec=dec, v=v, verr=verr)
-    if model == 1:
+    if model in (1, 6):
         cols.update(lnlike_bg=oracle.gaussian_background(v, verr, 0.0, 3 * sv), pmember=np.clip(rng.random(n), 0.02, 0.98))
-    elif model in (2, 4):
+    elif model in (2, 4, 8):
         cols.update(density=np.clip(rng.random(n), 0.05, 1.0))
+    elif model == 5:
+        cols.update(lnlike_bg=oracle.gaussian_background(v, verr, 0.0, 3 * sv), density=np.clip(rng.random(n), 0.05, 1.0))
     return cols, sv
 
 
@@ -263,15 +288,22 @@ def gpu_catalogue(native, ctx, rng, n, model, free):
                           centre=None if free else CENTRE, **kw), sv
 
 
-def gpu_box(cat, pos, model, sv):
-    """An inclusive box that rejects a few proposals: sigma_max > 0, a window around the ensemble's v_sys, f_back in [0, 1]."""
+def gpu_box(cat, pos, model, sv, margin=0.1):
+    """An inclusive box that rejects a few proposals: sigma_max > 0, a window around the ensemble's v_sys (``margin``
+    dispersions beyond its extremes), f_back in [0, 1]; the double models' r_peak_ratio in [1e-3, 1]
+    (analysis/double_model.py) and, from model 4 on, a free centre within 0.005 deg."""
     lo, hi = np.full(cat.k, -np.inf), np.full(cat.k, np.inf)
     lo[1] = 0.0
-    lo[0], hi[0] = pos[:, 0].min() - 0.1 * sv, pos[:, 0].max() + 0.1 * sv
-    if model in (2, 4):
+    lo[0], hi[0] = pos[:, 0].min() - margin * sv, pos[:, 0].max() + margin * sv
+    if model in (2, 4, 5, 8):
         lo[-1], hi[-1] = 0.0, 1.0
     if model >= 3:
         lo[2] = lo[5] = 1.0                                            # a, r_peak [arcsec] stay positive
+    if model >= 7:
+        lo[8], hi[8] = 1e-3, 1.0
+    if model >= 4 and cat.k == n_columns(model, True):
+        at = 9 if model >= 7 else 6
+        lo[at:at + 2], hi[at:at + 2] = np.array(CENTRE) - 0.005, np.array(CENTRE) + 0.005
     return lo, hi
 
 
@@ -285,39 +317,66 @@ def identity_plan(k, lo=None, hi=None, prior=None):
 
 
 def numpy_de_block(cat, plan, pos, lnp, nums, prior_eval=None):
-    """The sampler's DE half-step loop (one ensemble) with ``cat.loglike`` as the likelihood: box and structured priors from
-    the plan, always W/2 rows per launch (a row outside the prior is replaced by the first valid one)."""
+    """The samplers' DE half-step loop with ``cat.loglike`` as the likelihood: box and structured priors from the plan.
+
+    One ensemble -- ``pos`` (W, P), ``order`` (n, W), the other numbers (n, 2, W/2), ``cat.loglike`` on (W/2, K) rows -- or B
+    lock-stepped ones: ``pos`` (B, W, P), ``order`` (n, B, W), the others (n, 2, B, W/2), ONE call ``cat.loglike`` on
+    (B, W/2, K) rows per half step.  The launch always has all its rows: a row outside the prior is replaced by the first
+    valid row of the whole launch, counted ensemble by ensemble and slot by slot, and its value is never looked at (the
+    proposal is rejected); a half step without any valid row is not evaluated; an ensemble without a valid row keeps its
+    state through that half step.
+
+    -> (pos, lnp, chain, lnprob_chain, accepted, seen): ``seen["n_ok"]`` (n, 2, B) the valid rows of every ensemble in
+    every half step, ``seen["nonpositive"]`` (n, 2, B) its proposals with a log-normal coordinate <= 0, ``seen["mixed"]`` the
+    number of (half step, ensemble) pairs with 0 < n_ok < W/2, ``seen["half"]`` = W/2."""
+    single = np.ndim(pos) == 2
     order, pa, pb, gamma, thr = nums
+    if single:
+        order, (pa, pb, gamma, thr) = order[:, None], [a[:, :, None] for a in (pa, pb, gamma, thr)]
+        pos, lnp = pos[None], lnp[None]
     pos, lnp = pos.copy(), lnp.copy()
-    n_steps, w = order.shape
+    n_steps, n_ens, w = order.shape
     half = w // 2
-    chain, lnpc, acc = np.empty((n_steps,) + pos.shape), np.empty((n_steps, w)), np.zeros(w, dtype=np.int64)
+    chain, lnpc, acc = np.empty((n_steps,) + pos.shape), np.empty((n_steps, n_ens, w)), np.zeros((n_ens, w), dtype=np.int64)
     src, const, fac = plan["col_source"], plan["col_const"], plan["col_factor"]
     prior = plan.get("prior")
+    lognormal = np.zeros(pos.shape[-1], dtype=bool) if prior is None else np.asarray(prior[0]) == 2
+    n_ok = np.zeros((n_steps, 2, n_ens), dtype=np.int64)
+    nonpositive = np.zeros_like(n_ok)
+    ens = np.arange(n_ens)[:, None]
     for i in range(n_steps):
-        halves = (order[i, :half], order[i, half:])
+        halves = (order[i, :, :half], order[i, :, half:])
         for h in (0, 1):
-            first, second = halves[h], halves[1 - h]
-            proposal = pos[first] + (pos[second[pa[i, h]]] - pos[second[pb[i, h]]]) * gamma[i, h][:, None]
-            ok = np.all((proposal >= plan["lo"]) & (proposal <= plan["hi"]), axis=1)
-            lp = np.zeros(half)
+            first, second = halves[h], halves[1 - h]                   # (B, W/2) walker indices
+            xa, xb = np.take_along_axis(second, pa[i, h], axis=1), np.take_along_axis(second, pb[i, h], axis=1)
+            proposal = pos[ens, first] + (pos[ens, xa] - pos[ens, xb]) * gamma[i, h][..., None]
+            ok = np.all((proposal >= plan["lo"]) & (proposal <= plan["hi"]), axis=2)
+            lp = np.zeros((n_ens, half))
             if prior is not None:
-                lp = prior_eval(prior, proposal)
+                lp = np.asarray(prior_eval(prior, proposal.reshape(n_ens * half, -1))).reshape(n_ens, half)
                 ok &= np.isfinite(lp)
-            new = np.full(half, -np.inf)
+                nonpositive[i, h] = np.any(proposal[..., lognormal] <= 0.0, axis=2).sum(axis=1)
+            n_ok[i, h] = ok.sum(axis=1)
+            new = np.full((n_ens, half), -np.inf)
             if ok.any():
-                rows = np.empty((half, src.size))
+                rows = np.empty((n_ens, half, src.size))
                 for c in range(src.size):
-                    rows[:, c] = const[c] if src[c] < 0 else (proposal[:, src[c]] if fac[c] == 1.0 else proposal[:, src[c]] * fac[c])
-                rows[~ok] = rows[np.argmax(ok)]
-                ll = cat.loglike(np.ascontiguousarray(rows))
+                    rows[..., c] = const[c] if src[c] < 0 else (proposal[..., src[c]] if fac[c] == 1.0 else
+                                                                proposal[..., src[c]] * fac[c])
+                donor = int(np.argmax(ok.reshape(-1)))                 # first valid row in (ensemble, slot) order
+                rows[~ok] = rows.reshape(n_ens * half, -1)[donor]
+                ll = cat.loglike(np.ascontiguousarray(rows[0] if single else rows)).reshape(n_ens, half)
                 new[ok] = ll[ok] + lp[ok] if prior is not None else ll[ok]
-            accept = thr[i, h] < new - lnp[first]
-            idx = first[accept]
-            pos[idx], lnp[idx] = proposal[accept], new[accept]
-            acc[idx] += 1
+            accept = thr[i, h] < new - lnp[ens, first]
+            e, j = np.nonzero(accept)
+            idx = first[e, j]
+            pos[e, idx], lnp[e, idx] = proposal[e, j], new[e, j]
+            acc[e, idx] += 1                                           # (the walkers of a half step are distinct)
         chain[i], lnpc[i] = pos, lnp
-    return pos, lnp, chain, lnpc, acc
+    seen = {"n_ok": n_ok, "nonpositive": nonpositive, "mixed": int(((n_ok > 0) & (n_ok < half)).sum()), "half": half}
+    if single:
+        return pos[0], lnp[0], chain[:, 0], lnpc[:, 0], acc[0], seen
+    return pos, lnp, chain, lnpc, acc, seen
 
 
 def same(a, b):

@@ -192,6 +192,134 @@ def test_block_is_the_numpy_loop(W, P, case, built_library):
         assert empty                                          # (two proposals per half step, a step of 1.7 differences)
 
 
+class _LoopCatalogue(object):
+    """What numpy_de_block asks of a catalogue: ``loglike`` on ([B,] rows, K) -> ([B,] rows) around a callback on (n, K)."""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def loglike(self, rows):
+        rows = np.asarray(rows)
+        return self.fn(rows.reshape(-1, rows.shape[-1])).reshape(rows.shape[:-1])
+
+
+def _same_block(got, ref):
+    assert got["status"] == 0
+    return dh.same((got["pos"], got["lnp"], got["chain"], got["lnprob_chain"], got["accepted"]), ref)
+
+
+def test_host_block_is_the_numpy_loop_over_ensembles():
+    """de_block (CPU build) with B = 3 lock-stepped ensembles of 8 walkers against the multi-ensemble NumPy loop, whose donor
+    rule is stated without csrc/mcd_de.h.  The box is as wide as the start (+-0.02 under a likelihood of width 0.1: the
+    ensembles keep filling it), so that 12 steps hold, on the NumPy side alone: a half step with some rows inside and some
+    outside in EVERY ensemble; one in which an ensemble has no valid row and is lent another's; one without any valid row,
+    which is not evaluated."""
+    B, W, P, n, box = 3, 8, 4, 12, 0.02
+    half = W // 2
+    rng = np.random.default_rng(2001)
+    plan = dh.identity_plan(P, lo=np.full(P, -box), hi=np.full(P, box))
+    loglike = dh.table_loglike(rng.uniform(-0.01, 0.01, P), np.full(P, 0.1))
+    calls = []
+
+    def counted(table):
+        calls.append(len(table))
+        return loglike(table)
+    cat = _LoopCatalogue(counted)
+    pos0 = rng.uniform(-box, box, (B, W, P))
+    lnp0 = _LoopCatalogue(loglike).loglike(pos0)
+    nums = dh.numbers(SEED, 0, n, B, W, default_gamma0(P), 1e-5)
+    ref = dh.numpy_de_block(cat, plan, pos0, lnp0, nums)
+    n_ok = ref[5]["n_ok"]
+    assert n_ok.shape == (n, 2, B) and ref[5]["half"] == half
+    mixed_everywhere = np.all((n_ok > 0) & (n_ok < half), axis=2)
+    lent = (n_ok == 0).any(axis=2) & (n_ok > 0).any(axis=2)
+    empty = n_ok.sum(axis=2) == 0
+    print("half steps: mixed in every ensemble", mixed_everywhere.sum(), "donor of another ensemble", lent.sum(), "empty", empty.sum())
+    assert mixed_everywhere.any() and lent.any() and empty.any()
+    assert ref[5]["mixed"] == ((n_ok > 0) & (n_ok < half)).sum()
+    assert calls == [B * half] * int((~empty).sum())            # one call of all rows per half step, none for an empty one
+    assert ref[4].sum() > 0 and np.all(np.abs(ref[2]) <= box)
+    # (the NumPy loop leaves an ensemble without a valid row alone; de_block lends it the donor row and masks the value)
+    got = dh.block(plan, pos0, lnp0, nums, loglike)
+    assert _same_block(got, ref)
+    # the one-ensemble form is the special case B = 1 of the same loop
+    one = tuple(a[:, 0] if a.ndim == 3 else a[:, :, 0] for a in dh.numbers(SEED, 0, n, 1, W, default_gamma0(P), 1e-5))
+    ref1 = dh.numpy_de_block(cat, plan, pos0[0], lnp0[0], one)
+    lead = dh.numpy_de_block(cat, plan, pos0[:1], lnp0[:1], tuple(a[:, None] if a.ndim == 2 else a[:, :, None] for a in one))
+    assert ref1[0].shape == (W, P) and dh.same(ref1[:5], (lead[0][0], lead[1][0], lead[2][:, 0], lead[3][:, 0], lead[4][0]))
+    assert _same_block(dh.block(plan, pos0[0], lnp0[0], one, loglike), ref1)
+
+
+def test_host_block_with_a_log_normal_coordinate_across_zero(built_library):
+    """The same comparison with a log-normal prior on a coordinate whose walkers sit next to zero: proposals with that
+    coordinate <= 0 are outside the prior (mcd_prior.h: prior_row_inside), beside proposals inside, in one half step."""
+    from mcmc_dynamics_amd import _native
+    B, W, P, n = 3, 8, 3, 9
+    half = W // 2
+    rng = np.random.default_rng(2100)
+    kind = np.array([_native.PRIOR_NORMAL, _native.PRIOR_FLAT, _native.PRIOR_LOGNORMAL], dtype=np.int32)
+    prior = (kind, np.array([0.2, 0.0, np.log(0.1)]), np.array([0.8, 1.0, 1.5]))
+    plan = dh.identity_plan(P, prior=prior)
+    loglike = dh.table_loglike(np.array([0.1, -0.2, 0.1]), np.array([1.0, 0.7, 0.3]))
+    cat = _LoopCatalogue(loglike)
+    pos0 = rng.normal(0.0, 0.5, (B, W, P))
+    pos0[..., 2] = np.abs(rng.normal(0.0, 0.15, (B, W))) + 0.01
+    lnp0 = dh.plan_lnprob(plan, loglike, _native.prior_eval)(pos0)
+    assert np.all(np.isfinite(lnp0))
+    nums = dh.numbers(SEED, 0, n, B, W, default_gamma0(P), 1e-5)
+    ref = dh.numpy_de_block(cat, plan, pos0, lnp0, nums, _native.prior_eval)
+    below, n_ok = ref[5]["nonpositive"], ref[5]["n_ok"]
+    print("proposals with the log-normal coordinate <= 0:", below.sum(), "of", n * 2 * B * half)
+    assert np.any((below > 0) & (below < half)) and np.array_equal(n_ok, half - below)    # (nothing else rejects here)
+    assert np.all(ref[2][..., 2] > 0.0) and ref[4].sum() > 0
+    assert _same_block(dh.block(plan, pos0, lnp0, nums, loglike), ref)
+
+
+def test_four_walkers_leave_one_pair_of_partners():
+    """W = 4: half = 2, pick_b is whichever slot pick_a is not; both orders of the pair equally often."""
+    _, pa, pb, _, _ = dh.numbers(SEED, 0, 2000, 1, 4, 0.5, 1e-5)
+    assert pa.shape == (2000, 2, 1, 2)
+    assert np.all(pa != pb) and set(np.unique(pa)) == {0, 1} and set(np.unique(pb)) == {0, 1}
+    for pair in ((0, 1), (1, 0)):
+        share = float(np.mean((pa == pair[0]) & (pb == pair[1])))
+        print("ordered pair", pair, share)
+        assert 0.4 <= share <= 0.6
+
+
+class _Columns(object):
+    def __init__(self, k):
+        self.k = k
+
+
+@pytest.mark.parametrize("model,free,k", [(4, False, 9), (5, False, 7), (6, False, 6), (7, True, 11), (8, False, 12), (8, True, 14),
+                                          (5, True, 9), (7, False, 9)])
+def test_helper_models_give_rows_inside_their_box(model, free, k):
+    """de_helper's catalogues, walkers and box of the models the GPU tests add: K columns in the order of include/mcd.h,
+    every start row inside the box, the box closed where the model needs it."""
+    import double_helper
+    rng = np.random.default_rng(50 + model)
+    cols, sv = dh.gpu_columns(rng, 33, model)
+    want = {4: {"density"}, 5: {"lnlike_bg", "density"}, 6: {"lnlike_bg", "pmember"}, 7: set(), 8: {"density"}}[model]
+    assert set(cols) == {"ra", "dec", "v", "verr"} | want and all(len(c) == 33 for c in cols.values())
+    assert dh.n_columns(model, free) == k and (model < 7 or double_helper.n_columns(model, free) == k)
+    for w in (4, 48, 130):
+        pos = dh.gpu_walkers(rng, w, model, sv, free)
+        assert pos.shape == (w, k) and pos.flags["C_CONTIGUOUS"] and np.all(np.isfinite(pos))
+        lo, hi = dh.gpu_box(_Columns(k), pos, model, sv)
+        assert lo.shape == hi.shape == (k,) and np.all((pos >= lo) & (pos <= hi))
+        assert lo[1] == 0.0 and lo[2] == 1.0 and lo[5] == 1.0
+        if model in (4, 5, 8):
+            assert (lo[-1], hi[-1]) == (0.0, 1.0) and np.all((pos[:, -1] > 0) & (pos[:, -1] < 1))
+        if model >= 7:
+            names = double_helper.column_names(model, free)
+            at = names.index("r_peak_ratio")
+            assert (lo[at], hi[at]) == (1e-3, 1.0) and np.std(pos[:, names.index("v_maxx_c")]) > 0
+        if free:
+            at = 9 if model >= 7 else 6
+            assert np.all(np.abs(pos[:, at:at + 2] - np.array(dh.CENTRE)) <= 0.005) and np.all(np.isfinite(lo[at:at + 2]))
+    assert dh.gpu_box(_Columns(k), pos, model, sv, margin=0.0)[1][0] == pos[:, 0].max()
+
+
 # ---- stationarity and mixing ------------------------------------------------------------------------------------------
 _RUNS = {}
 

@@ -2,7 +2,13 @@
 loop of the same library (option "device_chain" = 0, csrc/mcd_de.h), against ``mcd_de_move`` fed the replayed numbers of
 ``mcd_de_numbers``, and against a NumPy restatement of the sampler's half-step loop around ``mcd_loglike_batch``.  The bar is
 bit-identity, also when the device gives a block back and however a run is cut into blocks; then the move end to end
-through ``ConstantFit``, ``BinnedConstantFit`` and the lock-stepped refits."""
+through ``ConstantFit``, ``BinnedConstantFit`` and the lock-stepped refits.
+
+Every device model (0 .. 8) runs the four-way comparison, the widest rows also against the 80-bit oracle at the chain's own
+rows; the NumPy loop reports the valid rows of every half step, and the tests assert from it that the masks they mean to
+exercise (some rows inside and some outside the prior in one half step, a log-normal coordinate on both sides of zero)
+did occur.  Beyond that: more ensembles than the step kernel has threads, W = 4 / 8192 / 8194, a seeded block longer than
+one grid of the numbers kernel, and each of the four reasons for which the device gives a block back."""
 import numpy as np
 import pytest
 
@@ -80,7 +86,11 @@ def test_resident_block_is_the_host_driven_one(native, ctx, model, free, n_stars
     nums = de_numbers(native, seed, 100, 7, 1, w, cat.k, g0, sigma, True)
     assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=0))
     assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=1))
-    assert dh.same(dev, dh.numpy_de_block(cat, plan, pos, lnp, nums))
+    loop = dh.numpy_de_block(cat, plan, pos, lnp, nums)
+    assert dh.same(dev, loop)
+    # the box did cut into the proposals of a half step without taking them all (otherwise the donor row, the masked rows
+    # of the launch and of the walker constants were not exercised)
+    assert loop[5]["mixed"] >= 1, loop[5]["n_ok"]
     assert 0 < dev[4].sum() < 7 * w and np.all(np.isfinite(dev[3]))
     # a second block of 5 steps continues the first through step0: resident == host-driven == one block of 12
     dev2 = run_seeded(cat, plan, dev[0], dev[1], g0, sigma, seed, 107, 5, device=1)
@@ -92,6 +102,290 @@ def test_resident_block_is_the_host_driven_one(native, ctx, model, free, n_stars
     assert cat.de_info()["discarded_blocks"] == before["discarded_blocks"]
     assert cat.stretch_info() == s_before                              # DE blocks are counted apart
     cat.close()
+
+
+WIDE_MODELS = [(4, False), (5, False), (6, False), (7, True), (8, False), (8, True)]   # ... BGDENS, BGFIXED, the double models
+WIDE_CASES = [(m, f, n, w) for (m, f) in WIDE_MODELS for (n, w) in [(33, 48), (4099, 130)]]
+
+
+def _oracle_errors(model, free, cols, rows, got):
+    """(error of the device's log-likelihoods against the 80-bit oracle at the same rows, its allowance), both on the scale
+    max(|lnL|, N): models 4 .. 6 by oracle/lnprob_numpy.py in longdouble under the rule of tests/test_gpu_variant_matrix.py
+    (2 x the error of the float64 oracle + that model's floor), models 7 and 8 by double_helper under the bound of
+    tests/test_gpu_double_live.py for the same sums (1e-12, the RTOL of the variant matrix)."""
+    import double_helper
+    import variant_helper as vh
+    from test_gpu_variant_matrix import FLOOR, RTOL
+    n, centre = len(cols["v"]), None if free else dh.CENTRE
+    mod = double_helper if model >= 7 else vh
+    exact = np.array([mod.exact(model, cols, row, centre) for row in rows], dtype=vh.L)
+    err = vh.scaled_err(got, exact, n)
+    if model >= 7:
+        return err, np.full(len(rows), RTOL)
+    f64 = np.array([vh.value(model, cols, row, centre) for row in rows])
+    return err, 2.0 * vh.scaled_err(f64, exact, n) + FLOOR[(model, free)]
+
+
+@pytest.mark.parametrize("model,free,n_stars,w", WIDE_CASES)
+def test_wide_rows_resident_host_driven_replayed_and_numpy(native, ctx, model, free, n_stars, w):
+    """The models with the widest rows (K up to 14), a fixed per-star background or f_back behind the centre: resident ==
+    host-driven == ``mcd_de_move`` fed ``mcd_de_numbers`` == the NumPy loop over 7 steps, continued by 5; the last stored
+    lnprob row against the 80-bit oracle at the chain's own rows."""
+    import variant_helper as vh
+    from mcmc_dynamics_amd.sampler import default_gamma0
+    rng = np.random.default_rng(7100 + 100 * model + 10 * free + n_stars + w)
+    cols, sv = dh.gpu_columns(rng, n_stars, model)
+    cat = native.Catalog(ctx, cols["ra"], cols["dec"], cols["v"], cols["verr"], model=model, centre=None if free else dh.CENTRE,
+                         **{k: v for k, v in cols.items() if k not in ("ra", "dec", "v", "verr")})
+    pos = dh.gpu_walkers(rng, w, model, sv, free)
+    assert pos.shape[1] == cat.k == dh.n_columns(model, free)
+    lo, hi = dh.gpu_box(cat, pos, model, sv)
+    plan = dh.identity_plan(cat.k, lo, hi)
+    lnp = cat.loglike(pos)
+    assert np.all(np.isfinite(lnp))
+    g0, sigma, seed = default_gamma0(cat.k), 1e-5, SEED + model
+    before = cat.de_info()
+    dev = run_seeded(cat, plan, pos, lnp, g0, sigma, seed, 100, 7, device=1)
+    mid = cat.de_info()
+    assert mid["device_blocks"] == before["device_blocks"] + 1 and mid["discarded_blocks"] == before["discarded_blocks"], mid
+    host = run_seeded(cat, plan, pos, lnp, g0, sigma, seed, 100, 7, device=0)
+    assert cat.de_info()["host_blocks"] == mid["host_blocks"] + 1
+    assert dh.same(dev, host)
+    nums = de_numbers(native, seed, 100, 7, 1, w, cat.k, g0, sigma, True)
+    assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=0))
+    assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=1))
+    loop = dh.numpy_de_block(cat, plan, pos, lnp, nums)
+    assert dh.same(dev, loop)
+    assert loop[5]["mixed"] >= 1, loop[5]["n_ok"]
+    assert 0 < dev[4].sum() < 7 * w and np.all(np.isfinite(dev[3]))
+    assert np.all((dev[2] >= lo) & (dev[2] <= hi))
+    dev2 = run_seeded(cat, plan, dev[0], dev[1], g0, sigma, seed, 107, 5, device=1)
+    whole = run_seeded(cat, plan, pos, lnp, g0, sigma, seed, 100, 12, device=1)
+    assert dh.same(dev2, run_seeded(cat, plan, host[0], host[1], g0, sigma, seed, 107, 5, device=0))
+    assert np.array_equal(np.concatenate([dev[2], dev2[2]]), whole[2]) and np.array_equal(dev[4] + dev2[4], whole[4])
+    assert cat.de_info()["discarded_blocks"] == before["discarded_blocks"]
+    cat.close()
+    if vh.HAVE_LONGDOUBLE:
+        err, allowed = _oracle_errors(model, free, cols, whole[2][-1], whole[3][-1])
+        worst = int(np.argmax(err / allowed))
+        print("oracle", (model, free, n_stars, w), "worst row", worst, "err %.2e allowed %.2e" % (err[worst], allowed[worst]))
+        assert np.all(err <= allowed), (worst, err[worst], allowed[worst])
+
+
+def _many_bins(native):
+    """The catalogue and binning of test_hundreds_of_ensembles (tests/test_gpu_device_chain.py): B > 300 bins of 50 stars."""
+    from mcmc_dynamics_amd import DataReader, synthetic
+    from mcmc_dynamics_amd.analysis import BinnedConstantFit
+    cat = synthetic.make_catalog(40000, config=5)
+    reader = DataReader({k: cat[k] for k in ("ra", "dec", "v", "verr")})
+    reader.make_radial_bins(synthetic.CENTER_RA_DEG, synthetic.CENTER_DEC_DEG, nstars=50, dlogr=0.002)
+    bf = BinnedConstantFit(reader)
+    bf.parameters["ra_center"].set(value=synthetic.CENTER_RA_DEG, fixed=True)
+    bf.parameters["dec_center"].set(value=synthetic.CENTER_DEC_DEG, fixed=True)
+    pos1 = synthetic.make_walkers(16, ["v_sys", "sigma_max", "v_maxx", "v_maxy"], cat["truth"], config=5)
+    pos = np.ascontiguousarray(np.broadcast_to(pos1, (bf.n_bins,) + pos1.shape)) * \
+        (1.0 + 1e-3 * np.random.default_rng(3).normal(size=(bf.n_bins, 16, 4)))
+    pos[..., 1] = np.abs(pos[..., 1])
+    return bf, pos
+
+
+def test_hundreds_of_ensembles(native):
+    """More ensembles than the step kernel has threads: workgroup 0 walks the table of all ensembles' ranges in strides.
+    Resident == host-driven == the multi-ensemble NumPy loop; an ensemble behind the first stride that has no valid proposal
+    (status 8), and one whose proposals alone change the guard's verdict (status 4), both give the block back."""
+    bf, pos = _many_bins(native)
+    B, W, P = bf.n_bins, 16, 4
+    assert B > 300 and pos.shape == (B, W, P), B
+    lnp = np.ascontiguousarray(bf.lnprob_batch(pos))
+    assert np.all(np.isfinite(lnp))
+    cat = bf._catalog
+    plan = dict(bf._stretch_plan())
+    g0 = 2.38 / np.sqrt(2.0 * P)
+    before = cat.de_info()
+    dev = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, 5, device=1)
+    dev2 = run_seeded(cat, plan, dev[0], dev[1], g0, 1e-5, SEED, 5, 4, device=1)
+    info = cat.de_info()
+    assert info["device_blocks"] == before["device_blocks"] + 2 and info["discarded_blocks"] == before["discarded_blocks"], info
+    host = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, 5, device=0)
+    host2 = run_seeded(cat, plan, host[0], host[1], g0, 1e-5, SEED, 5, 4, device=0)
+    assert dh.same(dev, host) and dh.same(dev2, host2)
+    nums = de_numbers(native, SEED, 0, 9, B, W, P, g0, 1e-5, False)
+    loop = dh.numpy_de_block(cat, plan, pos, lnp, nums, native.prior_eval)
+    assert np.array_equal(loop[2], np.concatenate([dev[2], dev2[2]])) and np.array_equal(loop[3], np.concatenate([dev[3], dev2[3]]))
+    assert np.array_equal(loop[0], dev2[0]) and np.array_equal(loop[1], dev2[1]) and np.array_equal(loop[4], dev[4] + dev2[4])
+    assert np.all(dev2[4].sum(axis=1) + dev[4].sum(axis=1) > 0) and np.all(np.isfinite(dev2[3]))
+    assert cat.de_info()["discarded_blocks"] == before["discarded_blocks"]
+    # an ensemble behind the first 256 entirely outside a tightened box: the block comes back with status 8
+    e = B - 2
+    assert e >= 256
+    tight = dict(plan, lo=plan["lo"].copy(), hi=plan["hi"].copy())
+    tight["hi"][0] = pos[..., 0].max() + 1.0
+    far, far_lnp = pos.copy(), lnp.copy()
+    far[e, :, 0] = tight["hi"][0] + 50.0
+    far_lnp[e] = -np.inf
+    before = cat.de_info()
+    dev3 = run_seeded(cat, tight, far, far_lnp, g0, 1e-5, SEED, 0, 3, device=1)
+    info = cat.de_info()
+    assert info["discarded_blocks"] == before["discarded_blocks"] + 1 and info["last_discard_status"] & 8, info
+    assert dh.same(dev3, run_seeded(cat, tight, far, far_lnp, g0, 1e-5, SEED, 0, 3, device=0)) and np.array_equal(dev3[0][e], far[e])
+    loop3 = dh.numpy_de_block(cat, tight, far, far_lnp, tuple(a[:3] for a in nums), native.prior_eval)
+    assert dh.same(dev3, loop3) and np.all(loop3[5]["n_ok"][:, :, e] == 0) and dev3[4].sum() > 0
+    # the scales of step 1, SECOND half step, of that ensemble alone are 1e20: its valid proposals (sigma_max > 0) have
+    # |v_sys| + |v_max| beyond the 2^50 the fast kernels of MODEL_CONST admit (mcd_guard.h: guard_verdict), so the verdict
+    # on the table of all ensembles is level 0 where the block was enqueued with level 1 -- seen only by a judge that
+    # reaches entry B + e of the ranges (parity 1, an ensemble behind the first stride)
+    open_plan = dict(plan, lo=np.array([-np.inf, 0.0, -np.inf, -np.inf]), hi=np.full(P, np.inf))
+    wild = [a[:3].copy() for a in nums]
+    wild[3][1, 1, e, :] = 1e20
+    before = cat.de_info()
+    calm = run_numbers(cat, open_plan, pos, lnp, [a[:3] for a in nums], device=1)
+    info = cat.de_info()
+    print("level of the calm block:", cat.fast_level, info)
+    assert info["device_blocks"] == before["device_blocks"] + 1 and info["discarded_blocks"] == before["discarded_blocks"], info
+    dev4 = run_numbers(cat, open_plan, pos, lnp, wild, device=1)
+    info = cat.de_info()
+    loop4 = dh.numpy_de_block(cat, open_plan, pos, lnp, wild, native.prior_eval)
+    assert 0 < loop4[5]["n_ok"][1, 1, e] and np.all(loop4[5]["n_ok"] > 0)
+    assert info["discarded_blocks"] == before["discarded_blocks"] + 1 and info["last_discard_status"] & 4, info
+    assert dh.same(dev4, run_numbers(cat, open_plan, pos, lnp, wild, device=0)) and dh.same(dev4, loop4)
+    assert not dh.same(dev4, calm)
+    bf.close()
+
+
+@pytest.mark.parametrize("w", [4, 8192, 8194])
+def test_ends_of_the_walker_range(native, ctx, w):
+    """W = 4: two slots per half step, pick_b forced, one wave mostly idle.  W = 8192: the numbers kernel's ordering keys
+    fill 64 KiB of LDS exactly and its rank loop runs 8192 times.  W = 8194: past that, the host fills the pinned numbers
+    (de_numbers_of_step) and the resident step kernel consumes them.  Neither may fall back to the host-driven block."""
+    rng = np.random.default_rng(7800 + w)
+    cat, sv = dh.gpu_catalogue(native, ctx, rng, 33, 0, False)
+    pos = dh.gpu_walkers(rng, w, 0, sv, False)
+    lo, hi = dh.gpu_box(cat, pos, 0, sv, margin=0.3 if w == 4 else 0.1)    # (two slots: a window that leaves each half step one)
+    plan = dh.identity_plan(4, lo, hi)
+    lnp = cat.loglike(pos)
+    g0, sigma, n = 2.38 / np.sqrt(8.0), 1e-5, 3
+    before = cat.de_info()
+    dev = run_seeded(cat, plan, pos, lnp, g0, sigma, SEED, 40, n, device=1)
+    info = cat.de_info()
+    assert info["device_blocks"] == before["device_blocks"] + 1 and info["host_blocks"] == before["host_blocks"] and \
+        info["discarded_blocks"] == before["discarded_blocks"], info
+    host = run_seeded(cat, plan, pos, lnp, g0, sigma, SEED, 40, n, device=0)
+    assert dh.same(dev, host)
+    nums = de_numbers(native, SEED, 40, n, 1, w, 4, g0, sigma, True)
+    assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=1))
+    assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=0))
+    info = cat.de_info()
+    assert info["device_blocks"] == before["device_blocks"] + 2 and info["discarded_blocks"] == before["discarded_blocks"], info
+    if w == 4:
+        assert np.all(nums[1] != nums[2]) and set(np.unique(nums[1])) <= {0, 1}
+        loop = dh.numpy_de_block(cat, plan, pos, lnp, nums)
+        assert dh.same(dev, loop) and loop[5]["mixed"] >= 1 and dev[4].sum() > 0
+    else:
+        assert np.array_equal(np.sort(nums[0], axis=1), np.broadcast_to(np.arange(w, dtype=np.int32), (n, w)))
+        assert 0 < dev[4].sum() < n * w
+    assert np.all(np.isfinite(dev[3])) and not np.array_equal(dev[0], pos)
+    cat.close()
+
+
+def test_seeded_block_longer_than_one_grid_of_the_numbers_kernel(native, ctx):
+    """65 540 steps of 4 walkers: launch_de_numbers needs a second launch (gridDim.y <= 65535), which starts at step
+    65 535 of the arrays.  Resident == host-driven == two resident blocks of 65 535 + 5 steps joined through step0.
+    (7.7 s on one MI355X for the four blocks together.)"""
+    rng = np.random.default_rng(7900)
+    cat, sv = dh.gpu_catalogue(native, ctx, rng, 33, 0, False)
+    pos = dh.gpu_walkers(rng, 4, 0, sv, False)
+    plan = dh.identity_plan(4)                                          # (no box: no half step of two slots without a proposal)
+    lnp = cat.loglike(pos)
+    g0, n, cut = 2.38 / np.sqrt(8.0), 65540, 65535
+    before = cat.de_info()
+    dev = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, n, device=1, outputs=False)
+    head = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, cut, device=1, outputs=False)
+    tail = run_seeded(cat, plan, head[0], head[1], g0, 1e-5, SEED, cut, n - cut, device=1, outputs=False)
+    info = cat.de_info()
+    assert info["device_blocks"] == before["device_blocks"] + 3 and info["discarded_blocks"] == before["discarded_blocks"], info
+    assert dh.same(dev, tail) and not np.array_equal(head[0], tail[0])
+    host = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, n, device=0, outputs=False)
+    assert dh.same(dev, host) and np.all(np.isfinite(dev[1]))
+    cat.close()
+
+
+def test_log_normal_coordinate_across_zero(native, ctx):
+    """The plan of test_priors_fixed_column_and_unit_factor with the log-normal prior on v_maxx (sampled in other units),
+    whose walkers sit next to zero: some proposals of a half step have it <= 0 -- outside the prior, no box involved -- and
+    some have not.  The block stays resident and equals the host-driven one and the NumPy loop around
+    ``mcd_prior_eval``."""
+    rng = np.random.default_rng(7250)
+    cat, sv = dh.gpu_catalogue(native, ctx, rng, 4099, 1, False)
+    w = 48
+    half = w // 2
+    full = dh.gpu_walkers(rng, w, 1, sv, False)
+    pos = np.ascontiguousarray(full[:, [1, 2, 3]])                     # v_sys fixed
+    pos[:, 1] = (np.abs(pos[:, 1]) + 0.05) * 60.0                      # v_maxx > 0, sampled in other units
+    kind = np.array([native.PRIOR_NORMAL, native.PRIOR_LOGNORMAL, native.PRIOR_FLAT], dtype=np.int32)
+    prior = (kind, np.array([sv, np.log(100.0), 0.0]), np.array([6.0, 1.5, 1.0]))
+    plan = {"col_source": np.array([-1, 0, 1, 2], dtype=np.int32), "col_const": np.array([0.3, 0, 0, 0]),
+            "col_factor": np.array([1.0, 1.0, 1.0 / 60.0, 1.0]), "lo": np.array([-np.inf, -np.inf, -np.inf]),
+            "hi": np.full(3, np.inf), "fixed_ok": True, "prior": prior}
+    table = np.column_stack([np.full(w, 0.3), pos[:, 0], pos[:, 1] * (1.0 / 60.0), pos[:, 2]])
+    lnp = cat.loglike(table) + native.prior_eval(prior, pos)
+    assert np.all(np.isfinite(lnp))
+    g0 = 2.38 / np.sqrt(6.0)
+    before = cat.de_info()
+    dev = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, 7, device=1)
+    info = cat.de_info()
+    assert info["device_blocks"] == before["device_blocks"] + 1 and info["discarded_blocks"] == before["discarded_blocks"], info
+    host = run_seeded(cat, plan, pos, lnp, g0, 1e-5, SEED, 0, 7, device=0)
+    assert dh.same(dev, host)
+    nums = de_numbers(native, SEED, 0, 7, 1, w, 3, g0, 1e-5, True)
+    assert dh.same(dev, run_numbers(cat, plan, pos, lnp, nums, device=1))
+    loop = dh.numpy_de_block(cat, plan, pos, lnp, nums, native.prior_eval)
+    below, n_ok = loop[5]["nonpositive"][:, :, 0], loop[5]["n_ok"][:, :, 0]
+    print("proposals with v_maxx <= 0 per half step:", below.ravel())
+    assert np.any((below > 0) & (below < half)) and np.array_equal(n_ok, half - below)
+    assert dh.same(dev, loop)
+    assert 0 < dev[4].sum() < 7 * w and np.all(dev[2][..., 1] > 0.0)
+    assert cat.de_info()["discarded_blocks"] == before["discarded_blocks"]
+    cat.close()
+
+
+def test_blocks_given_back_for_a_rerun_and_for_nan(native, ctx):
+    """The two reasons test_blocks_the_device_gives_back leaves out, after parts (2) and (1) of the stretch kernel's test
+    of that name (tests/test_gpu_device_chain.py)."""
+    # (2) re-run request of the fast mixture kernels: certain members that are gross outliers (denormal regime); the tag
+    # arrives behind the sums, where workgroup 0 of the next launch compares it
+    g = load_golden("constant_bg_gaussian_fixed")
+    pm, v = g["pmember"].copy(), g["v"].copy()
+    pm[:3] = 1.0
+    v[:3] = [900.0, -1500.0, 4000.0]
+    gc = (float(g["ra_center"]), float(g["dec_center"]))
+    mix = native.Catalog(ctx, g["ra"], g["dec"], v, g["verr"], model=native.MODEL_CONST_BGFIXED, centre=gc,
+                         lnlike_bg=g["lnlike_background"], pmember=pm)
+    rows = g["values"][np.isfinite(g["lnprior"]) & (g["values"][:, 1] > 0)]
+    pos = np.ascontiguousarray(rows[:16])
+    lnp = mix.loglike(pos)
+    plan = dh.identity_plan(4, lo=[-np.inf, 0.0, -np.inf, -np.inf])
+    reruns = mix.rerun_count
+    dev = run_seeded(mix, plan, pos, lnp, 0.8, 1e-5, SEED, 0, 4, device=1)
+    info = mix.de_info()
+    assert info["discarded_blocks"] == 1 and info["last_discard_status"] & 2 and mix.rerun_count > reruns, info
+    assert info["device_blocks"] == 0 and info["host_blocks"] == 1
+    assert dh.same(dev, run_seeded(mix, plan, pos, lnp, 0.8, 1e-5, SEED, 0, 4, device=0))
+    assert dh.same(dev, dh.numpy_de_block(mix, plan, pos, lnp, de_numbers(native, SEED, 0, 4, 1, 16, 4, 0.8, 1e-5, True)))
+    assert mix.stretch_info()["discarded_blocks"] == 0
+    mix.close()
+    # (1) a NaN log-likelihood: the error of the host loop (emcee: "Probability function returned NaN")
+    ra = np.array([dh.CENTRE[0] + 0.01, dh.CENTRE[0] - 0.01, dh.CENTRE[0]])
+    dec = np.array([dh.CENTRE[1], dh.CENTRE[1] + 0.01, dh.CENTRE[1] - 0.01])
+    nan_cat = native.Catalog(ctx, ra, dec, np.array([1.0, 2.0, 3.0]), np.array([0.0, 1.0, 1.0]), model=0, centre=dh.CENTRE)
+    pos = np.zeros((8, 4))
+    pos[:, 0] = 1.0                                                    # v_sys = v of the verr = 0 star, sigma = 0: 0 / 0
+    lnp = np.zeros(8)
+    for device in (1, 0):
+        with pytest.raises(native.NativeError, match="NaN"):
+            run_seeded(nan_cat, dh.identity_plan(4), pos, lnp, 0.8, 1e-5, SEED, 0, 2, device=device)
+    info = nan_cat.de_info()
+    assert info["last_discard_status"] & 1 and info["discarded_blocks"] == 1 and info["device_blocks"] == 0, info
+    nan_cat.close()
 
 
 def _bins(native):
