@@ -72,8 +72,17 @@ typedef enum {
                                      the second peak radius is r_peak_ratio * r_peak.  Columns: v_sys, sigma_max, a,
                                      v_maxx, v_maxy, r_peak, v_maxx_c, v_maxy_c, r_peak_ratio [, ra_center, dec_center].
                                      MCD_F64 only (mcd_catalog_create refuses the float32 precisions)            */
-    MCD_MODEL_DOUBLE_BGGAUSS = 8  /* DoubleModelFitGB: + per-walker Gaussian background and density prior, as
+    MCD_MODEL_DOUBLE_BGGAUSS = 8, /* DoubleModelFitGB: + per-walker Gaussian background and density prior, as
                                      MCD_MODEL_PROFILE_BGGAUSS: [, v_back, sigma_back, f_back] behind the centre */
+    /* 9 is unassigned: mcd_catalog_create answers it with "unknown model", as it always has */
+    MCD_MODEL_CONST_ESCALE = 10,  /* ConstantFitES: MCD_MODEL_CONST with a fitted velocity-error scale, one per row:
+                                     variance = err_scale^2 verr^2 + sigma_max^2, v_los unchanged.  Columns: v_sys,
+                                     sigma_max, v_maxx, v_maxy, err_scale [, ra_center, dec_center] (K = 5 / 7).
+                                     err_scale = 1 gives MCD_MODEL_CONST's bits.  No background; MCD_F64 only
+                                     (mcd_catalog_create refuses the float32 precisions); no narrow-range variant */
+    MCD_MODEL_PROFILE_ESCALE = 11 /* ModelFitES: MCD_MODEL_PROFILE likewise, variance = err_scale^2 verr^2 +
+                                     sigma_los^2(r).  Columns: v_sys, sigma_max, a, v_maxx, v_maxy, r_peak, err_scale
+                                     [, ra_center, dec_center] (K = 7 / 9)                                         */
 } mcd_model;
 
 typedef enum {

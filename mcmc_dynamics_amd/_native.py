@@ -17,6 +17,9 @@ LIB_PATH = os.environ.get("MCD_LIB_PATH") or os.path.join(_HERE, "libmcd_hip.so"
 MODEL_CONST, MODEL_CONST_BGFIXED, MODEL_CONST_BGGAUSS = 0, 1, 2
 MODEL_PROFILE, MODEL_PROFILE_BGGAUSS, MODEL_PROFILE_BGDENS, MODEL_PROFILE_BGFIXED = 3, 4, 5, 6
 MODEL_DOUBLE, MODEL_DOUBLE_BGGAUSS = 7, 8        # two Lynden-Bell components (analysis/double_model.py); float64 only
+# CONST / PROFILE with a fitted velocity-error scale: variance = err_scale^2 verr^2 + sigma_los^2 (analysis/error_scale.py);
+# err_scale follows the cluster columns, in front of the centre; float64 only, no background
+MODEL_CONST_ESCALE, MODEL_PROFILE_ESCALE = 10, 11      # (9 is not a model: mcd_catalog_create answers "unknown model")
 CENTRE_FIXED, CENTRE_FREE = 0, 1
 F64, F32, F32_ACC64 = 0, 1, 2
 PRECISIONS = {"f64": F64, "f32": F32, "f32acc64": F32_ACC64}

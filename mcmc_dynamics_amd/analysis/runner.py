@@ -2213,7 +2213,8 @@ class Runner(object):
     # ------------------------------------------------------------------ per-star posterior summaries (new)
     def _has_background(self):
         model = self._catalog_spec()[0][0]
-        return model not in (_native.MODEL_CONST, _native.MODEL_PROFILE, _native.MODEL_DOUBLE)
+        return model not in (_native.MODEL_CONST, _native.MODEL_PROFILE, _native.MODEL_DOUBLE,
+                             _native.MODEL_CONST_ESCALE, _native.MODEL_PROFILE_ESCALE)
 
     def _pointwise_posterior(self, chain, n_burn, thin, membership):
         """mcd_pointwise_posterior over the post-burn-in samples of ``chain`` (W, steps, P), every ``thin``-th step, in the

@@ -135,7 +135,7 @@ int stretch_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_
     const size_t o_order = take(n_in * BW * 4), o_zz = take(n_in * BW * 8);
     const size_t o_thr = take(n_in * BW * 8), o_pick = take(n_in * BW * 4);
     const size_t input_end = off;
-    const size_t o_prop = take(Bh * P * 8), o_ok = take(Bh), o_nok = take((size_t)2 * B * 4), o_ranges = take((size_t)2 * B * 10 * 8);
+    const size_t o_prop = take(Bh * P * 8), o_ok = take(Bh), o_nok = take((size_t)2 * B * 4), o_ranges = take((size_t)2 * B * mcd::kRangeDoubles * 8);
     const size_t o_pval = take(with_prior ? Bh * 8 : 0);
     const size_t o_nok_log = take(defer ? n_launches * 4 : 0), o_table_log = take(defer ? n_launches * half * K * 8 : 0);
     const size_t o_chain = take(chain ? (size_t)n_steps * BW * P * 8 : 0);

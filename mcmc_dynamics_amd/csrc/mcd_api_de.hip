@@ -74,7 +74,7 @@ int de_block_device(mcd_catalog* cat, const mcd_stretch_desc* d, int64_t n_steps
     const size_t o_order = take(n_in * BW * 4), o_pa = take(n_in * BW * 4), o_pb = take(n_in * BW * 4);
     const size_t o_gamma = take(n_in * BW * 8), o_thr = take(n_in * BW * 8);
     const size_t input_end = off;
-    const size_t o_prop = take(Bh * P * 8), o_ok = take(Bh), o_ranges = take((size_t)2 * B * 10 * 8);
+    const size_t o_prop = take(Bh * P * 8), o_ok = take(Bh), o_ranges = take((size_t)2 * B * mcd::kRangeDoubles * 8);
     const size_t o_pval = take(with_prior ? Bh * 8 : 0);
     const size_t o_chain = take(chain ? (size_t)n_steps * BW * P * 8 : 0);
     const size_t o_lnpc = take(lnprob_chain ? (size_t)n_steps * BW * 8 : 0);

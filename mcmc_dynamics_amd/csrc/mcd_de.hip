@@ -45,21 +45,22 @@ __device__ __forceinline__ void de_wave_merge(ParamRanges& r) {
     r.sb2_min = de_wave_lesser(r.sb2_min); r.sb2_max = de_wave_greater(r.sb2_max);
     r.f_min = de_wave_lesser(r.f_min); r.f_max = de_wave_greater(r.f_max);
     r.len_min = de_wave_lesser(r.len_min); r.len_max = de_wave_greater(r.len_max);
+    r.es2_min = de_wave_lesser(r.es2_min); r.es2_max = de_wave_greater(r.es2_max);
     r.finite = __all(r.finite ? 1 : 0) != 0;
 }
 __device__ __forceinline__ void de_store_ranges(const ParamRanges& r, double* o) {
     o[0] = r.s2_min; o[1] = r.s2_max; o[2] = r.amp; o[3] = r.sb2_min; o[4] = r.sb2_max; o[5] = r.f_min; o[6] = r.f_max;
-    o[7] = r.len_min; o[8] = r.len_max; o[9] = r.finite ? 1.0 : 0.0;
+    o[7] = r.len_min; o[8] = r.len_max; o[9] = r.finite ? 1.0 : 0.0; o[10] = r.es2_min; o[11] = r.es2_max;
 }
 __device__ __forceinline__ ParamRanges de_load_ranges(const double* o) {
     ParamRanges r;
     r.s2_min = o[0]; r.s2_max = o[1]; r.amp = o[2]; r.sb2_min = o[3]; r.sb2_max = o[4]; r.f_min = o[5]; r.f_max = o[6];
-    r.len_min = o[7]; r.len_max = o[8]; r.finite = o[9] != 0.0;
+    r.len_min = o[7]; r.len_max = o[8]; r.finite = o[9] != 0.0; r.es2_min = o[10]; r.es2_max = o[11];
     return r;
 }
 
 // the workgroup's ranges: every thread's -> one per wave -> thread 0 holds the merge of all in `out`
-__device__ __forceinline__ void de_block_merge(ParamRanges& mine, double (*s_ranges)[10], ParamRanges& out) {
+__device__ __forceinline__ void de_block_merge(ParamRanges& mine, double (*s_ranges)[kRangeDoubles], ParamRanges& out) {
     const int tid = threadIdx.x;
     de_wave_merge(mine);
     if ((tid & 63) == 0) de_store_ranges(mine, s_ranges[tid >> 6]);
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kDeBlock) void de_step_kernel(DeDevice dd, int64_t 
     const int P = d.n_dim, K = d.k;
     const int tid = threadIdx.x;
     __shared__ int s_n_ok, s_donor;
-    __shared__ double s_ranges[kDeBlock / 64][10];           // ParamRanges of each wave (a type with initialisers cannot be __shared__)
+    __shared__ double s_ranges[kDeBlock / 64][kRangeDoubles];           // ParamRanges of each wave (a type with initialisers cannot be __shared__)
     // arrays carry the ensemble index in front of the walker index
     double* const pos_b = d.pos + b * W * P;
     double* const lnp_b = d.lnp + b * W;
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(kDeBlock) void de_step_kernel(DeDevice dd, int64_t 
             // without a valid proposal raised CHAIN_NO_PROPOSAL itself: the block is given back whatever the verdict)
             ParamRanges mine, all;
             for (int64_t e = tid; e < B; e += kDeBlock)
-                if (d.n_ok[slot_acc + e] > 0) mine.merge(de_load_ranges(d.ranges + (slot_acc + e) * 10));
+                if (d.n_ok[slot_acc + e] > 0) mine.merge(de_load_ranges(d.ranges + (slot_acc + e) * kRangeDoubles));
             de_block_merge(mine, s_ranges, all);
             if (tid == 0 && !(d.meta[META_STATUS] & CHAIN_NO_PROPOSAL)) {
                 int level = 0;
@@ -188,7 +189,7 @@ __global__ __launch_bounds__(kDeBlock) void de_step_kernel(DeDevice dd, int64_t 
     if (tid == 0) {
         d.n_ok[slot_prop + b] = n_ok;
         if (n_ok == 0) atomicOr(&d.meta[META_STATUS], CHAIN_NO_PROPOSAL);   // (the host loop lends the ensemble another's row)
-        else de_store_ranges(all, d.ranges + (slot_prop + b) * 10);
+        else de_store_ranges(all, d.ranges + (slot_prop + b) * kRangeDoubles);
     }
 }
 

@@ -18,6 +18,8 @@
 //                  dd/dv_maxx_k = -f_k dy, dd/dv_maxy_k = f_k dx, dd/dr_p = g_1 + ratio g_2, dd/dratio = r_p g_2,
 //                  dd/d(dx) = sum_k f_k (v_maxy_k + 2 cross_k dx / D_k), dd/d(dy) = sum_k f_k (-v_maxx_k + 2 cross_k dy / D_k);
 //                  n and its partials are PROFILE's.  The value d itself is formed as the value path forms it (star_d_n).
+//   ESCALE         n = err_scale^2 verr^2 + sigma_los^2: dn/derr_scale = 2 err_scale verr^2; d and the other partials are the
+//                  base model's (dl/dn is the factor sigma_max's column already forms)
 //   free centre    chain rule through free_centre_xy (mcd_math.h): with t = B cos(ra_c) + A sin(ra_c),
 //                  dx/dra_c = t, dy/dra_c = sin(dec_c) x, dx/ddec_c = 0, dy/ddec_c = -(sd sin(dec_c) + cos(dec_c) t)
 //                  CONST:   sin(theta) = y/r, cos(theta) = x/r, so with u = cross / r (cross = v_maxx y - v_maxy x)
@@ -54,6 +56,8 @@ template <int MODEL, bool FREE> struct GradCols {
     static constexpr int kVsys = 0, kSigma = 1, kA = 2, kVx = kProf ? 3 : 2, kVy = kProf ? 4 : 3, kRp = 5;
     static constexpr bool kDouble = is_double(MODEL);
     static constexpr int kVxc = 6, kVyc = 7, kRatio = 8;     // (double models)
+    static constexpr bool kEscale = is_escale(MODEL);
+    static constexpr int kEs = cluster_columns(MODEL) - 1;   // (error-scale models: err_scale, the last cluster column)
     static constexpr int kRa = cluster_columns(MODEL), kDec = kRa + 1;
     static constexpr int kBg = kRa + (FREE ? 2 : 0);          // v_back, sigma_back, f_back | f_back
     static constexpr int kFb = bg_kind(MODEL) == BG_GAUSS ? kBg + 2 : kBg;
@@ -62,7 +66,7 @@ template <int MODEL, bool FREE> struct GradCols {
 
 // what the derivatives need of the parameter row itself (WalkerConsts holds squares and products only)
 template <class T> struct GradRaw {
-    T sigma, a, rp, sb, ratio;
+    T sigma, a, rp, sb, ratio, es;
     template <int MODEL, bool FREE>
     MCD_HD void load(const double* __restrict__ p) {
         using C = GradCols<MODEL, FREE>;
@@ -71,6 +75,7 @@ template <class T> struct GradRaw {
         rp = C::kProf ? (T)p[C::kRp] : T(0);
         sb = bg_kind(MODEL) == BG_GAUSS ? (T)p[C::kBg + 1] : T(0);
         ratio = C::kDouble ? (T)p[C::kRatio] : T(0);
+        es = C::kEscale ? (T)p[C::kEs] : T(0);
     }
 };
 
@@ -99,7 +104,8 @@ MCD_HD T grad_term_at(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q
         y_dec = -fma_(r[4], w.sdc, w.cdc * t);
     }
     if constexpr (!C::kProf) {
-        n = r[1] + w.s2;
+        if constexpr (C::kEscale) n = w.es2 * r[1] + w.s2;         // star_d_n's plain forms, here and below
+        else n = r[1] + w.s2;
         n_sigma = T(2) * q.sigma;
         if constexpr (FREE) {
             const T r2 = fma_(x, x, y * y);
@@ -148,7 +154,8 @@ MCD_HD T grad_term_at(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q
             d = fma_(-f, cross, r[0] - w.vsys);
             d_rp = T(-2) * cross * (r2 - w.rp2) * inv * inv;
         }
-        n = fma_(w.s2a, tt, r[1]);
+        if constexpr (C::kEscale) n = fma_(w.s2a, tt, w.es2 * r[1]);
+        else n = fma_(w.s2a, tt, r[1]);
         d_vx = -(f * dy);
         d_vy = f * dx;
         n_sigma = T(2) * q.sigma * q.a * tt;
@@ -231,6 +238,7 @@ MCD_HD T grad_term_at(RecPtr<T> r, const WalkerConsts<T>& w, const GradRaw<T>& q
         g[C::kVyc] += c_d * d_vyc;
         g[C::kRatio] += c_d * d_ratio;
     }
+    if constexpr (C::kEscale) g[C::kEs] += c_n * (T(2) * q.es * r[1]);      // dn/derr_scale = 2 err_scale verr^2
     if constexpr (FREE) {
         if constexpr (C::kProf) {
             g[C::kRa] += T(kDegToRad) * fma_(c_d, d_ra, c_n * n_ra);

@@ -76,7 +76,7 @@ hipError_t launch_loglike_grad(hipStream_t s, const LaunchShape& sh, const void*
                                int64_t n_chunks, const double* params, const void* wpar, double* partials,
                                int64_t n_walkers) {
     if (sh.precision != 0) return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_grad_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, params, wpar, partials,
                                                                            n_walkers);
     }, hipErrorInvalidValue);

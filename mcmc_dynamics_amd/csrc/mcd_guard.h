@@ -150,12 +150,17 @@ struct GuardRanges {
     double f_min = 0, f_max = 0;        // f_back (BG_GAUSS, BG_FIXED_DENSITY)
 };
 
+constexpr int kRangeDoubles = 12;      // a ParamRanges as doubles: what the device blocks keep per wave and per ensemble
 // Ranges of one parameter table, gathered row by row.  Only min / max of per-row quantities: the result does not depend
 // on the order in which rows (or partial results, merge()) are visited, so a parallel reduction on the device and the
 // serial loop on the host give the same bits.
 struct ParamRanges {
     double s2_min = kInfinity, s2_max = 0.0, amp = 0.0, sb2_min = kInfinity, sb2_max = 0.0, f_min = kInfinity, f_max = 0.0;
     double len_min = kInfinity, len_max = 0.0;                 // a and r_peak of the profile models
+    // err_scale^2 of the error-scale models, together with 1 (the range of the rows and the base model's scale: a bound
+    // that is at most wider, and minima and maxima still merge in any order); exactly 1 for every other model, whose verdicts
+    // keep their bits (fma(1, verr^2, s2) is verr^2 + s2)
+    double es2_min = 1.0, es2_max = 1.0;
     bool finite = true;                                        // every row finite where the guard needs it
 
     MCD_HD static double lesser(double a, double b) { return b < a ? b : a; }
@@ -178,6 +183,14 @@ struct ParamRanges {
             rc = p[8] * p[5];
             ok = ok && finite_value(rc);
         }
+        // error-scale models: err_scale is the last cluster column; a row with err_scale <= 0 (or NaN, inf) is not finite
+        const bool esc = is_escale(model);
+        double es2 = 1.0;
+        if (esc) {
+            const double es = p[cluster_columns(model) - 1];
+            es2 = es * es;
+            ok = ok && es > 0.0 && finite_value(es2);
+        }
         double sb2 = 0.0, f = 0.0;
         if (bg == BG_GAUSS) {
             sb2 = p[k - 2] * p[k - 2];
@@ -199,6 +212,7 @@ struct ParamRanges {
             len_max = greater(len_max, greater(p[2], p[5]));
         }
         if (dbl) { len_min = lesser(len_min, rc); len_max = greater(len_max, rc); }
+        if (esc) { es2_min = lesser(es2_min, es2); es2_max = greater(es2_max, es2); }
         if (bg == BG_GAUSS) { sb2_min = lesser(sb2_min, sb2); sb2_max = greater(sb2_max, sb2); }
         if (bg == BG_GAUSS || bg == BG_FIXED_DENSITY) { f_min = lesser(f_min, f); f_max = greater(f_max, f); }
         s2_min = lesser(s2_min, s2);
@@ -211,6 +225,7 @@ struct ParamRanges {
         sb2_min = lesser(sb2_min, o.sb2_min); sb2_max = greater(sb2_max, o.sb2_max);
         f_min = lesser(f_min, o.f_min); f_max = greater(f_max, o.f_max);
         len_min = lesser(len_min, o.len_min); len_max = greater(len_max, o.len_max);
+        es2_min = lesser(es2_min, o.es2_min); es2_max = greater(es2_max, o.es2_max);
         finite = finite && o.finite;
     }
 
@@ -229,7 +244,8 @@ MCD_HD bool guard_verdict(const StatsScalars& st, int model, bool f32, int64_t n
     const double d_max = st.v_abs_max + amp;
     if (!(d_max <= 0x1p58)) return false;
     // sigma_los of the profile models decays to 0 at large r: only verr^2 bounds the variance from below
-    const double n_min = st.e2_min + (prof ? 0.0 : s2_min), n_max = st.e2_max + s2_max;
+    // (error-scale models: verr^2 enters as err_scale^2 verr^2; es2_min = es2_max = 1 for every other model)
+    const double n_min = fma_(pr.es2_min, st.e2_min, prof ? 0.0 : s2_min), n_max = fma_(pr.es2_max, st.e2_max, s2_max);
     if (ranges) {
         ranges->n_min = n_min; ranges->n_max = n_max; ranges->d_max = d_max;
         ranges->nb_min = st.e2_min + sb2_min; ranges->nb_max = st.e2_max + sb2_max;
@@ -293,6 +309,7 @@ MCD_HD int level_verdict(const StatsScalars& st, int model, bool f32, int64_t n_
     if (!guard_verdict(st, model, f32, n_rows, pr, &g)) return 0;
     if (f32) return 1;
     if (is_double(model)) return 1;          // no narrow-range variant: the shared reciprocal is what the level-2 tree would replace
+    if (is_escale(model)) return 1;          // no narrow-range variant either (ProfileNarrowAcc is MODEL_PROFILE's alone)
     // MODEL_PROFILE with a fixed centre (ProfileNarrowAcc, mcd_math.h): m = r_peak^2 + r^2 <= 2^34 arcsec^2 (a 36 degree
     // field), lengths >= 2^-10 arcsec, variances within 2^-30 .. 2^30, residuals below 2^30: the 8-star tree on
     // ((dv m - K c)^2, m^2 n) stays within 2^+-820

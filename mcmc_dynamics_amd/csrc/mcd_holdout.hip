@@ -71,7 +71,7 @@ hipError_t launch_holdout_main(hipStream_t s, const void* records, const Chunk* 
 hipError_t launch_holdout(hipStream_t s, const LaunchShape& sh, const void* records, const Chunk* chunks, int64_t n_chunks,
                           const void* wpar, double* partials, int64_t n_rows) {
     if (sh.precision != 0 || n_rows <= 0) return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_holdout_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, wpar, partials,
                                                                               n_rows);
     }, hipErrorInvalidValue);

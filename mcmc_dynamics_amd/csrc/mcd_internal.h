@@ -165,7 +165,7 @@ struct StretchDevice {
     uint8_t* ok = nullptr;                 // [W/2]   proposal inside the prior
     int32_t* meta = nullptr;               // [META_WORDS]
     int32_t* n_ok = nullptr;               // [2][B] proposals inside the prior, per ensemble and half-step parity
-    double* ranges = nullptr;              // [2][B][10] ParamRanges of each ensemble's table (B > 1: judged by the next launch)
+    double* ranges = nullptr;              // [2][B][kRangeDoubles] ParamRanges of each ensemble's table (B > 1: judged by the next launch)
     double* table = nullptr;               // [W/2][k]   resolved parameter rows (the guard reads them back)
     // deferred guard (ONE ensemble, the in-LDS step kernel): the step kernel logs each launch's rows and the number of
     // proposals inside the prior; stretch_judge_kernel gives all verdicts at the end of the block (mcd_stretch.hip)

@@ -429,14 +429,14 @@ hipError_t launch_precision(hipStream_t s, const LaunchShape& sh, const void* re
             if (sh.fast) return launch_one<MODEL, FREE, double, double, 1>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
             return launch_one<MODEL, FREE, double, double, 0>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
         case 1:      // float32 terms and sums: fast formulations for every model when the f32 guard admits them (mcd_guard.h)
-            if constexpr (is_double(MODEL)) {
+            if constexpr (is_double(MODEL) || is_escale(MODEL)) {
                 return hipErrorInvalidValue;                  // float64 only, refused at catalogue creation
             } else {
                 if (sh.fast) return launch_one<MODEL, FREE, float, float, 1>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
                 return launch_one<MODEL, FREE, float, float, 0>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
             }
         case 2:      // float32 terms, float64 accumulation
-            if constexpr (is_double(MODEL)) {
+            if constexpr (is_double(MODEL) || is_escale(MODEL)) {
                 return hipErrorInvalidValue;
             } else {
                 if (sh.fast) return launch_one<MODEL, FREE, float, double, 1>(s, sh, records, chunks, n_chunks, wpar, partials, n_walkers);
@@ -485,7 +485,7 @@ hipError_t launch_prepare_walkers(hipStream_t s, const double* params, int64_t n
 
 hipError_t launch_loglike(hipStream_t s, const LaunchShape& sh, const void* records, const Chunk* chunks,
                           int64_t n_chunks, const void* wpar, double* partials, int64_t n_walkers) {
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_precision<decltype(M)::value, decltype(FREE)::value>(s, sh, records, chunks, n_chunks, wpar, partials,
                                                                            n_walkers);
     }, hipErrorInvalidValue);
@@ -533,7 +533,7 @@ hipError_t launch_per_star(hipStream_t s, const LaunchShape& sh, const void* rec
                            const void* wpar_row, int mode, double* out) {
     if (n <= 0) return hipSuccess;
     const unsigned grid = (unsigned)((n + kBlock - 1) / kBlock);
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         // the models without a background have no components to tell apart: no kernel for them
         if constexpr (bg_kind(decltype(M)::value) == BG_NONE) return hipErrorInvalidValue;
         else return dispatch_term_type(sh.precision, [&](auto t) {

@@ -345,12 +345,12 @@ hipError_t term_launch(hipStream_t s, int precision, const void* records, int64_
     int64_t slice_len = 0;
     const int64_t n_slices = posterior_slices(n, S, &slice_len);
     const dim3 grid((unsigned)((n + kWave - 1) / kWave * n_slices));
-    return dispatch_term_type(precision, [&](auto t) {
+    return dispatch_model_term_type<MODEL>(precision, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((loox_term_kernel<MODEL, FREE, MODE, T>), grid, dim3(kWave), term_lds_bytes(loox_rows(MODE)), s, (const T*)records, n,
                            (const T*)wpar, S, slice_len, n_slices, terms);
         return hipGetLastError();
-    });
+    }, hipErrorInvalidValue);
 }
 
 template <int XR>
@@ -369,7 +369,7 @@ hipError_t launch_loo_expect(hipStream_t s, const LaunchShape& sh, int mode, con
                              double* terms, double* out, int64_t out_stride) {
     if (n <= 0 || S <= 0) return hipSuccess;
     if (M > kPsisMaxTail || n_func < 0 || n_func > kLooMaxFunc) return hipErrorInvalidValue;
-    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         // pit_mix exists for the two models whose background has a CDF only

@@ -63,7 +63,8 @@ enum WalkerSlot : int {
     W_VB = 8, W_SB2 = 9, W_FB = 10,                 // v_back, sigma_back^2, f_back
     W_A2 = 11, W_S2A = 12, W_RP2 = 13, W_2RP = 14,  // profile models: a^2, sigma_max^2 a, r_peak^2, 2 r_peak (arcsec)
     W_VXC = 15, W_VYC = 16, W_RC2 = 17, W_2RC = 18, // double models: v_maxx_c, v_maxy_c, rho_2^2, 2 rho_2 (rho_2 = ratio r_peak)
-    KD = 20                                         // (a row stays a whole number of 32-byte segments; slot 19 is padding)
+    W_ES2 = 19,                                     // error-scale models: err_scale^2; 0 for every other model
+    KD = 20                                         // (a row stays a whole number of 32-byte segments)
 };
 
 // Likelihood variants.  Cluster part: CONST (analysis/constant.py) or PROFILE (analysis/model.py:93-180);
@@ -76,18 +77,33 @@ enum Model : int {
     // DoubleModelFit / DoubleModelFitGB: two Lynden-Bell components on one Plummer dispersion profile (star_d_n), without
     // background / with the per-walker Gaussian background and density prior of MODEL_PROFILE_BGGAUSS.  float64 only, no
     // narrow-range (level 2) variant.
-    MODEL_DOUBLE = 7, MODEL_DOUBLE_BGGAUSS = 8
+    MODEL_DOUBLE = 7, MODEL_DOUBLE_BGGAUSS = 8,
+    // ConstantFitES / ModelFitES: MODEL_CONST / MODEL_PROFILE with a fitted velocity-error scale, one per walker:
+    //   variance = err_scale^2 verr^2 + sigma_los^2,  v_los unchanged  (star_d_n).
+    // No background, float64 only, no narrow-range (level 2) variant.  Records are the base models'.
+    // (id 9 stays unassigned: mcd_catalog_create has always answered it with "unknown model", and callers rely on that)
+    MODEL_CONST_ESCALE = 10, MODEL_PROFILE_ESCALE = 11
 };
 constexpr int kNumModels = 7;           // the models of the reference's running classes: what dispatch_model lists
 constexpr int kNumAllModels = 9;        // ... and the double Lynden-Bell models: what dispatch_any_model lists (mcd_dispatch.h)
+constexpr int kNumLaunchModels = 12;    // one past the largest id dispatch_launch_model lists (the error-scale models; not 9)
 enum Background : int { BG_NONE = 0, BG_FIXED = 1, BG_GAUSS = 2, BG_FIXED_DENSITY = 3 };
 
-MCD_HD constexpr bool is_profile(int model) { return model >= MODEL_PROFILE; }
+MCD_HD constexpr bool is_escale(int model) { return model == MODEL_CONST_ESCALE || model == MODEL_PROFILE_ESCALE; }
+// the ids a catalogue can have: what dispatch_launch_model reaches
+MCD_HD constexpr bool is_launch_model(int model) { return (model >= 0 && model < kNumAllModels) || is_escale(model); }
+// the model an error-scale model is at err_scale = 1 (records, chunk functions, launch costs); every other model itself
+MCD_HD constexpr int base_model(int model) {
+    return model == MODEL_CONST_ESCALE ? (int)MODEL_CONST : model == MODEL_PROFILE_ESCALE ? (int)MODEL_PROFILE : model;
+}
+MCD_HD constexpr bool is_profile(int model) { return (model >= MODEL_PROFILE && model < kNumAllModels) || model == MODEL_PROFILE_ESCALE; }
 MCD_HD constexpr bool is_double(int model) { return model == MODEL_DOUBLE || model == MODEL_DOUBLE_BGGAUSS; }
-// kernel columns of the cluster part in front of the centre columns (mcd_prep.h has the order)
-MCD_HD constexpr int cluster_columns(int model) { return is_double(model) ? 9 : is_profile(model) ? 6 : 4; }
+// kernel columns of the cluster part in front of the centre columns (mcd_prep.h has the order); err_scale is the last of them
+MCD_HD constexpr int cluster_columns(int model) {
+    return (is_double(model) ? 9 : is_profile(model) ? 6 : 4) + (is_escale(model) ? 1 : 0);
+}
 MCD_HD constexpr int bg_kind(int model) {
-    return (model == MODEL_CONST || model == MODEL_PROFILE || model == MODEL_DOUBLE) ? BG_NONE
+    return (model == MODEL_CONST || model == MODEL_PROFILE || model == MODEL_DOUBLE || is_escale(model)) ? BG_NONE
            : (model == MODEL_BGFIXED || model == MODEL_PROFILE_BGFIXED) ? BG_FIXED
            : (model == MODEL_PROFILE_BGDENS) ? BG_FIXED_DENSITY : BG_GAUSS;
 }
@@ -1145,6 +1161,7 @@ struct RecordPrefetch {
 template <class T> struct WalkerConsts {
     T vsys, s2, vx, vy, sac, cac, sdc, cdc, vb, sb2, fb, a2, s2a, rp2, rp_2;
     T vxc, vyc, rc2, rc_2;                            // double models only: dead loads for every other MODEL
+    T es2;                                            // error-scale models only: likewise
     template <class P>
     MCD_HD void load(const P* __restrict__ p) {
         vsys = p[W_VSYS]; s2 = p[W_S2]; vx = p[W_VX]; vy = p[W_VY];
@@ -1152,6 +1169,7 @@ template <class T> struct WalkerConsts {
         vb = p[W_VB]; sb2 = p[W_SB2]; fb = p[W_FB];
         a2 = p[W_A2]; s2a = p[W_S2A]; rp2 = p[W_RP2]; rp_2 = p[W_2RP];
         vxc = p[W_VXC]; vyc = p[W_VYC]; rc2 = p[W_RC2]; rc_2 = p[W_2RC];
+        es2 = p[W_ES2];
     }
 };
 
@@ -1166,6 +1184,11 @@ template <class T> struct WalkerConsts {
 //            i.e. two crosses, the product m_1 m_2 and four multiply-adds more than PROFILE and no second reciprocal
 //            sequence.  The guard's general domain (lengths within 2^-100 .. 2^100, mcd_guard.h) keeps m_1 m_2 within
 //            2^+-402.  With both second amplitudes 0 the value is PROFILE's up to the rounding of the shared reciprocal.
+//   ESCALE:  the base model's d; the variance is err_scale^2 verr^2 + sigma_los^2 with es2 = err_scale^2 of the walker row:
+//            CONST    n = fma(es2, verr^2, sigma_max^2)                       one fma in place of the add (fast forms;
+//                                                                              the plain form multiplies, then adds)
+//            PROFILE  n = fma(sigma_max^2 a, t, es2 verr^2)                   one multiply more than PROFILE
+//            At es2 == 1 both are their base models' expressions bit for bit (1 x is exact), in every form.
 // NEWTON1 (narrow-range variants of the profile mixtures, f64): the Plummer root from ONE Newton step in its
 // three-instruction form (rsqrt2_newton: low by <= 4.1e-15 relative, see there), two instructions fewer than rsqrt_nr.
 template <int MODEL, class T, bool FREE, bool FASTMATH = false, bool NEWTON1 = false>
@@ -1173,7 +1196,10 @@ MCD_HD void star_d_n(RecPtr<T> r, const WalkerConsts<T>& w, T& d, T& n) {
     if constexpr (!is_profile(MODEL)) {
         if (FREE) d = free_centre_residual<FASTMATH>(r[2], r[3], r[4], w.sac, w.cac, w.sdc, w.cdc, w.vx, w.vy, r[0] - w.vsys);
         else d = fma_(-w.vx, r[2], fma_(w.vy, r[3], r[0] - w.vsys));
-        n = r[1] + w.s2;
+        // (plain form: multiply, then add -- with the fma the plain CONST kernel with a fixed centre takes 134 VGPRs, with
+        // the two operations 102; both are r[1] + w.s2 bit for bit at es2 == 1)
+        if constexpr (is_escale(MODEL)) n = FASTMATH ? fma_(w.es2, r[1], w.s2) : w.es2 * r[1] + w.s2;
+        else n = r[1] + w.s2;
     } else {
         T dx, dy, r2;
         if (FREE) {
@@ -1218,7 +1244,8 @@ MCD_HD void star_d_n(RecPtr<T> r, const WalkerConsts<T>& w, T& d, T& n) {
         }
         const T cross = fma_(w.vx, dy, -(w.vy * dx));
         d = fma_(-(w.rp_2 * inv), cross, r[0] - w.vsys);
-        n = fma_(w.s2a, t, r[1]);
+        if constexpr (is_escale(MODEL)) n = fma_(w.s2a, t, w.es2 * r[1]);
+        else n = fma_(w.s2a, t, r[1]);
     }
 }
 
@@ -1336,7 +1363,7 @@ MCD_HD double chunk_const_f32(RecPtr<float> r, int count, const WalkerConsts<flo
     acc.init();
     // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
     // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
-    constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
+    constexpr bool TREE16 = base_model(MODEL) == MODEL_CONST && !FREE;
     const int n16 = TREE16 ? count >> 4 : 0;
     for (int g = 0; g < n16; ++g, r += 16 * ND) {
         RecordPrefetch<16 * ND * 4, PF> pf;
@@ -1416,7 +1443,7 @@ MCD_HD double chunk_const_fast(RecPtr<double> r, int count, const WalkerConsts<d
     acc.init();
     // MODEL_CONST with a fixed centre has registers to spare for a 16-star tree (one reciprocal per 16 stars); the
     // other instantiations keep 8-star trees (a 16-star tree there costs occupancy)
-    constexpr bool TREE16 = MODEL == MODEL_CONST && !FREE;
+    constexpr bool TREE16 = base_model(MODEL) == MODEL_CONST && !FREE;
     const int n16 = TREE16 ? count >> 4 : 0;
     for (int g = 0; g < n16; ++g, r += 16 * ND) {
         RecordPrefetch<16 * ND * 8, PF> pf;

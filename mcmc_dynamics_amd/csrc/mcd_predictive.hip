@@ -93,12 +93,12 @@ hipError_t slice_launch(hipStream_t s, int precision, const void* records, int64
                         const double* inv, int64_t slice_len, int64_t n_slices, double* part) {
     const int64_t n_tasks = (n + kWave - 1) / kWave * n_slices;
     const dim3 grid((unsigned)((n_tasks + kWavesPerBlock - 1) / kWavesPerBlock));
-    return dispatch_term_type(precision, [&](auto t) {
+    return dispatch_model_term_type<MODEL>(precision, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((predictive_slice_kernel<MODEL, FREE, MIX, T>), grid, dim3(kBlock), 0, s, (const T*)records, n,
                            (const T*)wpar, n_samples, inv, slice_len, n_slices, part);
         return hipGetLastError();
-    });
+    }, hipErrorInvalidValue);
 }
 
 }  // namespace
@@ -107,7 +107,7 @@ hipError_t launch_predictive(hipStream_t s, const LaunchShape& sh, bool mix, con
                              const void* wpar, int64_t n_samples, const double* inv, int64_t slice_len, int64_t n_slices,
                              double* part, double* state, int64_t n_prev, int64_t n_total, double* out) {
     if (n <= 0 || n_samples <= 0) return hipSuccess;
-    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         // pit_mix exists for the two models whose background has a CDF only

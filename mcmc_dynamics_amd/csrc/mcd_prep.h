@@ -12,6 +12,7 @@ constexpr double kDeg2Rad = 0.017453292519943295769;
 
 // CONST:   v_sys, sigma_max, v_maxx, v_maxy [, ra_c, dec_c] [, v_back, sigma_back, f_back]
 // PROFILE: v_sys, sigma_max, a, v_maxx, v_maxy, r_peak [, ra_c, dec_c] [, v_back, sigma_back, f_back | f_back]
+// CONST_ESCALE / PROFILE_ESCALE: CONST / PROFILE with err_scale behind the cluster columns, in front of the centre
 // DOUBLE:  v_sys, sigma_max, a, v_maxx, v_maxy, r_peak, v_maxx_c, v_maxy_c, r_peak_ratio [, ra_c, dec_c] [, v_back, sigma_back, f_back]
 template <class T>
 __device__ __forceinline__ void walker_constants(const double* __restrict__ p, int model, bool free_centre, T* __restrict__ w) {
@@ -27,8 +28,10 @@ __device__ __forceinline__ void walker_constants(const double* __restrict__ p, i
     const bool dbl = is_double(model);
     const double rc = dbl ? p[8] * rp : 0.0;
     w[W_VXC] = (T)(dbl ? p[6] : 0.0); w[W_VYC] = (T)(dbl ? p[7] : 0.0); w[W_RC2] = (T)(rc * rc); w[W_2RC] = (T)(2.0 * rc);
-    w[19] = (T)0;
     int j = cluster_columns(model);
+    // error-scale models: err_scale is the last cluster column; zero for every other model
+    const double es = is_escale(model) ? p[j - 1] : 0.0;
+    w[W_ES2] = (T)(es * es);
     double sac = 0, cac = 1, sdc = 0, cdc = 1;
     if (free_centre) {
         sincos(p[j] * kDeg2Rad, &sac, &cac);

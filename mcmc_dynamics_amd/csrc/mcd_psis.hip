@@ -85,12 +85,12 @@ hipError_t term_launch(hipStream_t s, int precision, const void* records, int64_
     int64_t slice_len = 0;
     const int64_t n_slices = posterior_slices(n, S, &slice_len);
     const dim3 grid((unsigned)((n + kWave - 1) / kWave * n_slices));
-    return dispatch_term_type(precision, [&](auto t) {
+    return dispatch_model_term_type<MODEL>(precision, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL((psis_term_kernel<MODEL, FREE, T>), grid, dim3(kWave), 0, s, (const T*)records, n, (const T*)wpar,
                            S, slice_len, n_slices, terms);
         return hipGetLastError();
-    });
+    }, hipErrorInvalidValue);
 }
 
 }  // namespace
@@ -99,7 +99,7 @@ hipError_t launch_psis(hipStream_t s, const LaunchShape& sh, const void* records
                        int64_t M, double r_eff, double* terms, double* out, int64_t out_stride) {
     if (n <= 0 || S <= 0) return hipSuccess;
     if (M > kPsisMaxTail) return hipErrorInvalidValue;
-    const hipError_t e = dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    const hipError_t e = dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return term_launch<decltype(M)::value, decltype(FREE)::value>(s, sh.precision, records, n, wpar, S, terms);
     }, hipErrorInvalidValue);
     if (e != hipSuccess) return e;

@@ -85,7 +85,7 @@ hipError_t launch_replicate(hipStream_t s, const LaunchShape& sh, const void* re
                             const Chunk* chunks, int64_t n_chunks, const void* wpar, int64_t n_rows, int64_t row0,
                             uint64_t seed, double bg_mean, double bg_sigma2, double* partials) {
     if (sh.precision != 0 || n_rows <= 0 || n_rows > kRepMaxRows) return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_replicate_main<decltype(M)::value, decltype(FREE)::value>(s, records, order, chunks, n_chunks, wpar,
                                                                                 n_rows, row0, seed, bg_mean, bg_sigma2,
                                                                                 partials);

@@ -130,7 +130,7 @@ hipError_t launch_simulate(hipStream_t s, const LaunchShape& sh, const void* rec
     if (sh.precision != 0 || n_rows <= 0 || n_rows > kSimulatedPassSims || sim_begin < 0 || sim_begin + n_rows > n_sims ||
         !table || !bad)
         return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_simulate_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, wpar, n_rows,
                                                                                sim_begin, n_sims, sim0, seed, bg_mean, bg_sigma2,
                                                                                table, bad);
@@ -149,7 +149,7 @@ hipError_t launch_simulated_value(hipStream_t s, const LaunchShape& sh, const vo
                                   int64_t n_sims, double bg_mean, double bg_sigma2, double* partials, int64_t n_rows) {
     if (sh.precision != 0 || n_rows <= 0 || n_rows > kSimulatedMaxRows || !row_sim || !table || n_sims <= 0)
         return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_simulated_value_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, wpar, row_sim,
                                                                                       table, n_sims, bg_mean, bg_sigma2, partials,
                                                                                       n_rows);

@@ -84,7 +84,7 @@ hipError_t launch_simulated_grad(hipStream_t s, const LaunchShape& sh, const voi
                                  int64_t n_rows) {
     if (sh.precision != 0 || n_rows <= 0 || n_rows > kSimulatedMaxRows || !params || !row_sim || !table || n_sims <= 0)
         return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         return launch_simulated_grad_main<decltype(M)::value, decltype(FREE)::value>(s, records, chunks, n_chunks, params, wpar,
                                                                                      row_sim, table, n_sims, bg_mean, bg_sigma2,
                                                                                      partials, n_rows);

@@ -51,6 +51,7 @@ __device__ __forceinline__ void wave_merge(ParamRanges& r) {
     r.sb2_min = wave_lesser(r.sb2_min); r.sb2_max = wave_greater(r.sb2_max);
     r.f_min = wave_lesser(r.f_min); r.f_max = wave_greater(r.f_max);
     r.len_min = wave_lesser(r.len_min); r.len_max = wave_greater(r.len_max);
+    r.es2_min = wave_lesser(r.es2_min); r.es2_max = wave_greater(r.es2_max);
     r.finite = __all(r.finite ? 1 : 0) != 0;
 }
 
@@ -61,17 +62,18 @@ __device__ __forceinline__ void wave_merge_for(ParamRanges& r, int model) {
     if (bg == BG_GAUSS) { r.sb2_min = wave_lesser(r.sb2_min); r.sb2_max = wave_greater(r.sb2_max); }
     if (bg == BG_GAUSS || bg == BG_FIXED_DENSITY) { r.f_min = wave_lesser(r.f_min); r.f_max = wave_greater(r.f_max); }
     if (is_profile(model)) { r.len_min = wave_lesser(r.len_min); r.len_max = wave_greater(r.len_max); }
+    if (is_escale(model)) { r.es2_min = wave_lesser(r.es2_min); r.es2_max = wave_greater(r.es2_max); }
     r.finite = __all(r.finite ? 1 : 0) != 0;
 }
 
 __device__ __forceinline__ void store_ranges(const ParamRanges& r, double* o) {
     o[0] = r.s2_min; o[1] = r.s2_max; o[2] = r.amp; o[3] = r.sb2_min; o[4] = r.sb2_max; o[5] = r.f_min; o[6] = r.f_max;
-    o[7] = r.len_min; o[8] = r.len_max; o[9] = r.finite ? 1.0 : 0.0;
+    o[7] = r.len_min; o[8] = r.len_max; o[9] = r.finite ? 1.0 : 0.0; o[10] = r.es2_min; o[11] = r.es2_max;
 }
 __device__ __forceinline__ ParamRanges load_ranges(const double* o) {
     ParamRanges r;
     r.s2_min = o[0]; r.s2_max = o[1]; r.amp = o[2]; r.sb2_min = o[3]; r.sb2_max = o[4]; r.f_min = o[5]; r.f_max = o[6];
-    r.len_min = o[7]; r.len_max = o[8]; r.finite = o[9] != 0.0;
+    r.len_min = o[7]; r.len_max = o[8]; r.finite = o[9] != 0.0; r.es2_min = o[10]; r.es2_max = o[11];
     return r;
 }
 
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(kStepBlock) void stretch_step_kernel(StretchDevice 
     const int P = d.n_dim, K = d.k;
     const int tid = threadIdx.x;
     __shared__ int s_n_ok, s_donor;
-    __shared__ double s_ranges[kStepBlock / 64][10];          // ParamRanges of each wave (a type with initialisers cannot be __shared__)
+    __shared__ double s_ranges[kStepBlock / 64][kRangeDoubles];          // ParamRanges of each wave (a type with initialisers cannot be __shared__)
 
     if (acc_step >= 0) {
         const int32_t* first = d.order + acc_step * W + (acc_h == 0 ? 0 : half);
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
     const int64_t slot_acc = ((acc_step * 2 + acc_h) & 1) * B, slot_prop = ((prop_step * 2 + prop_h) & 1) * B;
     const bool active = j < half, do_acc = acc_step >= 0, do_prop = prop_step >= 0;
     __shared__ int s_wave_ok[kStepBlock / 64], s_wave_first[kStepBlock / 64];
-    __shared__ double s_ranges[kStepBlock / 64][10];
+    __shared__ double s_ranges[kStepBlock / 64][kRangeDoubles];
     __shared__ double s_donor_prop[kMaxCols];
     __shared__ double s_lo[kMaxCols], s_hi[kMaxCols], s_const[kMaxCols], s_factor[kMaxCols];
     __shared__ int s_source[kMaxCols];
@@ -306,11 +308,11 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
     // several ensembles: workgroup 0 judges the guard on the table of all of them (below); the first kStepBlock ensembles'
     // ranges are fetched with this round of loads, not behind the barrier
     int first_n_ok = 0;
-    double first_ranges[10];
+    double first_ranges[kRangeDoubles];
     if (kBinned && b == 0 && do_acc && j < B) {
         first_n_ok = d.n_ok[slot_acc + j];
 #pragma unroll
-        for (int i = 0; i < 10; ++i) first_ranges[i] = d.ranges[(slot_acc + j) * 10 + i];
+        for (int i = 0; i < kRangeDoubles; ++i) first_ranges[i] = d.ranges[(slot_acc + j) * kRangeDoubles + i];
     }
     int w_s = 0, pick_j = 0;
     double z_j = 0.0;
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
             ParamRanges mine;
             if (j < B && first_n_ok > 0) mine.merge(load_ranges(first_ranges));
             for (int64_t e = j + kStepBlock; e < B; e += kStepBlock)
-                if (d.n_ok[slot_acc + e] > 0) mine.merge(load_ranges(d.ranges + (slot_acc + e) * 10));
+                if (d.n_ok[slot_acc + e] > 0) mine.merge(load_ranges(d.ranges + (slot_acc + e) * kRangeDoubles));
             wave_merge(mine);
             if ((j & 63) == 0) store_ranges(mine, s_ranges[j >> 6]);
             __syncthreads();
@@ -493,7 +495,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
             if (B > 1) {
                 // the guard's verdict is on the table of ALL ensembles: this one's ranges go to memory and workgroup 0 of
                 // the next launch judges them together (below, judge_all_ensembles)
-                store_ranges(all, d.ranges + (slot_prop + b) * 10);
+                store_ranges(all, d.ranges + (slot_prop + b) * kRangeDoubles);
             } else {
                 int level = 0;
                 if (d.allow_fast) {
@@ -516,7 +518,7 @@ __global__ __launch_bounds__(kFused ? kFusedThreads : kStepBlock) void stretch_s
 // proposal inside the prior (no table); the host takes the first launch whose verdict differs as the next block's hint.
 __global__ __launch_bounds__(kStepBlock) void stretch_judge_kernel(StretchDevice d) {
     __shared__ double s_rows[kStepBlock][13];
-    __shared__ double s_ranges[kStepBlock / 64][10];
+    __shared__ double s_ranges[kStepBlock / 64][kRangeDoubles];
     const int64_t launch = blockIdx.x;
     const int j = threadIdx.x, half = (int)(d.n_walkers / 2), K = d.k;
     const int n_ok = d.n_ok_log[launch];                                 // (workgroup-uniform)

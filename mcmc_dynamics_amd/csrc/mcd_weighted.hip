@@ -88,7 +88,7 @@ hipError_t launch_weighted_grad(hipStream_t s, const LaunchShape& sh, int scheme
                                 int64_t n_rows) {
     if (sh.precision != 0 || n_rows <= 0 || !row_replicate) return hipErrorInvalidValue;
     if (scheme == kWeightExplicit && (!weights || n_replicates <= 0)) return hipErrorInvalidValue;
-    return dispatch_any_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
+    return dispatch_launch_model(sh.model, sh.free_centre, [&](auto M, auto FREE) {
         constexpr int MODEL = decltype(M)::value;
         constexpr bool kFree = decltype(FREE)::value;
         switch (scheme) {

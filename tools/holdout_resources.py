@@ -17,11 +17,12 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS", 10: "CONST_ESCALE", 11: "PROFILE_ESCALE"}
 # analyse() reports the seven models of the reference's running classes unless told otherwise (the tests that quote
 # its table count them); the double Lynden-Bell models: analyse(models=DOUBLE_MODELS), tests/test_double_resources_cpu.py
 BASE_MODELS, DOUBLE_MODELS, ALL_MODELS = tuple(range(7)), (7, 8), tuple(range(9))
-_MAIN = re.compile(r"holdout_kernelILi(\d)ELb(\d)EE")
+ESCALE_MODELS = (10, 11)      # the error-scale models: analyse(models=ESCALE_MODELS), `--escale` on the command line
+_MAIN = re.compile(r"holdout_kernelILi(\d+)ELb(\d)EE")
 _FIELD = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\w+) \[-Rpass")
 KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize": "scratch_bytes_per_lane",
         "Occupancy": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size": "lds_bytes"}
@@ -52,7 +53,9 @@ def analyse(models=None):
 
 
 def main():
-    rows = analyse(models=ALL_MODELS)
+    escale = "--escale" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--escale"]
+    rows = analyse(models=ESCALE_MODELS if escale else ALL_MODELS)
     print("{0:8s} {1:16s} {2:6s} {3:>6s} {4:>6s} {5:>8s} {6:>10s}".format("kernel", "model", "centre", "VGPRs", "SGPRs",
                                                                         "scratch", "waves/SIMD"))
     for r in rows:

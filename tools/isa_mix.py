@@ -71,6 +71,10 @@ KERNELS = [
     # second component on the shared reciprocal
     ("ILi7ELb0EddLi1E", "DOUBLE fixed centre", "double", 8, 1, None),
     ("ILi8ELb0EddLi1E", "DOUBLE_BGGAUSS fixed", "double_bggauss", 4, 1, _sel(frexp=4)),
+    # the error-scale models (one fast form each): CONST's 16-star tree and PROFILE's general loop with err_scale^2 verr^2 in
+    # the variance -- an FMA in place of CONST's add, one multiply more than PROFILE
+    ("ILi10ELb0EddLi1E", "CONST_ESCALE fixed centre", "const_escale", 16, 1, _sel(rsq=0, rcp=1)),
+    ("ILi11ELb0EddLi1E", "PROFILE_ESCALE fixed centre", "profile_escale", 8, 1, None),
     ("ILi0ELb0EffLi1E", "CONST fixed, f32", "const_f32", 16, 1, None),
     ("ILi0ELb0EfdLi1E", "CONST fixed, f32 terms f64 sums", "const_f32acc64", 16, 1, None),
     ("ILi1ELb0EffLi1E", "BGFIXED fixed, f32", "bgfixed_f32", 4, 1, None),
@@ -337,8 +341,17 @@ def main():
                        "product with m_1; K_1 cross_1 takes the place of PROFILE's K_1 inv), 2 v_fma_f64 (the second cross, "
                        "the numerator); no second v_rcp_f64 sequence",
         } if "double" in merged and "double_bggauss" in merged else None
+        # what err_scale^2 adds to the base models' loops per term (tests/test_escale_cpu.py holds the margin)
+        escale_note = {
+            "valu_per_term_over_const": merged["const_escale"]["valu_per_term"] - merged["const"]["valu_per_term"],
+            "valu_per_term_over_profile": merged["profile_escale"]["valu_per_term"] - merged["profile_general"]["valu_per_term"],
+            "margin": 1.0,
+            "listing": "per term: CONST v_fma_f64 (err_scale^2 verr^2 + sigma_max^2) in place of v_add_f64; PROFILE one "
+                       "v_mul_f64 (err_scale^2 verr^2) in front of the variance's v_fma_f64",
+        } if "const_escale" in merged and "profile_escale" in merged else None
         with open(sys.argv[2], "w") as f:
             json.dump({"source_sha16": source_hash(), "generated_by": "tools/isa_mix.py", "double_models": double_note,
+                       "escale_models": escale_note,
                        "note": "VALU wave-instructions per star-walker term in the hot loop nest of mcd::loglike_kernel "
                                "(gfx950 ISA from hipcc -save-temps); prologue, final log and tails not included",
                        "kernels": merged}, f, indent=1, sort_keys=True)

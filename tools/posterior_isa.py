@@ -22,12 +22,13 @@ from collections import Counter
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS", 10: "CONST_ESCALE", 11: "PROFILE_ESCALE"}
 # analyse() reports the seven models of the reference's running classes unless told otherwise (the tests that quote
 # its table count them); the double Lynden-Bell models: analyse(models=DOUBLE_MODELS), tests/test_double_resources_cpu.py
 BASE_MODELS, DOUBLE_MODELS, ALL_MODELS = tuple(range(7)), (7, 8), tuple(range(9))
+ESCALE_MODELS = (10, 11)      # the error-scale models: analyse(models=ESCALE_MODELS), `--escale` on the command line
 # _ZN3mcd12_GLOBAL__N_122posterior_slice_kernelILi<model>ELb<free>ELb<mem>E<d|f>EEvPKT2_...
-_NAME = re.compile(r"^(_ZN3mcd12_GLOBAL__N_122posterior_slice_kernelILi(\d)ELb(\d)ELb(\d)E([df])E\w*):")
+_NAME = re.compile(r"^(_ZN3mcd12_GLOBAL__N_122posterior_slice_kernelILi(\d+)ELb(\d)ELb(\d)E([df])E\w*):")
 
 
 def _ops(lines):
@@ -76,7 +77,9 @@ def analyse(out=None, models=None):
 
 
 def main():
-    rows = analyse(models=ALL_MODELS)
+    escale = "--escale" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--escale"]
+    rows = analyse(models=ESCALE_MODELS if escale else ALL_MODELS)
     print("{0:16s} {1:5s} {2:4s} {3:4s} {4:>10s} {5:>8s} {6:>7s} {7:>7s}".format("model", "free", "mem", "prec", "VALU/term",
                                                                                "f64", "s_load", "vload"))
     for r in sorted(rows, key=lambda r: (r["precision"], r["model"], r["free_centre"], r["membership"])):

@@ -16,12 +16,12 @@ import sys
 import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from weighted_resources import CSRC, KEYS, MODELS, _FIELD  # noqa: E402
+from weighted_resources import ALL_MODELS, CSRC, ESCALE_MODELS, KEYS, MODELS, _FIELD  # noqa: E402
 
-_MAIN = re.compile(r"(simulated_grad)_kernelILi(\d)ELb(\d)EE")
+_MAIN = re.compile(r"(simulated_grad)_kernelILi(\d+)ELb(\d)EE")
 
 
-def analyse():
+def analyse(models=None):
     """Rows (dicts) per kernel instantiation of the unit: 9 models x {fixed, free centre}."""
     out = tempfile.mkdtemp(prefix="simulated_grad_resources_")
     res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
@@ -42,11 +42,13 @@ def analyse():
         if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
             row[KEYS[f.group(1).strip()]] = int(f.group(2))
     rows.sort(key=lambda r: (r["kernel"], r["model_id"], r["free_centre"]))
-    return rows
+    return [r for r in rows if r["model_id"] in (ALL_MODELS if models is None else models)]
 
 
 def main():
-    rows = analyse()
+    escale = "--escale" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--escale"]
+    rows = analyse(models=ESCALE_MODELS if escale else ALL_MODELS)
     print("{0:16s} {1:16s} {2:6s} {3:>6s} {4:>6s} {5:>8s} {6:>5s} {7:>10s}".format(
         "kernel", "model", "centre", "VGPRs", "SGPRs", "scratch", "LDS", "waves/SIMD"))
     for r in rows:

@@ -18,15 +18,16 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmc_dynamics_amd", "csrc")
 MODELS = {0: "CONST", 1: "BGFIXED", 2: "BGGAUSS", 3: "PROFILE", 4: "PROFILE_BGGAUSS", 5: "PROFILE_BGDENS",
-          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS"}
+          6: "PROFILE_BGFIXED", 7: "DOUBLE", 8: "DOUBLE_BGGAUSS", 10: "CONST_ESCALE", 11: "PROFILE_ESCALE"}
+ALL_MODELS, ESCALE_MODELS = tuple(range(9)), (10, 11)      # analyse() reports the first nine unless told otherwise
 SCHEMES = {0: "exponential", 1: "poisson", 2: "explicit"}
-_MAIN = re.compile(r"weighted_grad_kernelILi(\d)ELb(\d)ELi(\d)EE")
+_MAIN = re.compile(r"weighted_grad_kernelILi(\d+)ELb(\d)ELi(\d)EE")
 _FIELD = re.compile(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\w+) \[-Rpass")
 KEYS = {"TotalSGPRs": "sgprs", "VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize": "scratch_bytes_per_lane",
         "Occupancy": "occupancy", "SGPRs Spill": "sgpr_spill", "VGPRs Spill": "vgpr_spill", "LDS Size": "lds_bytes"}
 
 
-def analyse():
+def analyse(models=None):
     """Rows (dicts) per kernel instantiation of the unit: 9 models x {fixed, free centre} x 3 schemes."""
     out = tempfile.mkdtemp(prefix="weighted_resources_")
     res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
@@ -47,11 +48,13 @@ def analyse():
         if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
             row[KEYS[f.group(1).strip()]] = int(f.group(2))
     rows.sort(key=lambda r: (r["model_id"], r["free_centre"], r["scheme"]))
-    return rows
+    return [r for r in rows if r["model_id"] in (ALL_MODELS if models is None else models)]
 
 
 def main():
-    rows = analyse()
+    escale = "--escale" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--escale"]
+    rows = analyse(models=ESCALE_MODELS if escale else ALL_MODELS)
     print("{0:16s} {1:6s} {2:12s} {3:>6s} {4:>6s} {5:>8s} {6:>5s} {7:>10s}".format("model", "centre", "scheme", "VGPRs", "SGPRs",
                                                                                 "scratch", "LDS", "waves/SIMD"))
     for r in rows:

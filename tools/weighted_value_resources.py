@@ -16,12 +16,12 @@ import sys
 import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from weighted_resources import CSRC, KEYS, MODELS, ROOT, SCHEMES, _FIELD  # noqa: E402
+from weighted_resources import ALL_MODELS, CSRC, ESCALE_MODELS, KEYS, MODELS, ROOT, SCHEMES, _FIELD  # noqa: E402
 
-_MAIN = re.compile(r"weighted_value_kernelILi(\d)ELb(\d)ELi(\d)EE")
+_MAIN = re.compile(r"weighted_value_kernelILi(\d+)ELb(\d)ELi(\d)EE")
 
 
-def analyse():
+def analyse(models=None):
     """Rows (dicts) per kernel instantiation of the unit: 9 models x {fixed, free centre} x 3 schemes."""
     out = tempfile.mkdtemp(prefix="weighted_value_resources_")
     res = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only",
@@ -42,7 +42,7 @@ def analyse():
         if f and row is not None and f.group(1).strip() in KEYS and f.group(2).isdigit():
             row[KEYS[f.group(1).strip()]] = int(f.group(2))
     rows.sort(key=lambda r: (r["model_id"], r["free_centre"], r["scheme"]))
-    return rows
+    return [r for r in rows if r["model_id"] in (ALL_MODELS if models is None else models)]
 
 
 def gradient_vgprs():
@@ -52,12 +52,14 @@ def gradient_vgprs():
 
 
 def main():
-    rows = analyse()
+    escale = "--escale" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--escale"]
+    rows = analyse(models=ESCALE_MODELS if escale else ALL_MODELS)
     grad = gradient_vgprs()
     print("{0:16s} {1:6s} {2:12s} {3:>6s} {4:>6s} {5:>8s} {6:>5s} {7:>10s} {8:>10s}".format(
         "model", "centre", "scheme", "VGPRs", "SGPRs", "scratch", "LDS", "waves/SIMD", "grad VGPRs"))
     for r in rows:
-        g = grad[(r["model_id"], r["free_centre"], r["scheme"])]
+        g = grad.get((r["model_id"], r["free_centre"], r["scheme"]), 0)         # (0: not in the committed gradient table)
         print("{0:16s} {1:6s} {2:12s} {3:6d} {4:6d} {5:8d} {6:5d} {7:10d} {8:10d}{9}".format(
             r["model"], "free" if r["free_centre"] else "fixed", r["scheme"], r["vgprs"], r["sgprs"],
             r["scratch_bytes_per_lane"], r["lds_bytes"], r["occupancy"], g, "  MORE than the gradient" if r["vgprs"] > g else ""))
